@@ -9,6 +9,7 @@ every step.
     python bench.py --gpus 8 ...      # starts its own 8 ranks (see launch_ranks)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus 8 ...      # or under an external launcher
+    python bench.py ... --dump-outputs DIR     # + the last timed step's decoded results as DIR/<name>.npy
 
 Prints ONE JSON line on rank 0.  A step = patchify -> ViT -> ProbMapHead ->
 fused decode (-> all-gather), inputs resident in HBM, synthetic crops and
@@ -303,6 +304,33 @@ def parity_block(cfg, sd, model, codec, x, dtype, n_crops: int = 8, fp32_steps: 
     return res
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, packed: torch.Tensor):
+    """--dump-outputs: the last timed step's result [global batch, K, 7] float64 as its caller receives it, unpacked
+    into Codec.decode's arrays (parallel.unpack_decoded), one <out_dir>/<name>.npy each: keypoints (B,K,2) f64,
+    keypoint_scores (B,K) f32, probabilities / visibilities / oks (B,1,K) f32, errors (B,1,K) f64.  A batch too large
+    for DUMP_LIMIT_BYTES is cut to a fixed seeded sample of crops (in crop order), their indices in crop_index.npy."""
+    from probpose_pytorch_amd import parallel
+    n = packed.shape[0]
+    per_crop = packed[0].numel() * packed.element_size()
+    if n * per_crop > DUMP_LIMIT_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(n, size=DUMP_LIMIT_BYTES // (per_crop + 8), replace=False))
+        packed = packed[torch.from_numpy(keep)]
+        arrays = [("crop_index", keep.astype(np.float64))]
+    else:
+        arrays = []
+    (kpts, scores), prob, vis, oks, err = parallel.unpack_decoded(packed)
+    arrays += [("keypoints", kpts), ("keypoint_scores", scores), ("probabilities", prob), ("visibilities", vis),
+               ("oks", oks), ("errors", err)]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays:
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    return [name for name, _ in arrays]
+
+
 def launcher_command(argv, n_ranks: int, port: int):
     """argv of the N-rank launch of this script: one process per GPU under torch.distributed.run, rendezvous on
     127.0.0.1 (the container hostname may not resolve).  ``argv`` = this script's own arguments, passed through."""
@@ -348,7 +376,12 @@ def main():
     ap.add_argument("--tune-cache", default=None,
                     help="JSON file of per-shape GEMM tile winners: loaded if present, written after the warm-up "
                          "(lets a profiled run start tuned, so its trace holds no tuning launches)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned (the decoded keypoints, scores and auxiliary "
+                         "heads of the whole global batch) as DIR/<name>.npy, so that two builds can be compared")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(sys.argv[1:], args.gpus))
@@ -454,6 +487,7 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
         assert result.shape == (B * world, cfg["K"], 7)
+        last_step = result.cpu() if args.dump_outputs and rank == 0 else None
 
         # ---- kernel-level timing with HIP events on the launch stream (eager pass, same inputs)
         from probpose_pytorch_amd import engine
@@ -515,6 +549,9 @@ def main():
             if args.dtype == "bf16":
                 line["roofline"]["frac_of_measured_mfma"] = round(achieved / mp["mfma_bf16_random_tflops"], 4)
         _progress(f"timed region done: {ms_per_step:.3f} ms/step; parity block / CPU baseline follow")
+        if last_step is not None:
+            names = dump_outputs(args.dump_outputs, last_step)
+            _progress(f"last step's outputs written to {args.dump_outputs}: {', '.join(names)}")
         if world == 1 and not args.no_parity:
             line["parity"] = parity_block(cfg, sd, model, codec, x, dtype)
             _progress("parity block done")

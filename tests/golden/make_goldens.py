@@ -148,12 +148,16 @@ def main():
     out_np = [o.numpy() for o in out]
     codec = Codec(ProbMap((192, 256), (48, 64), coco))
     kpts, scores, rest = ref_decode_batch(codec, out_np)
+    # the same head in float64: float32 CPU convolutions round differently with the host's thread count and vector
+    # ISA, float64 ones agree to ~1e-15, so the restatement is pinned on these on any host
+    with torch.no_grad():
+        out64 = [o.numpy() for o in head.double()(feats.double())]
     np.savez_compressed(
         os.path.join(HERE, "head_c384.npz"), C=C, K=K, pools=np.array(pools), feats_sha=sha(feats.numpy()),
         w_probe=sd["final_layer.weight"].numpy().ravel()[:8],
         heatmaps=out_np[0].astype(np.float16 if False else np.float32),
         prob=out_np[1], vis=out_np[2], oks=out_np[3], err=out_np[4], kpts=kpts, scores=scores,
-        dec_err=rest[3])
+        dec_err=rest[3], **{f"{k}_f64": o for k, o in zip(("heatmaps", "prob", "vis", "oks", "err"), out64)})
     print("head", [o.shape for o in out_np], "hm range", out_np[0].min(), out_np[0].max(),
           "frac>0", (out_np[0] > 0).mean())
 

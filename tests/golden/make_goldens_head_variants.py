@@ -49,8 +49,10 @@ def main():
         feats = syn.synthetic_features(2, C, h, w, seed=seed + 100)
         with torch.no_grad():
             res = head(feats)
-        for key, t in zip(("heatmaps", "prob", "vis", "oks", "err"), res):
+            res64 = head.double()(feats.double())          # host-independent to ~1e-15 (make_goldens.py, G3/G4)
+        for key, t, t64 in zip(("heatmaps", "prob", "vis", "oks", "err"), res, res64):
             out[f"{name}_{key}"] = t.numpy()
+            out[f"{name}_{key}_f64"] = t64.numpy()
         print(name, [tuple(t.shape) for t in res], "hm range", float(res[0].min()), float(res[0].max()),
               "frac in (0,1)", float(((res[0] > 0) & (res[0] < 1)).float().mean()))
     np.savez_compressed(os.path.join(HERE, "head_variants.npz"), **out)

@@ -119,7 +119,13 @@ def test_vit_restatement_self_consistency():
     torch.testing.assert_close(a.double(), c, rtol=0, atol=2e-5)
 
 
+def _f64(sd):
+    return {k: v.double() if v.is_floating_point() else v for k, v in sd.items()}
+
+
 def test_head_restatement_matches_reference_golden():
+    """The head restatement against the reference ProbMapHead, both run in float64: float32 CPU convolutions round
+    differently with the host's thread count and vector ISA (by up to 6e-6 between two hosts), float64 ones agree far below atol."""
     import torch
     from probpose_pytorch_amd.synthetic import synthetic_features, synthetic_head_state
     g = np.load(os.path.join(GOLDEN, "head_c384.npz"))
@@ -130,9 +136,10 @@ def test_head_restatement_matches_reference_golden():
     feats = synthetic_features(2, C, 16, 12, seed=12)
     assert sha(feats.numpy()) == str(g["feats_sha"])
     with torch.no_grad():
-        out = orc.head_forward(sd, feats, pools=pools)
+        out = orc.head_forward(_f64(sd), feats.double(), pools=pools)
     for o, key in zip(out, ("heatmaps", "prob", "vis", "oks", "err")):
-        np.testing.assert_allclose(o.numpy(), g[key], rtol=0, atol=1e-6)
+        assert o.dtype == torch.float64
+        np.testing.assert_allclose(o.numpy(), g[key + "_f64"], rtol=0, atol=1e-9)
     # chained decode on the *golden* heatmaps reproduces the reference's decoded keypoints
     (kpts, scores), *_rest, err = orc.codec_decode(
         tuple(g[k] for k in ("heatmaps", "prob", "vis", "oks", "err")), (192, 256), (48, 64),
@@ -170,7 +177,8 @@ HEAD_VARIANTS = {
 @pytest.mark.parametrize("name", sorted(HEAD_VARIANTS))
 def test_head_restatement_variants_match_reference_golden(name):
     """The constructor branches beside the default head: conv stack (head.py:407-431), final kernel 3, Identity final
-    layer (head.py:234-235), no deconvolution -- oracle vs the reference ProbMapHead's own outputs."""
+    layer (head.py:234-235), no deconvolution -- oracle vs the reference ProbMapHead's own outputs, both in float64
+    (see test_head_restatement_matches_reference_golden)."""
     import torch
     from probpose_pytorch_amd.synthetic import synthetic_features, synthetic_head_state
     C, K, pools, (h, w), dec, conv, ck, fk, seed = HEAD_VARIANTS[name]
@@ -179,9 +187,11 @@ def test_head_restatement_variants_match_reference_golden(name):
                               conv_kernels=ck)
     feats = synthetic_features(2, C, h, w, seed=seed + 100)
     with torch.no_grad():
-        out = orc.head_forward(sd, feats, pools=pools, n_deconv=len(dec), final_kernel=fk, conv_kernels=ck)
+        out = orc.head_forward(_f64(sd), feats.double(), pools=pools, n_deconv=len(dec), final_kernel=fk,
+                               conv_kernels=ck)
     for o, key in zip(out, ("heatmaps", "prob", "vis", "oks", "err")):
-        np.testing.assert_allclose(o.numpy(), g[f"{name}_{key}"], rtol=0, atol=1e-6)
+        assert o.dtype == torch.float64
+        np.testing.assert_allclose(o.numpy(), g[f"{name}_{key}_f64"], rtol=0, atol=1e-9)
 
 
 @pytest.mark.parametrize("C,depth,heads,img", [(96, 2, 4, (64, 48)), (384, 3, 12, (64, 48)), (128, 2, 2, (96, 64))])

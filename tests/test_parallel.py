@@ -109,6 +109,41 @@ def test_bench_starts_its_own_ranks(monkeypatch):
         assert e.code == 17
 
 
+def test_bench_dump_outputs_writes_the_decoded_arrays(tmp_path, monkeypatch):
+    """--dump-outputs: the step's packed result comes back as Codec.decode's arrays, float32 / float64 only, losslessly;
+    a result over the size limit becomes a fixed seeded sample of crops, the same one every time."""
+    import bench
+    out = _fake_decoded(6, 17, 1)
+    names = bench.dump_outputs(str(tmp_path / "a"), parallel.pack_decoded(out))
+    assert names == ["keypoints", "keypoint_scores", "probabilities", "visibilities", "oks", "errors"]
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in names}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    np.testing.assert_array_equal(got["keypoints"], out["kpts"].numpy())
+    np.testing.assert_array_equal(got["keypoint_scores"], out["scores"].numpy())
+    np.testing.assert_array_equal(got["visibilities"][:, 0], out["aux"][1].numpy())
+    np.testing.assert_array_equal(got["errors"][:, 0], out["err"].numpy())
+
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4 * 17 * 7 * 8 + 4 * 8)       # room for 4 of the 6 crops
+    packed = parallel.pack_decoded(out)
+    for d in ("b", "c"):
+        names = bench.dump_outputs(str(tmp_path / d), packed)
+    assert names[0] == "crop_index" and sum((tmp_path / "b" / f"{n}.npy").stat().st_size for n in names) < 4096
+    idx = np.load(tmp_path / "b" / "crop_index.npy")
+    np.testing.assert_array_equal(idx, np.load(tmp_path / "c" / "crop_index.npy"))
+    assert idx.dtype == np.float64 and len(idx) == 4 and (np.diff(idx) > 0).all()
+    np.testing.assert_array_equal(np.load(tmp_path / "b" / "keypoints.npy"), out["kpts"].numpy()[idx.astype(int)])
+
+
+def test_bench_refuses_zero_steps(monkeypatch):
+    import sys
+
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit) as e:
+        bench.main()
+    assert e.value.code == 2
+
+
 @pytest.mark.gpu
 def test_bench_gpus2_launches_two_ranks_on_the_gpu_box(tmp_path):
     """`python bench.py --gpus 2` started the way the driver starts `--gpus 1` (no launcher, no WORLD_SIZE): the parent
