@@ -307,6 +307,44 @@ int pp_heatmap_argmax(const float *heatmaps, long long maps, int H, int W, float
 int pp_pck_counts(const void *pred, const void *gt, int coord_f64, const unsigned char *mask, const double *norm,
                   const unsigned char *skip, double thr, int N, int K, int *counts, float *dist, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Validation loss (forward only).  Replaces
+ *   OKSHeatmapLoss.forward / _get_mask  probpose/loss.py:55-191  (pp_oks_heatmap_loss)
+ *   ProbPoseLoss.forward                probpose/loss.py:360-510 with _error_from_heatmaps (:512-548),
+ *                                        _oks_from_heatmaps (:550-640, its per-crop host decode replaced by
+ *                                        the batched decodes above), compute_oks (:715-764), get_mae (:699-712)
+ *                                        (pp_probpose_loss_terms)
+ *
+ * pp_oks_heatmap_loss: output / target [B,K,H,W] f32.  weights: NULL, [B,K] or, with weights_per_pixel,
+ * [B,K,H,W] f32; mask: NULL or f32 [H,W] maps at mask + b * mask_sb + k * mask_sk (element strides; 0
+ * broadcasts, e.g. mask_sk = 0 for a [B,1,H,W] mask); skip_empty: zero channels whose target is all 0;
+ * oks_type 0 = minus, 1 = plus, 2 = both.  oks_weight is 1 - smoothing_weight - gaussian_weight (the caller's
+ * float64 value).  Sobel gradients of `output` with zero 'same' padding, any H, W >= 1.  Outputs: per_pixel
+ * [B,K,H,W] (optional), per_keypoint [B,K] (optional), scalars[3] = (mean of the per-keypoint loss, mean of
+ * the per-pixel loss, number of target elements outside [0, 1]).  parts: caller-owned scratch of
+ * B*K*5 floats.  Two launches; deterministic (fixed-order reductions, no float atomics).
+ *
+ * pp_probpose_loss_terms: gt_kpts / dt_kpts [B,K,2] f64 decoded coordinates (input-image pixels; gt may be
+ * NaN for an empty map); in_image / annotated / visibility [B,K] int32 (the reference's .to(int) values);
+ * dt_prob / dt_vis / dt_oks / dt_err [B*K] f32 predictions; variance [K] f64 = (2 sigma_k)^2; oks_area =
+ * 0.53 * W * H + eps (loss.py:609-620 with heatmap_size = (W, H), compute_oks use_area=False).  Outputs
+ * (all required): gt_oks, gt_err (0 with freeze_error), vis_weight [B*K] f32 (the normalised weights of
+ * loss.py:439-450), oks_weight [B] f32 (1 for a crop with an in-image annotated keypoint), results[8] f32 =
+ * (probability BCE, visibility BCE, OKS MSE, error L1Log, OKS MAE, error MAE, flags, #annotated in-image
+ * keypoints); flags bit 0: no annotated keypoint (loss.py:448 raises), bit 1: a NaN error target
+ * (loss.py:546 asserts), bit 2: a probability or visibility outside [0, 1].  One launch, one workgroup.
+ * ---------------------------------------------------------------------- */
+int pp_oks_heatmap_loss(const float *output, const float *target, const float *weights, int weights_per_pixel,
+                        const float *mask, long long mask_sb, long long mask_sk, int skip_empty, int oks_type,
+                        float smoothing_weight, float oks_weight, float gaussian_weight, float loss_weight, int B,
+                        int K, int H, int W, float *per_pixel, float *per_keypoint, float *parts, float *scalars,
+                        void *stream);
+int pp_probpose_loss_terms(const double *gt_kpts, const double *dt_kpts, const int *in_image, const int *annotated,
+                           const int *visibility, const float *dt_prob, const float *dt_vis, const float *dt_oks,
+                           const float *dt_err, const double *variance, double oks_area, int B, int K,
+                           int freeze_error, float *gt_oks, float *gt_err, float *vis_weight, float *oks_weight,
+                           float *results, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

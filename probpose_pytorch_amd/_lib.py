@@ -76,6 +76,9 @@ _SIGNATURES = {
     "pp_frontend_plan_bytes": (C.c_longlong, [_i, _vp, _i, _i]),
     "pp_frontend_plan_build": (C.c_int, [_i, _vp, _i, _i, _vp, C.POINTER(C.c_int), C.POINTER(C.c_longlong)]),
     "pp_frontend_crop_resize": (C.c_int, [_vp, _i, _i, C.c_longlong, _vp, _i, _i, C.c_longlong, _i, _i, _vp, _vp]),
+    "pp_oks_heatmap_loss": (C.c_int, [_vp, _vp, _vp, _i, _vp, C.c_longlong, C.c_longlong, _i, _i] + [_f] * 4
+                            + [_i] * 4 + [_vp] * 5),
+    "pp_probpose_loss_terms": (C.c_int, [_vp] * 10 + [_d, _i, _i, _i] + [_vp] * 6),
 }
 EXPORTS = tuple(_SIGNATURES)
 

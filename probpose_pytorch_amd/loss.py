@@ -1,0 +1,362 @@
+"""The reference's ``probpose/loss.py`` (loss.py:18-712) for device tensors, forward only.
+
+* ``OKSHeatmapLoss`` runs ``pp_oks_heatmap_loss`` (csrc/pp_loss.hip): oks term, MSE term and Sobel gradient energy of
+  every pixel, their masks and the three reductions in one pass over the heatmaps (two launches).
+* ``BCELoss`` / ``MSELoss`` / ``L1LogLoss`` on their own are the reference's few torch ops on the device.
+* ``ProbPoseLoss`` decodes the gt and dt heatmap batches with ``codec.probmap.decode_device`` (one launch each, where
+  the reference copies both stacks to the host and decodes them crop by crop), runs the heatmap loss on them and gets
+  every B*K term -- the per-keypoint OKS and error targets, the visibility weights, the four small losses and the MAE
+  accuracies -- from one ``pp_probpose_loss_terms`` launch.  One small D2H brings back the scalars and the flags the
+  reference would raise on.  ``compute_acc`` adds the arg-max PCK of ``metrics.pose_pck_accuracy`` and the balanced
+  binary accuracies, which draw from numpy's global RNG exactly as the reference does (only B*K values leave the
+  device for them).
+
+The repo's model is forward-only HIP, so nothing here produces a gradient: a ``pred`` tensor that requires grad while
+grad mode is on is refused.  The evaluation metrics the reference keeps in the same file (loss.py:715-866) are
+re-exported from ``metrics`` as the same objects.
+"""
+from __future__ import annotations
+
+from functools import partial
+from typing import Sequence
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+from torch import Tensor, nn
+
+from . import _lib
+from .metrics import (compute_oks, get_heatmap_expected_value, get_heatmap_maximum,  # noqa: F401
+                      keypoint_pck_accuracy, oks_batch, pck_counts, pose_pck_accuracy, pose_pck_accuracy_expected)
+from .util import to_numpy
+
+__all__ = ["OKSHeatmapLoss", "BCELoss", "MSELoss", "L1LogLoss", "ProbPoseLoss", "compute_oks", "oks_batch",
+           "pck_counts", "keypoint_pck_accuracy", "pose_pck_accuracy", "pose_pck_accuracy_expected",
+           "get_heatmap_maximum", "get_heatmap_expected_value"]
+
+_OKS_TYPES = {"minus": 0, "plus": 1, "both": 2}
+# flags of pp_probpose_loss_terms (include/probpose_hip.h)
+_FLAG_NO_ANNOTATED, _FLAG_NAN_ERROR, _FLAG_BCE_RANGE = 1, 2, 4
+
+
+def _refuse_grad(*tensors) -> None:
+    if torch.is_grad_enabled() and any(isinstance(t, Tensor) and t.requires_grad for t in tensors):
+        raise RuntimeError("the ProbPose losses run forward only (HIP kernels, no backward): an input requires grad; "
+                           "call them under torch.no_grad() or pass detached tensors")
+
+
+def _f32(t: Tensor, device) -> Tensor:
+    t = torch.as_tensor(t)
+    return t.detach().to(device=device, dtype=torch.float32).contiguous()
+
+
+def _oks_heatmap_loss(output, target, weights, mask, skip_empty, oks_type, sw, gw, lw, per_pixel_out,
+                      per_keypoint_out, scalars):
+    """Launch pp_oks_heatmap_loss; the caller checks scalars[2] (target elements outside [0, 1])."""
+    B, K, H, W = output.shape
+    dev = output.device
+    per_pixel_weights = 0
+    if weights is not None:
+        per_pixel_weights = int(weights.ndim == 4)
+    mask_sb = mask_sk = 0
+    if mask is not None:
+        mb, mk = mask.shape[0], mask.shape[1]
+        mask_sb = 0 if mb == 1 else mk * H * W
+        mask_sk = 0 if mk == 1 else H * W
+    parts = torch.empty((B * K * 5,), dtype=torch.float32, device=dev)
+    ow = 1.0 - sw - gw
+    with torch.cuda.device(dev):
+        rc = _lib.lib().pp_oks_heatmap_loss(
+            _lib.ptr(output), _lib.ptr(target), _lib.ptr(weights), per_pixel_weights, _lib.ptr(mask), mask_sb,
+            mask_sk, int(bool(skip_empty)), _OKS_TYPES[oks_type], float(sw), float(ow), float(gw), float(lw),
+            B, K, H, W, _lib.ptr(per_pixel_out), _lib.ptr(per_keypoint_out), _lib.ptr(parts), _lib.ptr(scalars),
+            _lib.stream_ptr())
+    _lib.check(rc, "pp_oks_heatmap_loss")
+    return parts
+
+
+class OKSHeatmapLoss(nn.Module):
+    """Reference loss.py:18-191: expected-OKS heatmap loss plus Sobel smoothness and MSE terms, on the GPU."""
+
+    def __init__(self, use_target_weight: bool = False, skip_empty_channel: bool = False,
+                 smoothing_weight: float = 0.2, gaussian_weight: float = 0.0, loss_weight: float = 1.,
+                 oks_type: str = "minus"):
+        super().__init__()
+        self.use_target_weight = use_target_weight
+        self.skip_empty_channel = skip_empty_channel
+        self.loss_weight = loss_weight
+        self.smoothing_weight = smoothing_weight
+        self.gaussian_weight = gaussian_weight
+        self.oks_type = oks_type.lower()
+        assert self.oks_type in ["minus", "plus", "both"]
+
+    def _operands(self, output, target, target_weights, mask):
+        _lib.require_device(output)
+        assert output.ndim == 4 and target.shape == output.shape, \
+            f"output and target shapes differ: {tuple(output.shape)} v.s. {tuple(target.shape)}"
+        dev = output.device
+        out, tgt = _f32(output, dev), _f32(target, dev)
+        B, K, H, W = out.shape
+        if mask is not None:     # loss.py:155-161
+            mask = torch.as_tensor(mask)
+            assert (mask.ndim == tgt.ndim and all(d_m == d_t or d_m == 1 for d_m, d_t in zip(mask.shape, tgt.shape))), (
+                f'mask and target have mismatched shapes {mask.shape} v.s.{tgt.shape}')
+            mask = _f32(mask, dev)
+            if tuple(mask.shape[2:]) != (H, W):
+                mask = mask.expand(mask.shape[0], mask.shape[1], H, W).contiguous()
+        if target_weights is not None:     # loss.py:164-169
+            target_weights = torch.as_tensor(target_weights)
+            assert (target_weights.ndim in (2, 4) and target_weights.shape == tgt.shape[:target_weights.ndim]), (
+                'target_weights and target have mismatched shapes '
+                f'{target_weights.shape} v.s. {tgt.shape}')
+            target_weights = _f32(target_weights, dev)
+        return out, tgt, target_weights, mask
+
+    def forward(self, output: Tensor, target: Tensor, target_weights: Tensor | None = None,
+                mask: Tensor | None = None, per_pixel: bool = False, per_keypoint: bool = False) -> Tensor:
+        """loss.py:55-143.  Per-pixel map [B,K,H,W], per-keypoint loss [B,K] or the scalar mean (0-d)."""
+        _refuse_grad(output, target, target_weights, mask)
+        out, tgt, wts, msk = self._operands(output, target, target_weights, mask)
+        B, K, H, W = out.shape
+        scalars = torch.empty((3,), dtype=torch.float32, device=out.device)
+        pix = torch.empty_like(out) if per_pixel else None
+        kp = torch.empty((B, K), dtype=torch.float32, device=out.device) if (per_keypoint and not per_pixel) else None
+        _oks_heatmap_loss(out, tgt, wts, msk, self.skip_empty_channel, self.oks_type, self.smoothing_weight,
+                          self.gaussian_weight, self.loss_weight, pix, kp, scalars)
+        assert float(scalars[2]) == 0, 'target should be normalized'
+        if per_pixel:
+            return pix
+        if per_keypoint:
+            return kp
+        return scalars[0]
+
+
+class BCELoss(nn.Module):
+    """Reference loss.py:194-260.  ``use_sigmoid=True`` means the inputs are probabilities (F.binary_cross_entropy),
+    otherwise logits (F.binary_cross_entropy_with_logits)."""
+
+    def __init__(self, use_target_weight=False, loss_weight=1.0, reduction="mean", use_sigmoid=False):
+        super().__init__()
+        assert reduction in ("mean", "sum", "none"), (
+            f"the argument `reduction` should be either 'mean', 'sum' or 'none', but got {reduction}")
+        self.reduction = reduction
+        self.use_sigmoid = use_sigmoid
+        criterion = F.binary_cross_entropy if use_sigmoid else F.binary_cross_entropy_with_logits
+        self.criterion = partial(criterion, reduction="none")
+        self.use_target_weight = use_target_weight
+        self.loss_weight = loss_weight
+
+    def forward(self, output, target, target_weight=None):
+        _refuse_grad(output, target, target_weight)
+        _lib.require_device(output)
+        loss = self.criterion(output, target)
+        if self.use_target_weight:
+            assert target_weight is not None
+            if target_weight.dim() == 1:
+                target_weight = target_weight[:, None]
+            loss = loss * target_weight
+        if self.reduction == "sum":
+            loss = loss.sum()
+        elif self.reduction == "mean":
+            loss = loss.mean()
+        return loss * self.loss_weight
+
+
+class MSELoss(nn.Module):
+    """Reference loss.py:263-292.  With weights both operands are multiplied by them and the mean runs over every
+    entry, masked zeros included."""
+
+    def __init__(self, use_target_weight=False, loss_weight=1.0):
+        super().__init__()
+        self.criterion = F.mse_loss
+        self.use_target_weight = use_target_weight
+        self.loss_weight = loss_weight
+
+    def forward(self, output, target, target_weight=None):
+        _refuse_grad(output, target, target_weight)
+        _lib.require_device(output)
+        if self.use_target_weight:
+            assert target_weight is not None
+            loss = self.criterion(output * target_weight, target * target_weight)
+        else:
+            loss = self.criterion(output, target)
+        return loss * self.loss_weight
+
+
+class L1LogLoss(nn.Module):
+    """Reference loss.py:295-339: smooth-L1 (beta 1) between log(1 + x) of both operands -- ``log(1 + x)`` as
+    written, not ``log1p``."""
+
+    def __init__(self, use_target_weight=False, loss_weight=1.0):
+        super().__init__()
+        self.criterion = F.smooth_l1_loss
+        self.use_target_weight = use_target_weight
+        self.loss_weight = loss_weight
+
+    def forward(self, output, target, target_weight=None):
+        _refuse_grad(output, target, target_weight)
+        _lib.require_device(output)
+        output = torch.log(1 + output)
+        target = torch.log(1 + target)
+        if self.use_target_weight:
+            assert target_weight is not None
+            assert output.ndim >= target_weight.ndim
+            for _ in range(output.ndim - target_weight.ndim):
+                target_weight = target_weight.unsqueeze(-1)
+            loss = self.criterion(output * target_weight, target * target_weight)
+        else:
+            loss = self.criterion(output, target)
+        return loss * self.loss_weight
+
+
+def _host_int(x, B: int, C: int) -> np.ndarray:
+    """A (B,1,C) / (B,C) mask (numpy, host or device tensor) -> int64 (B,C) like the reference's ``.to(int)``."""
+    t = x.detach().cpu() if isinstance(x, Tensor) else torch.as_tensor(np.asarray(x))
+    return t.to(torch.int64).reshape(B, C).numpy()
+
+
+def _binary_accuracy(dt: np.ndarray, gt: np.ndarray, mask: np.ndarray, device, force_balanced=False):
+    """loss.py:653-697 on host copies of B*K values: the same numpy calls in the same order, so the same draws
+    from numpy's global RNG."""
+    assert dt.shape == gt.shape
+    dt = dt[mask]
+    gt = gt[mask]
+    gt = gt.astype(bool)
+    if force_balanced:
+        pos_num = np.sum(gt)
+        neg_num = len(gt) - pos_num
+        num = min(pos_num, neg_num)
+        if num == 0:
+            return torch.tensor([0.0], device=device), torch.tensor([0.0], device=device)
+        pos_idx = np.where(gt)[0]
+        neg_idx = np.where(~gt)[0]
+        np.random.shuffle(pos_idx)
+        np.random.shuffle(neg_idx)
+        idx = np.concatenate([pos_idx[:num], neg_idx[:num]])
+        dt = dt[idx]
+        gt = gt[idx]
+    n_samples = len(gt)
+    thresholds = np.arange(0.1, 1.0, 0.05)
+    preds = dt[:, None] > thresholds
+    correct = preds == gt[:, None]
+    counts = correct.sum(axis=0)
+    best_idx = np.argmax(counts)
+    best_threshold = thresholds[best_idx]
+    best_acc = counts[best_idx] / n_samples
+    return (torch.tensor(best_acc, device=device).float(), torch.tensor(best_threshold, device=device).float())
+
+
+class ProbPoseLoss(nn.Module):
+    """Reference loss.py:342-712 (forward only): the five per-head losses of the validation loop and, with
+    ``compute_acc``, the five accuracies."""
+
+    def __init__(self, codec, freeze_error: bool = True):
+        super().__init__()
+        self.codec = codec
+        self.keypoint_loss_module = OKSHeatmapLoss(use_target_weight=True, smoothing_weight=0.05, oks_type="minus")
+        self.probability_loss_module = BCELoss(use_target_weight=False, use_sigmoid=True)
+        self.visibility_loss_module = BCELoss(use_target_weight=False, use_sigmoid=True)
+        self.oks_loss_module = MSELoss(use_target_weight=True)
+        self.error_loss_module = L1LogLoss(use_target_weight=True)
+        self.freeze_error = freeze_error
+        self.freeze_oks = False
+        self._variance = {}
+
+    def _device_variance(self, K, dev):
+        sig = np.asarray(self.codec.probmap.sigmas)
+        key = (str(dev), sig.dtype.str, sig.tobytes())
+        v = self._variance.get(key)
+        if v is None:
+            v = torch.from_numpy(np.ascontiguousarray((sig * 2) ** 2, dtype=np.float64)).to(dev)   # compute_oks :716
+            self._variance = {key: v}
+        if v.numel() != K:
+            raise ValueError(f"{K} keypoints but {v.numel()} sigmas")
+        return v
+
+    def terms(self, gt, pred, keypoint_weights=None, learn_heatmaps_from_zeros: bool = False) -> dict:
+        """Every device-side quantity of one forward: the decodes (gt_kpts, dt_kpts), the B*K targets (gt_oks,
+        gt_err, vis_weight, oks_weight), ``res`` = the 11 scalars of both kernels, and the host int masks."""
+        if self.freeze_oks:
+            raise NotImplementedError("freeze_oks is not supported (the reference never sets it)")
+        dt_heatmaps, dt_probs, dt_vis, dt_oks, dt_errs = pred
+        _refuse_grad(*pred)
+        _lib.require_device(dt_heatmaps)
+        dev = dt_heatmaps.device
+        B, C, H, W = dt_heatmaps.shape
+        hm = _f32(dt_heatmaps, dev)
+        gt_hm = _f32(gt["heatmaps"], dev).view(B, C, H, W)
+        probs = _host_int(gt["in_image"], B, C)
+        annotated = _host_int(gt["keypoints_visible"], B, C)
+        vis = _host_int(gt["keypoints_visibility"], B, C)
+        masks = torch.from_numpy(np.stack([probs, annotated, vis]).astype(np.int32)).to(dev)
+        if keypoint_weights is None:
+            kw = torch.ones((B, C), device=dev, dtype=torch.float32)
+        else:
+            kw = _f32(keypoint_weights, dev).view(B, C)
+        heads = []
+        for t in (dt_probs, dt_vis, dt_oks, dt_errs):
+            t = _f32(t, dev).view(-1)
+            if t.numel() != B * C:
+                raise ValueError(f"scalar heads must hold B*K = {B * C} values, got {t.numel()}")
+            heads.append(t)
+        # both decodes on the whole batch, no heatmap leaves the device (loss.py:574-585 decodes crop by crop)
+        gt_kpts = self.codec.probmap.decode_device(gt_hm)["kpts"]
+        dt_kpts = self.codec.probmap.decode_device(hm)["kpts"]
+        res = torch.empty((11,), dtype=torch.float32, device=dev)
+        heat_weights = masks[1].float() if learn_heatmaps_from_zeros else kw     # loss.py:423-426
+        km = self.keypoint_loss_module
+        _oks_heatmap_loss(hm, gt_hm, heat_weights, None, km.skip_empty_channel, km.oks_type, km.smoothing_weight,
+                          km.gaussian_weight, km.loss_weight, None, None, res[0:3])
+        gt_oks = torch.empty((B, C), dtype=torch.float32, device=dev)
+        gt_err = torch.empty((B, C), dtype=torch.float32, device=dev)
+        vis_weight = torch.empty((B, C), dtype=torch.float32, device=dev)
+        oks_weight = torch.empty((B,), dtype=torch.float32, device=dev)
+        oks_area = (W * H) * 0.53 + np.spacing(1)    # bbox [0, 0, H, W] from heatmap_size=(W, H) (loss.py:395, :609-620)
+        var = self._device_variance(C, dev)
+        with torch.cuda.device(dev):
+            rc = _lib.lib().pp_probpose_loss_terms(
+                _lib.ptr(gt_kpts), _lib.ptr(dt_kpts), _lib.ptr(masks[0]), _lib.ptr(masks[1]), _lib.ptr(masks[2]),
+                *[_lib.ptr(t) for t in heads], _lib.ptr(var), float(oks_area), B, C, int(bool(self.freeze_error)),
+                _lib.ptr(gt_oks), _lib.ptr(gt_err), _lib.ptr(vis_weight), _lib.ptr(oks_weight), _lib.ptr(res[3:]),
+                _lib.stream_ptr())
+        _lib.check(rc, "pp_probpose_loss_terms")
+        return dict(hm=hm, gt_hm=gt_hm, kw=kw, heads=heads, gt_kpts=gt_kpts, dt_kpts=dt_kpts, gt_oks=gt_oks,
+                    gt_err=gt_err, vis_weight=vis_weight, oks_weight=oks_weight, res=res, probs=probs,
+                    annotated=annotated, vis=vis)
+
+    def forward(self, gt, pred: Sequence[Tensor], keypoint_weights: Tensor | None = None,
+                learn_heatmaps_from_zeros: bool = False, compute_acc: bool = False):
+        """loss.py:360-510: ``losses`` (kpt, probability, visibility, oks, error), and ``(losses, accs)`` with
+        ``compute_acc``; 0-d device tensors."""
+        T = self.terms(gt, pred, keypoint_weights, learn_heatmaps_from_zeros)
+        res = T["res"]
+        host = res.cpu().numpy()          # the one sync: the scalars the reference would raise on
+        flags = int(host[9])
+        if flags & _FLAG_NAN_ERROR:
+            raise AssertionError("Euclidean distance cannot be negative")
+        if host[2] != 0:
+            raise AssertionError('target should be normalized')
+        if flags & _FLAG_BCE_RANGE:
+            raise RuntimeError("all elements of input should be between 0 and 1")
+        if flags & _FLAG_NO_ANNOTATED:
+            raise RuntimeError("min(): Expected reduction dim to be specified for input.numel() == 0 "
+                               "(loss.py:448: the batch has no annotated keypoint)")
+        losses = dict(kpt=res[1], probability=res[3], visibility=res[4], oks=res[5], error=res[6])
+        if not compute_acc:
+            return losses
+        dev = res.device
+        _, avg_acc, _ = pose_pck_accuracy(T["hm"], T["gt_hm"], T["kw"] > 0.5, method="argmax")    # loss.py:642-651
+        acc_pose = torch.tensor(avg_acc, device=dev)
+        small = torch.stack([T["heads"][0], T["heads"][1]]).cpu().numpy()
+        B, C = T["probs"].shape
+        dt_probs, dt_vis = small[0].reshape(B, C), small[1].reshape(B, C)
+        annotated_in = T["annotated"] & (T["probs"] > 0.5)
+        acc_prob, _ = _binary_accuracy(dt_probs, T["probs"], T["annotated"] > 0.5, dev, force_balanced=True)
+        acc_vis, _ = _binary_accuracy(dt_vis, T["vis"], annotated_in > 0.5, dev, force_balanced=True)
+        return losses, {"kpt": acc_pose, "probability": acc_prob, "visibility": acc_vis, "oks": res[7],
+                        "error": res[8]}
+
+    def get_binary_accuracy(self, dt, gt, mask, force_balanced=False):
+        """loss.py:653-697."""
+        device = gt.device if isinstance(gt, Tensor) else None
+        return _binary_accuracy(to_numpy(dt), to_numpy(gt), to_numpy(mask), device, force_balanced)
