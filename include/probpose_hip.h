@@ -345,6 +345,47 @@ int pp_probpose_loss_terms(const double *gt_kpts, const double *dt_kpts, const i
                            int freeze_error, float *gt_oks, float *gt_err, float *vis_weight, float *oks_weight,
                            float *results, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Training loss gradients.  Differentiate
+ *   OKSHeatmapLoss.forward  probpose/loss.py:55-143  (pp_oks_heatmap_loss_backward, all three reductions)
+ *   BCELoss / MSELoss / L1LogLoss as ProbPoseLoss.forward uses them, loss.py:232-339 and :419-464
+ *                                                     (pp_probpose_loss_grads)
+ * The targets (the gt heatmaps, the OKS and error targets from detached decodes), weights and masks are constants:
+ * no gradient flows to them.  Deterministic: no float atomics, fixed-order sums.
+ *
+ * pp_oks_heatmap_loss_backward: output, target, weights, weights_per_pixel, mask and its strides, skip_empty,
+ * oks_type, the three weights and loss_weight exactly as pp_oks_heatmap_loss.  reduction 0 = per pixel: the upstream
+ * gradient G [B,K,H,W] at grad + b * grad_sb + k * grad_sk + r * grad_sh + c * grad_sw (element strides, 0
+ * broadcasts); 1 = per keypoint: G [B,K] at grad + b * grad_sb + k * grad_sk; 2 = the scalar mean: G = grad[0];
+ * 3 = the mean of the per-pixel loss (ProbPoseLoss's heatmap_loss_pxl.mean(), loss.py:427-431): G = grad[0].  The
+ * upstream gradient is read on the device.  Output grad_output [B,K,H,W] f32, every element written:
+ *   d/dh[q] = sum_p G[p] lw sw m[p] 2 (gx[p] Sx(q-p) + gy[p] Sy(q-p)) + G[q] lw m[q] (ow d oks/dh + gw 2 (h - t))
+ * with p over the 3x3 neighbours of q inside the map (the per-pixel reductions).  The per-keypoint and mean reductions
+ * take the max-gradient subgradient at the first maximal pixel of the masked energy in row-major order (a NaN counts
+ * as the maximum), as torch's max(dim) does, and divide the mse term by H*W.  One launch, one workgroup per map.
+ *
+ * pp_probpose_loss_grads: dt_prob / dt_vis / dt_oks / dt_err [B*K] f32 predictions; gt_oks / gt_err [B*K] f32 the
+ * targets pp_probpose_loss_terms wrote; in_image / annotated / visibility [B*K] int32 as there; u_prob, u_vis, u_oks,
+ * u_err: the upstream gradients of results[0..3] of pp_probpose_loss_terms, one float each on the device.  Outputs
+ * d_prob, d_vis, d_oks, d_err [B*K] f32: with N = B*K, g = u / N and w = annotated & in_image,
+ *   BCE (probability vs in_image, visibility vs visibility): g (x - y) / max((1 - x) x, 1e-12)
+ *   MSE (oks, weighted):                                    2 w (x w - y w) g
+ *   L1Log (error, weighted):                                clamp(z, -1, 1) g w / (1 + x), z = (log(1 + x) - log(1 + y)) w
+ * with 1 + x rounded to float32 (the reference's log(1 + x)).  The visibility BCE takes no weights: the reference's
+ * BCELoss(use_target_weight=False) ignores the visibility weights it is handed.  One launch.
+ * ---------------------------------------------------------------------- */
+int pp_oks_heatmap_loss_backward(const float *output, const float *target, const float *weights, int weights_per_pixel,
+                                 const float *mask, long long mask_sb, long long mask_sk, int skip_empty, int oks_type,
+                                 float smoothing_weight, float oks_weight, float gaussian_weight, float loss_weight,
+                                 int reduction, const float *grad, long long grad_sb, long long grad_sk,
+                                 long long grad_sh, long long grad_sw, int B, int K, int H, int W, float *grad_output,
+                                 void *stream);
+int pp_probpose_loss_grads(const float *dt_prob, const float *dt_vis, const float *dt_oks, const float *dt_err,
+                           const float *gt_oks, const float *gt_err, const int *in_image, const int *annotated,
+                           const int *visibility, const float *u_prob, const float *u_vis, const float *u_oks,
+                           const float *u_err, int B, int K, float *d_prob, float *d_vis, float *d_oks, float *d_err,
+                           void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -79,6 +79,9 @@ _SIGNATURES = {
     "pp_oks_heatmap_loss": (C.c_int, [_vp, _vp, _vp, _i, _vp, C.c_longlong, C.c_longlong, _i, _i] + [_f] * 4
                             + [_i] * 4 + [_vp] * 5),
     "pp_probpose_loss_terms": (C.c_int, [_vp] * 10 + [_d, _i, _i, _i] + [_vp] * 6),
+    "pp_oks_heatmap_loss_backward": (C.c_int, [_vp, _vp, _vp, _i, _vp, C.c_longlong, C.c_longlong, _i, _i]
+                                     + [_f] * 4 + [_i, _vp] + [C.c_longlong] * 4 + [_i] * 4 + [_vp, _vp]),
+    "pp_probpose_loss_grads": (C.c_int, [_vp] * 13 + [_i, _i] + [_vp] * 5),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -1,4 +1,4 @@
-// The validation loss of the reference (loss.py:18-712) on the device, forward only.
+// The losses of the reference (loss.py:18-712) on the device, and their gradients.
 //
 // pp_oks_heatmap_loss   OKSHeatmapLoss.forward (loss.py:55-143): one workgroup per (crop, keypoint) map.  The map of
 //                       `output` is staged tile by tile in LDS with a one-pixel zero halo (the 'same' padding of the
@@ -11,6 +11,14 @@
 //                       _error_from_heatmaps (:512-548), the visibility weights (:436-450), the four small losses and
 //                       the two MAE accuracies (:699-712).  One workgroup: the batch-wide counts the visibility
 //                       weights need are block reductions, no second launch.
+//
+// pp_oks_heatmap_loss_backward   d/d output of the three OKSHeatmapLoss reductions for an arbitrary upstream gradient,
+//                       one workgroup per map.  Per pixel, the Sobel term reaches a pixel q from the 3x3 neighbours p of
+//                       q inside the map, and each needs gx[p], gy[p]: a tile stages `output` with a two-pixel zero halo,
+//                       forms G*m*gx and G*m*gy on the tile plus a one-pixel ring (zero where p lies outside the map),
+//                       then correlates them with the flipped Sobel kernels.  The per-keypoint and mean reductions put
+//                       the max-gradient subgradient at the first maximal pixel of the masked energy (torch's max(dim)).
+// pp_probpose_loss_grads d/d prediction of the four small losses of ProbPoseLoss (loss.py:419-464), elementwise.
 //
 // Every reduction has a fixed shape (fixed lane -> element assignment, xor-butterfly wave sums, waves combined in
 // order by one lane), and there are no float atomics: repeated calls return identical bits.
@@ -309,6 +317,240 @@ __global__ __launch_bounds__(LT_THREADS) void probpose_loss_terms_kernel(
   }
 }
 
+
+// ---------------------------------------------------------------------------------------------------- backward
+constexpr int HB_THREADS = 256;
+constexpr int HB_TILE_H = 3584;      // LDS floats of `output` incl. a two-pixel halo (14 KiB)
+constexpr int HB_TILE_E = 3328;      // LDS floats of each of G*m*gx, G*m*gy incl. a one-pixel ring (13 KiB)
+constexpr int HB_MAX_COLS = 256;     // tile width cap: 3584 / 260 - 4 = 9 rows still fit
+// reductions of pp_oks_heatmap_loss_backward (include/probpose_hip.h)
+constexpr int HB_PIXEL = 0, HB_KEYPOINT = 1, HB_MEAN = 2, HB_PIXEL_MEAN = 3;
+
+// cross-correlation kernels, [dr + 1][dc + 1]: gx[p] = sum_d SX[d] * h[p + d], so d gx[p] / d h[q] = SX[q - p]
+__constant__ float SOBEL_X[3][3] = {{1.0f, 0.0f, -1.0f}, {2.0f, 0.0f, -2.0f}, {1.0f, 0.0f, -1.0f}};
+__constant__ float SOBEL_Y[3][3] = {{1.0f, 2.0f, 1.0f}, {0.0f, 0.0f, 0.0f}, {-1.0f, -2.0f, -1.0f}};
+
+// (v1, i1) precedes (v2, i2) in torch's max(dim) order: a NaN beats any number, then the larger value, then the
+// earlier pixel
+__device__ __forceinline__ bool max_before(float v1, int i1, float v2, int i2) {
+  const bool n1 = v1 != v1, n2 = v2 != v2;
+  if (n1 != n2) return n1;
+  if (!n1 && v1 != v2) return v1 > v2;
+  return i1 < i2;
+}
+
+// d oks / d output of loss.py:92-101
+__device__ __forceinline__ float d_oks(int oks_type, float tv) {
+  if (oks_type == 0) return 1.0f - tv;
+  if (oks_type == 1) return -tv;
+  return ((1.0f - tv) - tv) / 2.0f;
+}
+
+// grad (per-pixel reductions): G at g + b * gs[0] + k * gs[1] + r * gs[2] + c * gs[3]; per keypoint: g + b * gs[0]
+// + k * gs[1]; mean and pixel mean: g[0].  n_maps = B * K.
+__global__ __launch_bounds__(HB_THREADS) void oks_heatmap_loss_backward_kernel(
+    const float *__restrict__ output, const float *__restrict__ target, const float *__restrict__ weights,
+    int weights_per_pixel, const float *__restrict__ mask, long long mask_sb, long long mask_sk, int skip_empty,
+    int oks_type, float sw, float ow, float gw, float lw, int reduction, const float *__restrict__ grad,
+    long long gs_b, long long gs_k, long long gs_h, long long gs_w, long long n_maps, int K, int H, int W,
+    int tile_rows, int tile_cols, float *__restrict__ grad_output) {
+  __shared__ float th[HB_TILE_H];
+  __shared__ float tex[HB_TILE_E], tey[HB_TILE_E];
+  __shared__ float rv[HB_THREADS / 64];
+  __shared__ int ri[HB_THREADS / 64];
+  __shared__ float star[2];
+  const long long map = blockIdx.x;
+  const int b = (int)(map / K), k = (int)(map - (long long)b * K);
+  const long long HW = (long long)H * W;
+  const float *o = output + map * HW, *t = target + map * HW;
+  float *dh = grad_output + map * HW;
+  const float *pw = (weights && weights_per_pixel) ? weights + map * HW : nullptr;
+  const float kw = (weights && !weights_per_pixel) ? weights[map] : 1.0f;
+  const float *sm = mask ? mask + b * mask_sb + k * mask_sk : nullptr;
+  float nonempty = 1.0f;
+  if (skip_empty) {
+    int any = 0;
+    for (long long i = threadIdx.x; i < HW && !any; i += HB_THREADS) any = t[i] != 0.0f;
+    nonempty = __syncthreads_or(any) ? 1.0f : 0.0f;
+  }
+  // the forward's mask, bit for bit (oks_heatmap_loss_kernel)
+  auto mask_at = [&](long long idx) {
+    float m = sm ? sm[idx] : 1.0f;
+    m = m * (pw ? pw[idx] : kw);
+    return m * nonempty;
+  };
+  const float sw2 = 2.0f * sw;
+
+  if (reduction == HB_PIXEL || reduction == HB_PIXEL_MEAN) {
+    const float *gm = grad + b * gs_b + k * gs_k;
+    const float gconst = reduction == HB_PIXEL_MEAN ? grad[0] / (float)((double)n_maps * (double)HW) : 0.0f;
+    auto g_at = [&](int r, int c) { return reduction == HB_PIXEL_MEAN ? gconst : gm[r * gs_h + c * gs_w]; };
+    for (int r0 = 0; r0 < H; r0 += tile_rows) {
+      const int br = min(tile_rows, H - r0);
+      for (int c0 = 0; c0 < W; c0 += tile_cols) {
+        const int bc = min(tile_cols, W - c0), ph = bc + 4, pe = bc + 2;
+        // output rows r0-2 .. r0+br+1, columns c0-2 .. c0+bc+1; zero outside the map (the forward's padding)
+        for (int i = threadIdx.x; i < (br + 4) * ph; i += HB_THREADS) {
+          const int r = r0 - 2 + i / ph, c = c0 - 2 + i % ph;
+          th[i] = (r >= 0 && r < H && c >= 0 && c < W) ? o[(long long)r * W + c] : 0.0f;
+        }
+        __syncthreads();
+        // G*lw*m*gx and G*lw*m*gy at p = rows r0-1 .. r0+br, columns c0-1 .. c0+bc: zero for p outside the map,
+        // whose energy the forward never forms
+        for (int i = threadIdx.x; i < (br + 2) * pe; i += HB_THREADS) {
+          const int rr = i / pe, cc = i - rr * pe, r = r0 - 1 + rr, c = c0 - 1 + cc;
+          float ex = 0.0f, ey = 0.0f;
+          if (r >= 0 && r < H && c >= 0 && c < W) {
+            const float *a = th + rr * ph + cc;        // a[dr * ph + dc]: output[r - 1 + dr][c - 1 + dc]
+            const float gx = (a[0] - a[2]) + 2.0f * (a[ph] - a[ph + 2]) + (a[2 * ph] - a[2 * ph + 2]);
+            const float gy = (a[0] + 2.0f * a[1] + a[2]) - (a[2 * ph] + 2.0f * a[2 * ph + 1] + a[2 * ph + 2]);
+            const float s = (g_at(r, c) * lw) * mask_at((long long)r * W + c);
+            ex = s * gx;
+            ey = s * gy;
+          }
+          tex[i] = ex;
+          tey[i] = ey;
+        }
+        __syncthreads();
+        for (int p = threadIdx.x; p < br * bc; p += HB_THREADS) {
+          const int r = p / bc, c = p - r * bc;
+          const long long idx = (long long)(r0 + r) * W + (c0 + c);
+          // sum over the neighbours p = q - d of SX[d] * ex[p] + SY[d] * ey[p]; the ring index of q is (r+1, c+1)
+          float acc = 0.0f;
+#pragma unroll
+          for (int dr = -1; dr <= 1; ++dr)
+#pragma unroll
+            for (int dc = -1; dc <= 1; ++dc) {
+              const int e = (r + 1 - dr) * pe + (c + 1 - dc);
+              acc += SOBEL_X[dr + 1][dc + 1] * tex[e];
+              acc += SOBEL_Y[dr + 1][dc + 1] * tey[e];
+            }
+          const float ov = th[(r + 2) * ph + (c + 2)], tv = t[idx];
+          const float s = (g_at(r0 + r, c0 + c) * lw) * mask_at(idx);
+          const float local = s * (ow * d_oks(oks_type, tv) + gw * (2.0f * (ov - tv)));
+          dh[idx] = local + sw2 * acc;
+        }
+        __syncthreads();
+      }
+    }
+    return;
+  }
+
+  // per keypoint / mean: a = d loss / d (that map's per-keypoint loss without lw) * lw
+  const float a = reduction == HB_KEYPOINT ? grad[b * gs_b + k * gs_k] * lw : (grad[0] * lw) / (float)n_maps;
+  // (1) the first maximal masked energy, computed exactly as the forward does
+  float best = -__builtin_inff();
+  int besti = 0x7fffffff;
+  for (int r0 = 0; r0 < H; r0 += tile_rows) {
+    const int br = min(tile_rows, H - r0);
+    for (int c0 = 0; c0 < W; c0 += tile_cols) {
+      const int bc = min(tile_cols, W - c0), pitch = bc + 2;
+      for (int i = threadIdx.x; i < (br + 2) * pitch; i += HB_THREADS) {
+        const int r = r0 - 1 + i / pitch, c = c0 - 1 + i % pitch;
+        th[i] = (r >= 0 && r < H && c >= 0 && c < W) ? o[(long long)r * W + c] : 0.0f;
+      }
+      __syncthreads();
+      for (int p = threadIdx.x; p < br * bc; p += HB_THREADS) {
+        const int r = p / bc, c = p - r * bc;
+        const long long idx = (long long)(r0 + r) * W + (c0 + c);
+        const float *q = th + r * pitch + c;
+        const float gx = (q[0] - q[2]) + 2.0f * (q[pitch] - q[pitch + 2]) + (q[2 * pitch] - q[2 * pitch + 2]);
+        const float gy = (q[0] + 2.0f * q[1] + q[2]) - (q[2 * pitch] + 2.0f * q[2 * pitch + 1] + q[2 * pitch + 2]);
+        float e = gx * gx + gy * gy;
+        e = e * mask_at(idx);
+        if (max_before(e, (int)idx, best, besti)) {
+          best = e;
+          besti = (int)idx;
+        }
+      }
+      __syncthreads();
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const float v = __shfl_xor(best, off, 64);
+    const int i = __shfl_xor(besti, off, 64);
+    if (max_before(v, i, best, besti)) {
+      best = v;
+      besti = i;
+    }
+  }
+  if ((threadIdx.x & 63) == 0) {
+    rv[threadIdx.x >> 6] = best;
+    ri[threadIdx.x >> 6] = besti;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < HB_THREADS / 64; ++w)
+      if (max_before(rv[w], ri[w], rv[0], ri[0])) {
+        rv[0] = rv[w];
+        ri[0] = ri[w];
+      }
+    // gx, gy at the maximum p*, scaled by a * m[p*] * 2 sw
+    const int pr = ri[0] / W, pc = ri[0] - pr * W;
+    auto at = [&](int r, int c) { return (r >= 0 && r < H && c >= 0 && c < W) ? o[(long long)r * W + c] : 0.0f; };
+    const float a00 = at(pr - 1, pc - 1), a01 = at(pr - 1, pc), a02 = at(pr - 1, pc + 1), a10 = at(pr, pc - 1),
+                a12 = at(pr, pc + 1), a20 = at(pr + 1, pc - 1), a21 = at(pr + 1, pc), a22 = at(pr + 1, pc + 1);
+    const float gx = (a00 - a02) + 2.0f * (a10 - a12) + (a20 - a22);
+    const float gy = (a00 + 2.0f * a01 + a02) - (a20 + 2.0f * a21 + a22);
+    const float s = (a * mask_at(ri[0])) * sw2;
+    star[0] = s * gx;
+    star[1] = s * gy;
+  }
+  __syncthreads();
+  const int pstar = ri[0], pr = pstar / W, pc = pstar - pr * W;
+  const float sx = star[0], sy = star[1];
+  const float inv_hw = 2.0f / (float)HW;
+  // (2) every pixel: the oks and mse terms, plus the Sobel term on the 3x3 neighbours of p* inside the map
+  for (long long idx = threadIdx.x; idx < HW; idx += HB_THREADS) {
+    const float ov = o[idx], tv = t[idx];
+    const float s = a * mask_at(idx);
+    float v = s * (ow * d_oks(oks_type, tv) + gw * ((ov - tv) * inv_hw));
+    const int r = (int)(idx / W), c = (int)(idx - (long long)r * W), dr = r - pr, dc = c - pc;
+    if (dr >= -1 && dr <= 1 && dc >= -1 && dc <= 1)
+      v = v + (sx * SOBEL_X[dr + 1][dc + 1] + sy * SOBEL_Y[dr + 1][dc + 1]);
+    dh[idx] = v;
+  }
+}
+
+// torch's backward of the four small losses of ProbPoseLoss.forward, each a mean over the N = B*K keypoints:
+//   probability / visibility  binary_cross_entropy (ATen): g * (x - y) / max((1 - x) x, 1e-12)
+//   oks                       mse_loss of (x w, y w):      2 (x w - y w) g * w
+//   error                     smooth_l1 of (log(1 + x) w, log(1 + y) w), beta 1: clamp(z, -1, 1) g * w / (1 + x)
+// with g = upstream / N and w = annotated & in_image.  The visibility BCE is unweighted, as in the reference
+// (BCELoss(use_target_weight=False) ignores the visibility weights it is passed, loss.py:452-454).
+__global__ __launch_bounds__(256) void probpose_loss_grads_kernel(
+    const float *__restrict__ dt_prob, const float *__restrict__ dt_vis, const float *__restrict__ dt_oks,
+    const float *__restrict__ dt_err, const float *__restrict__ gt_oks, const float *__restrict__ gt_err,
+    const int *__restrict__ in_image, const int *__restrict__ annotated, const int *__restrict__ visibility,
+    const float *__restrict__ u_prob, const float *__restrict__ u_vis, const float *__restrict__ u_oks,
+    const float *__restrict__ u_err, long long N, float *__restrict__ d_prob, float *__restrict__ d_vis,
+    float *__restrict__ d_oks, float *__restrict__ d_err) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  const float n = (float)N;
+  const float ai = (float)(annotated[i] & (in_image[i] > 0));
+  {
+    const float x = dt_prob[i], y = (float)in_image[i];
+    d_prob[i] = ((u_prob[0] / n) * (x - y)) / fmaxf((1.0f - x) * x, 1e-12f);
+  }
+  {
+    const float x = dt_vis[i], y = (float)visibility[i];
+    d_vis[i] = ((u_vis[0] / n) * (x - y)) / fmaxf((1.0f - x) * x, 1e-12f);
+  }
+  {
+    const float x = dt_oks[i], y = gt_oks[i];
+    d_oks[i] = ((2.0f * (x * ai - y * ai)) * (u_oks[0] / n)) * ai;
+  }
+  {
+    const float x = dt_err[i], y = gt_err[i];
+    const float x1 = 1.0f + x;                 // rounded to float32, as torch.log(1 + x) sees it
+    const float z = logf(x1) * ai - logf(1.0f + y) * ai;
+    const float s = z < -1.0f ? -1.0f : (z > 1.0f ? 1.0f : z);
+    d_err[i] = ((s * (u_err[0] / n)) * ai) / x1;
+  }
+}
+
 }  // namespace pp
 
 extern "C" int pp_oks_heatmap_loss(const float *output, const float *target, const float *weights,
@@ -354,5 +596,57 @@ extern "C" int pp_probpose_loss_terms(const double *gt_kpts, const double *dt_kp
                      in_image, annotated, visibility, dt_prob, dt_vis, dt_oks, dt_err, variance, oks_area, B, K,
                      freeze_error, gt_oks, gt_err, vis_weight, oks_weight, results);
   PP_CHECK_LAUNCH("probpose_loss_terms_kernel");
+  return 0;
+}
+
+extern "C" int pp_oks_heatmap_loss_backward(const float *output, const float *target, const float *weights,
+                                            int weights_per_pixel, const float *mask, long long mask_sb,
+                                            long long mask_sk, int skip_empty, int oks_type, float smoothing_weight,
+                                            float oks_weight, float gaussian_weight, float loss_weight, int reduction,
+                                            const float *grad, long long grad_sb, long long grad_sk,
+                                            long long grad_sh, long long grad_sw, int B, int K, int H, int W,
+                                            float *grad_output, void *stream) {
+  using namespace pp;
+  PP_REQUIRE(B > 0 && K > 0 && H > 0 && W > 0, "pp_oks_heatmap_loss_backward: bad shape B=%d K=%d H=%d W=%d", B, K,
+             H, W);
+  PP_REQUIRE((long long)B * K < (1ll << 31) && (long long)H * W < (1ll << 31),
+             "pp_oks_heatmap_loss_backward: too many maps or pixels");
+  PP_REQUIRE(oks_type >= 0 && oks_type <= 2,
+             "pp_oks_heatmap_loss_backward: oks_type %d is not minus (0), plus (1), both (2)", oks_type);
+  PP_REQUIRE(reduction >= HB_PIXEL && reduction <= HB_PIXEL_MEAN,
+             "pp_oks_heatmap_loss_backward: reduction %d is not pixel (0), keypoint (1), mean (2), pixel mean (3)",
+             reduction);
+  PP_REQUIRE(output && target && grad && grad_output, "pp_oks_heatmap_loss_backward: null operand");
+  PP_REQUIRE(mask_sb >= 0 && mask_sk >= 0 && grad_sb >= 0 && grad_sk >= 0 && grad_sh >= 0 && grad_sw >= 0,
+             "pp_oks_heatmap_loss_backward: negative stride");
+  const int cols = W < HB_MAX_COLS ? W : HB_MAX_COLS;
+  int rows = HB_TILE_H / (cols + 4) - 4;
+  const int rows_e = HB_TILE_E / (cols + 2) - 2;
+  rows = rows < rows_e ? rows : rows_e;
+  rows = rows < H ? rows : H;
+  hipLaunchKernelGGL(oks_heatmap_loss_backward_kernel, dim3((unsigned)(B * K)), dim3(HB_THREADS), 0,
+                     (hipStream_t)stream, output, target, weights, weights_per_pixel, mask, mask_sb, mask_sk,
+                     skip_empty, oks_type, smoothing_weight, oks_weight, gaussian_weight, loss_weight, reduction,
+                     grad, grad_sb, grad_sk, grad_sh, grad_sw, (long long)B * K, K, H, W, rows, cols, grad_output);
+  PP_CHECK_LAUNCH("oks_heatmap_loss_backward_kernel");
+  return 0;
+}
+
+extern "C" int pp_probpose_loss_grads(const float *dt_prob, const float *dt_vis, const float *dt_oks,
+                                      const float *dt_err, const float *gt_oks, const float *gt_err,
+                                      const int *in_image, const int *annotated, const int *visibility,
+                                      const float *u_prob, const float *u_vis, const float *u_oks, const float *u_err,
+                                      int B, int K, float *d_prob, float *d_vis, float *d_oks, float *d_err,
+                                      void *stream) {
+  using namespace pp;
+  PP_REQUIRE(B > 0 && K > 0 && (long long)B * K < (1ll << 31), "pp_probpose_loss_grads: bad shape B=%d K=%d", B, K);
+  PP_REQUIRE(dt_prob && dt_vis && dt_oks && dt_err && gt_oks && gt_err && in_image && annotated && visibility &&
+                 u_prob && u_vis && u_oks && u_err && d_prob && d_vis && d_oks && d_err,
+             "pp_probpose_loss_grads: null operand");
+  const long long N = (long long)B * K;
+  hipLaunchKernelGGL(probpose_loss_grads_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     dt_prob, dt_vis, dt_oks, dt_err, gt_oks, gt_err, in_image, annotated, visibility, u_prob, u_vis,
+                     u_oks, u_err, N, d_prob, d_vis, d_oks, d_err);
+  PP_CHECK_LAUNCH("probpose_loss_grads_kernel");
   return 0;
 }

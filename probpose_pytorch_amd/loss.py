@@ -1,4 +1,4 @@
-"""The reference's ``probpose/loss.py`` (loss.py:18-712) for device tensors, forward only.
+"""The reference's ``probpose/loss.py`` (loss.py:18-712) for device tensors, with HIP backward kernels.
 
 * ``OKSHeatmapLoss`` runs ``pp_oks_heatmap_loss`` (csrc/pp_loss.hip): oks term, MSE term and Sobel gradient energy of
   every pixel, their masks and the three reductions in one pass over the heatmaps (two launches).
@@ -11,8 +11,13 @@
   binary accuracies, which draw from numpy's global RNG exactly as the reference does (only B*K values leave the
   device for them).
 
-The repo's model is forward-only HIP, so nothing here produces a gradient: a ``pred`` tensor that requires grad while
-grad mode is on is refused.  The evaluation metrics the reference keeps in the same file (loss.py:715-866) are
+By default the losses are forward only: a ``pred`` tensor that requires grad while grad mode is on is refused.  With
+``differentiable=True`` they carry a gradient to the predictions (a torch model trained on ROCm, as in the reference's
+train.py): ``OKSHeatmapLoss`` and ``ProbPoseLoss`` are ``torch.autograd.Function``s whose backward runs
+``pp_oks_heatmap_loss_backward`` and ``pp_probpose_loss_grads`` without a host sync; ``BCELoss`` / ``MSELoss`` /
+``L1LogLoss`` are torch ops and simply stop refusing.  The targets, weights and masks are constants, as in the reference
+(its targets come from detached decodes): one that requires grad is refused.  Without grad, ``differentiable=True`` runs
+exactly the forward-only path.  The evaluation metrics the reference keeps in the same file (loss.py:715-866) are
 re-exported from ``metrics`` as the same objects.
 """
 from __future__ import annotations
@@ -39,10 +44,33 @@ _OKS_TYPES = {"minus": 0, "plus": 1, "both": 2}
 _FLAG_NO_ANNOTATED, _FLAG_NAN_ERROR, _FLAG_BCE_RANGE = 1, 2, 4
 
 
+# reductions of pp_oks_heatmap_loss_backward (include/probpose_hip.h)
+_RED_PIXEL, _RED_KEYPOINT, _RED_MEAN, _RED_PIXEL_MEAN = 0, 1, 2, 3
+
+
 def _refuse_grad(*tensors) -> None:
-    if torch.is_grad_enabled() and any(isinstance(t, Tensor) and t.requires_grad for t in tensors):
+    if _wants_grad(*tensors):
         raise RuntimeError("the ProbPose losses run forward only (HIP kernels, no backward): an input requires grad; "
-                           "call them under torch.no_grad() or pass detached tensors")
+                           "call them under torch.no_grad() or pass detached tensors (or differentiable=True)")
+
+
+def _wants_grad(*tensors) -> bool:
+    return torch.is_grad_enabled() and any(isinstance(t, Tensor) and t.requires_grad for t in tensors)
+
+
+def _refuse_target_grad(**tensors) -> None:
+    """No gradient is provided for targets, weights or masks: refuse rather than return none."""
+    names = [k for k, t in tensors.items() if isinstance(t, Tensor) and t.requires_grad]
+    if names and torch.is_grad_enabled():
+        raise RuntimeError(f"the ProbPose losses differentiate the predictions only; {', '.join(names)} requires "
+                           "grad: detach it")
+
+
+def _grad_as(g: Tensor, like) -> Tensor:
+    """A float32 gradient in the (shape, dtype) of the prediction it belongs to."""
+    shape, dtype = like
+    g = g.view(shape)
+    return g if g.dtype == dtype else g.to(dtype)
 
 
 def _f32(t: Tensor, device) -> Tensor:
@@ -75,13 +103,71 @@ def _oks_heatmap_loss(output, target, weights, mask, skip_empty, oks_type, sw, g
     return parts
 
 
+def _mask_strides(mask, K, H, W):
+    if mask is None:
+        return 0, 0
+    mb, mk = mask.shape[0], mask.shape[1]
+    return (0 if mb == 1 else mk * H * W), (0 if mk == 1 else H * W)
+
+
+def _oks_heatmap_loss_backward(output, target, weights, mask, skip_empty, oks_type, sw, gw, lw, reduction, grad):
+    """Launch pp_oks_heatmap_loss_backward: d loss / d output [B,K,H,W] f32 for the upstream gradient ``grad`` (a
+    float32 device tensor, read through its strides: [B,K,H,W] per pixel, [B,K] per keypoint, 0-d for the means)."""
+    B, K, H, W = output.shape
+    dev = output.device
+    mask_sb, mask_sk = _mask_strides(mask, K, H, W)
+    strides = [0, 0, 0, 0]
+    if reduction in (_RED_PIXEL, _RED_KEYPOINT):
+        strides[:grad.ndim] = grad.stride()
+    grad_output = torch.empty((B, K, H, W), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        rc = _lib.lib().pp_oks_heatmap_loss_backward(
+            _lib.ptr(output), _lib.ptr(target), _lib.ptr(weights), int(weights is not None and weights.ndim == 4),
+            _lib.ptr(mask), mask_sb, mask_sk, int(bool(skip_empty)), _OKS_TYPES[oks_type], float(sw),
+            float(1.0 - sw - gw), float(gw), float(lw), reduction, _lib.ptr(grad), *strides, B, K, H, W,
+            _lib.ptr(grad_output), _lib.stream_ptr())
+    _lib.check(rc, "pp_oks_heatmap_loss_backward")
+    return grad_output
+
+
+def _upstream(g: Tensor, shape) -> Tensor:
+    """An upstream gradient as float32 with the output's shape, strides kept (an expanded one broadcasts)."""
+    g = g if g.dtype == torch.float32 else g.float()
+    return g if tuple(g.shape) == tuple(shape) else g.expand(shape)
+
+
+class _OKSHeatmapLossFn(torch.autograd.Function):
+    """OKSHeatmapLoss with a backward: inputs (module, reduction, output, f32 operands), output the loss."""
+
+    @staticmethod
+    def forward(ctx, module, reduction, output, out, tgt, wts, msk):
+        ctx.module, ctx.reduction, ctx.like = module, reduction, (output.shape, output.dtype)
+        ctx.save_for_backward(out, tgt, wts, msk)
+        return module._forward(out, tgt, wts, msk, reduction)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        out, tgt, wts, msk = ctx.saved_tensors
+        m, red = ctx.module, ctx.reduction
+        shape = {_RED_PIXEL: out.shape, _RED_KEYPOINT: out.shape[:2], _RED_MEAN: ()}[red]
+        dh = _oks_heatmap_loss_backward(out, tgt, wts, msk, m.skip_empty_channel, m.oks_type, m.smoothing_weight,
+                                        m.gaussian_weight, m.loss_weight, red, _upstream(g, shape))
+        return None, None, _grad_as(dh, ctx.like), None, None, None, None
+
+
 class OKSHeatmapLoss(nn.Module):
-    """Reference loss.py:18-191: expected-OKS heatmap loss plus Sobel smoothness and MSE terms, on the GPU."""
+    """Reference loss.py:18-191: expected-OKS heatmap loss plus Sobel smoothness and MSE terms, on the GPU.
+
+    ``differentiable=True``: with grad mode on and ``output`` requiring grad, the loss carries a gradient to
+    ``output`` (all three reductions, any upstream gradient; ``pp_oks_heatmap_loss_backward``).  The default stays
+    forward only; a later release may flip it."""
 
     def __init__(self, use_target_weight: bool = False, skip_empty_channel: bool = False,
                  smoothing_weight: float = 0.2, gaussian_weight: float = 0.0, loss_weight: float = 1.,
-                 oks_type: str = "minus"):
+                 oks_type: str = "minus", differentiable: bool = False):
         super().__init__()
+        self.differentiable = differentiable
         self.use_target_weight = use_target_weight
         self.skip_empty_channel = skip_empty_channel
         self.loss_weight = loss_weight
@@ -115,28 +201,46 @@ class OKSHeatmapLoss(nn.Module):
     def forward(self, output: Tensor, target: Tensor, target_weights: Tensor | None = None,
                 mask: Tensor | None = None, per_pixel: bool = False, per_keypoint: bool = False) -> Tensor:
         """loss.py:55-143.  Per-pixel map [B,K,H,W], per-keypoint loss [B,K] or the scalar mean (0-d)."""
-        _refuse_grad(output, target, target_weights, mask)
+        red = _RED_PIXEL if per_pixel else (_RED_KEYPOINT if per_keypoint else _RED_MEAN)
+        if not (self.differentiable and _wants_grad(output)):
+            _refuse_grad(output, target, target_weights, mask)
+            return self._forward(*self._operands(output, target, target_weights, mask), red)
+        _refuse_target_grad(target=target, target_weights=target_weights, mask=mask)
         out, tgt, wts, msk = self._operands(output, target, target_weights, mask)
+        return _OKSHeatmapLossFn.apply(self, red, output, out, tgt, wts, msk)
+
+    def _forward(self, out, tgt, wts, msk, red):
         B, K, H, W = out.shape
         scalars = torch.empty((3,), dtype=torch.float32, device=out.device)
-        pix = torch.empty_like(out) if per_pixel else None
-        kp = torch.empty((B, K), dtype=torch.float32, device=out.device) if (per_keypoint and not per_pixel) else None
+        pix = torch.empty_like(out) if red == _RED_PIXEL else None
+        kp = torch.empty((B, K), dtype=torch.float32, device=out.device) if red == _RED_KEYPOINT else None
         _oks_heatmap_loss(out, tgt, wts, msk, self.skip_empty_channel, self.oks_type, self.smoothing_weight,
                           self.gaussian_weight, self.loss_weight, pix, kp, scalars)
         assert float(scalars[2]) == 0, 'target should be normalized'
-        if per_pixel:
+        if red == _RED_PIXEL:
             return pix
-        if per_keypoint:
+        if red == _RED_KEYPOINT:
             return kp
         return scalars[0]
 
 
+def _check_grad(module, output, target, target_weight) -> None:
+    """The small losses are torch ops: differentiable ones let autograd through for ``output`` only."""
+    if module.differentiable:
+        _refuse_target_grad(target=target, target_weight=target_weight)
+    else:
+        _refuse_grad(output, target, target_weight)
+
+
 class BCELoss(nn.Module):
     """Reference loss.py:194-260.  ``use_sigmoid=True`` means the inputs are probabilities (F.binary_cross_entropy),
-    otherwise logits (F.binary_cross_entropy_with_logits)."""
+    otherwise logits (F.binary_cross_entropy_with_logits).  ``differentiable=True``: torch's autograd differentiates
+    ``output`` (the default stays forward only; a later release may flip it)."""
 
-    def __init__(self, use_target_weight=False, loss_weight=1.0, reduction="mean", use_sigmoid=False):
+    def __init__(self, use_target_weight=False, loss_weight=1.0, reduction="mean", use_sigmoid=False,
+                 differentiable: bool = False):
         super().__init__()
+        self.differentiable = differentiable
         assert reduction in ("mean", "sum", "none"), (
             f"the argument `reduction` should be either 'mean', 'sum' or 'none', but got {reduction}")
         self.reduction = reduction
@@ -147,7 +251,7 @@ class BCELoss(nn.Module):
         self.loss_weight = loss_weight
 
     def forward(self, output, target, target_weight=None):
-        _refuse_grad(output, target, target_weight)
+        _check_grad(self, output, target, target_weight)
         _lib.require_device(output)
         loss = self.criterion(output, target)
         if self.use_target_weight:
@@ -164,16 +268,17 @@ class BCELoss(nn.Module):
 
 class MSELoss(nn.Module):
     """Reference loss.py:263-292.  With weights both operands are multiplied by them and the mean runs over every
-    entry, masked zeros included."""
+    entry, masked zeros included.  ``differentiable`` as in ``BCELoss``."""
 
-    def __init__(self, use_target_weight=False, loss_weight=1.0):
+    def __init__(self, use_target_weight=False, loss_weight=1.0, differentiable: bool = False):
         super().__init__()
+        self.differentiable = differentiable
         self.criterion = F.mse_loss
         self.use_target_weight = use_target_weight
         self.loss_weight = loss_weight
 
     def forward(self, output, target, target_weight=None):
-        _refuse_grad(output, target, target_weight)
+        _check_grad(self, output, target, target_weight)
         _lib.require_device(output)
         if self.use_target_weight:
             assert target_weight is not None
@@ -185,16 +290,17 @@ class MSELoss(nn.Module):
 
 class L1LogLoss(nn.Module):
     """Reference loss.py:295-339: smooth-L1 (beta 1) between log(1 + x) of both operands -- ``log(1 + x)`` as
-    written, not ``log1p``."""
+    written, not ``log1p``.  ``differentiable`` as in ``BCELoss``."""
 
-    def __init__(self, use_target_weight=False, loss_weight=1.0):
+    def __init__(self, use_target_weight=False, loss_weight=1.0, differentiable: bool = False):
         super().__init__()
+        self.differentiable = differentiable
         self.criterion = F.smooth_l1_loss
         self.use_target_weight = use_target_weight
         self.loss_weight = loss_weight
 
     def forward(self, output, target, target_weight=None):
-        _refuse_grad(output, target, target_weight)
+        _check_grad(self, output, target, target_weight)
         _lib.require_device(output)
         output = torch.log(1 + output)
         target = torch.log(1 + target)
@@ -246,12 +352,64 @@ def _binary_accuracy(dt: np.ndarray, gt: np.ndarray, mask: np.ndarray, device, f
     return (torch.tensor(best_acc, device=device).float(), torch.tensor(best_threshold, device=device).float())
 
 
-class ProbPoseLoss(nn.Module):
-    """Reference loss.py:342-712 (forward only): the five per-head losses of the validation loop and, with
-    ``compute_acc``, the five accuracies."""
+_LOSS_KEYS = ("kpt", "probability", "visibility", "oks", "error")
 
-    def __init__(self, codec, freeze_error: bool = True):
+
+class _ProbPoseLossFn(torch.autograd.Function):
+    """ProbPoseLoss.forward as one autograd node: inputs (module, gt, keypoint_weights, learn_heatmaps_from_zeros, box,
+    the five predictions), outputs the five losses.  ``box`` receives the forward's terms for ``compute_acc``."""
+
+    @staticmethod
+    def forward(ctx, module, gt, keypoint_weights, from_zeros, box, *pred):
+        T = module.terms(gt, pred, keypoint_weights, from_zeros)
+        losses = module._losses(T)
+        box["T"] = T
+        ctx.module = module
+        ctx.like = [(p.shape, p.dtype) for p in pred]
+        ctx.save_for_backward(T["hm"], T["gt_hm"], T["heat_w"], *T["heads"], T["gt_oks"], T["gt_err"], T["masks"])
+        return tuple(losses[k] for k in _LOSS_KEYS)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_kpt, g_prob, g_vis, g_oks, g_err):
+        hm, gt_hm, heat_w, dt_prob, dt_vis, dt_oks, dt_err, gt_oks, gt_err, masks = ctx.saved_tensors
+        need = ctx.needs_input_grad[5:]
+        grads = [None] * 5
+        km = ctx.module.keypoint_loss_module
+        if need[0]:         # loss.py:427-431: heatmap_loss_pxl.mean()
+            dh = _oks_heatmap_loss_backward(hm, gt_hm, heat_w, None, km.skip_empty_channel, km.oks_type,
+                                            km.smoothing_weight, km.gaussian_weight, km.loss_weight, _RED_PIXEL_MEAN,
+                                            _upstream(g_kpt, ()))
+            grads[0] = _grad_as(dh, ctx.like[0])
+        if any(need[1:]):   # loss.py:432-464, one launch for the four heads
+            B, K = hm.shape[:2]
+            d = torch.empty((4, B * K), dtype=torch.float32, device=hm.device)
+            u = [_upstream(g, ()).contiguous() for g in (g_prob, g_vis, g_oks, g_err)]
+            with torch.cuda.device(hm.device):
+                rc = _lib.lib().pp_probpose_loss_grads(
+                    *[_lib.ptr(t) for t in (dt_prob, dt_vis, dt_oks, dt_err, gt_oks, gt_err, masks[0], masks[1],
+                                            masks[2], *u)], B, K, *[_lib.ptr(d[i]) for i in range(4)],
+                    _lib.stream_ptr())
+            _lib.check(rc, "pp_probpose_loss_grads")
+            for i in range(4):
+                if need[1 + i]:
+                    grads[1 + i] = _grad_as(d[i], ctx.like[1 + i])
+        return (None, None, None, None, None, *grads)
+
+
+class ProbPoseLoss(nn.Module):
+    """Reference loss.py:342-712: the five per-head losses of the training and validation loops and, with
+    ``compute_acc``, the five accuracies.
+
+    ``differentiable=True``: with grad mode on and a prediction requiring grad, the five losses come from one autograd
+    node whose backward computes the heatmap gradient (``pp_oks_heatmap_loss_backward``, skipped when the heatmaps need
+    none) and the four head gradients (``pp_probpose_loss_grads``) on the device, reading the upstream gradients there:
+    no host sync.  The OKS and error targets are constants, as in the reference (detached decodes); the accuracies
+    carry no gradient; double backward is an error.  The default stays forward only; a later release may flip it."""
+
+    def __init__(self, codec, freeze_error: bool = True, differentiable: bool = False):
         super().__init__()
+        self.differentiable = differentiable
         self.codec = codec
         self.keypoint_loss_module = OKSHeatmapLoss(use_target_weight=True, smoothing_weight=0.05, oks_type="minus")
         self.probability_loss_module = BCELoss(use_target_weight=False, use_sigmoid=True)
@@ -275,7 +433,8 @@ class ProbPoseLoss(nn.Module):
 
     def terms(self, gt, pred, keypoint_weights=None, learn_heatmaps_from_zeros: bool = False) -> dict:
         """Every device-side quantity of one forward: the decodes (gt_kpts, dt_kpts), the B*K targets (gt_oks,
-        gt_err, vis_weight, oks_weight), ``res`` = the 11 scalars of both kernels, and the host int masks."""
+        gt_err, vis_weight, oks_weight), ``res`` = the 11 scalars of both kernels, the int masks on the device
+        (``masks``: in_image, annotated, visibility) and on the host, and the heatmap weights (``heat_w``)."""
         if self.freeze_oks:
             raise NotImplementedError("freeze_oks is not supported (the reference never sets it)")
         dt_heatmaps, dt_probs, dt_vis, dt_oks, dt_errs = pred
@@ -322,13 +481,27 @@ class ProbPoseLoss(nn.Module):
         _lib.check(rc, "pp_probpose_loss_terms")
         return dict(hm=hm, gt_hm=gt_hm, kw=kw, heads=heads, gt_kpts=gt_kpts, dt_kpts=dt_kpts, gt_oks=gt_oks,
                     gt_err=gt_err, vis_weight=vis_weight, oks_weight=oks_weight, res=res, probs=probs,
-                    annotated=annotated, vis=vis)
+                    annotated=annotated, vis=vis, masks=masks, heat_w=heat_weights)
 
     def forward(self, gt, pred: Sequence[Tensor], keypoint_weights: Tensor | None = None,
                 learn_heatmaps_from_zeros: bool = False, compute_acc: bool = False):
         """loss.py:360-510: ``losses`` (kpt, probability, visibility, oks, error), and ``(losses, accs)`` with
         ``compute_acc``; 0-d device tensors."""
-        T = self.terms(gt, pred, keypoint_weights, learn_heatmaps_from_zeros)
+        if self.differentiable and _wants_grad(*pred):
+            gh = gt["heatmaps"] if isinstance(gt, dict) else None
+            _refuse_target_grad(gt_heatmaps=gh, keypoint_weights=keypoint_weights)
+            box = {}
+            out = _ProbPoseLossFn.apply(self, gt, keypoint_weights, learn_heatmaps_from_zeros, box, *pred)
+            T, losses = box["T"], dict(zip(_LOSS_KEYS, out))
+        else:
+            T = self.terms(gt, pred, keypoint_weights, learn_heatmaps_from_zeros)
+            losses = self._losses(T)
+        if not compute_acc:
+            return losses
+        return losses, self._accuracies(T)
+
+    def _losses(self, T) -> dict:
+        """The reference's raises from one small D2H, then the five losses (views of the kernels' results)."""
         res = T["res"]
         host = res.cpu().numpy()          # the one sync: the scalars the reference would raise on
         flags = int(host[9])
@@ -341,9 +514,10 @@ class ProbPoseLoss(nn.Module):
         if flags & _FLAG_NO_ANNOTATED:
             raise RuntimeError("min(): Expected reduction dim to be specified for input.numel() == 0 "
                                "(loss.py:448: the batch has no annotated keypoint)")
-        losses = dict(kpt=res[1], probability=res[3], visibility=res[4], oks=res[5], error=res[6])
-        if not compute_acc:
-            return losses
+        return dict(kpt=res[1], probability=res[3], visibility=res[4], oks=res[5], error=res[6])
+
+    def _accuracies(self, T) -> dict:
+        res = T["res"]
         dev = res.device
         _, avg_acc, _ = pose_pck_accuracy(T["hm"], T["gt_hm"], T["kw"] > 0.5, method="argmax")    # loss.py:642-651
         acc_pose = torch.tensor(avg_acc, device=dev)
@@ -353,8 +527,7 @@ class ProbPoseLoss(nn.Module):
         annotated_in = T["annotated"] & (T["probs"] > 0.5)
         acc_prob, _ = _binary_accuracy(dt_probs, T["probs"], T["annotated"] > 0.5, dev, force_balanced=True)
         acc_vis, _ = _binary_accuracy(dt_vis, T["vis"], annotated_in > 0.5, dev, force_balanced=True)
-        return losses, {"kpt": acc_pose, "probability": acc_prob, "visibility": acc_vis, "oks": res[7],
-                        "error": res[8]}
+        return {"kpt": acc_pose, "probability": acc_prob, "visibility": acc_vis, "oks": res[7], "error": res[8]}
 
     def get_binary_accuracy(self, dt, gt, mask, force_balanced=False):
         """loss.py:653-697."""
