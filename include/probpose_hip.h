@@ -386,6 +386,78 @@ int pp_probpose_loss_grads(const float *dt_prob, const float *dt_vis, const floa
                            const float *u_err, int B, int K, float *d_prob, float *d_vis, float *d_oks, float *d_err,
                            void *stream);
 
+/* ------------------------------------------------------------------------
+ * Training ProbMapHead (train-mode BatchNorm forward, backward).  Differentiate
+ *   ConvTranspose2d / Conv2d weights and biases, head.py:174-235, 255-405   (pp_wgrad_gemm; input gradients run on
+ *                                                      pp_gemm with transposed weights and pack.py's tables)
+ *   BatchNorm2d in train mode, head.py:190-222, 270-400                     (pp_bn_train_stats, pp_bn_apply_relu,
+ *                                                      pp_bn_pool_relu, pp_bn_train_backward)
+ *   nn.MaxPool2d + ReLU of the aux branches, head.py:270-400                (pp_bn_pool_relu, pp_bn_train_backward
+ *                                                      mode 2)
+ *   the 1x1 aux tails + Sigmoid / ReLU, head.py:270-400                     (pp_aux_tail_backward)
+ *   x / temperature, Sparsemax, * normalize, torch.clamp, head.py:526-532   (pp_heat_clamp, pp_heat_tail_backward)
+ * No allocation, no host sync; every reduction in a fixed order (no float atomics): repeated calls give the same bits.
+ *
+ * pp_wgrad_gemm: dW[n, k] = sum_m dY(m, n) A(m, k), f32 out, MFMA with f32 accumulation (dtype of dY and A: PP_F32,
+ * v_mfma_f32_16x16x4_f32; PP_BF16, v_mfma_f32_16x16x32_bf16), per batch entry b:
+ *   dY(m, n) = dY[b * strideDY + (dy_rowmap ? dy_rowmap[b * strideRowmap + m] : m) * ldd + n]
+ *   A(m, k)  = A[b * strideA + rowoff[b * strideRowoff + (k / seg_len) * M + m] + k % seg_len]  (-1 -> 0), or
+ *              A[b * strideA + m * lda + k] when rowoff is NULL (the layout of pp_gemm's A)
+ *   dW[b * strideDW + n * lddw + k];  dB (optional) [b * strideDB + n] = sum_m dY(m, n)
+ * Shapes with few output tiles split M; the f32 partials go to ``parts`` (pp_wgrad_workspace_floats(M, N, Kd, batch)
+ * floats; 0 = no split) and are summed in split order.
+ *
+ * pp_bn_train_stats: y [M, C] f32 (row pitch ldy), the batch mean and biased variance per channel (float64
+ * accumulation in a fixed order), mean / rstd = 1/sqrt(var + eps) / scale = gamma rstd / shift = beta - mean scale
+ * [C] f32 out; running_mean / running_var (may be NULL) <- (1 - momentum) r + momentum (mean, unbiased var).  M > 1.
+ * ws: pp_bn_workspace_bytes(M, C) bytes, shared with pp_bn_train_backward.
+ * pp_bn_apply_relu: out[r, c] = relu?(y[r, c] scale[c] + shift[c]) in dtype.
+ * pp_bn_pool_relu: y [B*h*w, C] f32 -> out [B*(h/kh)*(w/kw), C] dtype = ReLU(MaxPool_{kh x kw, stride = kernel}(y scale
+ *   + shift)), the first maximum in window scan order (a NaN wins); argmax [same] int32 = the winner's element index in
+ *   y, -1 where the ReLU passes no gradient.
+ * pp_bn_train_backward: the gradient g of the BN output z (mode 0: g [M, C] pitch ldg; mode 1: g where z > 0, z
+ *   recomputed from y, scale, shift; mode 2: the MaxPool scatter of g [B*(h/kh)*(w/kw), C] through argmax) ->
+ *   dbeta = sum g, dgamma = sum g xhat (either may be NULL), dx = gamma rstd (g - mean(g) - xhat mean(g xhat)) in dtype.
+ * pp_aux_tail_backward: x [B, 4C] the pooled rows, w [4, K, C], out / gout [4, B, K] f32 (the forward's outputs and
+ *   their upstream gradients) -> dW [4, K, C], dB [4, K], dx [B, 4C] f32 (each may be NULL); sigmoid for branches 0-2,
+ *   ReLU for branch 3.
+ * pp_heat_clamp: out = clamp(p scale, 0, 1) elementwise (a NaN stays a NaN).
+ * pp_heat_tail_backward: p [B*K, HW] (the logits / T, or with sparse = 1 their Sparsemax), g [B*K, HW] the upstream
+ *   gradient of the heatmaps -> dz[(b*HW + i) * ldz + k] in dtype: the gradient of the final layer's output (clamp
+ *   mask 0 <= p scale <= 1 inclusive, * scale, Sparsemax backward s (g - sum(g s) / sum(s)), / temperature); columns
+ *   K .. ldz-1 are written 0.  One workgroup per map.
+ * ---------------------------------------------------------------------- */
+typedef struct pp_wgrad_args {
+  const void *dY; const int32_t *dy_rowmap; long long ldd;
+  const void *A; const int32_t *rowoff; int seg_len; int lda;
+  float *dW; long long lddw;
+  float *dB;
+  float *parts;
+  int M, N, Kd, batch;
+  long long strideDY, strideA, strideRowoff, strideRowmap, strideDW, strideDB;
+  int dtype;
+} pp_wgrad_args;
+
+long long pp_wgrad_workspace_floats(int M, int N, int Kd, int batch);
+int pp_wgrad_gemm(const pp_wgrad_args *args, void *stream);
+long long pp_bn_workspace_bytes(int M, int C);
+int pp_bn_train_stats(const float *y, long long ldy, int M, int C, const float *gamma, const float *beta, float eps,
+                      float momentum, float *running_mean, float *running_var, float *mean, float *rstd, float *scale,
+                      float *shift, void *ws, void *stream);
+int pp_bn_apply_relu(const float *y, long long ldy, int M, int C, const float *scale, const float *shift, void *out,
+                     long long ldo, int relu, int dtype, void *stream);
+int pp_bn_pool_relu(const float *y, int B, int h, int w, int C, int kh, int kw, const float *scale, const float *shift,
+                    void *out, int32_t *argmax, int dtype, void *stream);
+int pp_bn_train_backward(const float *g, long long ldg, const float *y, long long ldy, int M, int C, const float *mean,
+                         const float *rstd, const float *scale, const float *shift, const float *gamma, int mode,
+                         const int32_t *argmax, int B, int h, int w, int kh, int kw, float *dgamma, float *dbeta,
+                         void *dx, long long ldx, int dtype, void *ws, void *stream);
+int pp_aux_tail_backward(const void *x, const void *w, const float *out, const float *gout, int B, int C, int K,
+                         float *dW, float *dB, float *dx, int dtype, void *stream);
+int pp_heat_clamp(const float *p, float *out, long long n, float scale, void *stream);
+int pp_heat_tail_backward(const float *p, const float *g, int B, int K, int HW, float scale, int sparse,
+                          float temperature, void *dz, int ldz, int dtype, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -46,6 +46,20 @@ class GemmArgs(C.Structure):
     ]
 
 
+class WgradArgs(C.Structure):
+    _fields_ = [
+        ("dY", C.c_void_p), ("dy_rowmap", C.c_void_p), ("ldd", C.c_longlong),
+        ("A", C.c_void_p), ("rowoff", C.c_void_p), ("seg_len", C.c_int), ("lda", C.c_int),
+        ("dW", C.c_void_p), ("lddw", C.c_longlong),
+        ("dB", C.c_void_p),
+        ("parts", C.c_void_p),
+        ("M", C.c_int), ("N", C.c_int), ("Kd", C.c_int), ("batch", C.c_int),
+        ("strideDY", C.c_longlong), ("strideA", C.c_longlong), ("strideRowoff", C.c_longlong),
+        ("strideRowmap", C.c_longlong), ("strideDW", C.c_longlong), ("strideDB", C.c_longlong),
+        ("dtype", C.c_int),
+    ]
+
+
 _vp, _i, _f, _d = C.c_void_p, C.c_int, C.c_float, C.c_double
 _SIGNATURES = {
     "pp_version": (C.c_int, []),
@@ -82,6 +96,17 @@ _SIGNATURES = {
     "pp_oks_heatmap_loss_backward": (C.c_int, [_vp, _vp, _vp, _i, _vp, C.c_longlong, C.c_longlong, _i, _i]
                                      + [_f] * 4 + [_i, _vp] + [C.c_longlong] * 4 + [_i] * 4 + [_vp, _vp]),
     "pp_probpose_loss_grads": (C.c_int, [_vp] * 13 + [_i, _i] + [_vp] * 5),
+    "pp_wgrad_workspace_floats": (C.c_longlong, [_i, _i, _i, _i]),
+    "pp_wgrad_gemm": (C.c_int, [C.POINTER(WgradArgs), _vp]),
+    "pp_bn_workspace_bytes": (C.c_longlong, [_i, _i]),
+    "pp_bn_train_stats": (C.c_int, [_vp, C.c_longlong, _i, _i, _vp, _vp, _f, _f] + [_vp] * 8),
+    "pp_bn_apply_relu": (C.c_int, [_vp, C.c_longlong, _i, _i, _vp, _vp, _vp, C.c_longlong, _i, _i, _vp]),
+    "pp_bn_pool_relu": (C.c_int, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp]),
+    "pp_bn_train_backward": (C.c_int, [_vp, C.c_longlong, _vp, C.c_longlong, _i, _i] + [_vp] * 5
+                             + [_i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, C.c_longlong, _i, _vp, _vp]),
+    "pp_aux_tail_backward": (C.c_int, [_vp] * 4 + [_i, _i, _i] + [_vp] * 3 + [_i, _vp]),
+    "pp_heat_clamp": (C.c_int, [_vp, _vp, C.c_longlong, _f, _vp]),
+    "pp_heat_tail_backward": (C.c_int, [_vp, _vp, _i, _i, _i, _f, _i, _f, _vp, _i, _i, _vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

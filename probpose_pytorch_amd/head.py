@@ -13,7 +13,7 @@ from typing import Sequence, Tuple, Union
 import torch
 from torch import Tensor, nn
 
-from . import _lib, engine, ops
+from . import _lib, engine, head_train, ops
 from .pack import deconv_geometry
 
 
@@ -54,6 +54,7 @@ class ProbMapHead(nn.Module):
         freeze_visibility: bool = False,
         freeze_oks: bool = False,
         freeze_error: bool = False,
+        differentiable: bool = False,
     ):
         super().__init__()
         self.in_channels = in_channels
@@ -65,6 +66,9 @@ class ProbMapHead(nn.Module):
         self.detach_visibility = detach_visibility
         self.freeze_oks = freeze_oks
         self.freeze_error = freeze_error
+        # True: .train() mode runs the reference's train-mode forward (batch-statistics BatchNorm) on HIP kernels and
+        # carries gradients to the parameters and to x (head_train.py); eval mode is unchanged
+        self.differentiable = differentiable
         self.compute_dtype = torch.float32
 
         # ---- heatmap branch (head.py:174-253)
@@ -154,8 +158,13 @@ class ProbMapHead(nn.Module):
                                "(the reference CLI's train-mode BN is a bug, SURVEY.md section 3.2)")
         return engine.plan_for(self, engine.build_head_plan, self.compute_dtype, device)
 
+    def _trains(self) -> bool:
+        return self.training and self.differentiable
+
     def forward_tokens(self, tokens: Tensor, B: int, h: int, w: int):
         """Channels-last rows [B*h*w, C] (compute dtype) -> the reference 5-tuple."""
+        if self._trains():
+            return head_train.train_forward(self, tokens=tokens, geom=(B, h, w))
         return self._plan(tokens.device).forward(tokens, B, h, w)
 
     def _to_tokens(self, x: Tensor):
@@ -168,6 +177,8 @@ class ProbMapHead(nn.Module):
 
     def forward(self, x: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
         """(B,C,h,w) -> (heatmaps, probabilities, visibilities, oks, error).  head.py:487-511."""
+        if self._trains():
+            return head_train.train_forward(self, x=x)
         return self.forward_tokens(*self._to_tokens(x))
 
     def forward_heatmap(self, x: Tensor) -> Tensor:

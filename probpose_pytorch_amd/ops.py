@@ -291,3 +291,96 @@ def nchw_to_tokens(x, out, B, Cc, HW):
     _lib.check(_lib.lib().pp_nchw_to_tokens(_p(x), _p(out), B, Cc, HW, dtype_code(out.dtype),
                                             _lib.stream_ptr()), "pp_nchw_to_tokens")
     return out
+
+
+# ---- training ProbMapHead (pp_head_grad.hip) ------------------------------------------------------------------
+def wgrad_workspace_floats(M, N, Kd, batch=1) -> int:
+    return int(_lib.lib().pp_wgrad_workspace_floats(M, N, Kd, batch))
+
+
+def wgrad(dY, A, dW, *, M, N, Kd, ldd, lda=0, rowoff=None, seg_len=0, dy_rowmap=None, dB=None, batch=1, lddw=None,
+          strideDY=0, strideA=0, strideRowoff=0, strideRowmap=0, strideDW=0, strideDB=0, parts=None):
+    """dW[n, k] = sum_m dY(m, n) A(m, k) (+ dB[n] = sum_m dY(m, n)); see pp_wgrad_gemm in include/probpose_hip.h."""
+    a = _lib.WgradArgs()
+    a.dY, a.dy_rowmap, a.ldd = _p(dY), _p(dy_rowmap), ldd
+    a.A, a.rowoff, a.seg_len, a.lda = _p(A), _p(rowoff), seg_len, lda
+    a.dW, a.lddw, a.dB, a.parts = _p(dW), Kd if lddw is None else lddw, _p(dB), _p(parts)
+    a.M, a.N, a.Kd, a.batch = M, N, Kd, batch
+    a.strideDY, a.strideA, a.strideRowoff, a.strideRowmap = strideDY, strideA, strideRowoff, strideRowmap
+    a.strideDW, a.strideDB = strideDW, strideDB
+    a.dtype = dtype_code(dY.dtype)
+    if A.dtype != dY.dtype:
+        raise TypeError(f"wgrad: dY ({dY.dtype}) and A ({A.dtype}) must share the compute dtype")
+    need = wgrad_workspace_floats(M, N, Kd, batch)
+    if need and (parts is None or parts.numel() < need or parts.dtype != torch.float32):
+        raise ValueError(f"wgrad: this shape needs a float32 parts workspace of {need} elements")
+    rc = _timed("wgrad", 2.0 * M * N * Kd * batch, lambda: _lib.lib().pp_wgrad_gemm(C.byref(a), _lib.stream_ptr()),
+                f"M={M} N={N} K={Kd} batch={batch}")
+    _lib.check(rc, "pp_wgrad_gemm")
+    return dW
+
+
+def bn_workspace_bytes(M, Cc) -> int:
+    return int(_lib.lib().pp_bn_workspace_bytes(M, Cc))
+
+
+def bn_train_stats(y, M, Cc, gamma, beta, eps, momentum, running_mean, running_var, mean, rstd, scale, shift, ws):
+    rc = _timed("bn_stats", float(M * Cc * 4),
+                lambda: _lib.lib().pp_bn_train_stats(_p(y), y.stride(0), M, Cc, _p(gamma), _p(beta), float(eps),
+                                                     float(momentum), _p(running_mean), _p(running_var), _p(mean),
+                                                     _p(rstd), _p(scale), _p(shift), _p(ws), _lib.stream_ptr()))
+    _lib.check(rc, "pp_bn_train_stats")
+
+
+def bn_apply_relu(y, M, Cc, scale, shift, out, relu=True):
+    rc = _timed("bn_apply", float(M * Cc * (4 + out.element_size())),
+                lambda: _lib.lib().pp_bn_apply_relu(_p(y), y.stride(0), M, Cc, _p(scale), _p(shift), _p(out),
+                                                    out.stride(0), int(relu), dtype_code(out.dtype),
+                                                    _lib.stream_ptr()))
+    _lib.check(rc, "pp_bn_apply_relu")
+    return out
+
+
+def bn_pool_relu(y, B, h, w, Cc, kh, kw, scale, shift, out, argmax):
+    rc = _timed("bn_pool", float(B * h * w * Cc * 4),
+                lambda: _lib.lib().pp_bn_pool_relu(_p(y), B, h, w, Cc, kh, kw, _p(scale), _p(shift), _p(out),
+                                                   _p(argmax), dtype_code(out.dtype), _lib.stream_ptr()))
+    _lib.check(rc, "pp_bn_pool_relu")
+    return out
+
+
+def bn_train_backward(g, y, M, Cc, mean, rstd, gamma, dx, ws, *, mode=0, scale=None, shift=None, argmax=None,
+                      pool=(0, 0, 0, 0, 0), dgamma=None, dbeta=None):
+    """mode 0: g is the gradient of the BN output; 1: ReLU follows the BN; 2: MaxPool + ReLU follow it (g is the
+    pooled gradient, pool = (B, h, w, kh, kw))."""
+    B, h, w, kh, kw = pool
+    rc = _timed("bn_backward", float(M * Cc * 12),
+                lambda: _lib.lib().pp_bn_train_backward(_p(g), g.stride(0), _p(y), y.stride(0), M, Cc, _p(mean),
+                                                        _p(rstd), _p(scale), _p(shift), _p(gamma), mode, _p(argmax),
+                                                        B, h, w, kh, kw, _p(dgamma), _p(dbeta), _p(dx), dx.stride(0),
+                                                        dtype_code(dx.dtype), _p(ws), _lib.stream_ptr()))
+    _lib.check(rc, "pp_bn_train_backward")
+    return dx
+
+
+def aux_tail_backward(x, w, out, gout, B, Cc, K, dW=None, dB=None, dx=None):
+    rc = _timed("aux_tail_backward", float(4 * B * K * Cc * 4),
+                lambda: _lib.lib().pp_aux_tail_backward(_p(x), _p(w), _p(out), _p(gout), B, Cc, K, _p(dW), _p(dB),
+                                                        _p(dx), dtype_code(w.dtype), _lib.stream_ptr()))
+    _lib.check(rc, "pp_aux_tail_backward")
+
+
+def heat_clamp(p, out, scale=1.0):
+    rc = _timed("heat_clamp", float(p.numel() * 8),
+                lambda: _lib.lib().pp_heat_clamp(_p(p), _p(out), p.numel(), float(scale), _lib.stream_ptr()))
+    _lib.check(rc, "pp_heat_clamp")
+    return out
+
+
+def heat_tail_backward(p, g, B, K, HW, scale, sparse, temperature, dz):
+    rc = _timed("heat_tail_backward", float(B * K * HW * 12),
+                lambda: _lib.lib().pp_heat_tail_backward(_p(p), _p(g), B, K, HW, float(scale), int(sparse),
+                                                         float(temperature), _p(dz), dz.stride(0),
+                                                         dtype_code(dz.dtype), _lib.stream_ptr()))
+    _lib.check(rc, "pp_heat_tail_backward")
+    return dz

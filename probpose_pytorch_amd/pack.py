@@ -153,3 +153,55 @@ def gather_rows(A: torch.Tensor, rowoff: torch.Tensor, seg_len: int) -> torch.Te
 def pool_out(h: int, w: int, k) -> Tuple[int, int, int, int]:
     kh, kw = (k, k) if isinstance(k, int) else (int(k[0]), int(k[1]))
     return kh, kw, h // kh, w // kw
+
+
+# ---- training: input gradients as implicit GEMMs over the output gradient dY ------------------------------------
+def conv3x3_data_grad_weights(w: torch.Tensor) -> torch.Tensor:
+    """Conv2d weight (Cout, Cin, 3, 3) -> (Cin, 9*Cout): the stride-1 convolution's data gradient is a 3x3 convolution
+    of dY with the taps flipped and the channel axes swapped, k = (ky'*3 + kx')*Cout + co holding w[co, ci, 2-ky', 2-kx']
+    (gathered through conv_gather_table over dY's rows)."""
+    Cout, Cin, kh, kw = w.shape
+    return w.flip(2, 3).permute(1, 2, 3, 0).reshape(Cin, kh * kw * Cout).contiguous()
+
+
+def deconv_data_grad_weights(w: torch.Tensor) -> torch.Tensor:
+    """ConvTranspose2d weight (Cin, Cout, k, k) -> (Cin, k*k*Cout), k = (ky*k + kx)*Cout + co."""
+    Cin, Cout, kh, kw = w.shape
+    return w.permute(0, 2, 3, 1).reshape(Cin, kh * kw * Cout).contiguous()
+
+
+def deconv_data_grad_table(B: int, h: int, w: int, k: int, row_stride: int) -> torch.Tensor:
+    """int32 [k*k, B*h*w]: the stride-2 deconvolution (h,w) -> (2h,2w) sends input (b, i, j) through tap (ky, kx) to
+    output (2i - pad + ky, 2j - pad + kx); its data gradient gathers dY there (element offset, -1 outside the map)."""
+    pad, _ = deconv_geometry(k)
+    H, W = 2 * h, 2 * w
+    b = torch.arange(B).view(B, 1, 1)
+    i = torch.arange(h).view(1, h, 1)
+    j = torch.arange(w).view(1, 1, w)
+    taps = []
+    for ky in range(k):
+        for kx in range(k):
+            oy, ox = 2 * i - pad + ky, 2 * j - pad + kx
+            ok = (oy >= 0) & (oy < H) & (ox >= 0) & (ox < W)
+            off = ((b * H + oy) * W + ox) * row_stride
+            taps.append(torch.where(ok.expand(B, h, w), off.expand(B, h, w), torch.full((), -1)).reshape(-1))
+    t = torch.stack(taps)
+    assert t.max().item() < 2 ** 31
+    return t.to(torch.int32).contiguous()
+
+
+def deconv_parity_index(k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(KY, KX) int64 [4 parities, 4 taps]: kernel position of parity p, tap t in pack_deconv_parities' layout, so that
+    packed[p, co, t*Cin + ci] = w[ci, co, KY[p, t], KX[p, t]] (k = 4: every kernel position appears exactly once)."""
+    if k != 4:
+        raise NotImplementedError(f"deconvolution kernel {k}: the training path packs kernel 4 only")
+    pad, _ = deconv_geometry(k)
+    taps = deconv_axis_taps(k, pad)
+    KY = torch.zeros((4, 4), dtype=torch.long)
+    KX = torch.zeros((4, 4), dtype=torch.long)
+    for py in (0, 1):
+        for px in (0, 1):
+            for a, (_, ky) in enumerate(taps[py]):
+                for b, (_, kx) in enumerate(taps[px]):
+                    KY[py * 2 + px, a * 2 + b], KX[py * 2 + px, a * 2 + b] = ky, kx
+    return KY, KX
