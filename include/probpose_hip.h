@@ -166,8 +166,8 @@ typedef struct pp_gemm_args {
                                    walking its tiles as one stream of 32-deep K-tiles, a finished tile's rows stored from
                                    the next tile's K-loop; plain bf16 -> bf16 layers with bias / GELU / ReLU (and the
                                    head-major qkv layout), M and N whole numbers of tiles, K >= 512 (qkv, fc1).
-                                   11, 12: round-2 experiments, removed (refused); 15 - 17: the per-launch four-wave forms,
-                                   lab builds only (refused by the shipped library). */
+                                   11, 12: round-2 experiments; 15 - 17: the per-launch four-wave forms; both removed
+                                   (refused). */
   float out_scale;              /* PP_EPI_OUT_FP8: 1 / (scale of the fp8 output tensor) */
   int splitk;                   /* 0 / 1 = off.  S > 1: the launch computes S partial products per batch entry, split s
                                    over the K range [s * Kd, (s + 1) * Kd) (Kd = the PER-SPLIT depth): operands advance

@@ -53,26 +53,9 @@ template <int HD> struct AttGeom {
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef float att_f32x2 __attribute__((ext_vector_type(2)));
 
-// Diagnostic build only (-DPP_ATT_STAMPS): phase cycle counts of wave 0 go behind the output tensor.
-#ifdef PP_ATT_STAMPS
-__device__ __forceinline__ unsigned long long att_stamp() {
-  unsigned long long t;
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  __builtin_amdgcn_sched_barrier(0);
-  return t;
-}
-#define ATT_STAMP(v) const unsigned long long v = att_stamp()
-#else
-#define ATT_STAMP(v)
-#endif
-
 __device__ __attribute__((aligned(256))) unsigned char g_att_zero[1024];
 
 __device__ __forceinline__ void att_glds16(const void *gsrc, unsigned lds_off_uniform) {
-#if defined(PP_ATT_ABL) && PP_ATT_ABL == 1
-  return;   // ablation (tools/att_ablate.sh): no K / V traffic
-#endif
   unsigned keep;
   asm volatile(
       "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
@@ -119,7 +102,6 @@ __global__ __launch_bounds__(256, 3) void attention_mfma_kernel(const bf16_t *__
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int lrow = lane & 15, g = lane >> 4;
 
-  ATT_STAMP(t0);
   const int q0 = wave * (AT_QT * 16);
   uint4 qf[AT_QT][G::KS];
   constexpr int NG = (AT_HD == 64) ? 4 : 2;            // DMA groups, 3 pieces per wave each
@@ -155,10 +137,8 @@ __global__ __launch_bounds__(256, 3) void attention_mfma_kernel(const bf16_t *__
   }
 #pragma unroll
   for (int j = 0; j < 3; ++j) issue_piece(0, j);        // group 0 now; the others are issued inside the first product
-  ATT_STAMP(t1);
   att_wait_barrier<0>();                               // Q and the first group have landed, for every wave
   __builtin_amdgcn_s_waitcnt(0x0F70);                  // the same vmcnt(0), visible to the compiler: no later Q waits
-  ATT_STAMP(t2);
 
   // ---- two key blocks of 96 keys, flash style: only 6 x QT score tiles (72 registers) are live at a
   // time, which lets three workgroups share a CU (768 (crop, head) problems = one full round of
@@ -174,9 +154,6 @@ __global__ __launch_bounds__(256, 3) void attention_mfma_kernel(const bf16_t *__
 #pragma unroll
     for (int dt = 0; dt < G::DT; ++dt) oacc[dt][t] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
-#if defined(PP_ATT_ABL) && PP_ATT_ABL == 3
-  if (N < 0)   // ablation: loads and stores only
-#endif
 #pragma unroll
   for (int kb = 0; kb < 2; ++kb) {
     if (kb == 1) att_wait_barrier<(AT_HD == 64) ? 3 : 0>();        // K (hd 32: K and V) of block 1
@@ -229,24 +206,11 @@ __global__ __launch_bounds__(256, 3) void attention_mfma_kernel(const bf16_t *__
       for (int kt = 0; kt < KB_TILES; ++kt)
 #pragma unroll
         for (int r = 0; r < 4; r += 2) {
-#if defined(PP_ATT_ABL) && PP_ATT_ABL == 4
-          const att_f32x2 e = {fmaf(sacc[kt][t][r], scale_log2e, -m_new), fmaf(sacc[kt][t][r + 1], scale_log2e, -m_new)};
-#else
           const att_f32x2 e = __builtin_elementwise_fma((att_f32x2){sacc[kt][t][r], sacc[kt][t][r + 1]}, c2, nm2);
-#endif
-#if defined(PP_ATT_ABL) && PP_ATT_ABL == 2
-          const att_f32x2 pv = e;   // ablation: no exponentials
-#else
           const att_f32x2 pv = {__builtin_amdgcn_exp2f(e.x), __builtin_amdgcn_exp2f(e.y)};
-#endif
           sacc[kt][t][r] = pv.x;
           sacc[kt][t][r + 1] = pv.y;
-#if defined(PP_ATT_ABL) && PP_ATT_ABL == 4
-          l2.x += pv.x;
-          l2.x += pv.y;
-#else
           l2 += pv;
-#endif
         }
       const float l = l2.x + l2.y;
       l_run[t] = l_run[t] * alpha + l;
@@ -299,7 +263,6 @@ __global__ __launch_bounds__(256, 3) void attention_mfma_kernel(const bf16_t *__
       }
     }
   }
-  ATT_STAMP(t3);
   float inv_l[AT_QT];
 #pragma unroll
   for (int t = 0; t < AT_QT; ++t) {
@@ -367,15 +330,6 @@ __global__ __launch_bounds__(256, 3) void attention_mfma_kernel(const bf16_t *__
       *reinterpret_cast<uint2 *>(orow + dt * 16 + g * 4) = pk;
     }
   }
-#ifdef PP_ATT_STAMPS
-  {
-    ATT_STAMP(t4);
-    if (tid == 0) {
-      unsigned long long *o = reinterpret_cast<unsigned long long *>(out + (size_t)gridDim.x / heads * N * C) + (size_t)blockIdx.x * 8;
-      o[0] = t1 - t0; o[1] = t2 - t1; o[2] = t3 - t2; o[3] = t4 - t3; o[4] = t4 - t0; o[5] = t0;
-    }
-  }
-#endif
 }
 
 // ---- streaming form: any N, head_dim 32 / 64 / 80.  Workgroup = NW waves x ST_QT query tiles (4 x 2 = 128 or
@@ -505,24 +459,11 @@ __global__ __launch_bounds__(NW * 64, 3) void attention_stream_kernel(const bf16
       for (int kt = 0; kt < KB_TILES; ++kt)
 #pragma unroll
         for (int r = 0; r < 4; r += 2) {
-#if defined(PP_ATT_ABL) && PP_ATT_ABL == 4
-          const att_f32x2 e = {fmaf(sacc[kt][t][r], scale_log2e, -m_new), fmaf(sacc[kt][t][r + 1], scale_log2e, -m_new)};
-#else
           const att_f32x2 e = __builtin_elementwise_fma((att_f32x2){sacc[kt][t][r], sacc[kt][t][r + 1]}, c2, nm2);
-#endif
-#if defined(PP_ATT_ABL) && PP_ATT_ABL == 2
-          const att_f32x2 pv = e;   // ablation: no exponentials
-#else
           const att_f32x2 pv = {__builtin_amdgcn_exp2f(e.x), __builtin_amdgcn_exp2f(e.y)};
-#endif
           sacc[kt][t][r] = pv.x;
           sacc[kt][t][r + 1] = pv.y;
-#if defined(PP_ATT_ABL) && PP_ATT_ABL == 4
-          l2.x += pv.x;
-          l2.x += pv.y;
-#else
           l2 += pv;
-#endif
         }
       const float l = l2.x + l2.y;
       l_run[t] = l_run[t] * alpha + l;
@@ -659,18 +600,11 @@ static int launch_stream_cfg(const void *qkv, void *out, int B, int N, int heads
 
 // 144-query workgroups (3 waves x 3 tiles) when they waste fewer query rows than 128-query ones (4 waves x 2); the
 // key block shrinks to 32 rows there (hd 64 / 80: 3 score tiles per key tile would not fit 168 registers otherwise).
-// Lab builds only (-DPP_ATT_LAB, tools/): the environment variable PP_ATT_STREAM = 4 / 3 forces one form.  The shipped
-// library reads no environment.
 template <int HD>
 static int launch_stream(const void *qkv, void *out, int B, int N, int heads, float fp8_inv_scale, hipStream_t s,
                          int headmajor = 0) {
-#ifdef PP_ATT_LAB
-  static const int forced = []() { const char *e = getenv("PP_ATT_STREAM"); return e ? atoi(e) : 0; }();
-#else
-  constexpr int forced = 0;
-#endif
   const int waste128 = (N + 127) / 128 * 128 - N, waste144 = (N + 143) / 144 * 144 - N;
-  const bool use144 = forced ? forced != 4 : waste144 < waste128;
+  const bool use144 = waste144 < waste128;
   if (use144) return launch_stream_cfg<HD, 3, 3, 32>(qkv, out, B, N, heads, fp8_inv_scale, s, headmajor);
   return launch_stream_cfg<HD, 4, 2, 64>(qkv, out, B, N, heads, fp8_inv_scale, s, headmajor);
 }

@@ -134,24 +134,8 @@ __device__ __forceinline__ void finalize(int map, int B, int K, int H, int W, in
 // LDS-resident path: 8 B (f64 row-pass intermediate) + 4 B (f32 map with a reflected 12-column halo,
 // later reused for the f32 convolved map) of LDS per pixel.
 // ---------------------------------------------------------------------------
-#ifndef PP_DEC_THREADS
-#define PP_DEC_THREADS 512   /* measured: 256 -> 512 threads per map: 64x48 maps +5 %, 96x72 maps +29 %; 1024: slower on 64x48 */
-#endif
-constexpr int DEC_THREADS = PP_DEC_THREADS;
-
-// Diagnostic build only (-DPP_DEC_STAMPS): wave-0 phase cycle counts are written through out_conv.
-#ifdef PP_DEC_STAMPS
-__device__ __forceinline__ unsigned long long dec_stamp() {
-  unsigned long long t;
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  __builtin_amdgcn_sched_barrier(0);
-  return t;
-}
-#define DEC_STAMP(v) const unsigned long long v = dec_stamp()
-#else
-#define DEC_STAMP(v)
-#endif
+// threads per map, measured: 256 -> 512: 64x48 maps +5 %, 96x72 maps +29 %; 1024: slower on 64x48
+constexpr int DEC_THREADS = 512;
 
 // Row pass + column pass for a compile-time radius R.  Each thread produces 4 adjacent outputs per
 // item from one shared window of 4 + 2R inputs (3.5x fewer LDS reads than one output per thread at
@@ -169,8 +153,7 @@ template <int R, int NT>   // NT = threads of the workgroup
 __device__ __forceinline__ void conv_passes(const float *__restrict__ rawp, int WP, float *__restrict__ buf,
                                             double *__restrict__ tmp, int H, int W,
                                             const double (&wk)[PP_MAX_TAPS], float *__restrict__ out_conv_map,
-                                            float &best_v, int &best_i, bool &have,
-                                            unsigned long long *dbg = nullptr) {
+                                            float &best_v, int &best_i, bool &have) {
   constexpr int T = 2 * R + 1, WIN = T + 3;
   constexpr int CR = (R + 3) / 4, NCH = 2 * CR + 1, SKIP = 4 * CR - R;  // aligned chunks around the window
   const int tid = threadIdx.x;
@@ -219,13 +202,7 @@ __device__ __forceinline__ void conv_passes(const float *__restrict__ rawp, int 
       }
     }
   }
-#ifdef PP_DEC_STAMPS
-  if (dbg) dbg[0] = dec_stamp();
-#endif
   __syncthreads();
-#ifdef PP_DEC_STAMPS
-  if (dbg) dbg[1] = dec_stamp();
-#endif
 
   const int H4 = (H + 3) >> 2;
   const int cstep_y = NT / W, cstep_x = NT - cstep_y * W;
@@ -296,7 +273,6 @@ __device__ __forceinline__ void decode_lds_map(
   const float *__restrict__ src = heatmaps + (size_t)map * HW;
   const int tid = threadIdx.x;
 
-  DEC_STAMP(t0);
   // taps and radius are block-uniform: scalar loads issued now, their latency hides under the map load
   const int r = __builtin_amdgcn_readfirstlane(radius[k]);
   double wk[PP_MAX_TAPS];
@@ -334,7 +310,6 @@ __device__ __forceinline__ void decode_lds_map(
     }
   }
   __syncthreads();
-  DEC_STAMP(t1);
 
   // 2+3. separable float64 convolution -> float32 map in LDS + per-thread running argmax
   Best mine;
@@ -342,43 +317,26 @@ __device__ __forceinline__ void decode_lds_map(
   mine.i = 0x7fffffff;
   bool have = false;
   float *ocm = out_conv ? out_conv + (size_t)map * HW : nullptr;
-  unsigned long long *dbgp = nullptr;
-#ifdef PP_DEC_STAMPS
-  unsigned long long dbg_st[2] = {0, 0};
-  dbgp = dbg_st;
-#endif
   switch (r) {  // block-uniform
-    case 2: conv_passes<2, NT>(rawp, WP, buf, tmp, H, W, wk, ocm, mine.v, mine.i, have, dbgp); break;
-    case 3: conv_passes<3, NT>(rawp, WP, buf, tmp, H, W, wk, ocm, mine.v, mine.i, have, dbgp); break;
-    case 4: conv_passes<4, NT>(rawp, WP, buf, tmp, H, W, wk, ocm, mine.v, mine.i, have, dbgp); break;
-    case 5: conv_passes<5, NT>(rawp, WP, buf, tmp, H, W, wk, ocm, mine.v, mine.i, have, dbgp); break;
-    case 6: conv_passes<6, NT>(rawp, WP, buf, tmp, H, W, wk, ocm, mine.v, mine.i, have, dbgp); break;
-    case 7: conv_passes<7, NT>(rawp, WP, buf, tmp, H, W, wk, ocm, mine.v, mine.i, have, dbgp); break;
-    case 8: conv_passes<8, NT>(rawp, WP, buf, tmp, H, W, wk, ocm, mine.v, mine.i, have, dbgp); break;
-    default: conv_passes<9, NT>(rawp, WP, buf, tmp, H, W, wk, ocm, mine.v, mine.i, have, dbgp); break;
+    case 2: conv_passes<2, NT>(rawp, WP, buf, tmp, H, W, wk, ocm, mine.v, mine.i, have); break;
+    case 3: conv_passes<3, NT>(rawp, WP, buf, tmp, H, W, wk, ocm, mine.v, mine.i, have); break;
+    case 4: conv_passes<4, NT>(rawp, WP, buf, tmp, H, W, wk, ocm, mine.v, mine.i, have); break;
+    case 5: conv_passes<5, NT>(rawp, WP, buf, tmp, H, W, wk, ocm, mine.v, mine.i, have); break;
+    case 6: conv_passes<6, NT>(rawp, WP, buf, tmp, H, W, wk, ocm, mine.v, mine.i, have); break;
+    case 7: conv_passes<7, NT>(rawp, WP, buf, tmp, H, W, wk, ocm, mine.v, mine.i, have); break;
+    case 8: conv_passes<8, NT>(rawp, WP, buf, tmp, H, W, wk, ocm, mine.v, mine.i, have); break;
+    default: conv_passes<9, NT>(rawp, WP, buf, tmp, H, W, wk, ocm, mine.v, mine.i, have); break;
   }
   if (!have) {  // more threads than pixels: never wins
     mine.v = -__builtin_inff();
     mine.i = 0x7fffffff;
   }
-  DEC_STAMP(t2);
   __syncthreads();
   const Best b = block_argmax(mine, red);
-  DEC_STAMP(t3);
   if (tid == 0) {
     auto at = [&](int yy, int xx) { return buf[yy * W + xx]; };
     finalize(map, B, K, H, W, b.i, at, src, prob, vis, oks, err, den_x, den_y, in_w, in_h, o);
   }
-#ifdef PP_DEC_STAMPS
-  {
-    DEC_STAMP(t4);
-    if (tid == 0 && out_conv == nullptr) {
-      unsigned long long *d = reinterpret_cast<unsigned long long *>(o.locs + (size_t)2 * B * K) + (size_t)map * 8;
-      d[0] = t1 - t0; d[1] = t2 - t1; d[2] = t3 - t2; d[3] = t4 - t3; d[4] = t4 - t0; d[5] = t0; d[6] = r;
-      d[7] = ((dbg_st[0] - t1) << 32) | ((dbg_st[1] - dbg_st[0]) & 0xffffffffull);
-    }
-  }
-#endif
 }
 
 __global__ __launch_bounds__(DEC_THREADS) void decode_lds_kernel(
@@ -524,13 +482,6 @@ __global__ __launch_bounds__(DF_THREADS, DF_KEEP <= 3 ? 5 : 4) void decode_scree
 
   const int map = blockIdx.x, k = map % K, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const float *__restrict__ src = heatmaps + (size_t)map * HW;
-#ifdef PP_DSC_STAMPS
-  unsigned long long st[8];
-#define DSC(i_) st[i_] = __builtin_amdgcn_s_memtime()
-#else
-#define DSC(i_)
-#endif
-  DSC(0);
   const int r = __builtin_amdgcn_readfirstlane(radius[k]);
   if (tid < PP_MAX_TAPS) wk[tid] = taps[k * PP_MAX_TAPS + tid];
   if (tid == 0) ncand_s = 0;
@@ -587,7 +538,6 @@ __global__ __launch_bounds__(DF_THREADS, DF_KEEP <= 3 ? 5 : 4) void decode_scree
     gmax = fmaxf(gmax, redmax[w_]);
   }
   const bool finite = A <= 3.0e38f;
-  DSC(1);
   if (finite && gmin == gmax) {
     // constant map (e.g. an all-zero channel after the clamp): every pixel's float64 chain sees the same inputs, so
     // every convolved value is the same number and np.argmax returns index 0 -- a border pixel, no sub-pixel step
@@ -629,7 +579,6 @@ __global__ __launch_bounds__(DF_THREADS, DF_KEEP <= 3 ? 5 : 4) void decode_scree
 #pragma unroll
     for (int w_ = 1; w_ < NW; ++w_) m32 = fmaxf(m32, redf[w_]);
     thr = m32 - 128.0f * 5.9604645e-08f * A;
-    DSC(2);
     if (keepable) {
       listed = true;
 #pragma unroll
@@ -647,7 +596,6 @@ __global__ __launch_bounds__(DF_THREADS, DF_KEEP <= 3 ? 5 : 4) void decode_scree
   }
   __syncthreads();
   const int nc = (finite && listed) ? ncand_s : DF_MAXCAND + 1;
-  DSC(3);
 
   // 4. exact values of the candidates, first-index arg-max (np.argmax semantics incl. NaN)
   Best mine;
@@ -683,7 +631,6 @@ __global__ __launch_bounds__(DF_THREADS, DF_KEEP <= 3 ? 5 : 4) void decode_scree
       mine.i = 0x7fffffff;
     }
   }
-  DSC(4);
   __syncthreads();
   // block_argmax's better() treats a NaN value as winning; the "no candidate" sentinel (-inf, INT_MAX) never wins
   const Best b = block_argmax(mine, red);
@@ -698,22 +645,12 @@ __global__ __launch_bounds__(DF_THREADS, DF_KEEP <= 3 ? 5 : 4) void decode_scree
     }
   }
   __syncthreads();
-  DSC(5);
   if (tid == 0) {
     auto at = [&](int yy, int xx) {
       return yy == by ? (xx == bx ? nbr[0] : (xx == bx + 1 ? nbr[1] : nbr[2])) : (yy == by + 1 ? nbr[3] : nbr[4]);
     };
     finalize(map, B, K, H, W, b.i, at, src, prob, vis, oks, err, den_x, den_y, in_w, in_h, o);
   }
-#ifdef PP_DSC_STAMPS
-  DSC(6);
-  if (tid == 0) {
-    unsigned long long *d = reinterpret_cast<unsigned long long *>(o.locs + (size_t)2 * B * K) + (size_t)map * 8;
-    d[0] = st[1] - st[0]; d[1] = st[2] - st[1]; d[2] = st[3] - st[2]; d[3] = st[4] - st[3]; d[4] = st[5] - st[4];
-    d[5] = st[6] - st[0]; d[6] = r; d[7] = nc;
-  }
-#endif
-#undef DSC
 }
 
 // ---------------------------------------------------------------------------
@@ -926,13 +863,6 @@ __device__ __forceinline__ void wave_decode_map(
   const int r = __builtin_amdgcn_readfirstlane(radius[k]);
   const double *__restrict__ wk = taps + (size_t)k * PP_MAX_TAPS;
 
-#ifdef PP_DWV_STAMPS
-  unsigned long long st[8];
-#define DWS(i_) st[i_] = __builtin_amdgcn_s_memtime()
-#else
-#define DWS(i_)
-#endif
-  DWS(0);
   // 1. HBM -> LDS (row stride RS), A = max |x| (NaN / inf make the map "not finite")
   float amax = 0.f, vmin = __builtin_inff(), vmax = -__builtin_inff();
   bool bad = false;
@@ -969,7 +899,6 @@ __device__ __forceinline__ void wave_decode_map(
     return;
   }
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");        // the map is in LDS (this wave's own buffer)
-  DWS(1);
   int cand_r[(DWV_MAXCAND + 63) / 64];                       // candidate ci lives in lane ci % 64 (register, not LDS:
   cand_r[0] = 0;                                             // the buffer still holds the convolved map while they are found)
   int ncand = DWV_MAXCAND + 1;                               // "every pixel" unless the screen says less
@@ -987,7 +916,6 @@ __device__ __forceinline__ void wave_decode_map(
     }
     const float m32 = wave_max(lm);
     const float thr = m32 - 128.0f * 5.9604645e-08f * A;     // see the error budget of the screened path above
-    DWS(2);
     // columns whose maximum reaches the threshold (usually one) are scanned by the whole wave, one row per lane.
     // A lane holds the maximum over its NCI columns, so every column of a flagged lane is scanned.
     ncand = 0;
@@ -1023,7 +951,6 @@ __device__ __forceinline__ void wave_decode_map(
     }
   }
 
-  DWS(3);
   if (ncand > DWV_MAXCAND) {
     // Flat map (a clamped plateau: hundreds of exact ties and near-ties) or non-finite map (every pixel counts): not
     // worth a wave's serial chains.  It goes on the work list of the all-pixel float64 decode (whole workgroups).
@@ -1073,7 +1000,6 @@ __device__ __forceinline__ void wave_decode_map(
       consider(p, exact_at(p / W, p % W));
     }
   }
-  DWS(4);
   // exact neighbours of the winner (interior only): lanes [0, T) column x + 1, [T, 2T) column x - 1, [2T, 3T + 2)
   // column x over rows y - 1 - r .. y + 1 + r; then four (five) column chains on lanes 0..3 (4)
   const int bx = best.i % W, by = best.i / W;
@@ -1106,15 +1032,6 @@ __device__ __forceinline__ void wave_decode_map(
     };
     finalize(map, B, K, H, W, best.i, at, src, prob, vis, oks, err, den_x, den_y, in_w, in_h, o);
   }
-#ifdef PP_DWV_STAMPS
-  DWS(5);
-  if (lane == 0) {   // diagnostic build: phase cycles behind the locs array (tools/dwv_stamps.py sizes it)
-    unsigned long long *d = reinterpret_cast<unsigned long long *>(o.locs + (size_t)2 * B * K) + (size_t)map * 8;
-    d[0] = st[1] - st[0]; d[1] = st[2] - st[1]; d[2] = st[3] - st[2]; d[3] = st[4] - st[3]; d[4] = st[5] - st[4];
-    d[5] = st[5] - st[0]; d[6] = r; d[7] = ncand;
-  }
-#endif
-#undef DWS
 }
 
 // NWV waves (= maps) per workgroup; MINW = waves per SIMD the register budget is cut for.
@@ -1255,7 +1172,6 @@ extern "C" int pp_decode_f32(const float *heatmaps, const float *prob, const flo
   hipStream_t s = (hipStream_t)stream;
   DecodeOut o{out_kpts, out_scores, out_locs, out_aux, out_err, out_packed};
   const int maps = B * K;
-#ifndef PP_DEC_STAMPS
   constexpr size_t SCREEN_DYN_LIMIT = 156 * 1024;    // the kernel also holds ~1.5 KB of static LDS
   // Measured (tools/decode_ab.py, one process, interleaved): 96x72 maps 699 vs 884 us per 128 x 133 maps (-21 %); 64x48
   // maps 24.3 vs 22.9 us at B = 64 and 236 vs 234 us at B = 1024 (a tie: both forms are bound by the latency of their
@@ -1319,7 +1235,6 @@ extern "C" int pp_decode_f32(const float *heatmaps, const float *prob, const flo
     PP_CHECK_LAUNCH("decode_screen_kernel");
     return 0;
   }
-#endif
   if (fits_lds(H, W)) {
     const size_t lds = lds_bytes(H, W);
     static thread_local unsigned long long attr_mask = 0;

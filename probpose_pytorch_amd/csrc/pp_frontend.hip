@@ -29,9 +29,8 @@ namespace pp {
 constexpr int FE_PRECISION_BITS = 32 - 8 - 2;   // Pillow Resample.c PRECISION_BITS
 constexpr int FE_HDR = 16;                      // int32 words per box header
 constexpr int FE_THREADS = 256;
-#ifndef FE_UNROLL
-#define FE_UNROLL 4     // taps in flight per thread in the horizontal pass (measured: 1 -> 4: 188 -> 170 us per 64 crops; 8: same)
-#endif
+// taps in flight per thread in the horizontal pass (measured: 1 -> 4: 188 -> 170 us per 64 crops; 8: same)
+constexpr int FE_TAPS_PER_TRIP = 4;
 constexpr size_t FE_LDS_TARGET = 64 * 1024, FE_LDS_MAX = 152 * 1024;
 
 // header words
@@ -249,11 +248,11 @@ __global__ __launch_bounds__(FE_THREADS) void crop_resize_kernel(const unsigned 
         const bool last_row = iy == img_h - 1;
         // four taps per trip: the four pixel loads (and coefficient loads) are independent, so they are in flight
         // together; taps past xmax or outside the frame contribute 0 (a zero pixel, as Image.crop pads)
-        for (int x = 0; x < xmax; x += FE_UNROLL) {
-          unsigned rgb[FE_UNROLL];
-          int kx[FE_UNROLL];
+        for (int x = 0; x < xmax; x += FE_TAPS_PER_TRIP) {
+          unsigned rgb[FE_TAPS_PER_TRIP];
+          int kx[FE_TAPS_PER_TRIP];
 #pragma unroll
-          for (int u = 0; u < FE_UNROLL; ++u) {
+          for (int u = 0; u < FE_TAPS_PER_TRIP; ++u) {
             const int ix = x0 + xmin + x + u;
             rgb[u] = 0;
             kx[u] = 0;
@@ -267,7 +266,7 @@ __global__ __launch_bounds__(FE_THREADS) void crop_resize_kernel(const unsigned 
             }
           }
 #pragma unroll
-          for (int u = 0; u < FE_UNROLL; ++u) {
+          for (int u = 0; u < FE_TAPS_PER_TRIP; ++u) {
             a0 += (int)(rgb[u] & 255u) * kx[u];
             a1 += (int)((rgb[u] >> 8) & 255u) * kx[u];
             a2 += (int)((rgb[u] >> 16) & 255u) * kx[u];

@@ -39,24 +39,6 @@ constexpr int gemm_lds_bytes(int BM, int BN, int stages) {
   return (BM == 192 && BN == 256 && fused > ring) ? fused : ring;
 }
 
-// Diagnostic build only (-DPP_GEMM_STAMPS, never shipped): per-wave cycle shares of the K-loop
-// phases are written to the buffer passed in GemmParams::rowbias when epilogue bit 30 is set.
-#ifdef PP_GEMM_STAMPS
-__device__ __forceinline__ unsigned long long stamp() {
-  unsigned long long t;
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  __builtin_amdgcn_sched_barrier(0);
-  return t;
-}
-#define PP_STAMP(var) const unsigned long long var = stamp()
-#define PP_ACC(dst, a, b) dst += (b) - (a)
-#else
-#define PP_STAMP(var)
-#define PP_ACC(dst, a, b)
-#endif
-
-
 // Zero rows (W rows beyond N, zero-padding taps of the implicit convolutions) are DMA'd from a 64 KiB
 // zero region, each lane/workgroup at a different 128-B line: one shared line would funnel every
 // such request of the chip through a single L2 channel (measured: the K=17 heatmap layer, whose W
@@ -100,10 +82,6 @@ template <typename T, int BM, int BN, int WGM, int WGN, int STAGES, bool GATHER,
           bool PINGPONG = false>
 __global__ __launch_bounds__(64 * (WGM * WGN + NWP), (WGM * WGN + NWP + 3) / 4 < 2 ? 2 : (WGM * WGN + NWP + 3) / 4) void gemm_kernel(GemmParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-#ifdef PP_GEMM_TIMELINE   // diagnostic build: wall-clock (100 MHz) marks per wave + where it ran
-  const unsigned long long rt_entry = __builtin_amdgcn_s_memrealtime();
-  unsigned long long rt_loop0 = 0, rt_loop1 = 0, ct_loop0 = 0, ct_loop1 = 0;   // ct_*: shader cycles (s_memtime)
-#endif
   constexpr int ES = (int)sizeof(T);
   constexpr int BK = ROW_BYTES / ES;  // elements of K per tile
   constexpr int NW = WGM * WGN;                         // consumer (MFMA) waves
@@ -538,18 +516,6 @@ __global__ __launch_bounds__(64 * (WGM * WGN + NWP), (WGM * WGN + NWP + 3) / 4 <
   // retires tile t is a COUNTED vmcnt (never 0 in steady state), then one raw s_barrier makes every
   // wave's pieces of tile t visible and proves every wave finished reading the buffer that tile
   // t+STAGES-1 is about to overwrite (it was consumed in iteration t-1).
-#ifdef PP_GEMM_STAMPS
-  unsigned long long c_wait = 0, c_bar = 0, c_stage = 0, c_comp = 0;
-#endif
-  PP_STAMP(t_begin);
-#ifdef PP_GEMM_STAMPS
-  unsigned long long t_pro_v = t_begin;
-#endif
-#ifdef PP_GEMM_TIMELINE
-  rt_loop0 = __builtin_amdgcn_s_memrealtime();
-  ct_loop0 = __builtin_amdgcn_s_memtime();
-  __builtin_amdgcn_s_waitcnt(0xC07F);
-#endif
   if constexpr (NWP > 0) {
     static_assert(!PINGPONG, "the ping-pong order is a form of the non-specialised kernel");
     // ---- wave-specialised K-loop: same barrier protocol, the two halves of each iteration on
@@ -557,14 +523,9 @@ __global__ __launch_bounds__(64 * (WGM * WGN + NWP), (WGM * WGN + NWP + 3) / 4 <
     {
       int buf = 0;
       for (int kt = 0; kt < nkt; ++kt) {
-        PP_STAMP(tb);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
-        PP_STAMP(tc);
         compute(buf, std::false_type{});
-        PP_STAMP(te);
-        PP_ACC(c_bar, tb, tc);
-        PP_ACC(c_comp, tc, te);
         if (++buf == STAGES) buf = 0;
       }
     }
@@ -577,14 +538,6 @@ __global__ __launch_bounds__(64 * (WGM * WGN + NWP), (WGM * WGN + NWP + 3) / 4 <
   // Retire them once here with a wait the compiler models: from now on only DMA pieces are outstanding and
   // the loop keeps nothing but the counted waits.  Cost: the first iteration also waits for K-tile 1.
   __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0), expcnt / lgkmcnt untouched
-#ifdef PP_GEMM_STAMPS
-  t_pro_v = stamp();
-#endif
-#ifdef PP_GEMM_TIMELINE
-  rt_loop0 = __builtin_amdgcn_s_memrealtime();
-  ct_loop0 = __builtin_amdgcn_s_memtime();
-  __builtin_amdgcn_s_waitcnt(0xC07F);
-#endif
   if constexpr (PINGPONG) {
     static_assert(STAGES == 3 && NW == 8, "ping-pong form: 8 waves, 3 LDS stages");
     // interval kt (between two barriers) reads K-tile kt and prefetches K-tile kt + 2 into the buffer that
@@ -596,25 +549,16 @@ __global__ __launch_bounds__(64 * (WGM * WGN + NWP), (WGM * WGN + NWP + 3) / 4 <
     auto nbuf = [&]() { int nb = buf + STAGES - 1; return nb >= STAGES ? nb - STAGES : nb; };
     if (!late) {
       for (; kt + 2 < nkt; ++kt) {
-        PP_STAMP(ta);
         wait_vmcnt<PIECES>();
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
-        PP_STAMP(tb);
         pp_load(buf);
         __builtin_amdgcn_sched_barrier(0);
-        PP_STAMP(tc);
         stage_all(kt + 2, nbuf());
         __builtin_amdgcn_sched_barrier(0);
-        PP_STAMP(td);
         pp_mma();
         __builtin_amdgcn_sched_barrier(0);
-        PP_STAMP(te);
-        PP_ACC(c_bar, ta, tb);
-        PP_ACC(c_wait, tb, tc);
-        PP_ACC(c_stage, tc, td);
-        PP_ACC(c_comp, td, te);
         advance();
       }
       for (; kt < nkt; ++kt) {
@@ -638,25 +582,16 @@ __global__ __launch_bounds__(64 * (WGM * WGN + NWP), (WGM * WGN + NWP + 3) / 4 <
       advance();
       kt = 1;
       for (; kt + 2 < nkt; ++kt) {
-        PP_STAMP(ta);
         wait_vmcnt<PIECES>();
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
-        PP_STAMP(tb);
         pp_mma();
         __builtin_amdgcn_sched_barrier(0);
-        PP_STAMP(tc);
         pp_load(buf);
         __builtin_amdgcn_sched_barrier(0);
-        PP_STAMP(td);
         stage_all(kt + 2, nbuf());
         __builtin_amdgcn_sched_barrier(0);
-        PP_STAMP(te);
-        PP_ACC(c_bar, ta, tb);
-        PP_ACC(c_comp, tb, tc);
-        PP_ACC(c_wait, tc, td);
-        PP_ACC(c_stage, td, te);
         advance();
       }
       for (; kt < nkt; ++kt) {
@@ -677,49 +612,30 @@ __global__ __launch_bounds__(64 * (WGM * WGN + NWP), (WGM * WGN + NWP + 3) / 4 <
   // steady state: every iteration prefetches tile kt + STAGES - 1 (one code path in the loop body,
   // so the accumulators stay in place across iterations)
   for (; kt + STAGES - 1 < nkt; ++kt) {
-    PP_STAMP(ta);
     wait_vmcnt<(STAGES - 2) * PIECES>();          // STAGES-2 younger tiles may still fly
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    PP_STAMP(tb);
     __builtin_amdgcn_s_barrier();
-    PP_STAMP(tc);
     int nb = buf + STAGES - 1;
     if (nb >= STAGES) nb -= STAGES;
     stage_begin(kt + STAGES - 1, nb);
     compute(buf, std::true_type{});
     stage_end(kt + STAGES - 1);
-    PP_STAMP(te);
-    PP_ACC(c_bar, tb, tc);
-    PP_ACC(c_wait, ta, tb);
-    PP_ACC(c_comp, tc, te);
     if (++buf == STAGES) buf = 0;
   }
   // tail: the last STAGES-1 tiles are already in flight, nothing left to prefetch
   for (; kt < nkt; ++kt) {
-    PP_STAMP(ta);
     if (kt + STAGES - 1 <= nkt) {
       wait_vmcnt<(STAGES - 2) * PIECES>();
     } else {
       wait_vmcnt<0>();
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    PP_STAMP(tb);
     __builtin_amdgcn_s_barrier();
-    PP_STAMP(tc);
     compute(buf, std::false_type{});
-    PP_STAMP(te);
-    PP_ACC(c_bar, tb, tc);
-    PP_ACC(c_wait, ta, tb);
-    PP_ACC(c_comp, tc, te);
     if (++buf == STAGES) buf = 0;
   }
   }
   }
-  PP_STAMP(t_loop);
-#ifdef PP_GEMM_TIMELINE
-  rt_loop1 = __builtin_amdgcn_s_memrealtime();
-  ct_loop1 = __builtin_amdgcn_s_memtime();
-#endif
 
   // ---- epilogue.  The W fragment is the MFMA "A" operand and the activation fragment the "B"
   // operand, so a 16x16 accumulator tile holds C^T: lane (frow, fq) owns output row m = .. + frow and
@@ -920,35 +836,13 @@ __global__ __launch_bounds__(64 * (WGM * WGN + NWP), (WGM * WGN + NWP + 3) / 4 <
       }
     }
   }
-#ifdef PP_GEMM_TIMELINE
-  if ((p.epilogue & (1 << 30)) && lane == 0) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the tile's stores have been accepted
-    const unsigned long long rt_end = __builtin_amdgcn_s_memrealtime();
-    unsigned long long *o = reinterpret_cast<unsigned long long *>(const_cast<float *>(p.rowbias)) +
-                            ((size_t)blockIdx.x * NW + wave) * 8;
-    o[0] = rt_entry; o[1] = rt_loop0; o[2] = rt_loop1; o[3] = rt_end;
-    o[4] = __builtin_amdgcn_s_getreg(63492);   // HW_REG_HW_ID
-    o[5] = __builtin_amdgcn_s_getreg(63508);   // HW_REG_XCC_ID
-    o[6] = ct_loop1 - ct_loop0 + 1;            // K-loop shader cycles (> 0: also the "this wave ran" mark)
-    o[7] = (unsigned long long)tm << 32 | (unsigned)tn;
-  }
-#endif
-#ifdef PP_GEMM_STAMPS
-  if ((p.epilogue & (1 << 30)) && lane == 0) {
-    PP_STAMP(t_end);
-    unsigned long long *o = reinterpret_cast<unsigned long long *>(const_cast<float *>(p.rowbias)) +
-                            ((size_t)blockIdx.x * NW + wave) * 8;
-    o[0] = t_pro_v - t_begin; o[1] = c_wait; o[2] = c_bar; o[3] = c_stage; o[4] = c_comp;  // stage now inside compute
-    o[5] = t_end - t_loop; o[6] = t_end - t_begin; o[7] = t_begin;
-  }
-#endif
 }
 
 
 // ---------------------------------------------------------------------------------------------------------
 // Persistent form of the 192x192 / 8-wave / 3-stage configuration for the plain bf16 -> bf16 layers (qkv, fc1).
 //
-// Measured on the per-launch form (tools/gemm_timeline.py, ViT-B bs 64, round 3): a workgroup of qkv lives 17.6 us, of
+// Measured on the per-launch form (timeline build, removed; ViT-B bs 64, round 3): a workgroup of qkv lives 17.6 us, of
 // which the K-loop is 12.0; 2.9 us go to the pipeline fill -- every CU of the chip asks for its first two K-tiles in
 // the same microsecond, a cold burst of ~25 MB -- 2.7 us to the epilogue (4.7 with GELU), and 0.4 us pass between one
 // workgroup's end and the next one's start on a CU.  With 3 (qkv) or 4 (fc1) tiles per CU the fill + gap are paid 3 - 4
@@ -966,10 +860,6 @@ __global__ __launch_bounds__(64 * (WGM * WGN + NWP), (WGM * WGN + NWP + 3) / 4 <
 template <int ACT>   // 0 none, 1 GELU, 2 ReLU (compile-time: see lds_epilogue of gemm_kernel)
 __global__ __launch_bounds__(512, 2) void gemm_persist_kernel(GemmParams p, int vblocks) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-#ifdef PP_GEMM_TIMELINE
-  const unsigned long long rt_entry = __builtin_amdgcn_s_memrealtime();
-  unsigned long long rt_loop0 = 0, rt_loop1 = 0, ct_loop0 = 0, ct_loop1 = 0, ct_epi = 0;
-#endif
   constexpr int BM = 192, BN = 192, WGN = 4, STAGES = 3, BK = 64;
   constexpr int PA = 3, PB = 3, PIECES = PA + PB, TM = 6, TN = 3;
   constexpr int A_BYTES = BM * ROW_BYTES, STAGE_BYTES = (BM + BN) * ROW_BYTES;
@@ -1203,11 +1093,6 @@ __global__ __launch_bounds__(512, 2) void gemm_persist_kernel(GemmParams p, int 
   // ---- the stream: fill two K-tiles, then one identical iteration per K-tile, tile after tile
   stage_all(0);
   stage_all(1);
-#ifdef PP_GEMM_TIMELINE
-  rt_loop0 = __builtin_amdgcn_s_memrealtime();
-  ct_loop0 = __builtin_amdgcn_s_memtime();
-  __builtin_amdgcn_s_waitcnt(0xC07F);
-#endif
   int buf = 0, c_slot = 0, post_store = 0;
   for (int t_vb = next_valid((int)blockIdx.x); t_vb >= 0; t_vb = next_valid(t_vb + (int)gridDim.x)) {
     int tm, tn;
@@ -1239,34 +1124,11 @@ __global__ __launch_bounds__(512, 2) void gemm_persist_kernel(GemmParams p, int 
       last = buf;
       if (++buf == STAGES) buf = 0;
     }
-#ifdef PP_GEMM_TIMELINE
-    const unsigned long long ce0 = __builtin_amdgcn_s_memtime();
-    __builtin_amdgcn_s_waitcnt(0xC07F);
-#endif
     epilogue(last, tm * BM, tn * BN, c_slot);
-#ifdef PP_GEMM_TIMELINE
-    ct_epi += __builtin_amdgcn_s_memtime() - ce0;
-    __builtin_amdgcn_s_waitcnt(0xC07F);
-#endif
     post_store = 2;
     c_slot = c_slot == 2 ? 0 : c_slot + 1;
   }
-#ifdef PP_GEMM_TIMELINE
-  rt_loop1 = __builtin_amdgcn_s_memrealtime();
-  ct_loop1 = __builtin_amdgcn_s_memtime();
-#endif
   wait_vmcnt<0>();      // the dummy pieces of the last two iterations must not outlive the workgroup's LDS allocation
-#ifdef PP_GEMM_TIMELINE
-  if ((p.epilogue & (1 << 30)) && lane == 0) {
-    const unsigned long long rt_end = __builtin_amdgcn_s_memrealtime();
-    unsigned long long *o = reinterpret_cast<unsigned long long *>(const_cast<float *>(p.rowbias)) +
-                            ((size_t)blockIdx.x * 8 + wave) * 8;
-    o[0] = rt_entry; o[1] = rt_loop0; o[2] = rt_loop1; o[3] = rt_end;
-    o[4] = __builtin_amdgcn_s_getreg(63492);
-    o[5] = __builtin_amdgcn_s_getreg(63508);
-    o[6] = ct_loop1 - ct_loop0 + 1; o[7] = ct_epi;      // stream cycles, of which epilogues
-  }
-#endif
 }
 
 
@@ -1274,7 +1136,7 @@ __global__ __launch_bounds__(512, 2) void gemm_persist_kernel(GemmParams p, int 
 // "Duo" form: 192x192 tile, FOUR waves (2 x 2, 96x96 per wave), K-tiles of 32 (64-byte rows), 3 LDS stages of
 // 24 KB = 72 KB per workgroup, <= 256 VGPRs: TWO workgroups are resident per CU (one wave of each per SIMD).
 //
-// Why: the per-launch timeline (tools/gemm_timeline.py) shows a workgroup of the 8-wave form spending 35-50 % of its
+// Why: the per-launch timeline (a diagnostic build, removed) shows a workgroup of the 8-wave form spending 35-50 % of its
 // life outside the K-loop -- pipeline fill, the residual / bias fetch, and an epilogue in which all 256 CUs store in
 // the same phase -- while nothing else can run on its CU (144 KB of LDS).  Two half-size workgroups per CU drift out
 // of phase on their own: one's fill / epilogue runs under the other's K-loop, and inside the K-loop one's DMA issue
@@ -1287,19 +1149,9 @@ __global__ __launch_bounds__(512, 2) void gemm_persist_kernel(GemmParams p, int 
 // ---------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256, 2) void gemm_duo_kernel(GemmParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-#ifdef PP_GEMM_TIMELINE
-  const unsigned long long rt_entry = __builtin_amdgcn_s_memrealtime();
-  unsigned long long rt_loop0 = 0, rt_loop1 = 0;
-#endif
-#ifndef PP_DUO_DELAY
-#define PP_DUO_DELAY 0       /* units of s_sleep(127) ~ 3.9 us; measured: 0 best (fc1 87.2 / 90.9 / 101 us at 0 / 2 / 4) */
-#endif
-  // Optional start stagger of the second slot of every CU (block ids b and b + 256 share a CU on a >= 512-workgroup
-  // launch; speed only, never correctness).  Tried because two workgroups that start together run the same phases at
-  // the same time; measured a loss at every delay, so it is off.
-  if (PP_DUO_DELAY > 0 && gridDim.x >= 512 && ((blockIdx.x >> 8) & 1)) {
-    for (int d = 0; d < PP_DUO_DELAY; ++d) __builtin_amdgcn_s_sleep(127);
-  }
+  // No start stagger of the second slot of every CU (block ids b and b + 256 share a CU on a >= 512-workgroup launch).
+  // Tried because two workgroups that start together run the same phases at the same time; measured a loss at every
+  // delay (units of s_sleep(127) ~ 3.9 us: fc1 87.2 / 90.9 / 101 us at 0 / 2 / 4).
   constexpr int BM = 192, BN = 192, STAGES = 3, BK = 32, RB = 64;          // RB: bytes of K per staged row
   constexpr int PA = 3, PB = 3, PIECES = PA + PB, TM = 6, TN = 6;           // 1-KiB pieces (16 rows) per wave per K-tile
   constexpr int A_BYTES = BM * RB, STAGE_BYTES = (BM + BN) * RB;
@@ -1422,9 +1274,6 @@ __global__ __launch_bounds__(256, 2) void gemm_duo_kernel(GemmParams p) {
     }
   }
   __builtin_amdgcn_s_waitcnt(0x0F70);     // retire them with a wait hipcc models (see gemm_kernel): no vmcnt(0) in the loop
-#ifdef PP_GEMM_TIMELINE
-  rt_loop0 = __builtin_amdgcn_s_memrealtime();
-#endif
 
   int buf = 0, kt = 0;
   for (; kt + STAGES - 1 < nkt; ++kt) {
@@ -1449,9 +1298,6 @@ __global__ __launch_bounds__(256, 2) void gemm_duo_kernel(GemmParams p) {
     if (++buf == STAGES) buf = 0;
   }
 
-#ifdef PP_GEMM_TIMELINE
-  rt_loop1 = __builtin_amdgcn_s_memrealtime();
-#endif
   // ---- epilogue: the tile goes through the (now idle) LDS ring in column passes and leaves as whole rows (16 B per
   // lane, contiguous per row); lane (frow, fq) of a wave owns row m and 4 consecutive columns of every 16-wide tile.
   const bool out_f32 = (epi & PP_EPI_OUT_F32) != 0;
@@ -1507,33 +1353,16 @@ __global__ __launch_bounds__(256, 2) void gemm_duo_kernel(GemmParams p) {
   };
   if (out_f32) staged(std::integral_constant<int, 4>{});
   else staged(std::integral_constant<int, 2>{});
-#ifdef PP_GEMM_TIMELINE
-  if ((p.epilogue & (1 << 30)) && lane == 0) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned long long rt_end = __builtin_amdgcn_s_memrealtime();
-    unsigned long long *o = reinterpret_cast<unsigned long long *>(const_cast<float *>(p.rowbias)) +
-                            ((size_t)blockIdx.x * 8 + wave) * 8;
-    o[0] = rt_entry; o[1] = rt_loop0; o[2] = rt_loop1; o[3] = rt_end;
-    o[4] = __builtin_amdgcn_s_getreg(63492);
-    o[5] = __builtin_amdgcn_s_getreg(63508);
-    o[6] = 1; o[7] = (unsigned long long)tm << 32 | (unsigned)tn;
-  }
-#endif
 }
 
-// pp_gemm_quad.hip: tiles 18 - 20 (four waves, one per SIMD, 128x96 / 96x144 / 96x128 wave tiles, persistent stream;
-// 15 - 17: the per-launch forms, lab builds only)
+// pp_gemm_quad.hip: tiles 18 - 20 (four waves, one per SIMD, 128x96 / 96x144 / 96x128 wave tiles, persistent stream)
 int gemm_quad_launch(const GemmParams &p, int cfg, dim3 grid, hipStream_t s);
 void gemm_quad_tile_shape(int cfg, int *bm, int *bn);
 
-}  // namespace pp
+// measured: one 8-wave 3-stage 192x192 tile per CU vs two co-resident 4-wave tiles
+constexpr double CFG3_SPEEDUP = 1.3;
 
-#ifndef PP_CFG5_VS_CFG3
-#define PP_CFG5_VS_CFG3 1.0
-#endif
-#ifndef PP_CFG3_SPEEDUP
-#define PP_CFG3_SPEEDUP 1.3  // measured: one 8-wave 3-stage 192x192 tile per CU vs two co-resident 4-wave tiles
-#endif
+}  // namespace pp
 
 extern "C" int pp_gemm(const pp_gemm_args *a, void *stream) {
   using namespace pp;
@@ -1620,8 +1449,9 @@ extern "C" int pp_gemm(const pp_gemm_args *a, void *stream) {
   // (8 consumer + 4 producer waves, 3 stages), 7 = 192x384 (8 waves, 2 stages; wide-N layers such as fc1),
   // 8 = 256x256 (8 waves, 2 stages), 9 = 192x256 (8 waves, 2 stages; N = 256 layers: one column tile, A read once).  Auto: cost = rounds of co-resident workgroups x padded tile area / relative per-CU
   // throughput of the configuration.
-  PP_REQUIRE(a->tile >= 0 && a->tile <= 20 && a->tile != 11 && a->tile != 12,
-             "pp_gemm: bad tile selector %d (11 / 12: round-2 experiments, removed)", a->tile);
+  PP_REQUIRE(a->tile >= 0 && a->tile <= 20 && a->tile != 11 && a->tile != 12 && !(a->tile >= 15 && a->tile <= 17),
+             "pp_gemm: bad tile selector %d (11 / 12: round-2 experiments; 15 - 17: per-launch four-wave forms that only lab "
+             "builds had; removed)", a->tile);
   auto rounds = [&](int bm, int bn, int slots) {
     const long long tiles = (long long)cdiv(a->M, bm) * cdiv(a->N, bn) * batch;
     return (tiles + slots - 1) / slots;
@@ -1632,21 +1462,21 @@ extern "C" int pp_gemm(const pp_gemm_args *a, void *stream) {
   if (cfg == 0) {
     const double c1 = (double)rounds(128, 128, 512) * 128 * 128 * 2;   // 2 workgroups share a CU
     const double c2 = (double)rounds(192, 96, 512) * 192 * 96 * 2;
-    const double c3 = (double)rounds(192, 192, 256) * 192 * 192 / PP_CFG3_SPEEDUP;
-    const double c4 = (double)rounds(192, 128, 256) * 192 * 128 / (PP_CFG3_SPEEDUP * 0.9);
+    const double c3 = (double)rounds(192, 192, 256) * 192 * 192 / CFG3_SPEEDUP;
+    const double c4 = (double)rounds(192, 128, 256) * 192 * 128 / (CFG3_SPEEDUP * 0.9);
     cfg = 1;
     double best = c1;
     if (c2 < best) { best = c2; cfg = 2; }
     if (c4 < best) { best = c4; cfg = 4; }
     if (c3 <= best) { best = c3; cfg = 3; }
     if (a->N <= 256) {  // narrow outputs (deconvolution layers): a taller tile restores the flop/byte ratio
-      const double c5 = (double)rounds(384, 128, 256) * 384 * 128 / (PP_CFG3_SPEEDUP * PP_CFG5_VS_CFG3);
+      const double c5 = (double)rounds(384, 128, 256) * 384 * 128 / CFG3_SPEEDUP;
       if (c5 < best) { best = c5; cfg = 5; }
     }
   }
   int bm = cfg == 1 ? 128 : (cfg == 5 ? 384 : (cfg == 8 ? 256 : 192));
   int bn = cfg == 1 ? 128 : (cfg == 2 ? 96 : ((cfg == 3 || cfg == 6 || cfg == 10 || cfg == 13 || cfg == 14) ? 192 : (cfg == 7 ? 384 : ((cfg == 8 || cfg == 9) ? 256 : 128))));
-  if (cfg >= 15) gemm_quad_tile_shape(cfg, &bm, &bn);
+  if (cfg >= 18) gemm_quad_tile_shape(cfg, &bm, &bn);
   p.tiles_m = cdiv(a->M, bm);
   p.tiles_n = cdiv(a->N, bn);
   dim3 grid;
@@ -1670,23 +1500,22 @@ extern "C" int pp_gemm(const pp_gemm_args *a, void *stream) {
     PP_REQUIRE(p.lds_epilogue && vec, "pp_gemm: PP_EPI_FUSE_FINAL runs inside the LDS epilogue: C must be 16-byte aligned "
                                       "(and N = ldc = 256)");
   hipStream_t s = (hipStream_t)stream;
-  if (cfg >= 15) {
+  if (cfg >= 18) {
     // quad forms (pp_gemm_quad.hip): plain bf16 -> bf16 layers, K-tiles of 32 walked in pairs behind a 4-deep ring
     PP_REQUIRE(a->dtype == PP_BF16 && !a->rowoff && !a->out_rowmap && vec && p.lds_epilogue && batch == 1 &&
-                   a->Kd % 64 == 0 && a->Kd >= 128 && (a->N & 7) == 0 &&
-                   !(a->epilogue & ~(PP_EPI_BIAS | PP_EPI_GELU | PP_EPI_RELU | PP_EPI_HEADMAJOR | (1 << 30))),
-               "pp_gemm: tiles 15 - 20 (four-wave forms) serve plain bf16 -> bf16 GEMMs with bias / GELU / ReLU epilogues, "
-               "K >= 128");
-    if (cfg >= 18)
-      PP_REQUIRE(a->M % bm == 0 && a->N % bn == 0 && a->Kd >= 512 && (unsigned long long)a->M * a->ldc * 2 < 0xFFFFFFF0ull,
-                 "pp_gemm: tiles 18 - 20 (four-wave stream) need M %% %d == 0, N %% %d == 0, K >= 512 and C below 4 GiB", bm, bn);
+                   a->Kd % 64 == 0 && (a->N & 7) == 0 &&
+                   !(a->epilogue & ~(PP_EPI_BIAS | PP_EPI_GELU | PP_EPI_RELU | PP_EPI_HEADMAJOR)),
+               "pp_gemm: four-wave tiles 15 - 20 (15 - 17 removed, 18 - 20 the stream) serve plain bf16 -> bf16 GEMMs with "
+               "bias / GELU / ReLU epilogues");
+    PP_REQUIRE(a->M % bm == 0 && a->N % bn == 0 && a->Kd >= 512 && (unsigned long long)a->M * a->ldc * 2 < 0xFFFFFFF0ull,
+               "pp_gemm: tiles 18 - 20 (four-wave stream) need M %% %d == 0, N %% %d == 0, K >= 512 and C below 4 GiB", bm, bn);
     return gemm_quad_launch(p, cfg, grid, s);
   }
   if (cfg == 14) {
     // duo form (gemm_duo_kernel): plain bf16 layers (K a multiple of 64 like every bf16 tile; it stages 32-deep K-tiles)
     PP_REQUIRE(a->dtype == PP_BF16 && !a->rowoff && !a->out_rowmap && vec && batch == 1 && a->Kd % 64 == 0 &&
                    !(a->epilogue & ~(PP_EPI_BIAS | PP_EPI_GELU | PP_EPI_RELU | PP_EPI_RESIDUAL | PP_EPI_OUT_F32 |
-                                     PP_EPI_ROWBIAS | (1 << 30))) &&
+                                     PP_EPI_ROWBIAS)) &&
                    (!(a->epilogue & (PP_EPI_RESIDUAL | PP_EPI_ROWBIAS)) || (a->epilogue & PP_EPI_OUT_F32)) &&
                    p.lds_epilogue,
                "pp_gemm: tile 14 (two workgroups per CU) serves plain bf16 GEMMs (bias / GELU / ReLU / f32 residual) whose "
@@ -1704,7 +1533,7 @@ extern "C" int pp_gemm(const pp_gemm_args *a, void *stream) {
   if (cfg == 13) {
     // persistent 192x192 form (gemm_persist_kernel): plain bf16 -> bf16 layers only
     PP_REQUIRE(a->dtype == PP_BF16 && !a->rowoff && !a->out_rowmap && vec && p.lds_epilogue && batch == 1 &&
-                   !(a->epilogue & ~(PP_EPI_BIAS | PP_EPI_GELU | PP_EPI_RELU | PP_EPI_HEADMAJOR | (1 << 30))) &&
+                   !(a->epilogue & ~(PP_EPI_BIAS | PP_EPI_GELU | PP_EPI_RELU | PP_EPI_HEADMAJOR)) &&
                    (unsigned long long)a->M * a->ldc * 2 < 0xFFFFFFF0ull,
                "pp_gemm: tile 13 (persistent) serves plain bf16 -> bf16 GEMMs with bias / GELU / ReLU epilogues only "
                "(C below 4 GiB: its rows leave through 32-bit buffer offsets)");
@@ -1760,13 +1589,6 @@ extern "C" int pp_gemm(const pp_gemm_args *a, void *stream) {
     else PP_LAUNCH_GEMM_V(T, BM_, BN_, WGM_, WGN_, ST_, false, true);                                 \
   } while (0)
   const bool gather = a->rowoff != nullptr;
-#ifdef PP_GEMM_LAB   // experiment builds (tools/build_lab.sh): only the plain bf16 192x192 forms, compiles in seconds
-  if (a->dtype != PP_BF16 || gather || !vec || !(cfg == 3 || cfg == 6 || cfg == 10))
-    return fail("pp_gemm (lab build): only plain bf16 tiles 3, 6, 10 (and 13 / 14, dispatched above)");
-  if (cfg == 3) PP_LAUNCH_GEMM_V(bf16_t, 192, 192, 2, 4, 3, false, true);
-  else if (cfg == 6) PP_LAUNCH_GEMM_W(bf16_t, 192, 192, 2, 4, 3, false, true, 4);
-  else PP_LAUNCH_GEMM_P(bf16_t, 192, 192, 2, 4, 3, false, true, 0, true);
-#else
   if (a->dtype == PP_FP8) {
     PP_REQUIRE(vec && p.lds_epilogue, "pp_gemm: fp8 needs the vector / LDS epilogue path (aligned N, ldc, C)");
     if (!(cfg == 2 || cfg == 3 || cfg == 10)) {
@@ -1811,7 +1633,6 @@ extern "C" int pp_gemm(const pp_gemm_args *a, void *stream) {
     else if (gather) PP_LAUNCH_GEMM_W(float, 192, 192, 2, 4, 3, true, true, 4);
     else PP_LAUNCH_GEMM_W(float, 192, 192, 2, 4, 3, false, true, 4);
   }
-#endif
 #undef PP_LAUNCH_GEMM_V
 #undef PP_LAUNCH_GEMM_W
 #undef PP_LAUNCH_GEMM_L

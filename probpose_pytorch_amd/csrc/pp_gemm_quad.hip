@@ -19,7 +19,7 @@
 // wave): 1 361 cycles as built; 8 DMA pieces cost 31 cycles each, the fragment reads and the barrier 75, loop control
 // and waits the rest (profiles/r03_gemm_quad_experiments.txt).
 //
-// The per-launch form (tiles 15 - 17) is kept for lab builds (tools/build_lab.sh), where its ablation switches live.
+// The per-launch form (tiles 15 - 17) and its ablation switches were removed; git history keeps them.
 #include <algorithm>
 #include <type_traits>
 #include <utility>
@@ -28,12 +28,6 @@
 
 namespace pp {
 
-constexpr int quad_lds_bytes(int TM, int TN) {
-  const int BM = 32 * TM, BN = 32 * TN;
-  const int ring = 4 * (BM + BN) * 64, ctile = BM * (BN * 2 + 16);
-  return (ring > ctile ? ring : ctile) + BN * 4;
-}
-
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 // The MFMA from inline asm with the accumulator TIED in the accumulation registers ("+a"): with 256 of the 256 AGPRs
@@ -41,31 +35,14 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 // shuffles tiles through v_accvgpr_mov / s_nop inside the loop (seen in the ISA of the builtin form: 136 moves and 74
 // nops per two K-tiles).  volatile also fixes the issue order the code is written in.
 __device__ __forceinline__ void mfma_bf16(f32x4 &c, const u32x4 &w, const u32x4 &a) {
-#ifdef PP_QUAD_BUILTIN_MFMA
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8 *>(&w), *reinterpret_cast<const bf16x8 *>(&a), c, 0, 0, 0);
-#else
   asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(c) : "v"(w), "v"(a));
-#endif
 }
 
 // LDS-DMA pieces: 64 lanes x 16 B each from (uniform 64-bit base + per-lane 32-bit offset) to LDS offset M0 + lane * 16.
 // The scalar-base form keeps the K-loop free of 64-bit vector address arithmetic (the K offset is a scalar add on the
-// base).  A burst (1 - 4 pieces) is issued only when bit BIT of the wave-uniform `mask` is set.  The predicate lives INSIDE
-// the asm statement on purpose: with 192 - 256 accumulator registers tied to asm MFMAs, any C++-level branch inside the
-// K-loop makes hipcc's allocator split the accumulators' live ranges (hundreds of v_accvgpr moves and scratch spills per
-// K-tile; seen in the ISA).  M0 is written without save / restore: nothing else in this translation unit uses it.
-#ifndef PP_QUAD_BURST
-#define PP_QUAD_BURST 0     /* lab (per-launch form): 0: every wave one piece per slot (2 722 cycles per two K-tiles of the
-                               192 x 288 tile); 1: staggered bursts skipped by a branch (2 841); 2: skipped by EXEC = 0 (4 575) */
-#endif
-#if PP_QUAD_BURST == 2
-#define PP_QB_OPEN(BIT) "s_bitcmp1_b32 %0, " #BIT "\n\ts_cselect_b64 exec, -1, 0\n\t"
-#define PP_QB_CLOSE "s_mov_b64 exec, -1"
-#else
-#define PP_QB_OPEN(BIT) "s_bitcmp1_b32 %0, " #BIT "\n\ts_cbranch_scc0 .Lsk_%=\n\t"
-#define PP_QB_CLOSE ".Lsk_%=:"
-#endif
-#define PP_QB_PIECE(L, O, B) "s_mov_b32 m0, " L "\n\ts_nop 0\n\tglobal_load_lds_dwordx4 " O ", " B "\n\t"
+// base).  M0 is written without save / restore: nothing else in this translation unit uses it.  Measured on the
+// per-launch form: every wave one piece per slot, 2 722 cycles per two K-tiles of the 192 x 288 tile; staggered bursts
+// skipped by a branch 2 841; skipped by EXEC = 0 4 575.
 struct QuadPiece {
   unsigned voff;                 // per-lane byte offset from the base
   unsigned long long sbase;      // uniform
@@ -73,52 +50,8 @@ struct QuadPiece {
 };
 // one piece, unconditionally (the stream form: a K-tile always has a successor to request)
 __device__ __forceinline__ void glds_piece(const QuadPiece &a) {
-  asm volatile(PP_QB_PIECE("%0", "%1", "%2") : : "s"(a.lds), "v"(a.voff), "s"(a.sbase) : "memory");
-}
-template <int BIT>
-__device__ __forceinline__ void glds_burst(int mask, const QuadPiece &a) {
-  asm volatile(PP_QB_OPEN(%c1) PP_QB_PIECE("%2", "%3", "%4") PP_QB_CLOSE
-               :
-               : "s"(__builtin_amdgcn_readfirstlane(mask)), "n"(BIT), "s"(a.lds), "v"(a.voff), "s"(a.sbase)
-               : "memory", "scc");
-}
-template <int BIT>
-__device__ __forceinline__ void glds_burst(int mask, const QuadPiece &a, const QuadPiece &b, const QuadPiece &c) {
-  asm volatile(PP_QB_OPEN(%c1) PP_QB_PIECE("%2", "%3", "%4") PP_QB_PIECE("%5", "%6", "%7") PP_QB_PIECE("%8", "%9", "%10")
-                   PP_QB_CLOSE
-               :
-               : "s"(__builtin_amdgcn_readfirstlane(mask)), "n"(BIT), "s"(a.lds), "v"(a.voff), "s"(a.sbase), "s"(b.lds),
-                 "v"(b.voff), "s"(b.sbase), "s"(c.lds), "v"(c.voff), "s"(c.sbase)
-               : "memory", "scc");
-}
-template <int BIT>
-__device__ __forceinline__ void glds_burst(int mask, const QuadPiece &a, const QuadPiece &b, const QuadPiece &c,
-                                           const QuadPiece &d) {
-  asm volatile(PP_QB_OPEN(%c1) PP_QB_PIECE("%2", "%3", "%4") PP_QB_PIECE("%5", "%6", "%7") PP_QB_PIECE("%8", "%9", "%10")
-                   PP_QB_PIECE("%11", "%12", "%13") PP_QB_CLOSE
-               :
-               : "s"(__builtin_amdgcn_readfirstlane(mask)), "n"(BIT), "s"(a.lds), "v"(a.voff), "s"(a.sbase), "s"(b.lds),
-                 "v"(b.voff), "s"(b.sbase), "s"(c.lds), "v"(c.voff), "s"(c.sbase), "s"(d.lds), "v"(d.voff), "s"(d.sbase)
-               : "memory", "scc");
-}
-// Top of a K-tile: s_waitcnt vmcnt(rem >= 2 ? N2 : rem == 1 ? N1 : 0) -- the choice between immediates is a branch inside
-// the asm statement, as above -- then lgkmcnt(0) and the barrier as BUILTINS: hipcc has to see that the fragment reads of
-// the previous iteration are complete.  With the lgkmcnt wait hidden in asm its wait-count pass assumed them still in
-// flight at the loop header and guarded this iteration's MFMAs with counted lgkmcnt waits that in fact waited for the
-// reads just issued for the NEXT K-tile: ~500 of 1370 cycles per K-tile (measured: the loop ran as long with no DMA piece).
-template <int N2, int N1>
-__device__ __forceinline__ void wait_tiles_barrier(int rem) {
-  asm volatile("s_cmp_lt_i32 %0, 2\n\ts_cbranch_scc1 .Lw1_%=\n\ts_waitcnt vmcnt(%1)\n\ts_branch .Lwd_%=\n"
-               ".Lw1_%=:\n\ts_cmp_lt_i32 %0, 1\n\ts_cbranch_scc1 .Lw0_%=\n\ts_waitcnt vmcnt(%2)\n\ts_branch .Lwd_%=\n"
-               ".Lw0_%=:\n\ts_waitcnt vmcnt(0)\n"
-               ".Lwd_%=:"
-               :
-               : "s"(__builtin_amdgcn_readfirstlane(rem)), "n"(N2), "n"(N1)
-               : "memory", "scc");
-  __builtin_amdgcn_s_waitcnt(0xC07F);       // lgkmcnt(0) only
-#ifndef PP_QUAD_ABL_NOBAR      /* lab: no barrier (racy) */
-  __builtin_amdgcn_s_barrier();
-#endif
+  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\t"
+               : : "s"(a.lds), "v"(a.voff), "s"(a.sbase) : "memory");
 }
 __device__ __forceinline__ unsigned long long uniform64(const void *p) {
   const unsigned long long v = (unsigned long long)p;
@@ -126,273 +59,10 @@ __device__ __forceinline__ unsigned long long uniform64(const void *p) {
          (unsigned)__builtin_amdgcn_readfirstlane((int)v);
 }
 
-#ifdef PP_GEMM_LAB   // the per-launch form: lab builds only (tools/build_lab.sh), where its ablation switches live
-template <int TM, int TN, int ACT>   // ACT: 0 none, 1 GELU, 2 ReLU
-__global__ __launch_bounds__(256, 1) void gemm_quad_kernel(GemmParams p) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-#ifdef PP_GEMM_TIMELINE
-  const unsigned long long rt_entry = __builtin_amdgcn_s_memrealtime();
-  unsigned long long rt_loop0 = 0, rt_loop1 = 0, ct_loop0 = 0, ct_loop1 = 0;
-#endif
-  constexpr int BM = 32 * TM, BN = 32 * TN, STAGES = 4, BK = 32, RB = 64;   // RB: bytes of K per staged row
-  constexpr int PTA = BM / 16, PT = (BM + BN) / 16;    // 1-KiB DMA pieces (16 rows x 64 B) of a K-tile: A rows, then W rows
-  constexpr int PMAX = (PT + 3) / 4, PREM = PT % 4;    // a wave issues pieces w, w + 4, ...; the last one only if w < PREM
-  constexpr int KA = PTA / 4;                           // pieces k < KA of every wave are A rows, the rest W rows
-  constexpr int KH = (PMAX + 1) / 2;                    // pieces per burst (two bursts per wave and K-tile)
-  constexpr int A_BYTES = BM * RB, STAGE_BYTES = (BM + BN) * RB, RING = STAGES * STAGE_BYTES;
-  constexpr int CS = BN * 2 + 16, CPR = BN / 8;         // staged C row stride (bytes), 16-byte chunks per row
-  constexpr int BIAS_OFF = RING > BM * CS ? RING : BM * CS;
-  static_assert(PTA % 4 == 0, "A pieces split evenly over the four waves");
-  static_assert(4 * PMAX + 2 <= 63, "vmcnt is a 6-bit counter");
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 1, wn = wave & 1;
-  const int frow = lane & 15, fq = lane >> 4;
-  const int epi = p.epilogue;
-
-  int tm, tn;
-  if (p.blocked) {   // XCD-blocked order (see gemm_kernel): speed only
-    constexpr int RM = 8;
-    const int RN = p.rn, RT = RM * RN;
-    const int nbm = (p.tiles_m + RM - 1) / RM, nbn = (p.tiles_n + RN - 1) / RN;
-    const int x = blockIdx.x & 7, j = blockIdx.x >> 3;
-    const int g = (j / RT) * 8 + x, idx = j % RT;
-    if (g >= nbm * nbn) return;
-    const int bmi = g / nbn, bni = g - bmi * nbn;
-    tm = bmi * RM + idx / RN;
-    tn = bni * RN + idx % RN;
-    if (tm >= p.tiles_m || tn >= p.tiles_n) return;
-  } else {
-    tm = blockIdx.x / p.tiles_n;
-    tn = blockIdx.x - tm * p.tiles_n;
-  }
-  const int m0 = tm * BM, n0 = tn * BN;
-  const int nkt = p.Kd / BK;                 // even and >= 4 (host)
-
-  // ---- staging: lane -> (row in piece = lane >> 2, physical chunk = lane & 3); logical chunk = physical ^ perm.
-  // Address = uniform tile base (A + m0 rows / W + n0 rows, advanced by 64 B per K-tile) + a per-lane 32-bit offset
-  // that never changes.  Rows past M / N re-read the last row: their outputs are never stored.
-  const int prow = lane >> 2, pchunk = lane & 3;
-  const int perm_p = (0x1230 >> (4 * ((prow >> 2) & 3))) & 3;      // {0, 3, 2, 1}[(row >> 2) & 3]
-  const int lchunk_off = (pchunk ^ perm_p) * 16;
-  unsigned off[PMAX];
-#pragma unroll
-  for (int k = 0; k < PMAX; ++k) {
-    const int q = wave + 4 * k;               // wave-uniform
-    if (k < KA) off[k] = (unsigned)(min(q * 16 + prow, p.M - 1 - m0) * p.lda * 2 + lchunk_off);
-    else off[k] = (unsigned)(min((min(q, PT - 1) - PTA) * 16 + prow, p.N - 1 - n0) * p.ldw * 2 + lchunk_off);
-  }
-  const unsigned long long baseA = uniform64(p.A + (size_t)m0 * p.lda * 2), baseW = uniform64(p.W + (size_t)n0 * p.ldw * 2);
-  const unsigned lds0 = lds_offset_of(smem);
-  // a wave without a piece PMAX - 1 (PT not a multiple of 4) re-issues its piece PMAX - 2 to the same place instead: every
-  // wave has PMAX pieces per K-tile in its vmcnt queue and the counted waits are the same for all
-  const int has_last = (PREM == 0 || wave < PREM) ? 1 : 0;
-  if (!has_last) off[PMAX - 1] = off[PMAX - 2];
-  const int last_k = has_last ? PMAX - 1 : PMAX - 2;
-  unsigned st_lds = 0;
-  unsigned long long st_A = 0, st_W = 0;
-  auto stage_begin = [&](int kt, int buf) __attribute__((always_inline)) {
-    st_lds = __builtin_amdgcn_readfirstlane(lds0 + buf * STAGE_BYTES + wave * 1024);
-    st_A = baseA + (unsigned)(kt * RB);
-    st_W = baseW + (unsigned)(kt * RB);
-  };
-  auto piece = [&](auto kc) __attribute__((always_inline)) {
-    constexpr int k = decltype(kc)::value;
-    static_assert(PMAX - 2 >= KA, "the re-issued piece is a W piece like the one it stands in for");
-    return QuadPiece{off[k], k < KA ? st_A : st_W,
-                     st_lds + (k == PMAX - 1 ? last_k : k) * 4096};
-  };
-#define PP_QP(K) piece(std::integral_constant<int, (K)>{})
-  // Slot B of a K-tile (B = 0 .. 7, spread evenly over the MFMA sequence).  Staggered (PP_QUAD_BURST 1 / 2): slot B belongs
-  // to wave B & 3 and carries half B >> 2 of that wave's pieces; mask bit B says whether this wave issues it.
-  // Unstaggered (0): slot B carries piece B of every wave (PMAX <= 8).
-  auto stage_slot = [&](auto bc, int mask) __attribute__((always_inline)) {
-    constexpr int B = decltype(bc)::value;
-#if PP_QUAD_BURST == 0
-    if constexpr (B < PMAX) glds_burst<B>(mask, PP_QP(B));
-#else
-    constexpr int h = B >> 2, k0 = h * KH, n = (h == 0 ? KH : PMAX - KH);
-    static_assert(KH == 4 && (PMAX == 7 || PMAX == 8), "bursts of 4 + 3 or 4 + 4 pieces");
-    if constexpr (n == 4) glds_burst<B>(mask, PP_QP(k0), PP_QP(k0 + 1), PP_QP(k0 + 2), PP_QP(k0 + 3));
-    else glds_burst<B>(mask, PP_QP(k0), PP_QP(k0 + 1), PP_QP(k0 + 2));
-#endif
-  };
-#if PP_QUAD_BURST == 0
-  const int my_slots = 0xFF;
-#else
-  const int my_slots = 0x11 << wave;
-#endif
-  // top of a K-tile: at most min(rem, 2) K-tiles of this wave's pieces may stay in flight, then everyone's (barrier)
-  auto top = [&](int rem) __attribute__((always_inline)) { wait_tiles_barrier<2 * PMAX, PMAX>(rem); };
-
-  f32x4 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  // fragment offsets inside a stage: row (w? * tile + 16 i + frow), chunk fq ^ perm[(frow >> 2) & 3]
-  const int perm_f = (0x1230 >> (4 * ((frow >> 2) & 3))) & 3;
-  const unsigned offA = (wm * 16 * TM + frow) * RB + ((fq ^ perm_f) << 4);
-  const unsigned offB = A_BYTES + (wn * 16 * TN + frow) * RB + ((fq ^ perm_f) << 4);
-  auto read_frags = [&](int buf, u32x4 (&fa)[TM], u32x4 (&fb)[TN]) __attribute__((always_inline)) {
-    const char *sb = smem + buf * STAGE_BYTES;
-#pragma unroll
-    for (int j = 0; j < TN; ++j) fb[j] = *reinterpret_cast<const u32x4 *>(sb + offB + j * 16 * RB);
-#pragma unroll
-    for (int i = 0; i < TM; ++i) fa[i] = *reinterpret_cast<const u32x4 *>(sb + offA + i * 16 * RB);
-  };
-  // One K-tile, straight-line code: TM x TN MFMAs from (ca, cb); the fragments of the next K-tile (ring buffer rbuf)
-  // go into (na, nb), two ds_read_b128 per row of MFMAs; when `on`, this wave's DMA pieces of K-tile t + 4 leave in two
-  // bursts, the eight bursts of the four waves spread evenly over the MFMA sequence: a wave's global_load_lds waits for
-  // the CU's one address unit, and four waves that reach their pieces together wait for each other (~55 cycles per
-  // piece measured, with one wave per SIMD all of it off the matrix pipe).
-  auto iter = [&](u32x4 (&ca)[TM], u32x4 (&cb)[TN], u32x4 (&na)[TM], u32x4 (&nb)[TN], int rbuf, int on)
-                  __attribute__((always_inline)) {
-    const char *sb = smem + rbuf * STAGE_BYTES;
-    [&]<int... MI>(std::integer_sequence<int, MI...>) {
-      ([&] {
-        constexpr int m = MI, i = m / TN, j = m % TN;
-#ifndef PP_QUAD_ABL_NOREAD   /* lab: no fragment prefetch (the next K-tile reuses stale fragments; results wrong) */
-        if constexpr (j == 0) {
-          na[i] = *reinterpret_cast<const u32x4 *>(sb + offA + i * 16 * RB);
-          [&]<int... J>(std::integer_sequence<int, J...>) {
-            ([&] {
-              if constexpr ((J * TM) / TN == i) nb[J] = *reinterpret_cast<const u32x4 *>(sb + offB + J * 16 * RB);
-            }(), ...);
-          }(std::make_integer_sequence<int, TN>{});
-        }
-#endif
-        [&]<int... B>(std::integer_sequence<int, B...>) {
-          ([&] {
-#ifndef PP_QUAD_ABL_NOPIECE   /* lab: no DMA statements at all in the K-loop (not even skipped ones) */
-            if constexpr ((B * TM * TN) / 8 == m) stage_slot(std::integral_constant<int, B>{}, on);
-#else
-            (void)B;
-#endif
-          }(), ...);
-        }(std::make_integer_sequence<int, 8>{});
-        mfma_bf16(acc[i][j], cb[j], ca[i]);
-      }(), ...);
-    }(std::make_integer_sequence<int, TM * TN>{});
-  };
-
-  // ---- fill: the bias first (oldest in the queue: every later counted wait retires it), then K-tiles 0 .. 3
-  if (epi & PP_EPI_BIAS) {
-    constexpr int NB = (BN + 255) / 256;
-    if (wave < NB) {
-      const int n = min(n0 + wave * 256 + lane * 4, p.N - 4);
-      glds16(p.bias + n, __builtin_amdgcn_readfirstlane(lds0 + BIAS_OFF + wave * 1024));
-    }
-  }
-#pragma unroll
-  for (int s_ = 0; s_ < STAGES; ++s_) {
-    stage_begin(s_, s_);
-    [&]<int... B>(std::integer_sequence<int, B...>) {
-      (stage_slot(std::integral_constant<int, B>{}, my_slots), ...);
-    }(std::make_integer_sequence<int, 8>{});
-  }
-  u32x4 fa0[TM], fb0[TN], fa1[TM], fb1[TN];
-  wait_vmcnt<3 * PMAX>();
-  __builtin_amdgcn_s_waitcnt(0xC07F);
-  __builtin_amdgcn_s_barrier();
-  read_frags(0, fa0, fb0);
-#ifdef PP_GEMM_TIMELINE
-  rt_loop0 = __builtin_amdgcn_s_memrealtime();
-  ct_loop0 = __builtin_amdgcn_s_memtime();
-#endif
-
-  // ---- ONE loop over all K-tiles, two per trip (the two fragment sets swap roles), no C++ branch inside: whether a
-  // K-tile still requests one is an operand of the DMA statements, and the last K-tile's fragment prefetch reads a ring
-  // buffer nobody uses any more.
-  for (int t = 0, b = 0; t < nkt; t += 2) {          // b = ring buffer of K-tile t
-    top(nkt - 2 - t);
-    stage_begin(t + 4, b);
-#ifdef PP_QUAD_ABL_NODMA      /* lab: K-loop without its DMA pieces (results wrong): what the pieces cost */
-    iter(fa0, fb0, fa1, fb1, (b + 1) & 3, 0);
-#else
-    iter(fa0, fb0, fa1, fb1, (b + 1) & 3, t + 4 < nkt ? my_slots : 0);
-#endif
-    b = (b + 1) & 3;
-    top(nkt - 3 - t);
-    stage_begin(t + 5, b);
-#ifdef PP_QUAD_ABL_NODMA
-    iter(fa1, fb1, fa0, fb0, (b + 1) & 3, 0);
-#else
-    iter(fa1, fb1, fa0, fb0, (b + 1) & 3, t + 5 < nkt ? my_slots : 0);
-#endif
-    b = (b + 1) & 3;
-    // hipcc does not know the asm statements are MFMAs: behind the loop it reads accumulators (v_accvgpr_read / _mov)
-    // right after the MFMA that writes them, a hazard the hardware does not interlock (seen: the first register of the
-    // last MFMA tile of a wave read before the last K-tile had been added).  12 wait states cover an 8-pass MFMA; they
-    // sit at the end of the loop body because register copies may be placed anywhere behind the loop.
-    asm volatile("s_nop 11" ::: "memory");
-  }
-#ifdef PP_GEMM_TIMELINE
-  rt_loop1 = __builtin_amdgcn_s_memrealtime();
-  ct_loop1 = __builtin_amdgcn_s_memtime();
-#endif
-  __builtin_amdgcn_s_waitcnt(0xC07F);
-  __builtin_amdgcn_s_barrier();     // every wave is past its last fragment read: the ring is dead
-
-  // ---- epilogue: bias + activation, the bf16 tile through LDS (row stride CS), then whole rows in 16-byte chunks.
-  // Lane (frow, fq) owns row 16 i + frow and the 4 consecutive columns 16 j + 4 fq .. + 3 of every MFMA tile.
-  const float *lbias = reinterpret_cast<const float *>(smem + BIAS_OFF);
-  const bool has_bias = (epi & PP_EPI_BIAS) != 0;
-#pragma unroll
-  for (int j = 0; j < TN; ++j) {
-    float4 b4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (has_bias) b4 = *reinterpret_cast<const float4 *>(lbias + wn * 16 * TN + j * 16 + fq * 4);
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-      float v[4] = {acc[i][j][0] + b4.x, acc[i][j][1] + b4.y, acc[i][j][2] + b4.z, acc[i][j][3] + b4.w};
-      if constexpr (ACT == 1) gelu4<bf16_t>(v);
-      if constexpr (ACT == 2) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-      }
-      uint2 pk;
-      pk.x = pack_bf16x2(v[0], v[1]);
-      pk.y = pack_bf16x2(v[2], v[3]);
-      *reinterpret_cast<uint2 *>(smem + (wm * 16 * TM + i * 16 + frow) * CS + (wn * 16 * TN + j * 16 + fq * 4) * 2) = pk;
-    }
-  }
-  __syncthreads();
-  const int ncols16 = max(0, min(CPR, (p.N - n0) / 8));
-  const bool headmajor = (epi & PP_EPI_HEADMAJOR) != 0;
-  for (int c = tid; c < BM * CPR; c += 256) {
-    const int lr = c / CPR, cc = c - lr * CPR;
-    const int r = m0 + lr;
-    if (r >= p.M || cc >= ncols16) continue;
-    const uint4 v = *reinterpret_cast<const uint4 *>(smem + lr * CS + cc * 16);
-    size_t off;
-    if (headmajor) {   // [3][heads][M][head_dim]: a 16-byte chunk never straddles a head (head_dim % 8 == 0)
-      const int n = n0 + cc * 8, hd = p.hm_HW, hh = n / hd, d = n - hh * hd;   // hh = which * heads + head
-      off = (((size_t)hh * p.M + r) * hd + d) * 2;
-    } else {
-      off = ((size_t)r * p.ldc + n0 + cc * 8) * 2;
-    }
-    *reinterpret_cast<uint4 *>(p.C + off) = v;
-  }
-#ifdef PP_GEMM_TIMELINE
-  if ((p.epilogue & (1 << 30)) && lane == 0) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned long long rt_end = __builtin_amdgcn_s_memrealtime();
-    unsigned long long *o = reinterpret_cast<unsigned long long *>(const_cast<float *>(p.rowbias)) +
-                            ((size_t)blockIdx.x * 8 + wave) * 8;
-    o[0] = rt_entry; o[1] = rt_loop0; o[2] = rt_loop1; o[3] = rt_end;
-    o[4] = __builtin_amdgcn_s_getreg(63492);
-    o[5] = __builtin_amdgcn_s_getreg(63508);
-    o[6] = ct_loop1 - ct_loop0 + 1; o[7] = (unsigned long long)tm << 32 | (unsigned)tn;
-  }
-#endif
-}
-
-#endif  // PP_GEMM_LAB
-
 // ---------------------------------------------------------------------------------------------------------
 // STREAM form of the quad kernel (tiles 18 / 19): one workgroup per CU walks its tiles as ONE stream of K-tiles.
 //
-// The per-launch form above spends a third of a workgroup's life outside its K-loop (timeline, ViT-B qkv, 192 x 288
+// The per-launch form (removed) spent a third of a workgroup's life outside its K-loop (timeline, ViT-B qkv, 192 x 288
 // tiles: 2.9 us fill + 17.4 us K-loop + 5.3 us epilogue + 0.3 us until the next workgroup starts), and with one wave
 // per SIMD nothing runs beside it.  Here the ring never drains: the last four K-tile slots of a tile already request
 // the next tile's first four K-tiles, and the finished tile leaves without LDS, without a workgroup barrier and without
@@ -420,7 +90,14 @@ __device__ __forceinline__ void store16(const u32x4 &v, unsigned voff, const i32
   // registers late: the next instruction must not overwrite them)
   asm volatile("s_nop 4\n\tbuffer_store_dwordx4 %0, %1, %2, 0 offen\n\ts_nop 1" : : "v"(v), "v"(voff), "s"(srd) : "memory");
 }
-// s_waitcnt vmcnt(sel ? N1 : N0), then lgkmcnt(0) and the barrier as builtins (see wait_tiles_barrier)
+// Top of a K-tile: s_waitcnt vmcnt(sel ? N1 : N0), then lgkmcnt(0) and the barrier as BUILTINS.  The choice between
+// immediates is a branch inside the asm statement on purpose: with 192 - 256 accumulator registers tied to asm MFMAs,
+// any C++-level branch inside the K-loop makes hipcc's allocator split the accumulators' live ranges (hundreds of
+// v_accvgpr moves and scratch spills per K-tile; seen in the ISA).  The lgkmcnt wait and the barrier are builtins
+// because hipcc has to see that the fragment reads of the previous iteration are complete.  With the lgkmcnt wait hidden
+// in asm its wait-count pass assumed them still in flight at the loop header and guarded this iteration's MFMAs with
+// counted lgkmcnt waits that in fact waited for the reads just issued for the NEXT K-tile: ~500 of 1370 cycles per
+// K-tile (measured: the loop ran as long with no DMA piece).
 template <int N1, int N0>
 __device__ __forceinline__ void wait_sel_barrier(int sel) {
   static_assert(N1 <= 63 && N0 <= 63, "vmcnt is a 6-bit counter");
@@ -449,10 +126,6 @@ constexpr int quad_stream_lds_bytes(int TM, int TN) {
 template <int TM, int TN, int ACT>   // ACT: 0 none, 1 GELU, 2 ReLU
 __global__ __launch_bounds__(256, 1) void gemm_quad_stream_kernel(GemmParams p, int vblocks) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-#ifdef PP_GEMM_TIMELINE
-  const unsigned long long rt_entry = __builtin_amdgcn_s_memrealtime();
-  unsigned long long rt_loop0 = 0, rt_loop1 = 0, ct_loop0 = 0, ct_loop1 = 0, ct_conv = 0;
-#endif
   constexpr int BM = 32 * TM, BN = 32 * TN, STAGES = 4, BK = 32, RB = 64;
   constexpr int PTA = BM / 16, PT = (BM + BN) / 16, PMAX = (PT + 3) / 4, PREM = PT % 4, KA = PTA / 4;
   constexpr int A_BYTES = BM * RB, STAGE_BYTES = (BM + BN) * RB, RING = STAGES * STAGE_BYTES;
@@ -480,7 +153,8 @@ __global__ __launch_bounds__(256, 1) void gemm_quad_stream_kernel(GemmParams p, 
   const int nkt = p.Kd / BK;                            // even, >= 16 (host)
   const int G = (int)gridDim.x;
 
-  // virtual block id -> tile: the per-launch kernel's XCD-aware order (G is a multiple of 8: a workgroup stays on its XCD)
+  // virtual block id -> tile: the XCD-aware order of pp_gemm.hip's kernels (G is a multiple of 8: a workgroup stays on
+  // its XCD)
   auto decode = [&](int vb, int &tm, int &tn) __attribute__((always_inline)) -> bool {
     if (p.blocked) {
       constexpr int RM = 8;
@@ -507,9 +181,12 @@ __global__ __launch_bounds__(256, 1) void gemm_quad_stream_kernel(GemmParams p, 
   int vb = next_valid((int)blockIdx.x);
   if (vb < 0) return;
 
-  // ---- staging geometry (see gemm_quad_kernel); the per-lane offsets hold for every tile (M % BM == N % BN == 0)
+  // ---- staging: lane -> (row in piece = lane >> 2, physical chunk = lane & 3); logical chunk = physical ^ perm.
+  // Address = uniform tile base (advanced by 64 B per K-tile) + a per-lane 32-bit offset that holds for every tile
+  // (M % BM == N % BN == 0).  Every wave has PMAX pieces per K-tile in its vmcnt queue: the counted waits are the same
+  // for all.
   const int prow = lane >> 2, pchunk = lane & 3;
-  const int perm_p = (0x1230 >> (4 * ((prow >> 2) & 3))) & 3;
+  const int perm_p = (0x1230 >> (4 * ((prow >> 2) & 3))) & 3;      // {0, 3, 2, 1}[(row >> 2) & 3]
   const int lchunk_off = (pchunk ^ perm_p) * 16;
   const int has_last = (PREM == 0 || wave < PREM) ? 1 : 0;
   const int last_k = has_last ? PMAX - 1 : PMAX - 2;      // a wave without a piece PMAX - 1 re-issues piece PMAX - 2 in its place
@@ -660,10 +337,6 @@ __global__ __launch_bounds__(256, 1) void gemm_quad_stream_kernel(GemmParams p, 
   for (int j = 0; j < TN; ++j) fb0[j] = *reinterpret_cast<const u32x4 *>(smem + offB + j * 16 * RB);
 #pragma unroll
   for (int i = 0; i < TM; ++i) fa0[i] = *reinterpret_cast<const u32x4 *>(smem + offA + i * 16 * RB);
-#ifdef PP_GEMM_TIMELINE
-  rt_loop0 = __builtin_amdgcn_s_memrealtime();
-  ct_loop0 = __builtin_amdgcn_s_memtime();
-#endif
 
   int b = 0;                  // ring buffer of the stream's current K-tile
   // VMEM operations of iteration t of a tile besides its PMAX pieces: the previous tile's chunk stores, the bias piece
@@ -717,11 +390,12 @@ __global__ __launch_bounds__(256, 1) void gemm_quad_stream_kernel(GemmParams p, 
       stage_begin(t + 1);
       iter(fa1, fb1, fa0, fb0, (b + 1) & 3, F, F, nbias, std::integral_constant<int, -1>{});
       b = (b + 1) & 3;
-      asm volatile("s_nop 11" ::: "memory");      // MFMA -> v_accvgpr_read hazard behind the loop (see gemm_quad_kernel)
+      // hipcc does not know the asm statements are MFMAs: behind the loop it reads accumulators (v_accvgpr_read / _mov)
+      // right after the MFMA that writes them, a hazard the hardware does not interlock (seen: the first register of the
+      // last MFMA tile of a wave read before the last K-tile had been added).  12 wait states cover an 8-pass MFMA; they
+      // sit at the end of the loop body because register copies may be placed anywhere behind the loop.
+      asm volatile("s_nop 11" ::: "memory");
     }
-#ifdef PP_GEMM_TIMELINE
-    const unsigned long long cc0 = __builtin_amdgcn_s_memtime();
-#endif
     // -- the finished tile, per wave, no LDS, no barrier: accumulators -> packed 16-byte chunks in registers; they leave from
     // the next tile's first NSI K-tiles, two or three per K-tile (3 % fewer cycles per workgroup than storing them here;
     // a real store takes ~236 cycles out of its wave wherever it is issued: DESIGN 4.1).
@@ -838,53 +512,12 @@ __global__ __launch_bounds__(256, 1) void gemm_quad_stream_kernel(GemmParams p, 
       if (has_next) blocks(std::false_type{});
       else blocks(std::true_type{});
     }
-#ifdef PP_GEMM_TIMELINE
-    ct_conv += __builtin_amdgcn_s_memtime() - cc0;
-#endif
     if (!has_next) break;
     vb = nvb; tm = ntm; tn = ntn; curA = nxtA; curW = nxtW; par ^= 1;
   }
-#ifdef PP_GEMM_TIMELINE
-  rt_loop1 = __builtin_amdgcn_s_memrealtime();
-  ct_loop1 = __builtin_amdgcn_s_memtime();
-#endif
   // ---- the stream's last (unused) K-tile requests must land before the LDS is freed
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifdef PP_GEMM_TIMELINE
-  if ((p.epilogue & (1 << 30)) && lane == 0) {
-    const unsigned long long rt_end = __builtin_amdgcn_s_memrealtime();
-    unsigned long long *o = reinterpret_cast<unsigned long long *>(const_cast<float *>(p.rowbias)) +
-                            ((size_t)blockIdx.x * 8 + wave) * 8;
-    o[0] = rt_entry; o[1] = rt_loop0; o[2] = rt_loop1; o[3] = rt_end;
-    o[4] = __builtin_amdgcn_s_getreg(63492);
-    o[5] = __builtin_amdgcn_s_getreg(63508);
-    o[6] = ct_loop1 - ct_loop0 + 1; o[7] = ct_conv;
-  }
-#endif
 }
-
-#ifdef PP_GEMM_LAB
-template <int TM, int TN>
-static int quad_launch_shape(const GemmParams &p, dim3 grid, hipStream_t s) {
-  constexpr int lds = quad_lds_bytes(TM, TN);
-  static thread_local unsigned long long attr_mask = 0;
-  int dev_ = 0;
-  if (attr_needed(attr_mask, dev_)) {
-    PP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_quad_kernel<TM, TN, 0>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    PP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_quad_kernel<TM, TN, 1>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    PP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_quad_kernel<TM, TN, 2>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-  }
-  if (p.epilogue & PP_EPI_GELU) hipLaunchKernelGGL((gemm_quad_kernel<TM, TN, 1>), grid, dim3(256), lds, s, p);
-  else if (p.epilogue & PP_EPI_RELU) hipLaunchKernelGGL((gemm_quad_kernel<TM, TN, 2>), grid, dim3(256), lds, s, p);
-  else hipLaunchKernelGGL((gemm_quad_kernel<TM, TN, 0>), grid, dim3(256), lds, s, p);
-  PP_CHECK_LAUNCH("gemm_quad_kernel");
-  return 0;
-}
-
-#endif
 
 template <int TM, int TN>
 static int quad_stream_launch_shape(const GemmParams &p, dim3 grid, hipStream_t s) {
@@ -916,24 +549,19 @@ static int quad_stream_launch_shape(const GemmParams &p, dim3 grid, hipStream_t 
   return 0;
 }
 
-// tiles 15 - 20 of pp_gemm (argument checks are the caller's: pp_gemm.hip)
+// tiles 18 - 20 of pp_gemm (argument checks are the caller's: pp_gemm.hip)
 int gemm_quad_launch(const GemmParams &p, int cfg, dim3 grid, hipStream_t s) {
   switch (cfg) {
-#ifdef PP_GEMM_LAB
-    case 15: return quad_launch_shape<8, 8>(p, grid, s);    // 256 x 256, per launch
-    case 16: return quad_launch_shape<8, 6>(p, grid, s);    // 256 x 192
-    case 17: return quad_launch_shape<6, 9>(p, grid, s);    // 192 x 288
-#endif
     case 18: return quad_stream_launch_shape<8, 6>(p, grid, s);   // 256 x 192, stream
     case 19: return quad_stream_launch_shape<6, 9>(p, grid, s);   // 192 x 288, stream
     case 20: return quad_stream_launch_shape<6, 8>(p, grid, s);   // 192 x 256, stream
-    default: return fail("pp_gemm: tile %d (the per-launch four-wave forms 15 - 17) exists in lab builds only", cfg);
+    default: return fail("pp_gemm: tile %d is not a four-wave stream form (tiles 18 - 20)", cfg);
   }
 }
 
 void gemm_quad_tile_shape(int cfg, int *bm, int *bn) {
-  *bm = (cfg == 17 || cfg == 19 || cfg == 20) ? 192 : 256;
-  *bn = (cfg == 15 || cfg == 20) ? 256 : ((cfg == 16 || cfg == 18) ? 192 : 288);
+  *bm = cfg == 18 ? 256 : 192;
+  *bn = cfg == 18 ? 192 : (cfg == 19 ? 288 : 256);
 }
 
 }  // namespace pp

@@ -166,9 +166,6 @@ template <typename T>
 static bool layernorm_rows_launch(const float *x, const float *gamma, const float *beta, float eps, int rows, int C,
                                   T *out, float qscale, hipStream_t s) {
   if ((C & 3) != 0 || C > 1280 || C <= 512 || rows < 2048) return false;   // narrow rows: the one-row form is faster (measured at C = 384)
-#ifdef PP_LN_ONE_ROW
-  return false;
-#endif
   // rows per wave: as close as the variants allow to one round of 4 workgroups (16 waves) per CU on 256 CUs
   const int want = (rows + 4095) / 4096;
   const int rpw = want >= 3 ? 3 : (want >= 2 ? 2 : 1);

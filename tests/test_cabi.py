@@ -68,10 +68,10 @@ def test_gemm_argument_validation_without_gpu(built_lib):
     a = _lib.GemmArgs()
     a.A, a.W, a.C = 0x1000, 0x2000, 0x3000
     a.M, a.N, a.Kd, a.lda, a.ldw, a.ldc, a.batch, a.dtype = 192, 256, 256, 256, 256, 256, 1, _lib.PP_BF16
-    for tile in (11, 12, 21, -1):
+    for tile in (11, 12, 15, 17, 21, -1):
         a.tile = tile
         assert built_lib.pp_gemm(C.byref(a), None) != 0 and b"tile" in built_lib.pp_last_error()
-    # the four-wave forms: 15 - 17 (per launch) exist in lab builds only; the stream forms 18 - 20 take whole tiles, K >= 512, bf16
+    # the four-wave forms: 15 - 17 (per launch, lab builds only) are removed; the stream forms 18 - 20 take whole tiles, K >= 512, bf16
     a.tile = 16
     assert built_lib.pp_gemm(C.byref(a), None) != 0 and b"lab builds" in built_lib.pp_last_error()
     a.M, a.N, a.Kd, a.lda, a.ldw, a.ldc = 300, 576, 512, 512, 512, 576
