@@ -458,6 +458,40 @@ int pp_heat_clamp(const float *p, float *out, long long n, float scale, void *st
 int pp_heat_tail_backward(const float *p, const float *g, int B, int K, int HW, float scale, int sparse,
                           float temperature, void *dz, int ldz, int dtype, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Training ScratchViTBackbone (ScratchViTBackbone(differentiable=True) in .train() mode).  Differentiate the timm
+ * VisionTransformer that probpose/backbone.py:23-40 builds (reached through ScratchViTBackbone.forward, model.py:10-11):
+ *   Block.norm1 / norm2 and the final norm (LayerNorm, eps 1e-6)   (pp_layernorm_backward)
+ *   Mlp.act (nn.GELU, exact erf) on the f32 fc1 pre-activation       (pp_gelu_forward, pp_gelu_backward)
+ *   Attention.forward: softmax(q k^T hd^-1/2) v                      (pp_attention_backward)
+ *   the pos_embed add of _pos_embed                                  (pp_rows_period_sum)
+ * The Linear layers' data gradients run on pp_gemm with transposed weights, their weight / bias gradients on
+ * pp_wgrad_gemm.  No allocation, no host sync; every reduction in a fixed order (no float atomics).
+ *
+ * pp_layernorm_backward: x [rows, C] f32 the LayerNorm's input (the statistics are recomputed as pp_layernorm takes
+ *   them), gamma [C] f32, dy [rows, C] f32 (row pitch ldy) the gradient of its output ->
+ *   dres [rows, C] f32 (+)= rstd (gamma dy - mean(gamma dy) - xhat mean(gamma dy xhat)) (accumulate = 1 adds, 0
+ *   overwrites), dres_c [rows, C] in dtype = the new dres; dgamma = sum dy xhat, dbeta = sum dy [C] f32 (either may be
+ *   NULL; fixed-order float64 partials).  ws: pp_layernorm_backward_workspace_bytes(rows, C) bytes, 8-byte aligned.
+ * pp_gelu_forward: out[i] = x Phi(x) in dtype (x [n] f32);  pp_gelu_backward: dx[i] = g (Phi(x) + x phi(x)) in dtype
+ *   (x, g [n] f32).  16-byte aligned buffers.
+ * pp_attention_backward: qkv [B*N, 3*heads*hd] in dtype laid out as pp_attention reads it, out / dout [B*N, heads*hd]
+ *   (the forward's output and its gradient) -> dqkv [B*N, 3*heads*hd] (dq, dk, dv in qkv's layout).  head_dim 32 / 64,
+ *   any N; PP_F32 or PP_BF16 storage, f32 arithmetic.  ws: pp_attention_backward_workspace_bytes(B, N, heads) bytes
+ *   (the rows' log-sum-exp and rowsum(dout o out)).
+ * pp_rows_period_sum: out[n, c] = sum_b x[(b N + n) C + c] (b ascending), x [B*N, C] f32, out [N, C] f32.
+ * ---------------------------------------------------------------------- */
+long long pp_layernorm_backward_workspace_bytes(int rows, int C);
+int pp_layernorm_backward(const float *x, const float *gamma, float eps, int rows, int C, const float *dy,
+                          long long ldy, float *dres, int accumulate, void *dres_c, int dtype, float *dgamma,
+                          float *dbeta, void *ws, void *stream);
+int pp_gelu_forward(const float *x, long long n, void *out, int dtype, void *stream);
+int pp_gelu_backward(const float *x, const float *g, long long n, void *dx, int dtype, void *stream);
+long long pp_attention_backward_workspace_bytes(int B, int N, int heads);
+int pp_attention_backward(const void *qkv, const void *out, const void *dout, void *dqkv, int B, int N, int heads,
+                          int hd, int dtype, void *ws, void *stream);
+int pp_rows_period_sum(const float *x, int B, int N, int C, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -107,6 +107,13 @@ _SIGNATURES = {
     "pp_aux_tail_backward": (C.c_int, [_vp] * 4 + [_i, _i, _i] + [_vp] * 3 + [_i, _vp]),
     "pp_heat_clamp": (C.c_int, [_vp, _vp, C.c_longlong, _f, _vp]),
     "pp_heat_tail_backward": (C.c_int, [_vp, _vp, _i, _i, _i, _f, _i, _f, _vp, _i, _i, _vp]),
+    "pp_layernorm_backward_workspace_bytes": (C.c_longlong, [_i, _i]),
+    "pp_layernorm_backward": (C.c_int, [_vp, _vp, _f, _i, _i, _vp, C.c_longlong, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp]),
+    "pp_gelu_forward": (C.c_int, [_vp, C.c_longlong, _vp, _i, _vp]),
+    "pp_gelu_backward": (C.c_int, [_vp, _vp, C.c_longlong, _vp, _i, _vp]),
+    "pp_attention_backward_workspace_bytes": (C.c_longlong, [_i, _i, _i]),
+    "pp_attention_backward": (C.c_int, [_vp] * 4 + [_i] * 5 + [_vp, _vp]),
+    "pp_rows_period_sum": (C.c_int, [_vp, _i, _i, _i, _vp, _vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

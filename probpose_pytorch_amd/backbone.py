@@ -13,7 +13,7 @@ from __future__ import annotations
 import torch
 from torch import nn
 
-from . import _lib, engine, ops
+from . import _lib, engine, ops, vit_train
 
 _DEFAULT_DTYPE = torch.float32
 
@@ -67,12 +67,15 @@ class VisionTransformer(nn.Module):
     absolute pos-emb (1,N,C), pre-LN blocks, final ``norm``)."""
 
     def __init__(self, img_size=(256, 192), patch_size: int = 16, in_chans: int = 3, embed_dim: int = 384,
-                 depth: int = 12, num_heads: int = 12, mlp_ratio: float = 4.0):
+                 depth: int = 12, num_heads: int = 12, mlp_ratio: float = 4.0, differentiable: bool = False):
         super().__init__()
         if in_chans != 3:
             raise ValueError("the HIP patch-embed path is built for 3-channel crops")
         self.embed_dim = self.num_features = embed_dim
         self.num_heads = num_heads
+        # True: in .train() mode with grad enabled and a parameter that requires grad, the forward runs as one
+        # differentiable node with a HIP backward (vit_train.py); otherwise the inference path runs unchanged
+        self.differentiable = differentiable
         self.patch_embed = PatchEmbed(img_size, patch_size, in_chans, embed_dim)
         self.pos_embed = nn.Parameter(torch.zeros(1, self.patch_embed.num_patches, embed_dim))
         self.blocks = nn.Sequential(*[Block(embed_dim, num_heads, mlp_ratio) for _ in range(depth)])
@@ -104,8 +107,14 @@ class VisionTransformer(nn.Module):
         self._plan(batches[0].device).calibrate(batches, margin)
         return self
 
+    def _trains(self) -> bool:
+        return (self.differentiable and self.training and torch.is_grad_enabled()
+                and any(p.requires_grad for p in self.parameters()))
+
     def forward_tokens(self, x: torch.Tensor) -> torch.Tensor:
         """(B,3,H,W) -> device-resident tokens [B*N, C] in the compute dtype (HIP only)."""
+        if self._trains():
+            return vit_train.train_forward(self, x)
         _lib.require_device(x)
         x = x.detach().contiguous().float()
         return self._plan(x.device).forward_tokens(x)
@@ -130,10 +139,19 @@ class ScratchViTBackbone(nn.Module):
     ViT-B/L/H configurations of BASELINE.json."""
 
     def __init__(self, input_image_size, patch_size: int, embed_dim: int = 384, depth: int = 12,
-                 num_heads: int = 12, mlp_ratio: float = 4.0):
+                 num_heads: int = 12, mlp_ratio: float = 4.0, differentiable: bool = False):
         super().__init__()
         self.model = VisionTransformer(img_size=input_image_size, patch_size=patch_size, embed_dim=embed_dim,
-                                       depth=depth, num_heads=num_heads, mlp_ratio=mlp_ratio)
+                                       depth=depth, num_heads=num_heads, mlp_ratio=mlp_ratio,
+                                       differentiable=differentiable)
+
+    @property
+    def differentiable(self) -> bool:
+        return self.model.differentiable
+
+    @differentiable.setter
+    def differentiable(self, value: bool):
+        self.model.differentiable = bool(value)
 
     def set_compute_dtype(self, dtype: torch.dtype):
         ops.dtype_code(dtype)
@@ -142,6 +160,8 @@ class ScratchViTBackbone(nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """(B,3,H,W) -> (B,C,gh,gw) float32 contiguous (backbone.py:35-40)."""
+        if self.model._trains():
+            return vit_train.train_forward(self.model, x, nchw=True)
         B, _, height, width = x.shape
         tokens = self.model.forward_tokens(x)
         gh, gw = self.model.patch_embed.dynamic_feat_size((height, width))

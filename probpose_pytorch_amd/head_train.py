@@ -247,7 +247,7 @@ class _HeadTrainFn(torch.autograd.Function):
         params = head_parameters(head)
         pidx = {id(p): i for i, p in enumerate(params)}
         grads = [None] * len(params)
-        x_needs = S["nchw"] and need[1]
+        x_needs = need[1]          # NCHW x, or channels-last tokens that carry a gradient (a training backbone)
 
         def wants(p):
             return p is not None and need[4 + pidx[id(p)]]
@@ -388,7 +388,10 @@ class _HeadTrainFn(torch.autograd.Function):
                         ops.gemm(dY, wt, gtok, M=M, N=C, Kd=9 * len(brs) * C, lda=4 * C, ldw=9 * len(brs) * C,
                                  ldc=C, rowoff=tab, seg_len=C, residual=gtok, epilogue=EPI_OUT_F32)
         gx = None
-        if x_needs:
+        if x_needs and not S["nchw"]:
+            # the token gradient as it is, f32 [B*h*w, C] (autograd casts it to the tokens' dtype)
+            gx = gtok if gtok is not None else torch.zeros((B * h * w, C), dtype=torch.float32, device=dev)
+        elif x_needs:
             if gtok is None:
                 gx = torch.zeros((B, C, h, w), dtype=torch.float32, device=dev)
             else:
@@ -409,8 +412,8 @@ def _aux0_dgrad_table(B, h, w, C, brs, dev):
 
 
 def train_forward(head, x: torch.Tensor = None, tokens: torch.Tensor = None, geom=None):
-    """The train-mode forward of ``head``: from an NCHW feature map ``x`` (gradient to x when it requires grad) or
-    from channels-last ``tokens`` [B*h*w, C] in the compute dtype, geom = (B, h, w) (no gradient to them)."""
+    """The train-mode forward of ``head``: from an NCHW feature map ``x`` or from channels-last ``tokens`` [B*h*w, C]
+    in the compute dtype, geom = (B, h, w); the gradient reaches either when it requires grad."""
     check_trainable(head)
     params = head_parameters(head)
     if x is not None:
@@ -425,7 +428,8 @@ def train_forward(head, x: torch.Tensor = None, tokens: torch.Tensor = None, geo
         B, h, w = geom
         if tokens.dtype != head.compute_dtype:
             raise TypeError(f"tokens are {tokens.dtype}, the head computes in {head.compute_dtype}")
-        inp, is_nchw, shape = tokens.detach(), False, (B, head.in_channels, h, w)
+        inp = tokens if tokens.requires_grad else tokens.detach()
+        is_nchw, shape = False, (B, head.in_channels, h, w)
         dev = tokens.device
     for p in params:
         if p.device != dev:

@@ -37,10 +37,11 @@ class ProbPoseModel(nn.Module):
     def forward(self, x: Tensor):
         if isinstance(self.backbone, ScratchViTBackbone) and isinstance(self.head, ProbMapHead) \
                 and self.head.training and self.head.differentiable and torch.is_grad_enabled() \
+                and not self.backbone.differentiable \
                 and any(p.requires_grad for p in self.backbone.parameters()):
             raise RuntimeError("ProbPoseModel: the HIP ScratchViTBackbone has no backward, so its parameters would get "
                                "no gradient; call model.backbone.requires_grad_(False) to train the head on a frozen "
-                               "backbone")
+                               "backbone, or construct it with differentiable=True")
         if isinstance(self.backbone, ScratchViTBackbone) and isinstance(self.head, ProbMapHead) \
                 and self.backbone.model.token_dtype == self.head.compute_dtype:
             B, _, height, width = x.shape

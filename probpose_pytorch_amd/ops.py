@@ -384,3 +384,56 @@ def heat_tail_backward(p, g, B, K, HW, scale, sparse, temperature, dz):
                                                          dtype_code(dz.dtype), _lib.stream_ptr()))
     _lib.check(rc, "pp_heat_tail_backward")
     return dz
+
+
+# ---- training ViT backbone (pp_vit_grad.hip) ------------------------------------------------------------------
+def layernorm_backward(x, gamma, eps, dy, dres, dres_c, accumulate, dgamma=None, dbeta=None, ws=None):
+    """dres (+)= the LayerNorm input gradient of x [rows, C] f32 given dy [rows, C] f32; dres_c = dres in its dtype;
+    dgamma / dbeta [C] f32 (optional)."""
+    rows, Cc = x.shape
+    if ws is None:
+        ws = torch.empty(int(_lib.lib().pp_layernorm_backward_workspace_bytes(rows, Cc)), dtype=torch.uint8,
+                         device=x.device)
+    rc = _timed("ln_backward", float(rows * Cc * 20),
+                lambda: _lib.lib().pp_layernorm_backward(_p(x), _p(gamma), float(eps), rows, Cc, _p(dy), dy.stride(0),
+                                                         _p(dres), int(accumulate), _p(dres_c),
+                                                         dtype_code(dres_c.dtype), _p(dgamma), _p(dbeta), _p(ws),
+                                                         _lib.stream_ptr()))
+    _lib.check(rc, "pp_layernorm_backward")
+    return dres
+
+
+def gelu_forward(x, out):
+    """out = GELU(x) (exact erf) in out's dtype; x f32 contiguous."""
+    rc = _timed("gelu", float(x.numel() * (4 + out.element_size())),
+                lambda: _lib.lib().pp_gelu_forward(_p(x), x.numel(), _p(out), dtype_code(out.dtype),
+                                                   _lib.stream_ptr()))
+    _lib.check(rc, "pp_gelu_forward")
+    return out
+
+
+def gelu_backward(x, g, dx):
+    """dx = g * GELU'(x) in dx's dtype; x, g f32 contiguous."""
+    rc = _timed("gelu_backward", float(x.numel() * (8 + dx.element_size())),
+                lambda: _lib.lib().pp_gelu_backward(_p(x), _p(g), x.numel(), _p(dx), dtype_code(dx.dtype),
+                                                    _lib.stream_ptr()))
+    _lib.check(rc, "pp_gelu_backward")
+    return dx
+
+
+def attention_backward(qkv, out, dout, dqkv, B, N, heads, hd, ws=None):
+    """dqkv [B*N, 3C] = the gradient of pp_attention (row-layout qkv) given its output and the output's gradient."""
+    if ws is None:
+        ws = torch.empty(int(_lib.lib().pp_attention_backward_workspace_bytes(B, N, heads)), dtype=torch.uint8,
+                         device=qkv.device)
+    rc = _timed("attention_backward", 10.0 * B * heads * N * N * hd,
+                lambda: _lib.lib().pp_attention_backward(_p(qkv), _p(out), _p(dout), _p(dqkv), B, N, heads, hd,
+                                                         dtype_code(qkv.dtype), _p(ws), _lib.stream_ptr()))
+    _lib.check(rc, "pp_attention_backward")
+    return dqkv
+
+
+def rows_period_sum(x, B, N, Cc, out):
+    """out [N, C] = sum over b of x [B*N, C] (f32, fixed order): the pos_embed gradient."""
+    _lib.check(_lib.lib().pp_rows_period_sum(_p(x), B, N, Cc, _p(out), _lib.stream_ptr()), "pp_rows_period_sum")
+    return out
