@@ -492,6 +492,42 @@ int pp_attention_backward(const void *qkv, const void *out, const void *dout, vo
                           int hd, int dtype, void *ws, void *stream);
 int pp_rows_period_sum(const float *x, int B, int N, int C, float *out, void *stream);
 
+/* ------------------------------------------------------------------------
+ * FusedAdamW (probpose_pytorch_amd/optim.py): train.py:113-115's clip_grad_norm_ + AdamW.step() over all parameter
+ * tensors in at most three launches, no host sync, no float atomics.  All tensors contiguous float32.
+ *
+ * The device table (8-byte aligned) that the kernels read:
+ *   header  32 B  {uint32 magic, int32 n_tensors, n_groups, n_chunks, chunk_elems, pad, int32 *arrive}
+ *   groups  n_groups x 40 B  {lr, beta1, beta2, eps, weight_decay} f64
+ *   tensors n_tensors x 56 B {float *p, *g, *exp_avg, *exp_avg_sq, *step; int64 count; int32 group, pad}
+ *   chunks  n_chunks x 8 B   {int32 tensor, chunk within the tensor}: one workgroup per chunk of at most
+ *                            PP_OPTIM_CHUNK elements of one tensor
+ * `step` points at the tensor's own step count t (one float32 on the device, torch's state["step"]); `arrive` at
+ * n_tensors zeroed int32 on the device (left zero by every launch).
+ * pp_optim_table_bytes: the table's size for these element counts, -1 (and pp_last_error) on bad arguments.
+ * pp_optim_table_build: checks every argument on the host and packs the table into HOST memory `table`; hyper is
+ *   [n_groups][5] f64 in the groups' order.  with_chunks = 0 leaves the chunk map unwritten (it depends on the counts
+ *   only).  *prefix_bytes = the bytes ahead of the chunk map, what changes from step to step.
+ * pp_grad_sqnorm_partials: partials[chunk] = sum of g^2 over the chunk in float64, fixed order.
+ * pp_grad_norm_finish: one workgroup adds the partials in a fixed order -> record (16 B on the device):
+ *   {f32 total_norm, f32 clip_coef = clip ? min(1, max_norm / (total_norm + 1e-6)) : 1, int32 finite,
+ *    int32 skipped_steps (+1 when count_skips and the norm is inf or NaN)}.
+ * pp_adamw_step: per element, with g' = g clip_coef (1 when record is NULL) and t = *step + 1:
+ *     p = p (1 - lr wd);  m = beta1 m + (1 - beta1) g';  v = beta2 v + (1 - beta2) g' g'
+ *     p = p - (lr / (1 - beta1^t)) m / (sqrt(v) / sqrt(1 - beta2^t) + eps);   *step = t
+ *   skip_nonfinite (needs record): a step whose record says "not finite" changes nothing.
+ * ---------------------------------------------------------------------- */
+#define PP_OPTIM_CHUNK 8192
+long long pp_optim_table_bytes(int n_tensors, const long long *counts, int n_groups);
+int pp_optim_table_build(int n_tensors, const void *const *p, const void *const *g, const void *const *m,
+                         const void *const *v, const void *const *step, const long long *counts, const int *group,
+                         int n_groups, const double *hyper, void *arrive, void *table, int with_chunks, int *n_chunks,
+                         long long *prefix_bytes);
+int pp_grad_sqnorm_partials(const void *table, int n_chunks, double *partials, void *stream);
+int pp_grad_norm_finish(const double *partials, int n_chunks, int clip, double max_norm, int count_skips, void *record,
+                        void *stream);
+int pp_adamw_step(const void *table, int n_chunks, const void *record, int skip_nonfinite, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

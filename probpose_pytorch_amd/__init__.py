@@ -12,7 +12,7 @@ from .util import to_numpy  # noqa: F401
 from .codec import ArgMaxProbMap, Codec, ProbMap  # noqa: F401
 from .heatmap import get_heatmap_expected_value  # noqa: F401
 
-__all__ = ["to_numpy", "Codec", "ProbMap", "ArgMaxProbMap", "get_heatmap_expected_value"]
+__all__ = ["to_numpy", "Codec", "ProbMap", "ArgMaxProbMap", "get_heatmap_expected_value", "FusedAdamW"]
 
 
 def __getattr__(name):  # lazy: the nn.Module side pulls in the engine
@@ -25,4 +25,7 @@ def __getattr__(name):  # lazy: the nn.Module side pulls in the engine
     if name == "ProbMapHead":
         from .head import ProbMapHead
         return ProbMapHead
+    if name == "FusedAdamW":
+        from .optim import FusedAdamW
+        return FusedAdamW
     raise AttributeError(name)
