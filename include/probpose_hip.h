@@ -279,6 +279,46 @@ int pp_frontend_crop_resize(const unsigned char *image, int img_w, int img_h, lo
                             int out_w, int out_h, float *out, void *stream);
 
 /* ------------------------------------------------------------------------
+ * Multi-source front end: pp_frontend_crop_resize with a source image PER BOX, so that one launch resizes a training
+ * batch of crops cut from different images (dataset.py:116-122 for a whole batch).  The sources lie in one packed
+ * uint8 buffer; box c reads the region sources[c] = {byte offset into the buffer, width, height, row stride in bytes}
+ * (int64 each, RGB, 3 bytes per pixel) and boxes_xyxy[c] is in that region's pixel frame (pixels outside the region
+ * are zero, as Image.crop pads).  Several boxes may name the same region.
+ *
+ * Every offset must be a multiple of PP_FRONTEND_SRC_ALIGN, and every region must end at least PP_FRONTEND_SRC_PAD
+ * bytes before the end of the buffer (src_bytes): the kernel loads dwords that start at any byte of a region's rows,
+ * never one that starts outside them, so with that padding no load leaves the buffer, the last region's included.
+ * pp_frontend_multi_plan_build (HOST, no GPU needed) checks both and emits the same bounds and 22-bit coefficient
+ * tables as pp_frontend_plan_build, the source records, and one workgroup table (box, first output row) over the
+ * whole batch: ONE launch.  The plan must be 8-byte aligned on the device.  Per box the result has the bits that
+ * pp_frontend_crop_resize gives for the same box on the same pixels.
+ * ---------------------------------------------------------------------- */
+#define PP_FRONTEND_SRC_ALIGN 4
+#define PP_FRONTEND_SRC_PAD 4
+long long pp_frontend_multi_plan_bytes(int n_boxes, const int *boxes_xyxy, int out_w, int out_h);   /* < 0: error */
+int pp_frontend_multi_plan_build(int n_boxes, const int *boxes_xyxy, const long long *sources, long long src_bytes,
+                                 int out_w, int out_h, void *plan, int *n_blocks_out, long long *lds_bytes_out);
+int pp_frontend_crop_resize_multi(const unsigned char *src, const void *plan_dev, int n_boxes, int n_blocks,
+                                  long long lds_bytes, int out_w, int out_h, float *out, void *stream);
+
+/* ------------------------------------------------------------------------
+ * Ground truth of a training batch apart from the maps (dataset.py:87-89, :121-135; codec.py:176-178, :195-204), all
+ * on the device.  kpts_raw [B,K,3] f32: (x, y, v) in image pixels, v in {0, 2} (a labelled 1 is 2 already);
+ * boxes_xywh [B,4] f64: the UN-rounded boxes.  Writes
+ *   kpts_crop [B,K,2] f32   (x - f32(box_x)) / f32(box_w) * f32(in_w), likewise y: three separate IEEE float32
+ *                           operations, as numpy evaluates scale_box on a float32 array
+ *   kpts_hm   [B,K,2] f32   kpts_crop / scale (float32 division; scale = (input - 1) / (heatmap - 1) in float32)
+ *   encode_visible [B,K] f32  1 where v == 2, else 0: the `visible` input of pp_encode_probmaps
+ *   in_image  [B,K] u8      0 <= x < in_w and 0 <= y < in_h on kpts_crop
+ *   keypoints_visible [B,K] u8   v == 2
+ *   keypoints_visibility [B,K] f32   min(v, 1)
+ * ---------------------------------------------------------------------- */
+int pp_dataset_ground_truth(const float *kpts_raw, const double *boxes_xywh, int B, int K, int in_w, int in_h,
+                            float scale_x, float scale_y, float *kpts_crop, float *kpts_hm, float *encode_visible,
+                            unsigned char *in_image, unsigned char *keypoints_visible, float *keypoints_visibility,
+                            void *stream);
+
+/* ------------------------------------------------------------------------
  * Training targets: the OKS probability maps of ProbMap.encode, batched over crops.  Replaces
  *   generate_probmaps   probpose/codec.py:11-70  (called from ProbMap.encode, codec.py:176-182)
  * kpts_hm [B,K,2] f32: keypoints in HEATMAP pixels (= keypoints / scale_factor, codec.py:178);

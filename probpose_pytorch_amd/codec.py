@@ -65,6 +65,43 @@ class ProbMap:
             s = np.full_like(s, float(self.sigma))
         return 2 * s
 
+    def _two_s_device(self, dev) -> torch.Tensor:
+        """``_two_s()`` on ``dev``: uploaded once per codec (and again only when sigmas / sigma / heatmap_size were
+        changed afterwards), not once per call."""
+        two_s = self._two_s()
+        key = (str(dev), two_s.tobytes())
+        hit = getattr(self, "_two_s_cache", None)
+        if hit is None or hit[0] != key:
+            hit = (key, torch.from_numpy(two_s).to(dev))
+            self._two_s_cache = hit
+        return hit[1]
+
+    def encode_device_tensors(self, kpts_hm: torch.Tensor, visible: torch.Tensor):
+        """The launch of ``encode_device`` on inputs that are on the GPU already: kpts_hm (B, K, 2) float32 keypoints
+        in HEATMAP pixels (= keypoints / scale_factor), visible (B, K) float32 -> (heatmaps (B, K, H, W) f32,
+        keypoint_weights (B, K) f32).  No host round trip and no synchronisation."""
+        _lib.require_device(kpts_hm)
+        _lib.require_device(visible)
+        if kpts_hm.dtype != torch.float32 or visible.dtype != torch.float32:
+            raise TypeError("encode_device_tensors takes float32 tensors")
+        if kpts_hm.dim() != 3 or kpts_hm.shape[2] != 2 or tuple(visible.shape) != tuple(kpts_hm.shape[:2]):
+            raise ValueError(f"kpts_hm {tuple(kpts_hm.shape)} / visible {tuple(visible.shape)}: expected (B, K, 2) / "
+                             "(B, K)")
+        kpts_hm, visible = kpts_hm.contiguous(), visible.contiguous()
+        B, K = int(kpts_hm.shape[0]), int(kpts_hm.shape[1])
+        W, H = self.heatmap_size
+        dev = kpts_hm.device
+        d_s = self._two_s_device(dev)
+        if d_s.numel() != K:
+            raise ValueError(f"{K} keypoints but {d_s.numel()} sigmas")
+        heat = torch.empty((B, K, H, W), dtype=torch.float32, device=dev)
+        wts = torch.empty((B, K), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            rc = _lib.lib().pp_encode_probmaps(_lib.ptr(kpts_hm), _lib.ptr(visible), _lib.ptr(d_s), B, K, H, W,
+                                               _lib.ptr(heat), _lib.ptr(wts), _lib.stream_ptr())
+        _lib.check(rc, "pp_encode_probmaps")
+        return heat, wts
+
     def encode_device(self, keypoints, keypoints_visible=None):
         """Batched target generation on the GPU: keypoints (B, K, 2) in input-image pixels (numpy or tensor),
         visibility (B, K) or None -> (heatmaps (B, K, H, W) f32, keypoint_weights (B, K) f32) device tensors.
@@ -75,20 +112,10 @@ class ProbMap:
         vis = (np.ones((B, K), dtype=np.float32) if keypoints_visible is None else
                np.asarray(keypoints_visible.cpu() if isinstance(keypoints_visible, torch.Tensor) else keypoints_visible))
         hm_kp = (kp[..., :2] / self.scale_factor).astype(np.float32)      # codec.py:178, float32 like the reference
-        W, H = self.heatmap_size
         dev = torch.device("cuda", torch.cuda.current_device())
         d_kp = torch.from_numpy(np.ascontiguousarray(hm_kp)).to(dev)
         d_vis = torch.from_numpy(np.ascontiguousarray(vis, dtype=np.float32)).to(dev)
-        d_s = torch.from_numpy(self._two_s()).to(dev)
-        if d_s.numel() != K:
-            raise ValueError(f"{K} keypoints but {d_s.numel()} sigmas")
-        heat = torch.empty((B, K, H, W), dtype=torch.float32, device=dev)
-        wts = torch.empty((B, K), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = _lib.lib().pp_encode_probmaps(_lib.ptr(d_kp), _lib.ptr(d_vis), _lib.ptr(d_s), B, K, H, W,
-                                               _lib.ptr(heat), _lib.ptr(wts), _lib.stream_ptr())
-        _lib.check(rc, "pp_encode_probmaps")
-        return heat, wts
+        return self.encode_device_tensors(d_kp, d_vis)
 
     def encode(self, keypoints, keypoints_visible=None, id_similarity=0.0, keypoints_visibility=None) -> dict:
         """Reference codec.py:138-212: single-instance keypoints (1, K, D) in input-image pixels -> the target

@@ -37,6 +37,10 @@ constexpr size_t FE_LDS_TARGET = 64 * 1024, FE_LDS_MAX = 152 * 1024;
 enum { H_X0 = 0, H_Y0, H_CW, H_CH, H_KSH, H_KSV, H_COEF_OFF, H_SRC_OFF, H_OFF_BH, H_OFF_KH, H_OFF_BV, H_OFF_KV,
        H_NEED_H, H_NEED_V, H_RB, H_STAGED };
 constexpr int FE_SRC_ROWS = 8;              // source rows staged in LDS per trip of the horizontal pass
+// multi-source plans: per box one record of four int64 {byte offset into the packed source buffer, width, height,
+// row stride in bytes} = FE_SRC_WORDS int32 words, stored between the headers and the block table
+constexpr int FE_SRC_WORDS = 8;
+constexpr long long FE_SRC_ALIGN = PP_FRONTEND_SRC_ALIGN, FE_SRC_PAD = PP_FRONTEND_SRC_PAD;
 
 static inline double fe_sinc(double x) {
   if (x == 0.0) return 1.0;
@@ -148,14 +152,25 @@ __device__ __forceinline__ int fe_clip8(int v) {   // Pillow clip8: lookup of v 
   return v < 0 ? 0 : (v > 255 ? 255 : v);
 }
 
+// MULTI = false: every box reads the one frame the arguments describe.  MULTI = true: `image` is the packed source
+// buffer and each box reads its own region of it, described by the box's source record in the plan; the box is in that
+// region's pixel frame.  Everything after the record is read is the same code.
+template <bool MULTI>
 __global__ __launch_bounds__(FE_THREADS) void crop_resize_kernel(const unsigned char *__restrict__ image, int img_w,
                                                                  int img_h, long long img_stride,
                                                                  const int *__restrict__ plan, int n_boxes,
                                                                  int out_w, int out_h, float *__restrict__ out) {
   extern __shared__ __attribute__((aligned(16))) unsigned char tmp[];   // [span][out_w][3] u8
-  // block table behind the headers: (box, first output row)
-  const int *bt = plan + (size_t)n_boxes * FE_HDR + 2 * blockIdx.x;
+  // block table behind the headers (and the source records): (box, first output row)
+  const int *bt = plan + (size_t)n_boxes * (FE_HDR + (MULTI ? FE_SRC_WORDS : 0)) + 2 * blockIdx.x;
   const int c = bt[0], r0 = bt[1];
+  if (MULTI) {
+    const long long *rec = reinterpret_cast<const long long *>(plan + (size_t)n_boxes * FE_HDR) + 4 * c;
+    image += rec[0];
+    img_w = (int)rec[1];
+    img_h = (int)rec[2];
+    img_stride = rec[3];
+  }
   const int *h = plan + (size_t)c * FE_HDR;
   const int x0 = h[H_X0], y0 = h[H_Y0], ksh = h[H_KSH], ksv = h[H_KSV];
   const int *bh = plan + h[H_OFF_BH], *kh = plan + h[H_OFF_KH], *bv = plan + h[H_OFF_BV], *kv = plan + h[H_OFF_KV];
@@ -334,12 +349,13 @@ __global__ __launch_bounds__(FE_THREADS) void crop_resize_kernel(const unsigned 
 // ---- C ABI ------------------------------------------------------------------------------------------
 using namespace pp;
 
-extern "C" long long pp_frontend_plan_bytes(int n_boxes, const int *boxes_xyxy, int out_w, int out_h) {
+// words of a plan: headers, (multi-source: source records,) block table, tables
+static long long fe_plan_bytes(const char *who, int n_boxes, const int *boxes_xyxy, int out_w, int out_h, bool multi) {
   if (n_boxes < 0 || out_w <= 0 || out_h <= 0 || (n_boxes > 0 && !boxes_xyxy)) {
-    fail("pp_frontend_plan_bytes: bad arguments");
+    fail("%s: bad arguments", who);
     return -1;
   }
-  size_t words = (size_t)n_boxes * FE_HDR;
+  size_t words = (size_t)n_boxes * (FE_HDR + (multi ? FE_SRC_WORDS : 0));
   for (int c = 0; c < n_boxes; ++c) {
     FeBox b;
     if (fe_prepare(boxes_xyxy + 4 * c, out_w, out_h, fe_rb_max(n_boxes, out_h), b, false) != 0) return -1;
@@ -348,12 +364,13 @@ extern "C" long long pp_frontend_plan_bytes(int n_boxes, const int *boxes_xyxy, 
   return (long long)(words * sizeof(int));
 }
 
-// Fills `plan` (host memory, pp_frontend_plan_bytes bytes) and returns the launch geometry.
-extern "C" int pp_frontend_plan_build(int n_boxes, const int *boxes_xyxy, int out_w, int out_h, void *plan,
-                                      int *n_blocks_out, long long *lds_bytes_out) {
+// Fills `plan` (host memory, fe_plan_bytes bytes) and returns the launch geometry.  sources != nullptr: a multi-source
+// plan, sources [n][4] int64 already checked by the caller.
+static int fe_plan_build(const char *who, int n_boxes, const int *boxes_xyxy, const long long *sources, int out_w,
+                         int out_h, void *plan, int *n_blocks_out, long long *lds_bytes_out) {
   PP_REQUIRE(n_boxes >= 0 && out_w > 0 && out_h > 0 && plan && n_blocks_out && lds_bytes_out &&
                  (n_boxes == 0 || boxes_xyxy),
-             "pp_frontend_plan_build: bad arguments");
+             "%s: bad arguments", who);
   int *w = static_cast<int *>(plan);
   std::vector<FeBox> bx((size_t)n_boxes);
   int nblocks = 0;
@@ -382,6 +399,10 @@ extern "C" int pp_frontend_plan_build(int n_boxes, const int *boxes_xyxy, int ou
     lds = std::max(lds, bx[c].lds);
   }
   size_t off = (size_t)n_boxes * FE_HDR;
+  if (sources) {   // 64 B of headers per box in front: the int64 records are 8-byte aligned when the plan is
+    memcpy(w + off, sources, (size_t)n_boxes * FE_SRC_WORDS * sizeof(int));
+    off += (size_t)n_boxes * FE_SRC_WORDS;
+  }
   int blk = 0;
   for (int c = 0; c < n_boxes; ++c)   // block table: (box, first output row)
     for (int r0 = 0; r0 < out_h; r0 += bx[c].rb) {
@@ -416,11 +437,40 @@ extern "C" int pp_frontend_plan_build(int n_boxes, const int *boxes_xyxy, int ou
     put(H_OFF_KH, b.kh);
     put(H_OFF_BV, b.bv);
     put(H_OFF_KV, b.kv);
-    PP_REQUIRE(off < (1ull << 31), "pp_frontend_plan_build: plan exceeds 2^31 words");
+    PP_REQUIRE(off < (1ull << 31), "%s: plan exceeds 2^31 words", who);
   }
   *n_blocks_out = nblocks;
   *lds_bytes_out = (long long)lds;
   return 0;
+}
+
+template <bool MULTI>
+static int fe_launch(const char *who, const unsigned char *image, int img_w, int img_h, long long img_stride,
+                     const void *plan_dev, int n_boxes, int n_blocks, long long lds_bytes, int out_w, int out_h,
+                     float *out, void *stream) {
+  PP_REQUIRE(lds_bytes > 0 && (size_t)lds_bytes <= FE_LDS_MAX, "%s: bad LDS size %lld", who, lds_bytes);
+  if (lds_bytes > 64 * 1024) {
+    static thread_local unsigned long long attr_mask = 0;
+    int dev_ = 0;
+    if (attr_needed(attr_mask, dev_))
+      PP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(crop_resize_kernel<MULTI>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)FE_LDS_MAX));
+  }
+  hipLaunchKernelGGL(crop_resize_kernel<MULTI>, dim3((unsigned)n_blocks), dim3(FE_THREADS), (size_t)lds_bytes,
+                     (hipStream_t)stream, image, img_w, img_h, img_stride, static_cast<const int *>(plan_dev), n_boxes,
+                     out_w, out_h, out);
+  PP_CHECK_LAUNCH("crop_resize_kernel");
+  return 0;
+}
+
+extern "C" long long pp_frontend_plan_bytes(int n_boxes, const int *boxes_xyxy, int out_w, int out_h) {
+  return fe_plan_bytes("pp_frontend_plan_bytes", n_boxes, boxes_xyxy, out_w, out_h, false);
+}
+
+extern "C" int pp_frontend_plan_build(int n_boxes, const int *boxes_xyxy, int out_w, int out_h, void *plan,
+                                      int *n_blocks_out, long long *lds_bytes_out) {
+  return fe_plan_build("pp_frontend_plan_build", n_boxes, boxes_xyxy, nullptr, out_w, out_h, plan, n_blocks_out,
+                       lds_bytes_out);
 }
 
 extern "C" int pp_frontend_crop_resize(const unsigned char *image, int img_w, int img_h, long long img_stride,
@@ -431,17 +481,40 @@ extern "C" int pp_frontend_crop_resize(const unsigned char *image, int img_w, in
              "pp_frontend_crop_resize: bad shape");
   if (n_boxes == 0 || n_blocks == 0) return 0;
   PP_REQUIRE(image && plan_dev && out, "pp_frontend_crop_resize: null pointer");
-  PP_REQUIRE(lds_bytes > 0 && (size_t)lds_bytes <= FE_LDS_MAX, "pp_frontend_crop_resize: bad LDS size %lld", lds_bytes);
-  if (lds_bytes > 64 * 1024) {
-    static thread_local unsigned long long attr_mask = 0;
-    int dev_ = 0;
-    if (attr_needed(attr_mask, dev_))
-      PP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(crop_resize_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)FE_LDS_MAX));
+  return fe_launch<false>("pp_frontend_crop_resize", image, img_w, img_h, img_stride, plan_dev, n_boxes, n_blocks,
+                          lds_bytes, out_w, out_h, out, stream);
+}
+
+// ---- multi-source: every box has its own region of one packed source buffer ----------------------------------------
+extern "C" long long pp_frontend_multi_plan_bytes(int n_boxes, const int *boxes_xyxy, int out_w, int out_h) {
+  return fe_plan_bytes("pp_frontend_multi_plan_bytes", n_boxes, boxes_xyxy, out_w, out_h, true);
+}
+
+extern "C" int pp_frontend_multi_plan_build(int n_boxes, const int *boxes_xyxy, const long long *sources,
+                                            long long src_bytes, int out_w, int out_h, void *plan, int *n_blocks_out,
+                                            long long *lds_bytes_out) {
+  const char *who = "pp_frontend_multi_plan_build";
+  PP_REQUIRE(n_boxes >= 0 && src_bytes >= 0 && (n_boxes == 0 || sources), "%s: bad arguments", who);
+  for (int c = 0; c < n_boxes; ++c) {
+    const long long off = sources[4 * c], sw = sources[4 * c + 1], sh = sources[4 * c + 2], st = sources[4 * c + 3];
+    PP_REQUIRE(sw > 0 && sh > 0 && sw < (1ll << 28) && sh < (1ll << 31) && st >= 3 * sw && st < (1ll << 40),
+               "%s: source %d is %lld x %lld with a row stride of %lld bytes", who, c, sw, sh, st);
+    PP_REQUIRE(off >= 0 && off % FE_SRC_ALIGN == 0,
+               "%s: source %d starts at byte %lld, not a multiple of %lld (misaligned)", who, c, off, FE_SRC_ALIGN);
+    // the last row holds 3 * width bytes, whatever the stride
+    PP_REQUIRE(off + (sh - 1) * st + 3 * sw + FE_SRC_PAD <= src_bytes,
+               "%s: source %d (bytes %lld to %lld, plus %lld of padding) reaches past the end of the %lld-byte buffer",
+               who, c, off, off + (sh - 1) * st + 3 * sw, FE_SRC_PAD, src_bytes);
   }
-  hipLaunchKernelGGL(crop_resize_kernel, dim3((unsigned)n_blocks), dim3(FE_THREADS), (size_t)lds_bytes,
-                     (hipStream_t)stream, image, img_w, img_h, img_stride, static_cast<const int *>(plan_dev), n_boxes,
-                     out_w, out_h, out);
-  PP_CHECK_LAUNCH("crop_resize_kernel");
-  return 0;
+  return fe_plan_build(who, n_boxes, boxes_xyxy, sources, out_w, out_h, plan, n_blocks_out, lds_bytes_out);
+}
+
+extern "C" int pp_frontend_crop_resize_multi(const unsigned char *src, const void *plan_dev, int n_boxes, int n_blocks,
+                                             long long lds_bytes, int out_w, int out_h, float *out, void *stream) {
+  PP_REQUIRE(n_boxes >= 0 && n_blocks >= 0 && out_w > 0 && out_h > 0, "pp_frontend_crop_resize_multi: bad shape");
+  if (n_boxes == 0 || n_blocks == 0) return 0;
+  PP_REQUIRE(src && plan_dev && out, "pp_frontend_crop_resize_multi: null pointer");
+  PP_REQUIRE(reinterpret_cast<uintptr_t>(plan_dev) % 8 == 0, "pp_frontend_crop_resize_multi: the plan is not 8-byte aligned");
+  return fe_launch<true>("pp_frontend_crop_resize_multi", src, 0, 0, 0, plan_dev, n_boxes, n_blocks, lds_bytes, out_w,
+                         out_h, out, stream);
 }

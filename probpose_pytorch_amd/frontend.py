@@ -73,6 +73,58 @@ def crop_resize(image: torch.Tensor, boxes_xywh, input_size: Sequence[int], plan
     return out
 
 
+SRC_ALIGN, SRC_PAD = 4, 4     # PP_FRONTEND_SRC_ALIGN / PP_FRONTEND_SRC_PAD of include/probpose_hip.h
+
+
+def multi_plan_bytes(boxes_xyxy: np.ndarray, input_size: Sequence[int]) -> int:
+    """Bytes of the multi-source plan for these integer boxes (host only)."""
+    boxes = np.ascontiguousarray(boxes_xyxy, dtype=np.int32).reshape(-1, 4)
+    nbytes = _lib.lib().pp_frontend_multi_plan_bytes(int(boxes.shape[0]), boxes.ctypes.data_as(C.c_void_p),
+                                                     int(input_size[0]), int(input_size[1]))
+    if nbytes < 0:
+        _lib.check(-1, "pp_frontend_multi_plan_bytes")
+    return int(nbytes)
+
+
+def multi_plan_build(boxes_xyxy: np.ndarray, sources: np.ndarray, src_bytes: int, input_size: Sequence[int],
+                     plan_ptr: int) -> Tuple[int, int]:
+    """Build the multi-source plan (host only, no GPU) into the ``multi_plan_bytes`` bytes of host memory at
+    ``plan_ptr``.  boxes_xyxy [n, 4] int32, each in the pixel frame of its own source; sources [n, 4] int64 =
+    (byte offset into the packed source buffer, width, height, row stride in bytes); src_bytes: that buffer's size.
+    Offsets must be multiples of SRC_ALIGN and every region must end SRC_PAD bytes before the end of the buffer.
+    Returns (workgroups of the launch, LDS bytes per workgroup)."""
+    boxes = np.ascontiguousarray(boxes_xyxy, dtype=np.int32).reshape(-1, 4)
+    src = np.ascontiguousarray(sources, dtype=np.int64).reshape(-1, 4)
+    if src.shape[0] != boxes.shape[0]:
+        raise ValueError(f"{boxes.shape[0]} boxes but {src.shape[0]} source records")
+    nb, lds = C.c_int(0), C.c_longlong(0)
+    _lib.check(_lib.lib().pp_frontend_multi_plan_build(int(boxes.shape[0]), boxes.ctypes.data_as(C.c_void_p),
+                                                       src.ctypes.data_as(C.c_void_p), int(src_bytes),
+                                                       int(input_size[0]), int(input_size[1]), C.c_void_p(plan_ptr),
+                                                       C.byref(nb), C.byref(lds)), "pp_frontend_multi_plan_build")
+    return int(nb.value), int(lds.value)
+
+
+def crop_resize_multi(src: torch.Tensor, plan_dev: torch.Tensor, n: int, n_blocks: int, lds_bytes: int,
+                      input_size: Sequence[int]) -> torch.Tensor:
+    """One launch over n boxes that each read their own region of the packed uint8 source buffer ``src`` (on the GPU),
+    as the device copy ``plan_dev`` of a ``multi_plan_build`` plan (built for a buffer of at most ``src.numel()``
+    bytes) describes.  Returns (n, 3, h, w) float32 in [0, 1]; per box the bits of ``crop_resize``."""
+    _lib.require_device(src)
+    _lib.require_device(plan_dev)
+    if src.dtype != torch.uint8 or not src.is_contiguous():
+        raise TypeError("src must be a contiguous uint8 tensor")
+    out_w, out_h = int(input_size[0]), int(input_size[1])
+    out = torch.empty((n, 3, out_h, out_w), dtype=torch.float32, device=src.device)
+    if n == 0:
+        return out
+    with torch.cuda.device(src.device):
+        rc = _lib.lib().pp_frontend_crop_resize_multi(_lib.ptr(src), _lib.ptr(plan_dev), n, n_blocks, lds_bytes,
+                                                      out_w, out_h, _lib.ptr(out), _lib.stream_ptr())
+    _lib.check(rc, "pp_frontend_crop_resize_multi")
+    return out
+
+
 def scale_box(image: torch.Tensor, bbox, image_size: Tuple[int, int], kps: np.ndarray):
     """Reference dataset.py:71-90 for one box: returns (crop (3, h, w) f32 in [0,1] on the GPU, kps)
     with the keypoints moved into the crop's pixel frame (kps is modified in place, like the
