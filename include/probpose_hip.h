@@ -319,6 +319,38 @@ int pp_dataset_ground_truth(const float *kpts_raw, const double *boxes_xywh, int
                             void *stream);
 
 /* ------------------------------------------------------------------------
+ * Augmented training batches (YOLOPoseDataset(augment=...); geometry: DESIGN §4.4c).  The host folds flip, scale,
+ * rotation and shift into two 2x3 matrices per sample; one launch warps the batch, one moves the keypoints.
+ *
+ * pp_augment_warp: src and sources are the packed buffer and the {byte offset, width, height, row stride} int64
+ * records of the multi-source front end, under the same alignment and padding rules.  warp [n, 8] f64 per sample:
+ * m00 m01 m02 m10 m11 m12 c b.  For output pixel (u, v): x = (m00 * u + m01 * v) + m02, y likewise with m1., in
+ * float64 in this order: the region's pixel-index coordinates (pixel (i, j) centred at (i, j)).  Bilinear over the
+ * taps floor(x), floor(x) + 1 (and y), a tap outside the region being zero, with float32 weights fx = f32(x -
+ * floor(x)) and 1 - fx: top = p00 * wx0 + p01 * wx1, bot = p10 * wx0 + p11 * wx1, val = top * wy0 + bot * wy1, then
+ * val / 255 and clamp(f32(c) * val + f32(b), 0, 1).  out [n, 3, in_h, in_w] f32.  The taps are read bytewise inside
+ * the region's rows only.
+ *
+ * pp_dataset_ground_truth_affine: pp_dataset_ground_truth with kp_affine [B, 8] f32 per sample (a00 a01 a02 a10 a11
+ * a12 flip 0) in place of the boxes: kpts_crop = ((a00 * kx + a01 * ky) + a02, (a10 * kx + a11 * ky) + a12) in
+ * float32 in this order.  Where flip is 1, output slot k takes coordinates and visibility of source keypoint
+ * perm[k] (perm [K] int32, an involution).  Every other output is formed from kpts_crop as pp_dataset_ground_truth
+ * forms it.
+ *
+ * pp_augment_check (HOST, no GPU needed) refuses what the launches cannot check on device memory: a region that
+ * breaks the rules of pp_frontend_multi_plan_build, a matrix or colour term that is not finite (or beyond 1e12), a
+ * singular matrix, a flip flag other than 0 or 1, and a permutation that leaves 0..K-1 or is not an involution.
+ * ---------------------------------------------------------------------- */
+int pp_augment_check(int n, const long long *sources, long long src_bytes, const double *warp,
+                     const float *kp_affine, int K, const int *perm);
+int pp_augment_warp(const unsigned char *src, const long long *sources, const double *warp, int n, int in_w,
+                    int in_h, float *out, void *stream);
+int pp_dataset_ground_truth_affine(const float *kpts_raw, const float *kp_affine, const int *perm, int B, int K,
+                                   int in_w, int in_h, float scale_x, float scale_y, float *kpts_crop,
+                                   float *kpts_hm, float *encode_visible, unsigned char *in_image,
+                                   unsigned char *keypoints_visible, float *keypoints_visibility, void *stream);
+
+/* ------------------------------------------------------------------------
  * Training targets: the OKS probability maps of ProbMap.encode, batched over crops.  Replaces
  *   generate_probmaps   probpose/codec.py:11-70  (called from ProbMap.encode, codec.py:176-182)
  * kpts_hm [B,K,2] f32: keypoints in HEATMAP pixels (= keypoints / scale_factor, codec.py:178);

@@ -13,3 +13,5 @@ for _name in ("model", "backbone", "head", "codec", "heatmap", "util", "inferenc
 
 # the reference keeps its losses and its evaluation metrics in one file, probpose/loss.py; probpose_pytorch_amd.loss
 # holds the losses (loss.py:18-712) and re-exports the metrics (loss.py:715-866) from probpose_pytorch_amd.metrics
+
+from probpose_pytorch_amd.dataset import Augment  # noqa: E402,F401  (probpose.Augment, as probpose.dataset.Augment)

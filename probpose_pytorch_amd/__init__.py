@@ -12,7 +12,8 @@ from .util import to_numpy  # noqa: F401
 from .codec import ArgMaxProbMap, Codec, ProbMap  # noqa: F401
 from .heatmap import get_heatmap_expected_value  # noqa: F401
 
-__all__ = ["to_numpy", "Codec", "ProbMap", "ArgMaxProbMap", "get_heatmap_expected_value", "FusedAdamW"]
+__all__ = ["to_numpy", "Codec", "ProbMap", "ArgMaxProbMap", "get_heatmap_expected_value", "FusedAdamW",
+           "Augment"]
 
 
 def __getattr__(name):  # lazy: the nn.Module side pulls in the engine
@@ -28,4 +29,7 @@ def __getattr__(name):  # lazy: the nn.Module side pulls in the engine
     if name == "FusedAdamW":
         from .optim import FusedAdamW
         return FusedAdamW
+    if name == "Augment":
+        from .dataset import Augment
+        return Augment
     raise AttributeError(name)

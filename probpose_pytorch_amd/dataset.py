@@ -12,10 +12,20 @@ the integer crop region out of it (``__getitem__``, CPU only); ``collate`` assem
   ``pp_encode_probmaps`` on those device buffers.
 
 No host synchronisation and no per-sample launch.  There is no CPU fallback: ``collate`` needs the GPU.
+
+With ``augment=Augment(...)`` the samples are flipped, scaled, rotated, shifted and colour-jittered on the way: the
+worker draws the sample's parameters from a counter-based generator keyed by (seed, epoch, index) and cuts the bounding
+rectangle of the transformed box; ``collate`` folds the geometry into two 2x3 matrices per sample and replaces launches
+one and two by ``pp_augment_warp`` (bilinear) and ``pp_dataset_ground_truth_affine`` (csrc/pp_augment.hip).  With
+``augment=None`` nothing changes.
 """
 from __future__ import annotations
 
+import ctypes as C
+import math
+from dataclasses import dataclass
 from pathlib import Path
+from typing import Sequence, Tuple
 
 import numpy as np
 import PIL.Image
@@ -77,6 +87,111 @@ def parse_annotations(split_folder: Path, target_single_class: int | None = None
     return annotations
 
 
+@dataclass(frozen=True)
+class Augment:
+    """Random augmentation of a training sample, applied on the GPU by ``YOLOPoseDataset.collate``.
+
+    flip_pairs   (i, j) keypoint index pairs that trade places under a horizontal flip; disjoint, below K
+    flip_prob    probability of the flip
+    scale        (lo, hi): a uniform factor on the box size; above 1 shows more context
+    rotate_deg   the angle is uniform in +-rotate_deg, applied with probability rotate_prob
+    shift        uniform +- fraction of the box width / height added to the box centre
+    brightness   b uniform in +-brightness;  contrast: c uniform in 1 +- contrast;  pixel = clamp(c * x + b, 0, 1)
+    seed         key of the generator
+
+    For output pixel (u, v) of an in_w x in_h crop: n = ((u + 0.5) / in_w - 0.5, (v + 0.5) / in_h - 0.5); with flip
+    n.x = -n.x; p = (n.x * bw * s, n.y * bh * s); the source point is centre + (tx * bw, ty * bh) + R(theta) p in image
+    pixels with pixel centres at half-integers, R(theta) = [[cos, -sin], [sin, cos]].  The box is stretched to the
+    input size as the un-augmented path stretches it; the rotation is a rotation in image space.  The pixels are
+    bilinear, not LANCZOS: identity parameters give the un-augmented geometry, not its bits."""
+    flip_pairs: Sequence[Tuple[int, int]] = ()
+    flip_prob: float = 0.5
+    scale: Tuple[float, float] = (0.75, 1.25)
+    rotate_deg: float = 40.0
+    rotate_prob: float = 0.6
+    shift: float = 0.0
+    brightness: float = 0.2
+    contrast: float = 0.2
+    seed: int = 0
+
+    def __post_init__(self):
+        object.__setattr__(self, "flip_pairs", tuple((int(i), int(j)) for i, j in self.flip_pairs))
+        object.__setattr__(self, "scale", (float(self.scale[0]), float(self.scale[1])))
+        if not 0 < self.scale[0] <= self.scale[1]:
+            raise ValueError(f"Augment: scale={self.scale}; expected 0 < lo <= hi")
+        if not (0 <= self.flip_prob <= 1 and 0 <= self.rotate_prob <= 1):
+            raise ValueError("Augment: flip_prob and rotate_prob are probabilities")
+        if self.shift < 0 or self.brightness < 0 or self.contrast < 0 or self.rotate_deg < 0 or self.seed < 0:
+            raise ValueError("Augment: shift, brightness, contrast, rotate_deg and seed must not be negative")
+
+    def draw(self, epoch: int, idx: int) -> np.ndarray:
+        """float64 [flip (0 or 1), s, theta (radians), tx, ty, c, b] of sample ``idx`` in epoch ``epoch``: a pure
+        function of (seed, epoch, idx).  Eight uniforms are drawn whatever the settings, so that changing one setting
+        leaves the other parameters of every sample as they were."""
+        r = np.random.Generator(np.random.Philox(key=int(self.seed), counter=[int(epoch), int(idx), 0, 0])).random(8)
+        lo, hi = self.scale
+        theta = math.radians((2.0 * r[3] - 1.0) * self.rotate_deg) if r[2] < self.rotate_prob else 0.0
+        return np.array([1.0 if r[0] < self.flip_prob else 0.0, lo + r[1] * (hi - lo), theta,
+                         (2.0 * r[4] - 1.0) * self.shift, (2.0 * r[5] - 1.0) * self.shift,
+                         1.0 + (2.0 * r[6] - 1.0) * self.contrast, (2.0 * r[7] - 1.0) * self.brightness],
+                        dtype=np.float64)
+
+    def permutation(self, K: int) -> np.ndarray:
+        """int32 [K]: the keypoint that output slot k of a flipped sample reads."""
+        perm = np.arange(K, dtype=np.int32)
+        seen = set()
+        for i, j in self.flip_pairs:
+            if not (0 <= i < K and 0 <= j < K):
+                raise ValueError(f"Augment: flip pair ({i}, {j}) with {K} keypoints")
+            if i == j or i in seen or j in seen:
+                raise ValueError(f"Augment: flip pair ({i}, {j}) repeats a keypoint index")
+            seen.update((i, j))
+            perm[i], perm[j] = j, i
+        return perm
+
+
+def augment_region(bbox, params) -> Tuple[int, int, int, int]:
+    """(x0, y0, x1, y1) of the pixels the warp of a sample can read: the bounding rectangle of the scaled, rotated,
+    shifted box, rounded outward, plus the one pixel on every side that a bilinear tap next to its edge reaches."""
+    x, y, bw, bh = (float(v) for v in bbox)
+    _, s, theta, tx, ty, _, _ = (float(v) for v in params)
+    cx, cy = x + bw / 2 + tx * bw, y + bh / 2 + ty * bh
+    hw, hh, co, si = bw * s / 2, bh * s / 2, math.cos(theta), math.sin(theta)
+    xs = [cx + co * px - si * py for px in (-hw, hw) for py in (-hh, hh)]
+    ys = [cy + si * px + co * py for px in (-hw, hw) for py in (-hh, hh)]
+    return (math.floor(min(xs)) - 1, math.floor(min(ys)) - 1, math.ceil(max(xs)) + 1, math.ceil(max(ys)) + 1)
+
+
+def augment_matrices(bboxes, origins, params, input_size):
+    """The geometry of ``Augment`` as matrices, numpy float64, for B samples at once.  bboxes [B, 4] un-rounded
+    [x, y, w, h], origins [B, 2] of the regions in image pixels, params [B, 7] of ``Augment.draw``.  Returns
+    (pixel [B, 2, 3], keypoint [B, 2, 3]): ``pixel`` maps an output pixel index (u, v, 1) to the region's pixel-index
+    coordinates (pixel (i, j) centred at (i, j): the half-integer centres of image and crop are folded in);
+    ``keypoint`` maps an image-pixel keypoint (kx, ky, 1) to crop coordinates (the frame of the un-augmented
+    ``scale_box``: the crop's left edge at 0, its right edge at in_w)."""
+    bboxes, origins, params = (np.asarray(a, dtype=np.float64) for a in (bboxes, origins, params))
+    in_w, in_h = float(input_size[0]), float(input_size[1])
+    bw, bh = bboxes[:, 2], bboxes[:, 3]
+    f = 1.0 - 2.0 * params[:, 0]
+    s, theta = params[:, 1], params[:, 2]
+    cx = bboxes[:, 0] + bw / 2 + params[:, 3] * bw
+    cy = bboxes[:, 1] + bh / 2 + params[:, 4] * bh
+    co, si = np.cos(theta), np.sin(theta)
+    gx, gy = f * bw * s / in_w, bh * s / in_h                 # source pixels per output pixel along the box's axes
+    pixel = np.empty((len(bboxes), 2, 3))
+    pixel[:, 0, 0], pixel[:, 0, 1] = co * gx, -si * gy
+    pixel[:, 1, 0], pixel[:, 1, 1] = si * gx, co * gy
+    hu, hv = 0.5 - in_w / 2, 0.5 - in_h / 2
+    pixel[:, 0, 2] = cx - origins[:, 0] - 0.5 + pixel[:, 0, 0] * hu + pixel[:, 0, 1] * hv
+    pixel[:, 1, 2] = cy - origins[:, 1] - 0.5 + pixel[:, 1, 0] * hu + pixel[:, 1, 1] * hv
+    keypoint = np.empty((len(bboxes), 2, 3))
+    keypoint[:, 0, 0], keypoint[:, 0, 1] = co / gx, si / gx
+    keypoint[:, 1, 0], keypoint[:, 1, 1] = -si / gy, co / gy
+    keypoint[:, 0, 2] = in_w / 2 - keypoint[:, 0, 0] * cx - keypoint[:, 0, 1] * cy
+    keypoint[:, 1, 2] = in_h / 2 - keypoint[:, 1, 0] * cx - keypoint[:, 1, 1] * cy
+    return pixel, keypoint
+
+
 class _RawBatch(list):
     """The samples of a batch that a DataLoader worker hands to the main process uncollated."""
 
@@ -94,23 +209,50 @@ class YOLOPoseDataset(Dataset):
     """Reference dataset.py:93-135 with the per-sample pixel and target work moved into ``collate`` (module
     docstring).  ``codec`` is a ``Codec`` whose ``probmap`` gives input_size [w, h], heatmap_size [W, H] and sigmas."""
 
-    def __init__(self, root: Path, split: str, codec, target_single_class: int | None = None):
+    def __init__(self, root: Path, split: str, codec, target_single_class: int | None = None,
+                 augment: Augment | None = None):
+        if augment is not None and not isinstance(augment, Augment):
+            raise TypeError(f"YOLOPoseDataset: augment must be an Augment or None, not {type(augment).__name__}")
         self.root = root
         self.split = split
         self.codec = codec
         self.target_single_class = target_single_class
+        self.augment = augment
+        self.epoch = 0
         self.annotations = parse_annotations(Path(root) / split, target_single_class)
         self._staging = []           # [(pinned host buffer, event after its last copy)]
+        self._perm = None            # (K, device, host int32 [K], device int32 [K]) of the flip permutation
 
     def __getstate__(self):          # workers started by spawn get a copy: without the pinned buffers and their events
         state = dict(self.__dict__)
         state["_staging"] = []
+        state["_perm"] = None
         return state
+
+    def set_epoch(self, epoch: int):
+        """The epoch that keys the augmentation parameters.  Call it before iterating a loader: its workers take the
+        value with their copy of the dataset when the iteration starts."""
+        self.epoch = int(epoch)
 
     def __len__(self):
         return len(self.annotations)
 
     def __getitem__(self, idx):
+        """CPU only.  Without ``augment``: ``plain_item(idx)``.  With it: (region, keypoints, bbox, origin, params),
+        where params float64 (7,) is ``augment.draw(epoch, idx)``, region the uint8 (h, w, 3) pixels of ``image.crop``
+        of ``augment_region(bbox, params)`` (zero outside the frame) and origin int64 (2,) that rectangle's corner."""
+        if getattr(self, "augment", None) is None:
+            return self.plain_item(idx)
+        ann = self.annotations[idx]
+        bbox = np.asarray(ann["bbox"], dtype=np.float64)
+        params = self.augment.draw(self.epoch, idx)
+        x0, y0, x1, y1 = augment_region(bbox, params)
+        with PIL.Image.open(ann["image_path"]) as im:
+            region = np.asarray(im.convert("RGB").crop((x0, y0, x1, y1)), dtype=np.uint8)
+        return (np.ascontiguousarray(region), np.array(ann["keypoints"], dtype=np.float32).reshape(-1, 3), bbox,
+                np.array([x0, y0], dtype=np.int64), params)
+
+    def plain_item(self, idx):
         """CPU only.  Returns (region, keypoints, bbox): the uint8 (h, w, 3) pixels of ``image.crop`` of the rounded
         box (all that Pillow's resize reads; zero outside the frame), the keypoints float32 (K, 3) in image pixels
         and the un-rounded bbox float64 (4,)."""
@@ -153,6 +295,8 @@ class YOLOPoseDataset(Dataset):
         return offs, total
 
     def _collate_device(self, samples):
+        if len(samples) and len(samples[0]) == 5:
+            return self._launch_augmented(*self._upload_augmented(samples))
         return self._launch(*self._upload(samples))
 
     def _upload(self, samples):
@@ -220,6 +364,91 @@ class YOLOPoseDataset(Dataset):
         return img, dict(heatmaps=heat, in_image=flags[0], keypoints_visible=flags[1],
                          keypoints_visibility=f32[5].view(B, 1, K))
 
+    # ---- the augmented batch: the same two copies, then warp, keypoints, maps ---------------------------------------
+    def _permutation(self, K, dev):
+        """The flip permutation for K keypoints, validated and uploaded once per dataset."""
+        if self._perm is None or self._perm[:2] != (K, dev):
+            perm = self.augment.permutation(K)
+            self._perm = (K, dev, perm, torch.from_numpy(perm).to(dev))
+        return self._perm[2], self._perm[3]
+
+    def _upload_augmented(self, samples):
+        """Host half of the augmented ``collate``: pack the regions (copy 1); build the source records, the two
+        matrices per sample in float64 and the keypoints into the meta buffer (copy 2); have the library check them."""
+        _lib.require_device()
+        if self.augment is None:
+            raise ValueError("YOLOPoseDataset.collate: augmented samples, but the dataset has augment=None")
+        B = len(samples)
+        pm = self.codec.probmap
+        in_w, in_h = int(pm.input_size[0]), int(pm.input_size[1])
+        K = int(samples[0][1].shape[0])
+        for s in samples:
+            region, kps = s[0], s[1]
+            if len(s) != 5:
+                raise ValueError("YOLOPoseDataset.collate: augmented and un-augmented samples in one batch")
+            if region.dtype != np.uint8 or region.ndim != 3 or region.shape[2] != 3 or region.size == 0:
+                raise ValueError(f"YOLOPoseDataset.collate: a region of shape {region.shape}, dtype {region.dtype}")
+            if kps.shape != (K, 3):
+                raise ValueError(f"YOLOPoseDataset.collate: keypoints of shapes {(K, 3)} and {kps.shape} in one batch")
+        dev = torch.device("cuda", torch.cuda.current_device())
+        perm, d_perm = self._permutation(K, dev)
+        shapes = [s[0].shape[:2] for s in samples]
+        offs, total = self.pack_layout(shapes)
+        # copy 1: the pixels
+        slot = self._staging_buffer(total)
+        host = slot[0].numpy()
+        for s, off in zip(samples, offs):
+            host[off:off + s[0].size] = s[0].reshape(-1)
+        d_src = torch.empty(total, dtype=torch.uint8, device=dev)
+        d_src.copy_(slot[0][:total], non_blocking=True)
+        slot[1].record()
+        # copy 2: [B x 4 i64 source records][B x 8 f64 pixel matrix, c, b][B x 8 f32 keypoint matrix, flip, 0][keypoints]
+        params = np.stack([s[4] for s in samples])
+        pixel, keypoint = augment_matrices(np.stack([s[2] for s in samples]), np.stack([s[3] for s in samples]),
+                                           params, (in_w, in_h))
+        warp_off, aff_off, kp_off = 32 * B, 96 * B, 128 * B
+        meta_bytes = kp_off + 12 * B * K
+        slot = self._staging_buffer(meta_bytes)
+        host = slot[0].numpy()
+        host[:warp_off].view(np.int64).reshape(B, 4)[:] = [[off, w, h, 3 * w] for off, (h, w) in zip(offs, shapes)]
+        warp = host[warp_off:aff_off].view(np.float64).reshape(B, 8)
+        warp[:, :6], warp[:, 6], warp[:, 7] = pixel.reshape(B, 6), params[:, 5], params[:, 6]
+        aff = host[aff_off:kp_off].view(np.float32).reshape(B, 8)
+        aff[:, :6], aff[:, 6], aff[:, 7] = keypoint.reshape(B, 6), params[:, 0], 0.0
+        host[kp_off:meta_bytes].view(np.float32).reshape(B, K, 3)[:] = [s[1] for s in samples]
+        base = slot[0].data_ptr()
+        _lib.check(_lib.lib().pp_augment_check(B, C.c_void_p(base), total, C.c_void_p(base + warp_off),
+                                               C.c_void_p(base + aff_off), K, perm.ctypes.data_as(C.c_void_p)),
+                   "pp_augment_check")
+        d_meta = torch.empty(meta_bytes, dtype=torch.uint8, device=dev)
+        d_meta.copy_(slot[0][:meta_bytes], non_blocking=True)
+        slot[1].record()
+        return d_src, d_meta, d_perm, B, K
+
+    def _launch_augmented(self, d_src, d_meta, d_perm, B, K):
+        """Device half of the augmented ``collate``: warp, keypoints and flags, maps."""
+        pm = self.codec.probmap
+        in_w, in_h = int(pm.input_size[0]), int(pm.input_size[1])
+        dev = d_src.device
+        L, meta = _lib.lib(), d_meta.data_ptr()
+        img = torch.empty((B, 3, in_h, in_w), dtype=torch.float32, device=dev)
+        f32 = torch.empty((6, B, K), dtype=torch.float32, device=dev)    # as _launch
+        flags = torch.empty((2, B, 1, K), dtype=torch.bool, device=dev)
+        kp_crop, kp_hm = f32[0:2].view(B, K, 2), f32[2:4].view(B, K, 2)
+        sx, sy = (float(v) for v in np.asarray(pm.scale_factor, dtype=np.float32))
+        with torch.cuda.device(dev):
+            rc = L.pp_augment_warp(_lib.ptr(d_src), meta, meta + 32 * B, B, in_w, in_h, _lib.ptr(img),
+                                   _lib.stream_ptr())
+            _lib.check(rc, "pp_augment_warp")
+            rc = L.pp_dataset_ground_truth_affine(meta + 128 * B, meta + 96 * B, _lib.ptr(d_perm), B, K, in_w, in_h,
+                                                  sx, sy, _lib.ptr(kp_crop), _lib.ptr(kp_hm), _lib.ptr(f32[4]),
+                                                  _lib.ptr(flags[0]), _lib.ptr(flags[1]), _lib.ptr(f32[5]),
+                                                  _lib.stream_ptr())
+            _lib.check(rc, "pp_dataset_ground_truth_affine")
+        heat, _ = pm.encode_device_tensors(kp_hm, f32[4])
+        return img, dict(heatmaps=heat, in_image=flags[0], keypoints_visible=flags[1],
+                         keypoints_visibility=f32[5].view(B, 1, K))
+
     def loader(self, batch_size, shuffle=False, num_workers=0, **kw):
         """A DataLoader over this dataset whose batches are ``collate``'s.  The workers do file reading, decoding and
         the integer crop; the batch is assembled in the main process."""
@@ -228,11 +457,15 @@ class YOLOPoseDataset(Dataset):
                              "inherit the open GPU, and 16 processes in all may hold it)")
         if "collate_fn" in kw:
             raise TypeError("YOLOPoseDataset.loader sets collate_fn itself")
+        if getattr(self, "augment", None) is not None and kw.get("persistent_workers"):
+            raise ValueError("YOLOPoseDataset.loader: persistent workers keep the epoch they were started with; with "
+                             "augment set, start the workers per epoch")
         return _DeviceLoader(self, batch_size=batch_size, shuffle=shuffle, num_workers=num_workers,
                              collate_fn=self.collate, **kw)
 
     def reference_item(self, idx):
         """The reference's ``__getitem__`` value (dataset.py:130-135): img (3, h, w) and the gt dict with heatmaps
-        (K, H, W) and the three (1, K) arrays, as device tensors, through the batch path with B = 1."""
-        img, gt = self._collate_device([self[idx]])
+        (K, H, W) and the three (1, K) arrays, as device tensors, through the batch path with B = 1.  Always the
+        un-augmented item, whatever ``augment`` is."""
+        img, gt = self._collate_device([self.plain_item(idx)])
         return img[0], {k: v[0] for k, v in gt.items()}

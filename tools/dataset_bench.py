@@ -11,6 +11,11 @@ from a seeded 1080p frame (what `__getitem__` hands over), held in memory: no fi
            float32 keypoint rescale, the K float64 numpy maps (the oracle's restatement of generate_probmaps)
 
 `--repeats` windows of `--steps` calls after `--warmup` calls; median, min and max over the windows.  One JSON line.
+
+`--augment` adds the augmented batch (Augment defaults with shift 0.1 and eight flip pairs; the regions are the bounding
+rectangles of the transformed boxes, cut from the same frame) to the same process, its windows alternating with the
+un-augmented ones: the three launches together and one by one (warp, keypoints, maps; the LANCZOS launch it replaces
+beside the warp), a whole collate() in HIP-event and in host time, and the warp's store bandwidth.
 """
 import argparse
 import json
@@ -59,6 +64,20 @@ def cpu_path(frame, samples, boxes, sigmas):
     return out
 
 
+def make_augmented_samples(frame, samples, augment):
+    """What __getitem__ hands over with augment set, for the boxes of make_samples, from the frame in memory."""
+    import PIL.Image
+    from probpose_pytorch_amd.dataset import augment_region
+    image = PIL.Image.fromarray(frame, "RGB")
+    out = []
+    for idx, (_, kps, bbox) in enumerate(samples):
+        params = augment.draw(0, idx)
+        x0, y0, x1, y1 = augment_region(bbox, params)
+        region = np.ascontiguousarray(np.asarray(image.crop((x0, y0, x1, y1)), dtype=np.uint8))
+        out.append((region, kps, bbox, np.array([x0, y0], dtype=np.int64), params))
+    return out
+
+
 def stats(ts):
     return dict(ms_median=round(statistics.median(ts), 4), ms_min=round(min(ts), 4), ms_max=round(max(ts), 4))
 
@@ -69,6 +88,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--cpu-repeats", type=int, default=3)
+    ap.add_argument("--augment", action="store_true", help="also time the augmented batch, alternating windows")
     ap.add_argument("--out")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "dataset_bench needs the GPU: there is nothing to time without it"
@@ -77,6 +97,7 @@ def main():
     sigmas = np.full(K, 0.05)
     ds = YOLOPoseDataset.__new__(YOLOPoseDataset)              # no tree on disk: the samples are made in memory
     ds.codec, ds.annotations, ds._staging = Codec(ArgMaxProbMap(INPUT, HEAT, sigmas)), [], []
+    ds.augment, ds.epoch, ds._perm = None, 0, None
     frame, samples, boxes = make_samples()
     src_bytes = sum(s[0].size for s in samples)
 
@@ -93,7 +114,61 @@ def main():
     up = ds._upload(samples)
     packed_bytes, plan_bytes = int(up[0].numel()), int(up[1].numel())       # the two copies of a batch
     device, copies, host = [], [], []
+    aug = None
+    if args.augment:
+        from probpose_pytorch_amd import _lib, frontend
+        from probpose_pytorch_amd.dataset import Augment
+        ds.augment = Augment(flip_pairs=[(2 * i + 1, 2 * i + 2) for i in range(8)], shift=0.1)
+        aug_samples = make_augmented_samples(frame, samples, ds.augment)
+        for _ in range(args.warmup):
+            ds.collate(aug_samples)
+        torch.cuda.synchronize()
+        aug = dict(device=[], copies=[], host=[], warp=[], keypoints=[], maps=[], lanczos=[])
+        L, pm = _lib.lib(), ds.codec.probmap
+        sx, sy = (float(v) for v in np.asarray(pm.scale_factor, dtype=np.float32))
+
+    def window(fn):
+        """HIP-event time per call of `--steps` calls of fn, the queue drained before."""
+        torch.cuda.synchronize()
+        a, b = ev(), ev()
+        a.record()
+        for _ in range(args.steps):
+            fn()
+        b.record()
+        b.synchronize()
+        return a.elapsed_time(b) / args.steps
+
     for _ in range(args.repeats):
+        if aug is not None:
+            up_plain = ds._upload(samples)
+            d_src, d_meta, d_perm, _, _ = up_a = ds._upload_augmented(aug_samples)
+            meta = d_meta.data_ptr()
+            img = torch.empty((B, 3, INPUT[1], INPUT[0]), dtype=torch.float32, device="cuda")
+            f32 = torch.empty((6, B, K), dtype=torch.float32, device="cuda")
+            flags = torch.empty((2, B, K), dtype=torch.bool, device="cuda")
+            kp_hm = f32[2:4].view(B, K, 2)
+            aug["device"].append(window(lambda: ds._launch_augmented(*up_a)))
+            aug["warp"].append(window(lambda: L.pp_augment_warp(_lib.ptr(d_src), meta, meta + 32 * B, B, INPUT[0],
+                                                                INPUT[1], _lib.ptr(img), _lib.stream_ptr())))
+            aug["lanczos"].append(window(lambda: frontend.crop_resize_multi(up_plain[0], up_plain[1], B, up_plain[4],
+                                                                            up_plain[5], INPUT)))
+            aug["keypoints"].append(window(lambda: L.pp_dataset_ground_truth_affine(
+                meta + 128 * B, meta + 96 * B, _lib.ptr(d_perm), B, K, INPUT[0], INPUT[1], sx, sy, _lib.ptr(f32[0:2]),
+                _lib.ptr(kp_hm), _lib.ptr(f32[4]), _lib.ptr(flags[0]), _lib.ptr(flags[1]), _lib.ptr(f32[5]),
+                _lib.stream_ptr())))
+            aug["maps"].append(window(lambda: pm.encode_device_tensors(kp_hm, f32[4])))
+            torch.cuda.synchronize()
+            a, b = ev(), ev()
+            t0 = time.perf_counter()
+            a.record()
+            for _ in range(args.steps):
+                ds.collate(aug_samples)
+            b.record()
+            t1 = time.perf_counter()
+            b.synchronize()
+            aug["host"].append((t1 - t0) * 1e3 / args.steps)
+            aug["copies"].append(a.elapsed_time(b) / args.steps)
+            aug["bytes"] = (int(d_src.numel()), int(d_meta.numel()))
         up = ds._upload(samples)
         torch.cuda.synchronize()
         a, b = ev(), ev()
@@ -127,6 +202,15 @@ def main():
     res["samples_per_s"] = dict(device=round(B / (res["device_three_launches"]["ms_median"] * 1e-3)),
                                 host=round(B / (res["host_collate_wall"]["ms_median"] * 1e-3)),
                                 cpu_one_thread=round(B / (res["cpu_reference_path_one_thread"]["ms_median"] * 1e-3)))
+    if aug is not None:
+        image_bytes = res["image_bytes"]
+        res["augment"] = dict(
+            copy_pixels_bytes=aug["bytes"][0], copy_meta_bytes=aug["bytes"][1],
+            device_three_launches=stats(aug["device"]), warp=stats(aug["warp"]),
+            lanczos_launch_it_replaces=stats(aug["lanczos"]), keypoints=stats(aug["keypoints"]),
+            maps=stats(aug["maps"]), device_collate_with_copies=stats(aug["copies"]),
+            host_collate_wall=stats(aug["host"]),
+            warp_store_TB_per_s=round(image_bytes / (statistics.median(aug["warp"]) * 1e-3) / 1e12, 3))
     line = json.dumps(res)
     print(line)
     if args.out:
