@@ -351,6 +351,26 @@ int pp_dataset_ground_truth_affine(const float *kpts_raw, const float *kp_affine
                                    unsigned char *keypoints_visible, float *keypoints_visibility, void *stream);
 
 /* ------------------------------------------------------------------------
+ * Flip test at inference (ProbPoseModel(..., flip_pairs=...)).  float32 only.
+ *
+ * pp_hflip_pair: x [B,C,H,W] -> out [2B,C,H,W]: out[b] = x[b] and out[B + b, c, y, u] = x[b, c, y, W - 1 - u], the
+ * batch and its mirror image in one launch (bit copies: nothing is computed on the values).
+ *
+ * pp_flip_merge: heat2 [2B,K,H,W] and aux2 [4,2B,K] (the head's probability, visibility, oks and error planes) ->
+ *   heat_out[b, k, y, u] = (heat2[b, k, y, u] + heat2[B + b, perm[k], y, W - 1 - u]) * 0.5f      [B,K,H,W]
+ *   aux_out[j, b, k]     = (aux2[j, b, k] + aux2[j, B + b, perm[k]]) * 0.5f                      [4,B,K]
+ * in float32 in exactly this order (one add, one multiply by 0.5).  perm [K] int32 on the device, an involution
+ * (left <-> right keypoints); the caller validates it.  One launch for the five outputs; no atomics.
+ *
+ * Both refuse on the host, before any launch: null pointers, non-positive sizes, more than 2^31 elements in the
+ * 2B-batch tensor, and an output that overlaps an input (no in-place use).  W % 4 == 0 with 16-byte aligned
+ * pointers takes the 128-bit form (4 pixels a thread), anything else one pixel a thread.
+ * ---------------------------------------------------------------------- */
+int pp_hflip_pair(const float *x, float *out, int B, int C, int H, int W, void *stream);
+int pp_flip_merge(const float *heat2, const float *aux2, const int *perm, int B, int K, int H, int W,
+                  float *heat_out, float *aux_out, void *stream);
+
+/* ------------------------------------------------------------------------
  * Training targets: the OKS probability maps of ProbMap.encode, batched over crops.  Replaces
  *   generate_probmaps   probpose/codec.py:11-70  (called from ProbMap.encode, codec.py:176-182)
  * kpts_hm [B,K,2] f32: keypoints in HEATMAP pixels (= keypoints / scale_factor, codec.py:178);

@@ -98,6 +98,8 @@ _SIGNATURES = {
     "pp_augment_check": (C.c_int, [_i, _vp, C.c_longlong, _vp, _vp, _i, _vp]),
     "pp_augment_warp": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "pp_dataset_ground_truth_affine": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _f] + [_vp] * 7),
+    "pp_hflip_pair": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "pp_flip_merge": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "pp_oks_heatmap_loss": (C.c_int, [_vp, _vp, _vp, _i, _vp, C.c_longlong, C.c_longlong, _i, _i] + [_f] * 4
                             + [_i] * 4 + [_vp] * 5),
     "pp_probpose_loss_terms": (C.c_int, [_vp] * 10 + [_d, _i, _i, _i] + [_vp] * 6),

@@ -33,6 +33,7 @@ import torch
 from torch.utils.data import DataLoader, Dataset, get_worker_info
 
 from . import _lib, frontend
+from .flip import pair_permutation
 
 _REGION_ALIGN = 16          # byte alignment of a region in the packed buffer (a multiple of frontend.SRC_ALIGN)
 MAX_WORKERS = 15            # 16 processes may hold one GPU open: the workers (which inherit it) plus the main process
@@ -138,16 +139,7 @@ class Augment:
 
     def permutation(self, K: int) -> np.ndarray:
         """int32 [K]: the keypoint that output slot k of a flipped sample reads."""
-        perm = np.arange(K, dtype=np.int32)
-        seen = set()
-        for i, j in self.flip_pairs:
-            if not (0 <= i < K and 0 <= j < K):
-                raise ValueError(f"Augment: flip pair ({i}, {j}) with {K} keypoints")
-            if i == j or i in seen or j in seen:
-                raise ValueError(f"Augment: flip pair ({i}, {j}) repeats a keypoint index")
-            seen.update((i, j))
-            perm[i], perm[j] = j, i
-        return perm
+        return pair_permutation(self.flip_pairs, K, "Augment")
 
 
 def augment_region(bbox, params) -> Tuple[int, int, int, int]:

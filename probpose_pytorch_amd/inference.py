@@ -9,7 +9,10 @@ function, ``run_inference``: ``Codec(ProbMap(input_size, heatmap_size, sigmas))`
   ``--trust-pickle`` is given;
 * ``--backbone`` defaults to the in-tree ViT: ``RadioBackbone`` needs a ``torch.hub`` download;
 * the model runs in ``.eval()`` mode (the reference never calls it, i.e. runs train-mode BatchNorm);
-* image I/O needs PIL; without ``--image`` a seeded synthetic crop is used.
+* image I/O needs PIL; without ``--image`` a seeded synthetic crop is used;
+* ``--flip-test`` averages the outputs with those of the mirrored crop (``ProbPoseModel.set_flip_test``), the way the
+  accuracy of top-down estimators is usually reported; ``--flip-pairs "1-2,3-4,..."`` names the left/right keypoint
+  pairs (default for 17 keypoints: COCO's 1-2, 3-4, ..., 15-16).
 """
 from __future__ import annotations
 
@@ -21,6 +24,7 @@ import torch
 
 from .backbone import ScratchViTBackbone
 from .codec import Codec, ProbMap
+from .flip import COCO17_FLIP_PAIRS, flip_permutation, parse_flip_pairs
 from .head import ProbMapHead
 from .model import ProbPoseModel
 
@@ -96,6 +100,25 @@ def load_weights(model: ProbPoseModel, path: Path, model_type: str, trust_pickle
     return target.load_state_dict(sd)
 
 
+def resolve_flip_pairs(parser, args):
+    """The flip pairs the command line asks for, or None; argument errors go through ``parser.error``."""
+    if not args.flip_test:
+        if args.flip_pairs is not None:
+            parser.error("--flip-pairs needs --flip-test")
+        return None
+    if args.flip_pairs is None:
+        if args.num_keypoints != 17:
+            parser.error(f"--flip-test with --num_keypoints {args.num_keypoints} needs --flip-pairs (only the COCO-17 "
+                         "pairs are built in)")
+        return COCO17_FLIP_PAIRS
+    try:
+        pairs = parse_flip_pairs(args.flip_pairs)
+        flip_permutation(pairs, args.num_keypoints)
+    except ValueError as e:
+        parser.error(f"--flip-pairs: {e}")
+    return pairs
+
+
 def main(argv=None):
     p = argparse.ArgumentParser(description="Inference script for ProbPose (MI355X-native path)")
     p.add_argument("--model", type=Path, default=None, help="state_dict checkpoint (omit: seeded synthetic weights)")
@@ -109,7 +132,11 @@ def main(argv=None):
     p.add_argument("--bf16", action="store_true", help="bf16 MFMA instead of exact-fp32 MFMA")
     p.add_argument("--normalize", action="store_true", help="divide each dumped heatmap by its maximum")
     p.add_argument("--trust-pickle", action="store_true")
+    p.add_argument("--flip-test", action="store_true", help="average with the outputs of the mirrored crop")
+    p.add_argument("--flip-pairs", type=str, default=None,
+                   help='left/right keypoint pairs "1-2,3-4,..." (default for 17 keypoints: the COCO pairs)')
     args = p.parse_args(argv)
+    flip_pairs = resolve_flip_pairs(p, args)
     input_size = tuple(map(int, args.input_size.split(",")))
     model, heatmap_size = build_model(input_size, args.num_keypoints, args.backbone)
     if args.model is not None:
@@ -122,6 +149,7 @@ def main(argv=None):
     model = model.to("cuda").eval()
     if args.bf16:
         model.set_compute_dtype(torch.bfloat16)
+    model.set_flip_test(flip_pairs)
     codec = Codec(ProbMap(input_size, heatmap_size, np.array([args.sigma] * args.num_keypoints)))
     if args.image is not None:
         x = load_image(args.image, input_size)

@@ -293,6 +293,27 @@ def nchw_to_tokens(x, out, B, Cc, HW):
     return out
 
 
+# ---- flip test (pp_flip.hip) ------------------------------------------------------------------------------------
+def hflip_pair(x, out):
+    """x [B,C,H,W] f32 -> out [2B,C,H,W] f32: the batch followed by its mirror image (columns reversed)."""
+    B, Cc, H, W = x.shape
+    rc = _timed("hflip_pair", float(x.numel() * 12),
+                lambda: _lib.lib().pp_hflip_pair(_p(x), _p(out), B, Cc, H, W, _lib.stream_ptr()))
+    _lib.check(rc, "pp_hflip_pair")
+    return out
+
+
+def flip_merge(heat2, aux2, perm, heat_out, aux_out):
+    """heat2 [2B,K,H,W], aux2 [4,2B,K] f32, perm [K] int32 -> heat_out [B,K,H,W], aux_out [4,B,K]: the average of the
+    straight half and the un-mirrored, left/right-swapped second half (pp_flip_merge in include/probpose_hip.h)."""
+    B, K, H, W = heat_out.shape
+    rc = _timed("flip_merge", float((heat_out.numel() + aux_out.numel()) * 12),
+                lambda: _lib.lib().pp_flip_merge(_p(heat2), _p(aux2), _p(perm), B, K, H, W, _p(heat_out), _p(aux_out),
+                                                 _lib.stream_ptr()))
+    _lib.check(rc, "pp_flip_merge")
+    return heat_out, aux_out
+
+
 # ---- training ProbMapHead (pp_head_grad.hip) ------------------------------------------------------------------
 def wgrad_workspace_floats(M, N, Kd, batch=1) -> int:
     return int(_lib.lib().pp_wgrad_workspace_floats(M, N, Kd, batch))
