@@ -150,24 +150,23 @@ typedef struct pp_gemm_args {
   int stats_parts;              /* reserved */
   const float *colsum;          /* PP_FP8: [N] f32 column scales (batch stride strideBias)               */
   float ln_eps;                 /* reserved */
-  int tile;                     /* 0 = auto (fewest rounds of resident workgroups), 1 = 128x128,
-                                   2 = 192x96 (4 waves, 2 LDS stages), 3 = 192x192, 4 = 192x128 (8 waves, 3 stages), 5 = 384x128 (8 waves, 2 stages),
-                                   6 = 192x192 wave-specialised (8 MFMA + 4 DMA waves, 3 stages),
-                                   7 = 192x384, 8 = 256x256, 9 = 192x256 (8 waves, 2 stages; bf16),
-                                   10 = 192x192 with the two wave quartets half a K-tile apart (one loads fragments and
-                                   issues DMA while the other runs MFMAs; bf16 / fp8 plain layers),
-                                   14 = 192x192 as TWO 4-wave workgroups per CU (96x96 wave tiles, 32-deep K-tiles, 72 KB
-                                   of LDS each; plain bf16 layers with bias / GELU / ReLU / f32 residual).
-                                   13 = persistent 192x192 stream (one workgroup per CU walks its tiles as one stream of
-                                   K-tiles, the next tile's first K-tiles land under the epilogue; plain bf16 -> bf16
-                                   layers with bias / GELU / ReLU, e.g. qkv and fc1).
-                                   18 / 19 / 20 = four-wave stream forms (pp_gemm_quad.hip): 256x192 / 192x288 / 192x256
-                                   tiles, one wave per SIMD with a 128x96 / 96x144 / 96x128 wave tile, one workgroup per CU
-                                   walking its tiles as one stream of 32-deep K-tiles, a finished tile's rows stored from
-                                   the next tile's K-loop; plain bf16 -> bf16 layers with bias / GELU / ReLU (and the
-                                   head-major qkv layout), M and N whole numbers of tiles, K >= 512 (qkv, fc1).
-                                   11, 12: round-2 experiments; 15 - 17: the per-launch four-wave forms; both removed
-                                   (refused). */
+  int tile;                     /* the tile form, one line per row of csrc/pp_gemm_forms.h (BM x BN, waves, LDS stages):
+                                    0 = auto: the cheapest of 1 - 5 by rounds of resident workgroups x padded tile area
+                                    1 = 128x128, 4 waves, 2 stages, two workgroups per CU; f32 / bf16; also every ragged call
+                                    2 = 192x96, 4 waves, 2 stages, two workgroups per CU; f32 / bf16 / fp8
+                                    3 = 192x192, 8 waves, 3 stages, one workgroup per CU; f32 / bf16 / fp8
+                                    4 = 192x128, 8 waves, 3 stages; f32 / bf16
+                                    5 = 384x128, 8 waves, 2 stages; f32 / bf16; auto considers it for N <= 256
+                                    6 = 192x192 wave-specialised, 8 MFMA + 4 DMA waves, 3 stages; f32 / bf16
+                                    7 = 192x384, 8 waves, 2 stages; f32 / bf16
+                                    8 = 256x256, 8 waves, 2 stages; bf16
+                                    9 = 192x256, 8 waves, 2 stages; bf16; the form of PP_EPI_FUSE_FINAL
+                                   10 = 192x192 ping-pong, 8 waves, 3 stages, wave quartets half a K-tile apart; f32 / bf16 / fp8
+                                   13 = 192x192 persistent stream, 8 waves, 3 stages; plain bf16 -> bf16, bias / GELU / ReLU
+                                   14 = 192x192 as two 4-wave workgroups per CU; plain bf16, bias / GELU / ReLU / f32 residual
+                                   18 / 19 / 20 = 256x192 / 192x288 / 192x256 four-wave stream (pp_gemm_quad.hip); plain bf16
+                                        -> bf16, bias / GELU / ReLU, M and N whole numbers of tiles, K >= 512
+                                   11, 12 (round-2 experiments), 15 - 17 (per-launch four-wave forms): removed, refused. */
   float out_scale;              /* PP_EPI_OUT_FP8: 1 / (scale of the fp8 output tensor) */
   int splitk;                   /* 0 / 1 = off.  S > 1: the launch computes S partial products per batch entry, split s
                                    over the K range [s * Kd, (s + 1) * Kd) (Kd = the PER-SPLIT depth): operands advance

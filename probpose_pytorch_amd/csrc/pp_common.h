@@ -6,6 +6,8 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <vector>
+
 #include "../../include/probpose_hip.h"
 
 namespace pp {
@@ -74,17 +76,36 @@ __device__ __forceinline__ float wave_max(float v) {
 
 inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
-// hipFuncSetAttribute (dynamic-LDS limit) is per device: the "already raised" caches are bitmasks over the device
-// ordinal of the calling thread's current device, not a single flag (a second GPU in the same thread would otherwise
-// launch with the 64 KB default limit and fail).
-inline bool attr_needed(unsigned long long &mask, int &dev_out) {
+// Raise a kernel's dynamic-LDS limit to `bytes` on the calling thread's current device, once per (kernel, device): the
+// attribute is per device, and a device is marked only after hipFuncSetAttribute has succeeded there.
+template <typename K>
+inline int ensure_dynamic_lds(K *kernel, size_t bytes) {
+  struct Raised { const void *kernel; int dev; size_t bytes; };
+  static thread_local std::vector<Raised> raised;
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-  dev_out = dev;
-  const unsigned long long bit = 1ull << (dev & 63);
-  if (mask & bit) return false;
-  mask |= bit;
-  return true;
+  PP_CHECK_HIP(hipGetDevice(&dev));
+  Raised *r = nullptr;
+  for (Raised &e : raised)
+    if (e.kernel == (const void *)kernel && e.dev == dev) r = &e;
+  if (r && r->bytes >= bytes) return 0;
+  PP_CHECK_HIP(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  if (r) r->bytes = bytes;
+  else raised.push_back({(const void *)kernel, dev, bytes});
+  return 0;
+}
+
+// Compute units of the calling thread's current device, cached per device ordinal.
+inline int cu_count(int *out) {
+  static thread_local int cached[64] = {};
+  int dev = 0;
+  PP_CHECK_HIP(hipGetDevice(&dev));
+  int &n = cached[dev & 63];
+  if (n == 0) {
+    PP_CHECK_HIP(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev));
+    if (n <= 0) n = 256;
+  }
+  *out = n;
+  return 0;
 }
 
 }  // namespace pp

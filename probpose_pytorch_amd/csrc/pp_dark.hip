@@ -200,11 +200,8 @@ extern "C" int pp_dark_decode_f32(const float *heatmaps, int B, int K, int H, in
              ksize, lds);
   DarkTaps t;
   for (int i = 0; i < DK_MAX_TAPS; ++i) t.k[i] = i < ksize ? taps_host[i] : 0.f;
-  static thread_local unsigned long long attr_mask = 0;
-  int dev_ = 0;
-  if (lds > 64 * 1024 && attr_needed(attr_mask, dev_))
-    PP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(dark_decode_kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+  if (lds > 64 * 1024)
+    if (int rc = ensure_dynamic_lds(dark_decode_kernel, 150 * 1024)) return rc;
   hipLaunchKernelGGL(dark_decode_kernel, dim3((unsigned)(B * K)), dim3(DK_THREADS), lds, (hipStream_t)stream, heatmaps,
                      H, W, t, ksize, in_w, in_h, out_kpts, out_scores, out_locs);
   PP_CHECK_LAUNCH("dark_decode_kernel");

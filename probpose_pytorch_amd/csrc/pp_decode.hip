@@ -1186,14 +1186,9 @@ extern "C" int pp_decode_f32(const float *heatmaps, const float *prob, const flo
   // kernel: ONE launch, 22 - 24 us at bs 64 x 17 whatever the maps hold, where the wave kernel + its list kernel need
   // 20 - 25 us on peaked maps and ~27 on the bench model's plateau-ridden ones.  Above that the wave kernel wins by up to
   // 2.4x (B = 1024: 94 - 99 vs 232 us) and the second launch is noise.  PP_DECODE_WAVE forces the wave path at any size.
-  static int ncu_ = 0;                       // (one device class per process; a wrong count only moves the cross-over)
-  if (ncu_ == 0) {
-    int dev_w = 0, n = 0;
-    if (hipGetDevice(&dev_w) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev_w) != hipSuccess || n <= 0)
-      n = 256;
-    ncu_ = n;
-  }
-  const long long small_batch = 2ll * ncu_ * (H == 64 ? 3 : 1);
+  int ncu = 0;
+  if (cu_count(&ncu) != 0) ncu = 256;        // a wrong count only moves the cross-over
+  const long long small_batch = 2ll * ncu * (H == 64 ? 3 : 1);
   const bool wave_wanted = (flags & PP_DECODE_WAVE) || maps > small_batch;
   if (!out_conv && !(flags & PP_DECODE_NO_WAVE) && wave_wanted && !exact_all && workspace && ((uintptr_t)heatmaps & 15) == 0 &&
       ((uintptr_t)workspace & 3) == 0 && wave_geometry(H, W)) {
@@ -1206,11 +1201,8 @@ extern "C" int pp_decode_f32(const float *heatmaps, const float *prob, const flo
                          err, B, K, taps, radius, den_x, den_y, in_w, in_h, o, ws);
     PP_CHECK_LAUNCH("decode_wave_kernel");
     const size_t lds = lds_bytes(H, W);
-    static thread_local unsigned long long attr_mask3 = 0;
-    int dev3 = 0;
-    if (lds > 64 * 1024 && attr_needed(attr_mask3, dev3))
-      PP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(decode_lds_list_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT));
+    if (lds > 64 * 1024)
+      if (int rc = ensure_dynamic_lds(decode_lds_list_kernel, LDS_LIMIT)) return rc;
     hipLaunchKernelGGL(decode_lds_list_kernel, dim3((unsigned)(maps < 256 ? maps : 256)), dim3(DEC_THREADS), lds, s, ws,
                        heatmaps, prob, vis, oks, err, B, K, H, W, taps, radius, den_x, den_y, in_w, in_h, o);
     PP_CHECK_LAUNCH("decode_lds_list_kernel");
@@ -1224,11 +1216,8 @@ extern "C" int pp_decode_f32(const float *heatmaps, const float *prob, const flo
       hipLaunchKernelGGL(decode_screen_kernel<3>, dim3(maps), dim3(DF_THREADS), lds, s, heatmaps, prob, vis, oks, err, B,
                          K, H, W, taps, radius, den_x, den_y, in_w, in_h, o);
     } else {
-      static thread_local unsigned long long attr_mask2 = 0;
-      int dev2 = 0;
-      if (lds > 48 * 1024 && attr_needed(attr_mask2, dev2))
-        PP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(decode_screen_kernel<7>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)SCREEN_DYN_LIMIT));
+      if (lds > 48 * 1024)
+        if (int rc = ensure_dynamic_lds(decode_screen_kernel<7>, SCREEN_DYN_LIMIT)) return rc;
       hipLaunchKernelGGL(decode_screen_kernel<7>, dim3(maps), dim3(DF_THREADS), lds, s, heatmaps, prob, vis, oks, err, B,
                          K, H, W, taps, radius, den_x, den_y, in_w, in_h, o);
     }
@@ -1237,11 +1226,8 @@ extern "C" int pp_decode_f32(const float *heatmaps, const float *prob, const flo
   }
   if (fits_lds(H, W)) {
     const size_t lds = lds_bytes(H, W);
-    static thread_local unsigned long long attr_mask = 0;
-    int dev_ = 0;
-    if (lds > 64 * 1024 && attr_needed(attr_mask, dev_))
-      PP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(decode_lds_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT));
+    if (lds > 64 * 1024)
+      if (int rc = ensure_dynamic_lds(decode_lds_kernel, LDS_LIMIT)) return rc;
     hipLaunchKernelGGL(decode_lds_kernel, dim3(maps), dim3(DEC_THREADS), lds, s, heatmaps, prob, vis,
                        oks, err, B, K, H, W, taps, radius, den_x, den_y, in_w, in_h, o, out_conv);
     PP_CHECK_LAUNCH("decode_lds_kernel");

@@ -449,13 +449,8 @@ static int fe_launch(const char *who, const unsigned char *image, int img_w, int
                      const void *plan_dev, int n_boxes, int n_blocks, long long lds_bytes, int out_w, int out_h,
                      float *out, void *stream) {
   PP_REQUIRE(lds_bytes > 0 && (size_t)lds_bytes <= FE_LDS_MAX, "%s: bad LDS size %lld", who, lds_bytes);
-  if (lds_bytes > 64 * 1024) {
-    static thread_local unsigned long long attr_mask = 0;
-    int dev_ = 0;
-    if (attr_needed(attr_mask, dev_))
-      PP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(crop_resize_kernel<MULTI>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)FE_LDS_MAX));
-  }
+  if (lds_bytes > 64 * 1024)
+    if (int rc = ensure_dynamic_lds(crop_resize_kernel<MULTI>, FE_LDS_MAX)) return rc;
   hipLaunchKernelGGL(crop_resize_kernel<MULTI>, dim3((unsigned)n_blocks), dim3(FE_THREADS), (size_t)lds_bytes,
                      (hipStream_t)stream, image, img_w, img_h, img_stride, static_cast<const int *>(plan_dev), n_boxes,
                      out_w, out_h, out);

@@ -7,9 +7,8 @@
 // buffer), C rows optionally scattered through a row map.
 //
 // Structure (CDNA4): BM x BN output tile per workgroup of WGM x WGN waves, each wave TM x TN MFMA 16x16
-// tiles.  Instantiations (pp_gemm's `tile` selector): 128x128, 192x96 (4 waves, 2 LDS stages, two workgroups
-// per CU), 192x192 / 192x128 (8 waves, 3 stages, one workgroup per CU), 384x128, 192x384, 256x256, 192x256
-// (8 waves, 2 stages).  192 rows = one crop's tokens, so at B = 64 the four ViT GEMMs are whole rounds.
+// tiles.  The instantiations (pp_gemm's `tile` selector) are the rows of pp_gemm_forms.h.  192 rows = one crop's
+// tokens, so at B = 64 the four ViT GEMMs are whole rounds.
 // K-tiles of 128 B per row (64 bf16 / 32 fp32 / 128 fp8) are staged HBM/L2 -> LDS by global_load_lds_dwordx4
 // (no VGPR round trip) into a 2- or 3-deep ring: counted s_waitcnt vmcnt(N) + one raw s_barrier per K-tile,
 // the DMA pieces issued between the MFMA groups; the 16-B chunks are XOR-swizzled on the SOURCE address
@@ -26,6 +25,7 @@
 
 #include "pp_common.h"
 #include "pp_gemm_shared.h"
+#include "pp_gemm_forms.h"
 
 namespace pp {
 
@@ -1355,32 +1355,28 @@ __global__ __launch_bounds__(256, 2) void gemm_duo_kernel(GemmParams p) {
   else staged(std::integral_constant<int, 2>{});
 }
 
-// pp_gemm_quad.hip: tiles 18 - 20 (four waves, one per SIMD, 128x96 / 96x144 / 96x128 wave tiles, persistent stream)
-int gemm_quad_launch(const GemmParams &p, int cfg, dim3 grid, hipStream_t s);
-void gemm_quad_tile_shape(int cfg, int *bm, int *bn);
+// pp_gemm_quad.hip: the QuadStream family
+int gemm_quad_launch(const GemmParams &p, int tile, dim3 grid, hipStream_t s);
 
-// measured: one 8-wave 3-stage 192x192 tile per CU vs two co-resident 4-wave tiles
-constexpr double CFG3_SPEEDUP = 1.3;
+// ---- host side: pp_gemm = argument checks -> form selection -> admission -> parameters and grid -> launch, each step a
+// function of the call and the table of forms (pp_gemm_forms.h)
+struct GemmCall {
+  const pp_gemm_args *a;
+  bool vec;            // N and ldc multiples of 4 and no NCHW heatmap store: 4-wide bias / residual / stores
+  bool lds_epilogue;   // C rows are whole 16-byte chunks: the tile can leave through LDS
+  int batch;           // grid.y: batch entries x K splits
+};
 
-}  // namespace pp
-
-extern "C" int pp_gemm(const pp_gemm_args *a, void *stream) {
-  using namespace pp;
-  PP_REQUIRE(a, "pp_gemm: null args");
-  PP_REQUIRE(a->dtype == PP_F32 || a->dtype == PP_BF16 || a->dtype == PP_FP8, "pp_gemm: bad dtype %d", a->dtype);
-  const int es = a->dtype == PP_BF16 ? 2 : (a->dtype == PP_FP8 ? 1 : 4);
+// Checks that hold whatever the form (M > 0, batch != 0, dtype and shape already checked).
+static int check_args(const pp_gemm_args *a, int es) {
   const int bk = ROW_BYTES / es;
-  PP_REQUIRE(a->M >= 0 && a->N > 0 && a->Kd > 0, "pp_gemm: bad shape M=%d N=%d K=%d", a->M, a->N, a->Kd);
-  if (a->M == 0 || a->batch == 0) return 0;
   PP_REQUIRE(a->A && a->W && a->C, "pp_gemm: null operand");
   PP_REQUIRE(a->Kd % bk == 0, "pp_gemm: K=%d must be a multiple of %d for this dtype", a->Kd, bk);
-  PP_REQUIRE(a->lda % (16 / es) == 0 && a->ldw % (16 / es) == 0,
-             "pp_gemm: lda/ldw must keep rows 16-byte aligned");
+  PP_REQUIRE(a->lda % (16 / es) == 0 && a->ldw % (16 / es) == 0, "pp_gemm: lda/ldw must keep rows 16-byte aligned");
   PP_REQUIRE(((uintptr_t)a->A & 15) == 0 && ((uintptr_t)a->W & 15) == 0, "pp_gemm: operands must be 16-byte aligned");
   if (a->rowoff)
     PP_REQUIRE(a->seg_len > 0 && a->seg_len % bk == 0 && a->Kd % a->seg_len == 0,
-               "pp_gemm: gather segment length %d must divide K=%d and be a multiple of %d", a->seg_len,
-               a->Kd, bk);
+               "pp_gemm: gather segment length %d must divide K=%d and be a multiple of %d", a->seg_len, a->Kd, bk);
   if (a->epilogue & PP_EPI_BIAS) PP_REQUIRE(a->bias, "pp_gemm: PP_EPI_BIAS without bias");
   if (a->epilogue & PP_EPI_RESIDUAL) PP_REQUIRE(a->residual, "pp_gemm: PP_EPI_RESIDUAL without residual");
   if (a->epilogue & PP_EPI_ROWBIAS)
@@ -1397,14 +1393,79 @@ extern "C" int pp_gemm(const pp_gemm_args *a, void *stream) {
                    !(a->epilogue & (PP_EPI_OUT_F32 | PP_EPI_HEATMAP | PP_EPI_RESIDUAL | PP_EPI_FUSE_FINAL | PP_EPI_OUT_FP8)),
                "pp_gemm: PP_EPI_HEADMAJOR serves the bf16 qkv projection: N = 3 * heads (hm_K) * head_dim (hm_HW), head_dim a "
                "multiple of 8, C 16-byte aligned, a plain single launch (not tile 14)");
-  if (a->epilogue & PP_EPI_FUSE_FINAL) {
+  if (a->epilogue & PP_EPI_FUSE_FINAL)
     PP_REQUIRE(a->dtype == PP_BF16 && a->N == 256 && a->final_w && a->final_b && a->hm_K > 0 && a->hm_K <= 32 &&
-                   a->hm_HW > 0 && a->hm_temperature != 0.f && (a->tile == 9 || a->tile == 0) &&
+                   a->hm_HW > 0 && a->hm_temperature != 0.f && (a->tile == GEMM_TILE_FUSE_FINAL || a->tile == 0) &&
                    !(a->epilogue & (PP_EPI_OUT_F32 | PP_EPI_HEATMAP | PP_EPI_RESIDUAL)) &&
                    ((uintptr_t)a->final_w & 15) == 0,
                "pp_gemm: PP_EPI_FUSE_FINAL serves bf16 layers with N = 256 outputs (tile 9), K <= 32 keypoint maps");
+  if (a->splitk > 1) {
+    PP_REQUIRE(a->epilogue == PP_EPI_OUT_F32 && a->dtype != PP_FP8 && !a->out_rowmap,
+               "pp_gemm: split-K launches write plain f32 partials (epilogue must be PP_EPI_OUT_F32 alone)");
+    PP_REQUIRE(!a->rowoff || a->Kd % (a->seg_len > 0 ? a->seg_len : a->Kd) == 0,
+               "pp_gemm: split-K depth %d must be a whole number of gather segments (%d)", a->Kd, a->seg_len);
   }
-  GemmParams p;
+  if (a->dtype == PP_FP8) {
+    PP_REQUIRE(a->colsum && !a->rowoff && !a->out_rowmap && !(a->epilogue & (PP_EPI_ROWBIAS | PP_EPI_HEATMAP)),
+               "pp_gemm: fp8 needs colsum = per-column dequantisation scales and a plain (non-gather, non-fused) GEMM");
+    if (a->epilogue & PP_EPI_OUT_FP8)
+      PP_REQUIRE(a->out_scale > 0.f && !(a->epilogue & PP_EPI_OUT_F32), "pp_gemm: PP_EPI_OUT_FP8 needs out_scale > 0");
+  } else {
+    PP_REQUIRE(!(a->epilogue & PP_EPI_OUT_FP8), "pp_gemm: PP_EPI_OUT_FP8 is an fp8-GEMM epilogue");
+  }
+  return 0;
+}
+
+// The form a call runs on: the one `tile` names, or for tile 0 the cheapest by the cost model
+//   cost = rounds of co-resident workgroups x padded tile area / relative per-CU throughput of the form
+// over the rows that carry an auto_rate.  Ragged calls have one form only, and so has the fused final layer.
+static int select_form(const GemmCall &c, const GemmForm **out) {
+  const pp_gemm_args *a = c.a;
+  for (const RetiredTile &r : GEMM_RETIRED)
+    PP_REQUIRE(a->tile < r.first || a->tile > r.last, "pp_gemm: bad tile selector %d (tiles %d - %d: %s; removed)", a->tile,
+               r.first, r.last, r.reason);
+  PP_REQUIRE(a->tile == 0 || gemm_form_or_null(a->tile), "pp_gemm: bad tile selector %d", a->tile);
+  const int tile = (a->epilogue & PP_EPI_FUSE_FINAL) ? GEMM_TILE_FUSE_FINAL : (c.vec ? a->tile : GEMM_TILE_RAGGED);
+  const GemmForm *f = gemm_form_or_null(tile);
+  double best = 0;
+  for (const GemmForm &g : GEMM_FORMS) {
+    if (tile != 0 || g.auto_rate == 0 || (g.auto_max_n && a->N > g.auto_max_n)) continue;
+    const long long tiles = (long long)cdiv(a->M, g.bm) * cdiv(a->N, g.bn) * c.batch;
+    const double cost = (double)((tiles + g.slots - 1) / g.slots) * g.bm * g.bn / g.auto_rate;
+    if (!f || cost < best || (cost == best && g.auto_wins_ties)) { best = cost; f = &g; }
+  }
+  *out = f;
+  return 0;
+}
+
+// Does the chosen form take this call?  Every condition is the row's.  One rule is the dispatcher's own: when AUTO
+// selection lands on a form that fp8 is not built for, the call runs on GEMM_TILE_FP8_FALLBACK instead.
+static int admit(const GemmCall &c, const GemmForm **form) {
+  const pp_gemm_args *a = c.a;
+  const GemmForm *f = *form;
+  if (a->epilogue & PP_EPI_FUSE_FINAL)
+    PP_REQUIRE(c.lds_epilogue && c.vec, "pp_gemm: PP_EPI_FUSE_FINAL runs inside the LDS epilogue: C must be 16-byte aligned "
+                                        "(and N = ldc = 256)");
+  if (a->dtype == PP_FP8) {
+    PP_REQUIRE(c.vec && c.lds_epilogue, "pp_gemm: fp8 needs the vector / LDS epilogue path (aligned N, ldc, C)");
+    if (!(f->dtypes & DT_FP8) && a->tile == 0) *form = f = gemm_form_or_null(GEMM_TILE_FP8_FALLBACK);
+  }
+  const bool f32_ok = !(a->epilogue & (PP_EPI_RESIDUAL | PP_EPI_ROWBIAS)) || (a->epilogue & PP_EPI_OUT_F32);
+  PP_REQUIRE((f->dtypes >> a->dtype & 1) && !(a->epilogue & ~f->epilogues) && (f32_ok || !f->residual_f32_only) &&
+                 (!f->plain || (!a->rowoff && !a->out_rowmap && c.batch == 1)) &&
+                 (c.lds_epilogue || !f->lds_epilogue) && a->Kd % f->k_multiple == 0,
+             "pp_gemm: %s", f->serves);
+  PP_REQUIRE((!f->whole_tiles || (a->M % f->bm == 0 && a->N % f->bn == 0)) && a->Kd >= f->k_min,
+             "pp_gemm: tile %d needs M %% %d == 0, N %% %d == 0 and K >= %d (%s)", f->tile, f->bm, f->bn, f->k_min, f->serves);
+  PP_REQUIRE(!f->c_below_4g || (unsigned long long)a->M * a->ldc * 2 < 0xFFFFFFF0ull,
+             "pp_gemm: tile %d: C must lie below 4 GiB (its rows leave through 32-bit buffer offsets)", f->tile);
+  return 0;
+}
+
+// Kernel parameters and the grid of the form's tiles: XCD-blocked order for large grids, plain order otherwise.
+// The streaming families read grid.x as their count of virtual blocks.
+static dim3 fill_params(const GemmCall &c, const GemmForm &f, GemmParams &p) {
+  const pp_gemm_args *a = c.a;
   p.A = (const char *)a->A;
   p.W = (const char *)a->W;
   p.C = (char *)a->C;
@@ -1421,224 +1482,132 @@ extern "C" int pp_gemm(const pp_gemm_args *a, void *stream) {
   p.strideBias = a->strideBias; p.strideRowoff = a->strideRowoff; p.strideRowmap = a->strideRowmap;
   p.splitk = a->splitk > 1 ? a->splitk : 1;
   p.strideA_k = a->strideA_k; p.strideW_k = a->strideW_k; p.strideC_k = a->strideC_k; p.strideRowoff_k = a->strideRowoff_k;
-  if (a->epilogue & PP_EPI_HEADMAJOR) { p.hm_K = a->hm_K; p.hm_HW = a->hm_HW; }
-  if (p.splitk > 1) {
-    PP_REQUIRE(a->epilogue == PP_EPI_OUT_F32 && a->dtype != PP_FP8 && !a->out_rowmap,
-               "pp_gemm: split-K launches write plain f32 partials (epilogue must be PP_EPI_OUT_F32 alone)");
-    PP_REQUIRE(!a->rowoff || a->Kd % (a->seg_len > 0 ? a->seg_len : a->Kd) == 0,
-               "pp_gemm: split-K depth %d must be a whole number of gather segments (%d)", a->Kd, a->seg_len);
-  }
   p.epilogue = a->epilogue;
   p.hm_K = a->hm_K; p.hm_HW = a->hm_HW; p.hm_temperature = a->hm_temperature;
   p.colsum = a->colsum;
   p.out_scale = a->out_scale;
   p.final_w = (const char *)a->final_w; p.final_b = a->final_b;
-  if (a->dtype == PP_FP8) {
-    PP_REQUIRE(a->colsum && !a->rowoff && !a->out_rowmap && !(a->epilogue & (PP_EPI_ROWBIAS | PP_EPI_HEATMAP)),
-               "pp_gemm: fp8 needs colsum = per-column dequantisation scales and a plain (non-gather, non-fused) GEMM");
-    if (a->epilogue & PP_EPI_OUT_FP8)
-      PP_REQUIRE(a->out_scale > 0.f && !(a->epilogue & PP_EPI_OUT_F32), "pp_gemm: PP_EPI_OUT_FP8 needs out_scale > 0");
-  } else {
-    PP_REQUIRE(!(a->epilogue & PP_EPI_OUT_FP8), "pp_gemm: PP_EPI_OUT_FP8 is an fp8-GEMM epilogue");
-  }
-  const int batch = (a->batch > 0 ? a->batch : 1) * (a->splitk > 1 ? a->splitk : 1);   // grid.y
-  PP_REQUIRE(batch <= 65535, "pp_gemm: batch too large");
-  // Tile configuration.  0 = auto, 1 = 128x128 (4 waves, 2 stages), 2 = 192x96 (4 waves, 2 stages),
-  // 3 = 192x192 (8 waves, 3 stages, one workgroup per CU), 4 = 192x128 (8 waves, 3 stages),
-  // 5 = 384x128 (8 waves, 2 stages; the N = 256 deconvolution layers), 6 = 192x192 wave-specialised
-  // (8 consumer + 4 producer waves, 3 stages), 7 = 192x384 (8 waves, 2 stages; wide-N layers such as fc1),
-  // 8 = 256x256 (8 waves, 2 stages), 9 = 192x256 (8 waves, 2 stages; N = 256 layers: one column tile, A read once).  Auto: cost = rounds of co-resident workgroups x padded tile area / relative per-CU
-  // throughput of the configuration.
-  PP_REQUIRE(a->tile >= 0 && a->tile <= 20 && a->tile != 11 && a->tile != 12 && !(a->tile >= 15 && a->tile <= 17),
-             "pp_gemm: bad tile selector %d (11 / 12: round-2 experiments; 15 - 17: per-launch four-wave forms that only lab "
-             "builds had; removed)", a->tile);
-  auto rounds = [&](int bm, int bn, int slots) {
-    const long long tiles = (long long)cdiv(a->M, bm) * cdiv(a->N, bn) * batch;
-    return (tiles + slots - 1) / slots;
-  };
-  const bool vec = (a->N & 3) == 0 && (a->ldc & 3) == 0 && !(a->epilogue & PP_EPI_HEATMAP);
-  int cfg = vec ? a->tile : 1;
-  if (a->epilogue & PP_EPI_FUSE_FINAL) cfg = 9;     // the one configuration that holds all 256 channels of a pixel
-  if (cfg == 0) {
-    const double c1 = (double)rounds(128, 128, 512) * 128 * 128 * 2;   // 2 workgroups share a CU
-    const double c2 = (double)rounds(192, 96, 512) * 192 * 96 * 2;
-    const double c3 = (double)rounds(192, 192, 256) * 192 * 192 / CFG3_SPEEDUP;
-    const double c4 = (double)rounds(192, 128, 256) * 192 * 128 / (CFG3_SPEEDUP * 0.9);
-    cfg = 1;
-    double best = c1;
-    if (c2 < best) { best = c2; cfg = 2; }
-    if (c4 < best) { best = c4; cfg = 4; }
-    if (c3 <= best) { best = c3; cfg = 3; }
-    if (a->N <= 256) {  // narrow outputs (deconvolution layers): a taller tile restores the flop/byte ratio
-      const double c5 = (double)rounds(384, 128, 256) * 384 * 128 / CFG3_SPEEDUP;
-      if (c5 < best) { best = c5; cfg = 5; }
-    }
-  }
-  int bm = cfg == 1 ? 128 : (cfg == 5 ? 384 : (cfg == 8 ? 256 : 192));
-  int bn = cfg == 1 ? 128 : (cfg == 2 ? 96 : ((cfg == 3 || cfg == 6 || cfg == 10 || cfg == 13 || cfg == 14) ? 192 : (cfg == 7 ? 384 : ((cfg == 8 || cfg == 9) ? 256 : 128))));
-  if (cfg >= 18) gemm_quad_tile_shape(cfg, &bm, &bn);
-  p.tiles_m = cdiv(a->M, bm);
-  p.tiles_n = cdiv(a->N, bn);
-  dim3 grid;
-  auto set_grid = [&](int c) {   // c = tile configuration; tiles_m / tiles_n are set
-    const int rn_ = std::min((c >= 3) ? 4 : 8, p.tiles_n);
-    const long long nblk = (long long)cdiv(p.tiles_m, 8) * cdiv(p.tiles_n, rn_);
-    p.rn = rn_;
-    p.blocked = nblk >= 16 ? 1 : 0;
-    grid = dim3(p.blocked ? (unsigned)(((nblk + 7) / 8) * 8 * 8 * rn_) : (unsigned)(p.tiles_m * p.tiles_n), batch);
-  };
-  set_grid(cfg);
-  {
-    const int oes = (a->dtype == PP_F32 || (a->epilogue & PP_EPI_OUT_F32)) ? 4 : ((a->epilogue & PP_EPI_OUT_FP8) ? 1 : 2),
-              per16 = 16 / oes;
-    p.lds_epilogue = (vec && a->N % per16 == 0 && a->ldc % per16 == 0 && ((uintptr_t)a->C & 15) == 0 &&
-                      (a->strideC % per16) == 0)
-                         ? 1
-                         : 0;
-  }
-  if (a->epilogue & PP_EPI_FUSE_FINAL)
-    PP_REQUIRE(p.lds_epilogue && vec, "pp_gemm: PP_EPI_FUSE_FINAL runs inside the LDS epilogue: C must be 16-byte aligned "
-                                      "(and N = ldc = 256)");
-  hipStream_t s = (hipStream_t)stream;
-  if (cfg >= 18) {
-    // quad forms (pp_gemm_quad.hip): plain bf16 -> bf16 layers, K-tiles of 32 walked in pairs behind a 4-deep ring
-    PP_REQUIRE(a->dtype == PP_BF16 && !a->rowoff && !a->out_rowmap && vec && p.lds_epilogue && batch == 1 &&
-                   a->Kd % 64 == 0 && (a->N & 7) == 0 &&
-                   !(a->epilogue & ~(PP_EPI_BIAS | PP_EPI_GELU | PP_EPI_RELU | PP_EPI_HEADMAJOR)),
-               "pp_gemm: four-wave tiles 15 - 20 (15 - 17 removed, 18 - 20 the stream) serve plain bf16 -> bf16 GEMMs with "
-               "bias / GELU / ReLU epilogues");
-    PP_REQUIRE(a->M % bm == 0 && a->N % bn == 0 && a->Kd >= 512 && (unsigned long long)a->M * a->ldc * 2 < 0xFFFFFFF0ull,
-               "pp_gemm: tiles 18 - 20 (four-wave stream) need M %% %d == 0, N %% %d == 0, K >= 512 and C below 4 GiB", bm, bn);
-    return gemm_quad_launch(p, cfg, grid, s);
-  }
-  if (cfg == 14) {
-    // duo form (gemm_duo_kernel): plain bf16 layers (K a multiple of 64 like every bf16 tile; it stages 32-deep K-tiles)
-    PP_REQUIRE(a->dtype == PP_BF16 && !a->rowoff && !a->out_rowmap && vec && batch == 1 && a->Kd % 64 == 0 &&
-                   !(a->epilogue & ~(PP_EPI_BIAS | PP_EPI_GELU | PP_EPI_RELU | PP_EPI_RESIDUAL | PP_EPI_OUT_F32 |
-                                     PP_EPI_ROWBIAS)) &&
-                   (!(a->epilogue & (PP_EPI_RESIDUAL | PP_EPI_ROWBIAS)) || (a->epilogue & PP_EPI_OUT_F32)) &&
-                   p.lds_epilogue,
-               "pp_gemm: tile 14 (two workgroups per CU) serves plain bf16 GEMMs (bias / GELU / ReLU / f32 residual) whose "
-               "output rows are whole 16-byte chunks (N, ldc multiples of 8 for bf16 / 4 for f32 outputs, C 16-byte aligned)");
-    constexpr int lds = 3 * (192 + 192) * 64;
-    static thread_local unsigned long long attr_mask = 0;
-    int dev_ = 0;
-    if (attr_needed(attr_mask, dev_))
-      PP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_duo_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    hipLaunchKernelGGL(gemm_duo_kernel, grid, dim3(256), lds, s, p);
-    PP_CHECK_LAUNCH("gemm_duo_kernel");
-    return 0;
-  }
-  if (cfg == 13) {
-    // persistent 192x192 form (gemm_persist_kernel): plain bf16 -> bf16 layers only
-    PP_REQUIRE(a->dtype == PP_BF16 && !a->rowoff && !a->out_rowmap && vec && p.lds_epilogue && batch == 1 &&
-                   !(a->epilogue & ~(PP_EPI_BIAS | PP_EPI_GELU | PP_EPI_RELU | PP_EPI_HEADMAJOR)) &&
-                   (unsigned long long)a->M * a->ldc * 2 < 0xFFFFFFF0ull,
-               "pp_gemm: tile 13 (persistent) serves plain bf16 -> bf16 GEMMs with bias / GELU / ReLU epilogues only "
-               "(C below 4 GiB: its rows leave through 32-bit buffer offsets)");
-    static int ncu = 0;
-    if (ncu == 0) {
-      int dev = 0, n = 0;
-      PP_CHECK_HIP(hipGetDevice(&dev));
-      PP_CHECK_HIP(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev));
-      ncu = n > 0 ? n : 256;
-    }
-    const int vblocks = (int)grid.x;
-    int wgs = std::min(vblocks, ncu);
-    if (wgs >= 8) wgs &= ~7;                      // a multiple of 8 keeps every workgroup's tiles on its XCD
-    constexpr int lds = 3 * (192 + 192) * ROW_BYTES + 3 * 192 * 4;
-    static thread_local unsigned long long attr_mask = 0;
-    int dev_ = 0;
-    if (attr_needed(attr_mask, dev_)) {
-      PP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_persist_kernel<0>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-      PP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_persist_kernel<1>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-      PP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_persist_kernel<2>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    }
-    if (a->epilogue & PP_EPI_GELU) hipLaunchKernelGGL(gemm_persist_kernel<1>, dim3(wgs), dim3(512), lds, s, p, vblocks);
-    else if (a->epilogue & PP_EPI_RELU) hipLaunchKernelGGL(gemm_persist_kernel<2>, dim3(wgs), dim3(512), lds, s, p, vblocks);
-    else hipLaunchKernelGGL(gemm_persist_kernel<0>, dim3(wgs), dim3(512), lds, s, p, vblocks);
-    PP_CHECK_LAUNCH("gemm_persist_kernel");
-    return 0;
-  }
-#define PP_LAUNCH_GEMM_P(T, BM_, BN_, WGM_, WGN_, ST_, G_, V_, NWP_, PP_)                         \
-  do {                                                                                                \
-    constexpr int lds = gemm_lds_bytes(BM_, BN_, ST_);                                                \
-    static thread_local unsigned long long attr_mask = 0;                                             \
-    int dev_ = 0;                                                                                     \
-    if (attr_needed(attr_mask, dev_))                                                                 \
-      PP_CHECK_HIP(hipFuncSetAttribute(                                                               \
-          reinterpret_cast<const void *>(gemm_kernel<T, BM_, BN_, WGM_, WGN_, ST_, G_, V_, NWP_, PP_>), \
-          hipFuncAttributeMaxDynamicSharedMemorySize, lds));                                          \
-    hipLaunchKernelGGL((gemm_kernel<T, BM_, BN_, WGM_, WGN_, ST_, G_, V_, NWP_, PP_>), grid,     \
-                       dim3(64 * (WGM_ * WGN_ + NWP_)), lds, s, p);                                   \
-  } while (0)
-#define PP_LAUNCH_GEMM_PP(T, BM_, BN_, WGM_, WGN_, ST_)                                               \
-  do {                                                                                                \
-    if (gather) PP_LAUNCH_GEMM_P(T, BM_, BN_, WGM_, WGN_, ST_, true, true, 0, true);               \
-    else PP_LAUNCH_GEMM_P(T, BM_, BN_, WGM_, WGN_, ST_, false, true, 0, true);                     \
-  } while (0)
-#define PP_LAUNCH_GEMM_W(T, BM_, BN_, WGM_, WGN_, ST_, G_, V_, NWP_) PP_LAUNCH_GEMM_P(T, BM_, BN_, WGM_, WGN_, ST_, G_, V_, NWP_, false)
-#define PP_LAUNCH_GEMM_V(T, BM_, BN_, WGM_, WGN_, ST_, G_, V_) PP_LAUNCH_GEMM_W(T, BM_, BN_, WGM_, WGN_, ST_, G_, V_, 0)
-#define PP_LAUNCH_GEMM(T, BM_, BN_, WGM_, WGN_, ST_)                                                  \
-  do {                                                                                                \
-    if (gather) PP_LAUNCH_GEMM_V(T, BM_, BN_, WGM_, WGN_, ST_, true, true);                           \
-    else PP_LAUNCH_GEMM_V(T, BM_, BN_, WGM_, WGN_, ST_, false, true);                                 \
-  } while (0)
-  const bool gather = a->rowoff != nullptr;
-  if (a->dtype == PP_FP8) {
-    PP_REQUIRE(vec && p.lds_epilogue, "pp_gemm: fp8 needs the vector / LDS epilogue path (aligned N, ldc, C)");
-    if (!(cfg == 2 || cfg == 3 || cfg == 10)) {
-      PP_REQUIRE(a->tile == 0, "pp_gemm: fp8 is built for tiles 2, 3 and 10, got tile %d", cfg);
-      cfg = 3;
-      p.tiles_m = cdiv(a->M, 192);
-      p.tiles_n = cdiv(a->N, 192);
-      set_grid(3);
-    }
-    if (cfg == 2) PP_LAUNCH_GEMM_V(fp8_t, 192, 96, 2, 2, 2, false, true);
-    else if (cfg == 10) PP_LAUNCH_GEMM_P(fp8_t, 192, 192, 2, 4, 3, false, true, 0, true);
-    else PP_LAUNCH_GEMM_V(fp8_t, 192, 192, 2, 4, 3, false, true);
-  } else if (!vec) {  // ragged N / heatmap epilogue: element-wise variant, 128x128 only
-    if (a->dtype == PP_BF16) {
-      if (gather) PP_LAUNCH_GEMM_V(bf16_t, 128, 128, 2, 2, 2, true, false);
-      else PP_LAUNCH_GEMM_V(bf16_t, 128, 128, 2, 2, 2, false, false);
-    } else {
-      if (gather) PP_LAUNCH_GEMM_V(float, 128, 128, 2, 2, 2, true, false);
-      else PP_LAUNCH_GEMM_V(float, 128, 128, 2, 2, 2, false, false);
-    }
-  } else if (a->dtype == PP_BF16) {
-    if (cfg == 1) PP_LAUNCH_GEMM(bf16_t, 128, 128, 2, 2, 2);
-    else if (cfg == 2) PP_LAUNCH_GEMM(bf16_t, 192, 96, 2, 2, 2);
-    else if (cfg == 3) PP_LAUNCH_GEMM(bf16_t, 192, 192, 2, 4, 3);
-    else if (cfg == 4) PP_LAUNCH_GEMM(bf16_t, 192, 128, 2, 4, 3);
-    else if (cfg == 5) PP_LAUNCH_GEMM(bf16_t, 384, 128, 2, 4, 2);
-    else if (cfg == 7) PP_LAUNCH_GEMM(bf16_t, 192, 384, 2, 4, 2);
-    else if (cfg == 8) PP_LAUNCH_GEMM(bf16_t, 256, 256, 2, 4, 2);
-    else if (cfg == 9) PP_LAUNCH_GEMM(bf16_t, 192, 256, 2, 4, 2);
-    else if (cfg == 10) PP_LAUNCH_GEMM_PP(bf16_t, 192, 192, 2, 4, 3);
-    else if (gather) PP_LAUNCH_GEMM_W(bf16_t, 192, 192, 2, 4, 3, true, true, 4);
-    else PP_LAUNCH_GEMM_W(bf16_t, 192, 192, 2, 4, 3, false, true, 4);
-  } else {
-    if (cfg == 1) PP_LAUNCH_GEMM(float, 128, 128, 2, 2, 2);
-    else if (cfg == 2) PP_LAUNCH_GEMM(float, 192, 96, 2, 2, 2);
-    else if (cfg == 3) PP_LAUNCH_GEMM(float, 192, 192, 2, 4, 3);
-    else if (cfg == 4) PP_LAUNCH_GEMM(float, 192, 128, 2, 4, 3);
-    else if (cfg == 5) PP_LAUNCH_GEMM(float, 384, 128, 2, 4, 2);
-    else if (cfg == 7) PP_LAUNCH_GEMM(float, 192, 384, 2, 4, 2);
-    else if (cfg == 8 || cfg == 9) return fail("pp_gemm: the 256-wide tiles are built for bf16 only (fp32 fragments do not fit the register file)");
-    else if (cfg == 10) PP_LAUNCH_GEMM_PP(float, 192, 192, 2, 4, 3);
-    else if (gather) PP_LAUNCH_GEMM_W(float, 192, 192, 2, 4, 3, true, true, 4);
-    else PP_LAUNCH_GEMM_W(float, 192, 192, 2, 4, 3, false, true, 4);
-  }
-#undef PP_LAUNCH_GEMM_V
-#undef PP_LAUNCH_GEMM_W
-#undef PP_LAUNCH_GEMM_L
-#undef PP_LAUNCH_GEMM_P
-#undef PP_LAUNCH_GEMM_PP
-#undef PP_LAUNCH_GEMM
+  p.lds_epilogue = c.lds_epilogue;
+  p.tiles_m = cdiv(a->M, f.bm);
+  p.tiles_n = cdiv(a->N, f.bn);
+  p.rn = std::min(f.xcd_rn, p.tiles_n);
+  const long long nblk = (long long)cdiv(p.tiles_m, 8) * cdiv(p.tiles_n, p.rn);
+  p.blocked = nblk >= 16 ? 1 : 0;
+  return dim3(p.blocked ? (unsigned)(((nblk + 7) / 8) * 8 * 8 * p.rn) : (unsigned)(p.tiles_m * p.tiles_n), c.batch);
+}
+
+// ---- launchers, one per kernel family.  Template arguments come from the form's row, so a launch cannot disagree
+// with the table about its tile.
+template <typename T, int BM, int BN, int WGM, int WGN, int ST, bool GATHER, bool VEC, int NWP, bool PP>
+static int launch_grid(const GemmParams &p, dim3 grid, hipStream_t s) {
+  constexpr int lds = gemm_lds_bytes(BM, BN, ST);
+  constexpr auto kernel = gemm_kernel<T, BM, BN, WGM, WGN, ST, GATHER, VEC, NWP, PP>;
+  if (int rc = ensure_dynamic_lds(kernel, lds)) return rc;
+  hipLaunchKernelGGL(kernel, grid, dim3(64 * (WGM * WGN + NWP)), lds, s, p);
   PP_CHECK_LAUNCH("gemm_kernel");
   return 0;
+}
+
+// Grid form TILE for storage type T, in the instantiations that exist: no gather for fp8, VEC = false for one form.
+template <typename T, int TILE>
+static int launch_grid_form(const GemmCall &c, const GemmParams &p, dim3 grid, hipStream_t s) {
+  constexpr GemmForm f = gemm_form(TILE);
+  constexpr int dtype = std::is_same_v<T, float> ? PP_F32 : (std::is_same_v<T, bf16_t> ? PP_BF16 : PP_FP8);
+  static_assert(f.family == GemmFamily::Grid && (f.dtypes >> dtype & 1), "this form is not built for this dtype");
+  if constexpr (TILE == GEMM_TILE_RAGGED) {
+    if (!c.vec)
+      return p.rowoff ? launch_grid<T, f.bm, f.bn, f.wgm, f.wgn, f.stages, true, false, f.nwp, f.pingpong>(p, grid, s)
+                      : launch_grid<T, f.bm, f.bn, f.wgm, f.wgn, f.stages, false, false, f.nwp, f.pingpong>(p, grid, s);
+  }
+  if constexpr (dtype != PP_FP8) {
+    if (p.rowoff) return launch_grid<T, f.bm, f.bn, f.wgm, f.wgn, f.stages, true, true, f.nwp, f.pingpong>(p, grid, s);
+  }
+  return launch_grid<T, f.bm, f.bn, f.wgm, f.wgn, f.stages, false, true, f.nwp, f.pingpong>(p, grid, s);
+}
+
+// one workgroup per CU walks the tiles: a multiple of 8 workgroups keeps every workgroup's tiles on its XCD
+static int launch_persist(const GemmParams &p, dim3 grid, hipStream_t s) {
+  constexpr GemmForm f = gemm_form(13);
+  static_assert(f.family == GemmFamily::Persist && f.wgm * f.wgn == 8);
+  constexpr int lds = f.stages * (f.bm + f.bn) * ROW_BYTES + 3 * f.bn * 4;   // the ring, then 3 bias slots of bn floats
+  int ncu = 0;
+  if (int rc = cu_count(&ncu)) return rc;
+  const int vblocks = (int)grid.x;
+  int wgs = std::min(vblocks, ncu);
+  if (wgs >= 8) wgs &= ~7;
+  const auto kernel = (p.epilogue & PP_EPI_GELU)   ? gemm_persist_kernel<1>
+                      : (p.epilogue & PP_EPI_RELU) ? gemm_persist_kernel<2>
+                                                   : gemm_persist_kernel<0>;
+  if (int rc = ensure_dynamic_lds(kernel, lds)) return rc;
+  hipLaunchKernelGGL(kernel, dim3(wgs), dim3(64 * f.wgm * f.wgn), lds, s, p, vblocks);
+  PP_CHECK_LAUNCH("gemm_persist_kernel");
+  return 0;
+}
+
+static int launch_duo(const GemmParams &p, dim3 grid, hipStream_t s) {
+  constexpr GemmForm f = gemm_form(14);
+  static_assert(f.family == GemmFamily::Duo && f.wgm * f.wgn == 4);
+  constexpr int lds = f.stages * (f.bm + f.bn) * 64;   // 32-deep bf16 K-tiles: 64 bytes per staged row
+  if (int rc = ensure_dynamic_lds(gemm_duo_kernel, lds)) return rc;
+  hipLaunchKernelGGL(gemm_duo_kernel, grid, dim3(64 * f.wgm * f.wgn), lds, s, p);
+  PP_CHECK_LAUNCH("gemm_duo_kernel");
+  return 0;
+}
+
+// (form, dtype) -> the kernel instantiation.  A case that names a form the table does not build for that dtype does
+// not compile; a pair without a case was refused by admit().
+static int launch(const GemmCall &c, const GemmForm &f, const GemmParams &p, dim3 grid, hipStream_t s) {
+  constexpr auto key = [](int tile, int dtype) { return tile * 4 + dtype; };
+  switch (key(f.tile, c.a->dtype)) {
+    case key(1, PP_F32): return launch_grid_form<float, 1>(c, p, grid, s);
+    case key(2, PP_F32): return launch_grid_form<float, 2>(c, p, grid, s);
+    case key(3, PP_F32): return launch_grid_form<float, 3>(c, p, grid, s);
+    case key(4, PP_F32): return launch_grid_form<float, 4>(c, p, grid, s);
+    case key(5, PP_F32): return launch_grid_form<float, 5>(c, p, grid, s);
+    case key(6, PP_F32): return launch_grid_form<float, 6>(c, p, grid, s);
+    case key(7, PP_F32): return launch_grid_form<float, 7>(c, p, grid, s);
+    case key(10, PP_F32): return launch_grid_form<float, 10>(c, p, grid, s);
+    case key(1, PP_BF16): return launch_grid_form<bf16_t, 1>(c, p, grid, s);
+    case key(2, PP_BF16): return launch_grid_form<bf16_t, 2>(c, p, grid, s);
+    case key(3, PP_BF16): return launch_grid_form<bf16_t, 3>(c, p, grid, s);
+    case key(4, PP_BF16): return launch_grid_form<bf16_t, 4>(c, p, grid, s);
+    case key(5, PP_BF16): return launch_grid_form<bf16_t, 5>(c, p, grid, s);
+    case key(6, PP_BF16): return launch_grid_form<bf16_t, 6>(c, p, grid, s);
+    case key(7, PP_BF16): return launch_grid_form<bf16_t, 7>(c, p, grid, s);
+    case key(8, PP_BF16): return launch_grid_form<bf16_t, 8>(c, p, grid, s);
+    case key(9, PP_BF16): return launch_grid_form<bf16_t, 9>(c, p, grid, s);
+    case key(10, PP_BF16): return launch_grid_form<bf16_t, 10>(c, p, grid, s);
+    case key(2, PP_FP8): return launch_grid_form<fp8_t, 2>(c, p, grid, s);
+    case key(3, PP_FP8): return launch_grid_form<fp8_t, 3>(c, p, grid, s);
+    case key(10, PP_FP8): return launch_grid_form<fp8_t, 10>(c, p, grid, s);
+    case key(13, PP_BF16): return launch_persist(p, grid, s);
+    case key(14, PP_BF16): return launch_duo(p, grid, s);
+    case key(18, PP_BF16): case key(19, PP_BF16): case key(20, PP_BF16): return gemm_quad_launch(p, f.tile, grid, s);
+    default: return fail("pp_gemm: no kernel for tile %d with dtype %d", f.tile, c.a->dtype);
+  }
+}
+
+}  // namespace pp
+
+extern "C" int pp_gemm(const pp_gemm_args *a, void *stream) {
+  using namespace pp;
+  PP_REQUIRE(a, "pp_gemm: null args");
+  PP_REQUIRE(a->dtype == PP_F32 || a->dtype == PP_BF16 || a->dtype == PP_FP8, "pp_gemm: bad dtype %d", a->dtype);
+  PP_REQUIRE(a->M >= 0 && a->N > 0 && a->Kd > 0, "pp_gemm: bad shape M=%d N=%d K=%d", a->M, a->N, a->Kd);
+  if (a->M == 0 || a->batch == 0) return 0;
+  const int es = a->dtype == PP_BF16 ? 2 : (a->dtype == PP_FP8 ? 1 : 4);
+  if (int rc = check_args(a, es)) return rc;
+  GemmCall c{a};
+  c.batch = (a->batch > 0 ? a->batch : 1) * (a->splitk > 1 ? a->splitk : 1);
+  PP_REQUIRE(c.batch <= 65535, "pp_gemm: batch too large");
+  c.vec = (a->N & 3) == 0 && (a->ldc & 3) == 0 && !(a->epilogue & PP_EPI_HEATMAP);
+  const int out_es = (a->dtype == PP_F32 || (a->epilogue & PP_EPI_OUT_F32)) ? 4 : ((a->epilogue & PP_EPI_OUT_FP8) ? 1 : 2),
+            per16 = 16 / out_es;
+  c.lds_epilogue = c.vec && a->N % per16 == 0 && a->ldc % per16 == 0 && ((uintptr_t)a->C & 15) == 0 && a->strideC % per16 == 0;
+  const GemmForm *f = nullptr;
+  if (int rc = select_form(c, &f)) return rc;
+  if (int rc = admit(c, &f)) return rc;
+  GemmParams p;
+  const dim3 grid = fill_params(c, *f, p);
+  return launch(c, *f, p, grid, (hipStream_t)stream);
 }

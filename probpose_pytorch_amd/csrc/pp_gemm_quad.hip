@@ -25,6 +25,7 @@
 #include <utility>
 
 #include "pp_gemm_shared.h"
+#include "pp_gemm_forms.h"
 
 namespace pp {
 
@@ -519,49 +520,35 @@ __global__ __launch_bounds__(256, 1) void gemm_quad_stream_kernel(GemmParams p, 
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-template <int TM, int TN>
-static int quad_stream_launch_shape(const GemmParams &p, dim3 grid, hipStream_t s) {
-  constexpr int lds = quad_stream_lds_bytes(TM, TN);
-  static thread_local unsigned long long attr_mask = 0;
-  static int ncu = 0;
-  int dev_ = 0;
-  if (attr_needed(attr_mask, dev_)) {
-    PP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_quad_stream_kernel<TM, TN, 0>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    PP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_quad_stream_kernel<TM, TN, 1>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    PP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_quad_stream_kernel<TM, TN, 2>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-  }
-  if (ncu == 0) {
-    int dev = 0, n = 0;
-    PP_CHECK_HIP(hipGetDevice(&dev));
-    PP_CHECK_HIP(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev));
-    ncu = n > 0 ? n : 256;
-  }
+// One workgroup per CU walks the form's tiles (grid.x = their count): a multiple of 8 workgroups keeps every
+// workgroup's tiles on its XCD.  The wave tile follows from the form's row: 2 x 2 waves of TM x TN 16x16 MFMA tiles.
+template <int TILE>
+static int quad_stream_launch(const GemmParams &p, dim3 grid, hipStream_t s) {
+  constexpr GemmForm f = gemm_form(TILE);
+  static_assert(f.family == GemmFamily::QuadStream && f.wgm == 2 && f.wgn == 2 && f.stages == 4);
+  constexpr int TM = f.bm / 32, TN = f.bn / 32, lds = quad_stream_lds_bytes(TM, TN);
+  int ncu = 0;
+  if (int rc = cu_count(&ncu)) return rc;
   const int vblocks = (int)grid.x;
   int wgs = std::min(vblocks, ncu);
-  if (wgs >= 8) wgs &= ~7;                      // a multiple of 8 keeps every workgroup's tiles on its XCD
-  if (p.epilogue & PP_EPI_GELU) hipLaunchKernelGGL((gemm_quad_stream_kernel<TM, TN, 1>), dim3(wgs), dim3(256), lds, s, p, vblocks);
-  else if (p.epilogue & PP_EPI_RELU) hipLaunchKernelGGL((gemm_quad_stream_kernel<TM, TN, 2>), dim3(wgs), dim3(256), lds, s, p, vblocks);
-  else hipLaunchKernelGGL((gemm_quad_stream_kernel<TM, TN, 0>), dim3(wgs), dim3(256), lds, s, p, vblocks);
+  if (wgs >= 8) wgs &= ~7;
+  const auto kernel = (p.epilogue & PP_EPI_GELU)   ? gemm_quad_stream_kernel<TM, TN, 1>
+                      : (p.epilogue & PP_EPI_RELU) ? gemm_quad_stream_kernel<TM, TN, 2>
+                                                   : gemm_quad_stream_kernel<TM, TN, 0>;
+  if (int rc = ensure_dynamic_lds(kernel, lds)) return rc;
+  hipLaunchKernelGGL(kernel, dim3(wgs), dim3(256), lds, s, p, vblocks);
   PP_CHECK_LAUNCH("gemm_quad_stream_kernel");
   return 0;
 }
 
-// tiles 18 - 20 of pp_gemm (argument checks are the caller's: pp_gemm.hip)
-int gemm_quad_launch(const GemmParams &p, int cfg, dim3 grid, hipStream_t s) {
-  switch (cfg) {
-    case 18: return quad_stream_launch_shape<8, 6>(p, grid, s);   // 256 x 192, stream
-    case 19: return quad_stream_launch_shape<6, 9>(p, grid, s);   // 192 x 288, stream
-    case 20: return quad_stream_launch_shape<6, 8>(p, grid, s);   // 192 x 256, stream
-    default: return fail("pp_gemm: tile %d is not a four-wave stream form (tiles 18 - 20)", cfg);
+// the QuadStream forms of pp_gemm (argument checks are the caller's: pp_gemm.hip)
+int gemm_quad_launch(const GemmParams &p, int tile, dim3 grid, hipStream_t s) {
+  switch (tile) {
+    case 18: return quad_stream_launch<18>(p, grid, s);
+    case 19: return quad_stream_launch<19>(p, grid, s);
+    case 20: return quad_stream_launch<20>(p, grid, s);
+    default: return fail("pp_gemm: tile %d is not a four-wave stream form (tiles 18 - 20)", tile);
   }
-}
-
-void gemm_quad_tile_shape(int cfg, int *bm, int *bn) {
-  *bm = cfg == 18 ? 256 : 192;
-  *bn = cfg == 18 ? 192 : (cfg == 19 ? 288 : 256);
 }
 
 }  // namespace pp

@@ -750,8 +750,7 @@ static int final_heatmap_launch(const void *x, const void *w, const float *bias,
 #define PP_FHM(NT_)                                                                                       \
   do {                                                                                                    \
     if (lds_w > 64 * 1024)                                                                                \
-      PP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&final_heatmap_mfma_kernel<NT_, CLAMP>),    \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_w));          \
+      if (int rc = ensure_dynamic_lds(final_heatmap_mfma_kernel<NT_, CLAMP>, lds_w)) return rc;           \
     hipLaunchKernelGGL((final_heatmap_mfma_kernel<NT_, CLAMP>), dim3(grid), dim3(256), lds_w, sm, (const bf16_t *)x, \
                        (const bf16_t *)w, bias, out, tiles, HW, Cin, K, temperature);                     \
   } while (0)
@@ -768,14 +767,12 @@ static int final_heatmap_launch(const void *x, const void *w, const float *bias,
   const int grid = cdiv(M, FH_ROWS);
   if (dtype == PP_BF16) {
     if (lds > 64 * 1024)
-      PP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(final_heatmap_kernel<bf16_t, CLAMP>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      if (int rc = ensure_dynamic_lds(final_heatmap_kernel<bf16_t, CLAMP>, lds)) return rc;
     hipLaunchKernelGGL((final_heatmap_kernel<bf16_t, CLAMP>), dim3(grid), dim3(256), lds, s, (const bf16_t *)x,
                        (const bf16_t *)w, bias, out, (int)M, HW, Cin, K, temperature);
   } else {
     if (lds > 64 * 1024)
-      PP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(final_heatmap_kernel<float, CLAMP>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      if (int rc = ensure_dynamic_lds(final_heatmap_kernel<float, CLAMP>, lds)) return rc;
     hipLaunchKernelGGL((final_heatmap_kernel<float, CLAMP>), dim3(grid), dim3(256), lds, s, (const float *)x,
                        (const float *)w, bias, out, (int)M, HW, Cin, K, temperature);
   }
