@@ -584,6 +584,33 @@ int pp_attention_backward(const void *qkv, const void *out, const void *dout, vo
 int pp_rows_period_sum(const float *x, int B, int N, int C, float *out, void *stream);
 
 /* ------------------------------------------------------------------------
+ * Stochastic depth in the training backbone (ScratchViTBackbone(drop_path_rate=...), timm's DropPath with
+ * scale_by_keep): r_out[b] = r_in[b] + keep[b] / (1 - p) branch(r_in)[b] per crop b.  The branch (LayerNorm, GEMMs,
+ * attention, GELU: the kernels above, unchanged) runs on the kept crops only, on compact buffers [kept*N, C]; these
+ * three kernels move whole crops (N rows of C) between the residual stream [B*N, C] and the compact buffers.
+ * idx [kept] int32: the kept crops, each at most once (ascending as vit_train.py builds it); slot [B] int32: a crop's
+ * position in idx, or -1 for a dropped crop.  0 < kept <= B <= 65535.  128-bit accesses where C % 4 == 0 and every
+ * buffer is 16-byte aligned, scalar accesses otherwise.  One writer per output element, no atomics: repeated calls
+ * give the same bits.  A table entry out of range is skipped (idx) or taken as dropped (slot).
+ *
+ * pp_crop_rows_gather: dst[(j N + n) C + c] = scale src[(idx[j] N + n) C + c], j < kept; src [B*N, C] f32, dst
+ *   [kept*N, C] in dtype (PP_F32 / PP_BF16), one f32 multiply, then rounded once to dtype.  scale == 1 and PP_F32: an
+ *   exact copy.
+ * pp_droppath_add: out[b] = fmaf(scale, branch[slot[b]], r[b]) where slot[b] >= 0 (a single fma: ONE rounding of the
+ *   exact r + scale branch), else out[b] = r[b] with its bits; r, out [B*N, C] f32, branch [kept*N, C] f32.  out must
+ *   not alias r or branch.
+ * pp_crop_rows_scatter_add: dres[idx[j]] += dx[j] in place (one f32 add), and the same rows of dres_c = the new dres
+ *   rounded to dtype; dx [kept*N, C] f32, dres [B*N, C] f32, dres_c [B*N, C] in dtype.  Rows of crops that are not in
+ *   idx are not touched in either buffer.
+ * ---------------------------------------------------------------------- */
+int pp_crop_rows_gather(const float *src, const int *idx, int B, int kept, int N, int C, float scale, void *dst,
+                        int dtype, void *stream);
+int pp_droppath_add(const float *r, const float *branch, const int *slot, int B, int kept, int N, int C, float scale,
+                    float *out, void *stream);
+int pp_crop_rows_scatter_add(const float *dx, const int *idx, int B, int kept, int N, int C, float *dres, void *dres_c,
+                             int dtype, void *stream);
+
+/* ------------------------------------------------------------------------
  * FusedAdamW (probpose_pytorch_amd/optim.py): train.py:113-115's clip_grad_norm_ + AdamW.step() over all parameter
  * tensors in at most three launches, no host sync, no float atomics.  All tensors contiguous float32.
  *

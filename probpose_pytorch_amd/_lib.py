@@ -124,6 +124,9 @@ _SIGNATURES = {
     "pp_attention_backward_workspace_bytes": (C.c_longlong, [_i, _i, _i]),
     "pp_attention_backward": (C.c_int, [_vp] * 4 + [_i] * 5 + [_vp, _vp]),
     "pp_rows_period_sum": (C.c_int, [_vp, _i, _i, _i, _vp, _vp]),
+    "pp_crop_rows_gather": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _f, _vp, _i, _vp]),
+    "pp_droppath_add": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp]),
+    "pp_crop_rows_scatter_add": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     "pp_optim_table_bytes": (C.c_longlong, [_i, _vp, _i]),
     "pp_optim_table_build": (C.c_int, [_i] + [_vp] * 7 + [_i] + [_vp] * 3 + [_i, C.POINTER(C.c_int),
                                                                              C.POINTER(C.c_longlong)]),

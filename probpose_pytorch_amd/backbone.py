@@ -67,15 +67,23 @@ class VisionTransformer(nn.Module):
     absolute pos-emb (1,N,C), pre-LN blocks, final ``norm``)."""
 
     def __init__(self, img_size=(256, 192), patch_size: int = 16, in_chans: int = 3, embed_dim: int = 384,
-                 depth: int = 12, num_heads: int = 12, mlp_ratio: float = 4.0, differentiable: bool = False):
+                 depth: int = 12, num_heads: int = 12, mlp_ratio: float = 4.0, differentiable: bool = False,
+                 drop_path_rate: float = 0.0):
         super().__init__()
         if in_chans != 3:
             raise ValueError("the HIP patch-embed path is built for 3-channel crops")
+        if not 0.0 <= drop_path_rate < 1.0:
+            raise ValueError(f"drop_path_rate must be in [0, 1), got {drop_path_rate}")
         self.embed_dim = self.num_features = embed_dim
         self.num_heads = num_heads
         # True: in .train() mode with grad enabled and a parameter that requires grad, the forward runs as one
         # differentiable node with a HIP backward (vit_train.py); otherwise the inference path runs unchanged
         self.differentiable = differentiable
+        # stochastic depth (timm's linear schedule): block i drops each crop's attention / MLP branch with probability
+        # drop_path_rates[i] where the training path runs (vit_train.py); plain floats, no parameter and no buffer
+        self.drop_path_rate = float(drop_path_rate)
+        self.drop_path_rates = [float(v) for v in torch.linspace(0, drop_path_rate, depth)]
+        self.last_drop_path_keep = None     # the [depth, 2, B] keep mask of the latest training forward (None: rate 0)
         self.patch_embed = PatchEmbed(img_size, patch_size, in_chans, embed_dim)
         self.pos_embed = nn.Parameter(torch.zeros(1, self.patch_embed.num_patches, embed_dim))
         self.blocks = nn.Sequential(*[Block(embed_dim, num_heads, mlp_ratio) for _ in range(depth)])
@@ -136,14 +144,24 @@ class ScratchViTBackbone(nn.Module):
 
     The reference hard-codes ``embed_dim=384`` with timm's default depth 12 /
     12 heads; ``embed_dim``/``depth``/``num_heads`` are extensions for the
-    ViT-B/L/H configurations of BASELINE.json."""
+    ViT-B/L/H configurations of BASELINE.json, ``drop_path_rate`` is timm's
+    ``VisionTransformer`` argument (stochastic depth in the training path)."""
 
     def __init__(self, input_image_size, patch_size: int, embed_dim: int = 384, depth: int = 12,
-                 num_heads: int = 12, mlp_ratio: float = 4.0, differentiable: bool = False):
+                 num_heads: int = 12, mlp_ratio: float = 4.0, differentiable: bool = False,
+                 drop_path_rate: float = 0.0):
         super().__init__()
         self.model = VisionTransformer(img_size=input_image_size, patch_size=patch_size, embed_dim=embed_dim,
                                        depth=depth, num_heads=num_heads, mlp_ratio=mlp_ratio,
-                                       differentiable=differentiable)
+                                       differentiable=differentiable, drop_path_rate=drop_path_rate)
+
+    @property
+    def drop_path_rates(self):
+        return self.model.drop_path_rates
+
+    @property
+    def last_drop_path_keep(self):
+        return self.model.last_drop_path_keep
 
     @property
     def differentiable(self) -> bool:

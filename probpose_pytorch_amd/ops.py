@@ -458,3 +458,34 @@ def rows_period_sum(x, B, N, Cc, out):
     """out [N, C] = sum over b of x [B*N, C] (f32, fixed order): the pos_embed gradient."""
     _lib.check(_lib.lib().pp_rows_period_sum(_p(x), B, N, Cc, _p(out), _lib.stream_ptr()), "pp_rows_period_sum")
     return out
+
+
+# ---- stochastic depth in the training backbone (pp_droppath.hip) -----------------------------------------------
+def crop_rows_gather(src, idx, B, N, Cc, out, scale=1.0):
+    """out [kept*N, C] (f32 or bf16) = scale * the crops idx [kept] (int32) of src [B*N, C] f32."""
+    kept = idx.numel()
+    rc = _timed("crop_rows_gather", float(kept * N * Cc * (4 + out.element_size())),
+                lambda: _lib.lib().pp_crop_rows_gather(_p(src), _p(idx), B, kept, N, Cc, float(scale), _p(out),
+                                                       dtype_code(out.dtype), _lib.stream_ptr()))
+    _lib.check(rc, "pp_crop_rows_gather")
+    return out
+
+
+def droppath_add(r, branch, slot, B, kept, N, Cc, scale, out):
+    """out [B*N, C] = r + scale * branch[slot[b]] for the kept crops (slot [B] int32 >= 0), r's bits for the others;
+    r, out f32 [B*N, C], branch f32 [kept*N, C]."""
+    rc = _timed("droppath_add", float((2 * B + kept) * N * Cc * 4),
+                lambda: _lib.lib().pp_droppath_add(_p(r), _p(branch), _p(slot), B, kept, N, Cc, float(scale), _p(out),
+                                                   _lib.stream_ptr()))
+    _lib.check(rc, "pp_droppath_add")
+    return out
+
+
+def crop_rows_scatter_add(dx, idx, B, N, Cc, dres, dres_c):
+    """dres[idx[j]] += dx[j] (crops of N rows, f32) in place; the same rows of dres_c = the new dres in its dtype."""
+    kept = idx.numel()
+    rc = _timed("crop_rows_scatter_add", float(kept * N * Cc * (12 + dres_c.element_size())),
+                lambda: _lib.lib().pp_crop_rows_scatter_add(_p(dx), _p(idx), B, kept, N, Cc, _p(dres), _p(dres_c),
+                                                            dtype_code(dres_c.dtype), _lib.stream_ptr()))
+    _lib.check(rc, "pp_crop_rows_scatter_add")
+    return dres

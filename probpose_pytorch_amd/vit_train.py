@@ -11,11 +11,20 @@ call: no host copy, no ``VitPlan`` rebuild.  The backward packs the transposed w
 are then; the parameters are saved with ``save_for_backward``, so an in-place update between the forward and the
 backward (an optimizer step before a delayed backward) raises instead of mixing weights.  The saved activations are
 released as soon as the backward has run.
+
+Stochastic depth (``drop_path_rate > 0``, timm's DropPath with scale_by_keep): block i drops each crop's attention
+branch and MLP branch independently with probability ``drop_path_rates[i]``; r_out[b] = r_in[b] + keep[b] / (1 - p_i)
+branch(r_in)[b].  The keep mask is drawn on the host (``draw_keep``), so the host knows every branch's kept count and
+nothing is read back.  A branch with p_i > 0 gathers the kept crops' residual rows into a compact buffer, runs the
+same kernels on it at batch B' and ends in pp_droppath_add; its backward gathers the scaled output gradient, runs on
+the compact rows and ends in pp_crop_rows_scatter_add (csrc/pp_droppath.hip).  A branch with nothing kept launches
+nothing; a branch with p_i == 0 runs exactly the path above.
 """
 from __future__ import annotations
 
-from typing import List
+from typing import List, Optional
 
+import numpy as np
 import torch
 from torch import nn
 
@@ -52,6 +61,57 @@ def check_trainable(vit, x) -> None:
         raise NotImplementedError("ScratchViTBackbone training: engine.DUAL_CHAIN (two half-batch kernel chains)")
 
 
+def draw_keep(rates, B: int, generator: Optional[torch.Generator] = None) -> torch.Tensor:
+    """The keep mask of one training forward: bool [depth, 2, B] on the CPU, [:, 0] the attention branches, [:, 1] the
+    MLP branches, True with probability 1 - rates[i].  Drawn from torch's default CPU generator (``torch.manual_seed``
+    makes a run reproducible) or from ``generator``; a block at rate 0 is all True and draws nothing."""
+    keep = torch.ones((len(rates), 2, B), dtype=torch.bool)
+    for i, p in enumerate(rates):
+        if p > 0:
+            keep[i] = torch.rand((2, B), generator=generator) >= p
+    return keep
+
+
+def _check_keep(vit, keep, B):
+    rates = vit.drop_path_rates
+    if not (isinstance(keep, torch.Tensor) and keep.dtype == torch.bool and keep.device.type == "cpu"
+            and tuple(keep.shape) == (len(rates), 2, B)):
+        raise ValueError(f"keep must be a bool CPU tensor of shape ({len(rates)}, 2, {B})")
+    for i, p in enumerate(rates):
+        if p == 0 and not bool(keep[i].all()):
+            raise ValueError(f"keep drops a crop in block {i}, whose drop-path rate is 0")
+
+
+def _drop_plan(vit, keep, B, device):
+    """Per block (attention, MLP): None for a branch at rate 0, else dict(k = kept crops, scale = 1 / (1 - p), idx
+    [k] / slot [B] int32 on the device).  Every table goes up in one asynchronous copy from one pinned buffer."""
+    k_np = keep.numpy()
+    slots = np.where(k_np, np.cumsum(k_np, axis=-1, dtype=np.int32) - 1, -1).astype(np.int32)
+    plan, parts, off = [], [], 0
+    for i, p in enumerate(vit.drop_path_rates):
+        if p == 0:
+            plan.append((None, None))
+            continue
+        pair = []
+        for j in range(2):
+            idx = np.flatnonzero(k_np[i, j]).astype(np.int32)
+            pair.append(dict(k=int(idx.size), scale=1.0 / (1.0 - p), off=off))
+            if idx.size:
+                parts += [idx, slots[i, j]]
+                off += idx.size + B
+        plan.append(tuple(pair))
+    if parts:
+        host = torch.empty(off, dtype=torch.int32, pin_memory=True)
+        host.numpy()[:] = np.concatenate(parts)
+        table = host.to(device, non_blocking=True)
+        for pair in plan:
+            for d in pair:
+                if d is not None and d["k"]:
+                    d["idx"] = table[d["off"]:d["off"] + d["k"]]
+                    d["slot"] = table[d["off"] + d["k"]:d["off"] + d["k"] + B]
+    return plan
+
+
 def _w(p, dt):
     return p.detach().to(dt).contiguous()
 
@@ -67,7 +127,7 @@ def _f(p):
 
 class _VitTrainFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, vit, x, nchw, *params):
+    def forward(ctx, vit, x, nchw, keep, *params):
         dt = vit.compute_dtype
         dev = x.device
         B, _, H, W = x.shape
@@ -84,26 +144,60 @@ class _VitTrainFn(torch.autograd.Function):
         ops.gemm(a0, _w(pe.proj.weight.reshape(C, K0), dt), r, M=M, N=C, Kd=K0, lda=K0, ldw=K0, ldc=C,
                  bias=_f(pe.proj.bias), rowbias=_f(vit.pos_embed.reshape(N, C)), rowbias_period=N,
                  epilogue=EPI_OUT_F32)
+        drop = [(None, None)] * len(vit.blocks) if keep is None else _drop_plan(vit, keep, B, dev)
         res, blocks = [r], []
-        for blk in vit.blocks:
+        for blk, (dpa, dpm) in zip(vit.blocks, drop):
             hidden = blk.mlp.fc1.out_features
-            ln1 = torch.empty((M, C), dtype=dt, device=dev)
-            ops.layernorm(r, _f(blk.norm1.weight), _f(blk.norm1.bias), blk.norm1.eps, ln1)
-            qkv = torch.empty((M, 3 * C), dtype=dt, device=dev)
-            ops.linear(ln1, _w(blk.attn.qkv.weight, dt), _f(blk.attn.qkv.bias), out=qkv)
-            ao = torch.empty((M, C), dtype=dt, device=dev)
-            ops.attention(qkv, ao, B, N, heads, hd)
-            r1 = torch.empty((M, C), dtype=f32, device=dev)
-            ops.linear(ao, _w(blk.attn.proj.weight, dt), _f(blk.attn.proj.bias), out=r1, residual=r)
-            ln2 = torch.empty((M, C), dtype=dt, device=dev)
-            ops.layernorm(r1, _f(blk.norm2.weight), _f(blk.norm2.bias), blk.norm2.eps, ln2)
-            pre = torch.empty((M, hidden), dtype=f32, device=dev)
-            ops.linear(ln2, _w(blk.mlp.fc1.weight, dt), _f(blk.mlp.fc1.bias), out=pre, out_dtype=f32)
-            hid = torch.empty((M, hidden), dtype=dt, device=dev)
-            ops.gelu_forward(pre, hid)
-            r2 = torch.empty((M, C), dtype=f32, device=dev)
-            ops.linear(hid, _w(blk.mlp.fc2.weight, dt), _f(blk.mlp.fc2.bias), out=r2, residual=r1)
-            blocks.append(dict(ln1=ln1, qkv=qkv, ao=ao, ln2=ln2, pre=pre, hid=hid))
+            s = dict(dpa=dpa, dpm=dpm)
+            # ---- attention branch: on all rows (rate 0), on the kept crops' rows, or not at all
+            if dpa is None or dpa["k"]:
+                Bb = B if dpa is None else dpa["k"]
+                Mb = Bb * N
+                xa = r
+                if dpa is not None:
+                    xa = dpa["x"] = torch.empty((Mb, C), dtype=f32, device=dev)
+                    ops.crop_rows_gather(r, dpa["idx"], B, N, C, xa)
+                ln1 = torch.empty((Mb, C), dtype=dt, device=dev)
+                ops.layernorm(xa, _f(blk.norm1.weight), _f(blk.norm1.bias), blk.norm1.eps, ln1)
+                qkv = torch.empty((Mb, 3 * C), dtype=dt, device=dev)
+                ops.linear(ln1, _w(blk.attn.qkv.weight, dt), _f(blk.attn.qkv.bias), out=qkv)
+                ao = torch.empty((Mb, C), dtype=dt, device=dev)
+                ops.attention(qkv, ao, Bb, N, heads, hd)
+                r1 = torch.empty((M, C), dtype=f32, device=dev)
+                if dpa is None:
+                    ops.linear(ao, _w(blk.attn.proj.weight, dt), _f(blk.attn.proj.bias), out=r1, residual=r)
+                else:
+                    br = torch.empty((Mb, C), dtype=f32, device=dev)
+                    ops.linear(ao, _w(blk.attn.proj.weight, dt), _f(blk.attn.proj.bias), out=br, out_dtype=f32)
+                    ops.droppath_add(r, br, dpa["slot"], B, Bb, N, C, dpa["scale"], r1)
+                s.update(ln1=ln1, qkv=qkv, ao=ao)
+            else:
+                r1 = r
+            # ---- MLP branch
+            if dpm is None or dpm["k"]:
+                Bb = B if dpm is None else dpm["k"]
+                Mb = Bb * N
+                xm = r1
+                if dpm is not None:
+                    xm = dpm["x"] = torch.empty((Mb, C), dtype=f32, device=dev)
+                    ops.crop_rows_gather(r1, dpm["idx"], B, N, C, xm)
+                ln2 = torch.empty((Mb, C), dtype=dt, device=dev)
+                ops.layernorm(xm, _f(blk.norm2.weight), _f(blk.norm2.bias), blk.norm2.eps, ln2)
+                pre = torch.empty((Mb, hidden), dtype=f32, device=dev)
+                ops.linear(ln2, _w(blk.mlp.fc1.weight, dt), _f(blk.mlp.fc1.bias), out=pre, out_dtype=f32)
+                hid = torch.empty((Mb, hidden), dtype=dt, device=dev)
+                ops.gelu_forward(pre, hid)
+                r2 = torch.empty((M, C), dtype=f32, device=dev)
+                if dpm is None:
+                    ops.linear(hid, _w(blk.mlp.fc2.weight, dt), _f(blk.mlp.fc2.bias), out=r2, residual=r1)
+                else:
+                    br = torch.empty((Mb, C), dtype=f32, device=dev)
+                    ops.linear(hid, _w(blk.mlp.fc2.weight, dt), _f(blk.mlp.fc2.bias), out=br, out_dtype=f32)
+                    ops.droppath_add(r1, br, dpm["slot"], B, Bb, N, C, dpm["scale"], r2)
+                s.update(ln2=ln2, pre=pre, hid=hid)
+            else:
+                r2 = r1
+            blocks.append(s)
             res += [r1, r2]
             r = r2
         feats = torch.empty((M, C), dtype=dt, device=dev)
@@ -126,11 +220,11 @@ class _VitTrainFn(torch.autograd.Function):
             raise RuntimeError("ScratchViTBackbone training: backward through the same forward twice (its saved "
                                "activations are released after the first backward)")
         ctx.saved = None         # once differentiable: the activations go with this call
-        need = ctx.needs_input_grad[3:]
+        need = ctx.needs_input_grad[4:]
         params = list(ctx.saved_tensors)     # raises if a parameter was modified in place since the forward
         grads = [None] * len(params)
         if g is None or not any(need):
-            return (None, None, None, *grads)
+            return (None, None, None, None, *grads)
         dt = vit.compute_dtype
         dev = g.device
         B, N, C, heads = S["B"], S["N"], vit.embed_dim, vit.num_heads
@@ -149,21 +243,98 @@ class _VitTrainFn(torch.autograd.Function):
             if wants(i):
                 grads[i] = t.reshape(params[i].shape).to(params[i].dtype)
 
-        def linear_wgrad(i, dY, A, n_out, k_in):
+        def put_zeros(lo, hi):          # a branch that kept no crop: its parameters' gradients are zero
+            for i in range(lo, hi):
+                if wants(i):
+                    grads[i] = torch.zeros_like(params[i])
+
+        def linear_wgrad(i, dY, A, n_out, k_in, rows):
             if wants(i) or wants(i + 1):
                 dW = torch.empty((n_out, k_in), dtype=f32, device=dev)
                 dB = torch.empty((n_out,), dtype=f32, device=dev)
-                _wgrad(dY, A, dW, M=M, N=n_out, Kd=k_in, ldd=n_out, lda=k_in, dB=dB)
+                _wgrad(dY, A, dW, M=rows, N=n_out, Kd=k_in, ldd=n_out, lda=k_in, dB=dB)
                 put(i, dW)
                 put(i + 1, dB)
 
-        def ln_backward(i, ln, x, dy, accumulate):
+        def ln_backward(i, ln, x, dy, accumulate, dp=None):
+            """The LayerNorm's input gradient into dR / dRc: added in place, or (a branch on compact rows, dp) written
+            to compact scratch and added to its crops' rows by pp_crop_rows_scatter_add."""
             dgb = torch.empty((2, C), dtype=f32, device=dev) if (wants(i) or wants(i + 1)) else None
-            ops.layernorm_backward(x, _f(ln.weight), ln.eps, dy, dR, dRc, accumulate,
+            if dp is None:
+                out, out_c = dR, dRc
+            else:
+                out, out_c, accumulate = torch.empty_like(x), torch.empty(x.shape, dtype=dt, device=dev), False
+            ops.layernorm_backward(x, _f(ln.weight), ln.eps, dy, out, out_c, accumulate,
                                    dgamma=None if dgb is None else dgb[0], dbeta=None if dgb is None else dgb[1])
+            if dp is not None:
+                ops.crop_rows_scatter_add(out, dp["idx"], B, N, C, dR, dRc)
             if dgb is not None:
                 put(i, dgb[0])
                 put(i + 1, dgb[1])
+
+        def branch_grad(dp):
+            """(rows, crops, the branch's output gradient in the compute dtype): dRc itself, or the kept crops' rows
+            of dR times 1 / (1 - p)."""
+            if dp is None:
+                return M, B, dRc
+            dY = torch.empty((dp["k"] * N, C), dtype=dt, device=dev)
+            ops.crop_rows_gather(dR, dp["idx"], B, N, C, dY, dp["scale"])
+            return dp["k"] * N, dp["k"], dY
+
+        def mlp_backward(bi, base, blk, s):
+            """False: nothing below needs a gradient."""
+            dp = s["dpm"]
+            hidden = blk.mlp.fc1.out_features
+            if dp is not None and not dp["k"]:
+                put_zeros(base + 6, base + 12)
+                return below(base + 6)
+            Mb, _, dY = branch_grad(dp)
+            # fc2 (+ residual): its output gradient is dR
+            linear_wgrad(base + 10, dY, s["hid"], C, hidden, Mb)
+            if not below(base + 10):
+                return False
+            dH = torch.empty((Mb, hidden), dtype=f32, device=dev)
+            ops.gemm(dY, _wt(blk.mlp.fc2.weight, dt), dH, M=Mb, N=hidden, Kd=C, lda=C, ldw=C, ldc=hidden,
+                     epilogue=EPI_OUT_F32)
+            dPre = torch.empty((Mb, hidden), dtype=dt, device=dev)
+            ops.gelu_backward(s["pre"], dH, dPre)
+            del dH
+            # fc1
+            linear_wgrad(base + 8, dPre, s["ln2"], hidden, C, Mb)
+            if not below(base + 8):
+                return False
+            dL = torch.empty((Mb, C), dtype=f32, device=dev)
+            ops.gemm(dPre, _wt(blk.mlp.fc1.weight, dt), dL, M=Mb, N=C, Kd=hidden, lda=hidden, ldw=hidden, ldc=C,
+                     epilogue=EPI_OUT_F32)
+            del dPre
+            ln_backward(base + 6, blk.norm2, res[2 * bi + 1] if dp is None else dp["x"], dL, True, dp)
+            return below(base + 6)
+
+        def attn_backward(bi, base, blk, s):
+            dp = s["dpa"]
+            if dp is not None and not dp["k"]:
+                put_zeros(base, base + 6)
+                return below(base)
+            Mb, Bb, dY = branch_grad(dp)
+            # proj (+ residual)
+            linear_wgrad(base + 4, dY, s["ao"], C, C, Mb)
+            if not below(base + 4):
+                return False
+            dO = torch.empty((Mb, C), dtype=dt, device=dev)
+            ops.gemm(dY, _wt(blk.attn.proj.weight, dt), dO, M=Mb, N=C, Kd=C, lda=C, ldw=C, ldc=C)
+            dqkv = torch.empty((Mb, 3 * C), dtype=dt, device=dev)
+            ops.attention_backward(s["qkv"], s["ao"], dO, dqkv, Bb, N, heads, hd)
+            del dO
+            # qkv
+            linear_wgrad(base + 2, dqkv, s["ln1"], 3 * C, C, Mb)
+            if not below(base + 2):
+                return False
+            dL = torch.empty((Mb, C), dtype=f32, device=dev)
+            ops.gemm(dqkv, _wt(blk.attn.qkv.weight, dt), dL, M=Mb, N=C, Kd=3 * C, lda=3 * C, ldw=3 * C, ldc=C,
+                     epilogue=EPI_OUT_F32)
+            del dqkv
+            ln_backward(base, blk.norm1, res[2 * bi] if dp is None else dp["x"], dL, True, dp)
+            return below(base)
 
         # ---- final LayerNorm: dR (f32) and dR_c (compute dtype) = the residual stream's gradient
         if S["nchw"]:
@@ -174,57 +345,13 @@ class _VitTrainFn(torch.autograd.Function):
         dR = torch.empty((M, C), dtype=f32, device=dev)
         dRc = torch.empty((M, C), dtype=dt, device=dev)
         ln_backward(3 + PER_BLOCK * D, vit.norm, res[-1], gy, False)
-        reached_embed = True
+        reached_embed = below(3 + PER_BLOCK * D)
         for bi in range(D - 1, -1, -1):
+            if not reached_embed:
+                break
             base = 3 + PER_BLOCK * bi
             blk, s = vit.blocks[bi], S["blocks"][bi]
-            hidden = blk.mlp.fc1.out_features
-            if not below(base + PER_BLOCK):
-                reached_embed = False
-                break
-            # fc2 (+ residual): its output gradient is dR
-            linear_wgrad(base + 10, dRc, s["hid"], C, hidden)
-            if not below(base + 10):
-                reached_embed = False
-                break
-            dH = torch.empty((M, hidden), dtype=f32, device=dev)
-            ops.gemm(dRc, _wt(blk.mlp.fc2.weight, dt), dH, M=M, N=hidden, Kd=C, lda=C, ldw=C, ldc=hidden,
-                     epilogue=EPI_OUT_F32)
-            dPre = torch.empty((M, hidden), dtype=dt, device=dev)
-            ops.gelu_backward(s["pre"], dH, dPre)
-            del dH
-            # fc1
-            linear_wgrad(base + 8, dPre, s["ln2"], hidden, C)
-            if not below(base + 8):
-                reached_embed = False
-                break
-            dL = torch.empty((M, C), dtype=f32, device=dev)
-            ops.gemm(dPre, _wt(blk.mlp.fc1.weight, dt), dL, M=M, N=C, Kd=hidden, lda=hidden, ldw=hidden, ldc=C,
-                     epilogue=EPI_OUT_F32)
-            del dPre
-            ln_backward(base + 6, blk.norm2, res[2 * bi + 1], dL, True)
-            if not below(base + 6):
-                reached_embed = False
-                break
-            # proj (+ residual)
-            linear_wgrad(base + 4, dRc, s["ao"], C, C)
-            if not below(base + 4):
-                reached_embed = False
-                break
-            dO = torch.empty((M, C), dtype=dt, device=dev)
-            ops.gemm(dRc, _wt(blk.attn.proj.weight, dt), dO, M=M, N=C, Kd=C, lda=C, ldw=C, ldc=C)
-            dqkv = torch.empty((M, 3 * C), dtype=dt, device=dev)
-            ops.attention_backward(s["qkv"], s["ao"], dO, dqkv, B, N, heads, hd)
-            del dO
-            # qkv
-            linear_wgrad(base + 2, dqkv, s["ln1"], 3 * C, C)
-            if not below(base + 2):
-                reached_embed = False
-                break
-            ops.gemm(dqkv, _wt(blk.attn.qkv.weight, dt), dL, M=M, N=C, Kd=3 * C, lda=3 * C, ldw=3 * C, ldc=C,
-                     epilogue=EPI_OUT_F32)
-            del dqkv
-            ln_backward(base, blk.norm1, res[2 * bi], dL, True)
+            reached_embed = mlp_backward(bi, base, blk, s) and attn_backward(bi, base, blk, s)
         if reached_embed:
             K0 = S["a0"].shape[1]
             if wants(0) or wants(1):
@@ -237,12 +364,14 @@ class _VitTrainFn(torch.autograd.Function):
                 pos = torch.empty((N, C), dtype=f32, device=dev)
                 ops.rows_period_sum(dR, B, N, C, pos)
                 put(2, pos)
-        return (None, None, None, *grads)
+        return (None, None, None, None, *grads)
 
 
-def train_forward(vit, x: torch.Tensor, nchw: bool = False) -> torch.Tensor:
+def train_forward(vit, x: torch.Tensor, nchw: bool = False, keep: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The training forward of ``vit`` (backbone.VisionTransformer) on crops x (B, 3, H, W): tokens [B*N, C] in the
-    compute dtype, or (nchw=True) the (B, C, gh, gw) f32 map of ScratchViTBackbone.forward; both carry the gradient."""
+    compute dtype, or (nchw=True) the (B, C, gh, gw) f32 map of ScratchViTBackbone.forward; both carry the gradient.
+    ``keep``: an explicit drop-path mask (bool [depth, 2, B] on the CPU, as ``draw_keep`` returns) in place of a draw;
+    the mask that was used is left in ``vit.last_drop_path_keep`` (None when every rate is 0)."""
     _lib.require_device(x)
     check_trainable(vit, x)
     params = vit_parameters(vit)
@@ -250,5 +379,12 @@ def train_forward(vit, x: torch.Tensor, nchw: bool = False) -> torch.Tensor:
         if p.device != x.device:
             raise ValueError(f"ScratchViTBackbone parameters are on {p.device}, the input on {x.device}: move the "
                              "backbone first")
+    if keep is not None:
+        _check_keep(vit, keep, x.shape[0])
+    if not any(vit.drop_path_rates):
+        keep = None
+    elif keep is None:
+        keep = draw_keep(vit.drop_path_rates, x.shape[0])
+    vit.last_drop_path_keep = keep
     with torch.cuda.device(x.device):
-        return _VitTrainFn.apply(vit, x, nchw, *params)
+        return _VitTrainFn.apply(vit, x, nchw, keep, *params)

@@ -6,6 +6,8 @@ events, median of --iters), and torch autograd of an equivalent torch ViT (nn.Li
 F.scaled_dot_product_attention; same weights, same GPU) for comparison.  One JSON line per configuration.
 Per-kernel times of the step:
   rocprofv3 --kernel-trace --stats -d <dir> -o run -- python tools/vit_grad_bench.py --only-steps
+--drop-path RATE builds the backbone with drop_path_rate=RATE (stochastic depth; the masks are drawn from a fixed
+seed, a new one every step as in training) and adds the rate and the share of kept branch-crops to the JSON line.
 """
 from __future__ import annotations
 
@@ -55,36 +57,47 @@ def _torch_features(vit, x, heads):
     return F.layer_norm(t, (C,), vit.norm.weight, vit.norm.bias, 1e-6)
 
 
-def run(name, cfg, dtype, iters, only_steps):
+def run(name, cfg, dtype, iters, only_steps, drop_path=None):
     import copy
 
     from probpose_pytorch_amd.backbone import ScratchViTBackbone
     from probpose_pytorch_amd.synthetic import synthetic_crops, synthetic_vit_state
     img, C, heads, depth, B = cfg["img"], cfg["C"], cfg["heads"], cfg["depth"], cfg["B"]
-    bb = ScratchViTBackbone(img, 16, embed_dim=C, depth=depth, num_heads=heads, differentiable=True)
+    kw = {} if drop_path is None else dict(drop_path_rate=drop_path)
+    bb = ScratchViTBackbone(img, 16, embed_dim=C, depth=depth, num_heads=heads, differentiable=True, **kw)
     bb.model.load_state_dict(synthetic_vit_state(img, 16, C, depth, seed=1))
     bb = bb.cuda().set_compute_dtype(dtype).train()
     x = synthetic_crops(B, *img, seed=2).cuda()
     f = bb.model.forward_tokens(x)
     up = torch.randn_like(f)
+    kept = []
+    if drop_path is not None:
+        torch.manual_seed(1234)
 
     def fwd():
         return bb.model.forward_tokens(x)
 
     def step():
         bb.model.forward_tokens(x).backward(up)
+        if bb.last_drop_path_keep is not None:
+            kept.append(float(bb.last_drop_path_keep.float().mean()))
 
     for _ in range(2):
         step()
     res = dict(config=name, dtype=str(dtype).replace("torch.", ""), batch=B, depth=depth)
+    if drop_path is not None:
+        res.update(drop_path_rate=drop_path)
     if only_steps:
         for _ in range(iters):
             step()
         torch.cuda.synchronize()
         return res
     t_f = _median_ms(fwd, iters)
+    del kept[:]
     t_s = _median_ms(step, iters)
     res.update(forward_ms=round(t_f, 3), backward_ms=round(t_s - t_f, 3), step_ms=round(t_s, 3))
+    if kept:
+        res.update(kept_share=round(sum(kept) / len(kept), 4))
     tv = copy.deepcopy(bb.model).to(dtype)
     xt = x.to(dtype)
     upt = up.to(dtype).reshape(B, -1, C)
@@ -103,11 +116,13 @@ def main():
     ap.add_argument("--configs", default=",".join(CONFIGS))
     ap.add_argument("--dtypes", default="bf16,fp32")
     ap.add_argument("--only-steps", action="store_true", help="just run bf16 steps (for a rocprofv3 kernel trace)")
+    ap.add_argument("--drop-path", type=float, default=None, metavar="RATE",
+                    help="drop_path_rate of the backbone (masks drawn from a fixed seed)")
     a = ap.parse_args()
     dts = {"bf16": torch.bfloat16, "fp32": torch.float32}
     for name in a.configs.split(","):
         for d in (["bf16"] if a.only_steps else a.dtypes.split(",")):
-            print(json.dumps(run(name, CONFIGS[name], dts[d], a.iters, a.only_steps)), flush=True)
+            print(json.dumps(run(name, CONFIGS[name], dts[d], a.iters, a.only_steps, a.drop_path)), flush=True)
 
 
 if __name__ == "__main__":
