@@ -92,6 +92,45 @@ class _Workspace:
 # ---------------------------------------------------------------------------
 # ViT backbone
 # ---------------------------------------------------------------------------
+def pack_embed(vit, dtype, device=None):
+    """(patch_embed.proj weight [C, 3 p p] in ``dtype``, its bias, pos_embed [N, C]) as patch_embed() reads them."""
+    C = vit.embed_dim
+    pe = vit.patch_embed.proj
+    return (_dev(pe.weight.reshape(C, -1), device, dtype), _dev(pe.bias, device, torch.float32),
+            _dev(vit.pos_embed.reshape(-1, C), device, torch.float32))
+
+
+def pack_block(blk, dtype, device=None) -> dict:
+    """One ViT block's parameters as the kernels read them: the four weight matrices in ``dtype``, biases and LayerNorm
+    parameters f32; detached, contiguous, on ``device`` (None: where they are).  VitPlan keeps the result; the training
+    path (vit_train.py) packs at every forward."""
+    f32 = torch.float32
+    a, m = blk.attn, blk.mlp
+    return dict(
+        n1w=_dev(blk.norm1.weight, device, f32), n1b=_dev(blk.norm1.bias, device, f32), eps1=blk.norm1.eps,
+        qkv_w=_dev(a.qkv.weight, device, dtype), qkv_b=_dev(a.qkv.bias, device, f32),
+        proj_w=_dev(a.proj.weight, device, dtype), proj_b=_dev(a.proj.bias, device, f32),
+        n2w=_dev(blk.norm2.weight, device, f32), n2b=_dev(blk.norm2.bias, device, f32), eps2=blk.norm2.eps,
+        fc1_w=_dev(m.fc1.weight, device, dtype), fc1_b=_dev(m.fc1.bias, device, f32),
+        fc2_w=_dev(m.fc2.weight, device, dtype), fc2_b=_dev(m.fc2.bias, device, f32))
+
+
+def patch_embed(x, a0, xres, patch, w, bias, pos):
+    """patchify, then patch_embed.proj as a GEMM, + bias, + pos_embed (row m uses pos[m % N]) -> the f32 residual
+    stream xres [B*N, C]; a0 [B*N, 3 p p] is the patch matrix."""
+    M, K0 = a0.shape
+    C = w.shape[0]
+    ops.patchify(x, a0, patch)
+    ops.gemm(a0, w, xres, M=M, N=C, Kd=K0, lda=K0, ldw=K0, ldc=C, bias=bias, rowbias=pos,
+             rowbias_period=pos.shape[0], epilogue=EPI_OUT_F32)
+
+
+FP8_MARGIN = 1.25      # head-room of the static activation scales over the calibration amax (e4m3 saturates at 448)
+# the four quantised activations of a block (LN1 output, attention output, LN2 output, GELU output) and the fp8 linear
+# that reads each
+_FP8_POINTS = dict(h1="qkv", ao="proj", h2="fc1", hid="fc2")
+
+
 class VitPlan:
     def __init__(self, vit, dtype: torch.dtype, device, fp8: bool = False):
         self.dtype, self.device, self.fp8 = dtype, device, fp8
@@ -102,29 +141,15 @@ class VitPlan:
         self.heads = vit.num_heads
         self.hd = C // self.heads
         self.N = pe.num_patches
-        self.pe_w = _dev(pe.proj.weight.reshape(C, -1), device, dtype)
-        self.pe_b = _dev(pe.proj.bias, device, torch.float32)
-        self.pos = _dev(vit.pos_embed.reshape(self.N, C), device, torch.float32)
-        self.blocks = []
-        for blk in vit.blocks:
-            self.blocks.append(dict(
-                n1w=_dev(blk.norm1.weight, device, torch.float32), n1b=_dev(blk.norm1.bias, device, torch.float32),
-                eps1=blk.norm1.eps,
-                qkv_w=_dev(blk.attn.qkv.weight, device, dtype), qkv_b=_dev(blk.attn.qkv.bias, device, torch.float32),
-                proj_w=_dev(blk.attn.proj.weight, device, dtype), proj_b=_dev(blk.attn.proj.bias, device, torch.float32),
-                n2w=_dev(blk.norm2.weight, device, torch.float32), n2b=_dev(blk.norm2.bias, device, torch.float32),
-                eps2=blk.norm2.eps,
-                fc1_w=_dev(blk.mlp.fc1.weight, device, dtype), fc1_b=_dev(blk.mlp.fc1.bias, device, torch.float32),
-                fc2_w=_dev(blk.mlp.fc2.weight, device, dtype), fc2_b=_dev(blk.mlp.fc2.bias, device, torch.float32),
-            ))
+        self.pe = pack_embed(vit, dtype, device)
+        self.blocks = [pack_block(blk, dtype, device) for blk in vit.blocks]
         if fp8:
             # qkv / proj / fc1 / fc2 on fp8 MFMA: e4m3 weights, one scale per output channel (row of W); the activation
             # scales are static per tensor and come from a calibration pass on the first batch (_calibrate_fp8)
             for b, blk in zip(self.blocks, vit.blocks):
                 for name, lin in (("qkv", blk.attn.qkv), ("proj", blk.attn.proj), ("fc1", blk.mlp.fc1),
                                   ("fc2", blk.mlp.fc2)):
-                    w8, sw = ops.quantize_rows_fp8(lin.weight.detach().to(device))
-                    b[name + "_w8"], b[name + "_sw"] = w8, sw
+                    b[name + "_w8"], b[name + "_sw"] = ops.quantize_rows_fp8(lin.weight.detach().to(device))
             self.fp8_calibrated = False
         self.nw = _dev(vit.norm.weight, device, torch.float32)
         self.nb = _dev(vit.norm.bias, device, torch.float32)
@@ -137,6 +162,15 @@ class VitPlan:
         self.ws = _Workspace()
         self._chain_stream = None
 
+    def _buffers(self, B: int) -> Dict[str, torch.Tensor]:
+        """The workspace of a batch of B crops, by name; fp8 mode adds the e4m3 twins h8 / ao8 / hid8."""
+        dt, C = self.dtype, self.C
+        cols = dict(a0=(3 * self.patch ** 2, dt), xres=(C, torch.float32), h=(C, dt), qkv=(3 * C, dt), ao=(C, dt),
+                    hid=(self.hidden, dt), feats=(C, dt))
+        if self.fp8:
+            cols.update(h8=(C, ops.FP8), ao8=(C, ops.FP8), hid8=(self.hidden, ops.FP8))
+        return {k: self.ws.get(k, (B * self.N, n), t, self.device) for k, (n, t) in cols.items()}
+
     def forward_tokens(self, x: torch.Tensor) -> torch.Tensor:
         """x (B,3,H,W) f32 on the device -> tokens [B*N, C] in the compute dtype
         (= channels-last (B,gh,gw,C) feature map), final LayerNorm applied."""
@@ -147,29 +181,15 @@ class VitPlan:
             return self._forward_tokens(x, B)
 
     def _forward_tokens(self, x: torch.Tensor, B: int) -> torch.Tensor:
-        dev, dt, C, N = self.device, self.dtype, self.C, self.N
-        M = B * N
-        g = self.ws.get
-        a0 = g("a0", (M, 3 * self.patch ** 2), dt, dev)
-        xres = g("xres", (M, C), torch.float32, dev)
-        h = g("h", (M, C), dt, dev)
-        qkv = g("qkv", (M, 3 * C), dt, dev)
-        ao = g("ao", (M, C), dt, dev)
-        hid = g("hid", (M, self.hidden), dt, dev)
-        feats = g("feats", (M, C), dt, dev)
-        bufs = (a0, xres, h, qkv, ao, hid, feats)
+        bufs = self._buffers(B)
         if self.fp8:
             if not self.fp8_calibrated:
                 if torch.cuda.is_current_stream_capturing():
                     raise RuntimeError("fp8 mode calibrates its activation scales on the first batch: run one eager "
                                        "forward before capturing a graph")
                 self._calibrate_fp8(x, B, bufs)
-            h8 = g("h8", (M, C), ops.FP8, dev)
-            ao8 = g("ao8", (M, C), ops.FP8, dev)
-            hid8 = g("hid8", (M, self.hidden), ops.FP8, dev)
-            self._run_chain_fp8(x, B, (a0, xres, h8, qkv, ao8, hid8, feats))
-            return feats
-        if DUAL_CHAIN and not SERIALIZE_HEAD and B % 2 == 0 and B >= DUAL_CHAIN_MIN_BATCH:
+            self._run_blocks(x, B, bufs, fp8=True)
+        elif DUAL_CHAIN and not SERIALIZE_HEAD and B % 2 == 0 and B >= DUAL_CHAIN_MIN_BATCH:
             # Two half-batches as two independent kernel chains on two HIP streams (row slices of the same
             # buffers, same weights).  Every kernel of the path is bulk-synchronous: all its workgroups
             # run their matrix phase together and then their store phase together, so one chain alone
@@ -177,135 +197,89 @@ class VitPlan:
             # GEMM later, so its memory phases fall into the first chain's matrix phases, and each
             # chain's tail wave is filled by the other chain's next kernel.
             if self._chain_stream is None:
-                self._chain_stream = torch.cuda.Stream(device=dev)
-            cur, s2 = torch.cuda.current_stream(dev), self._chain_stream
-            Bh, Mh = B // 2, M // 2
+                self._chain_stream = torch.cuda.Stream(device=self.device)
+            cur, s2 = torch.cuda.current_stream(self.device), self._chain_stream
+            Bh, Mh = B // 2, B * self.N // 2
             offset = torch.cuda.Event()
-            self._run_chain(x[:Bh], Bh, tuple(t[:Mh] for t in bufs), offset)
+            self._run_blocks(x[:Bh], Bh, {k: t[:Mh] for k, t in bufs.items()}, offset_event=offset)
             s2.wait_event(offset)
             with torch.cuda.stream(s2):
-                self._run_chain(x[Bh:], Bh, tuple(t[Mh:] for t in bufs))
+                self._run_blocks(x[Bh:], Bh, {k: t[Mh:] for k, t in bufs.items()})
             cur.wait_stream(s2)
         else:
-            self._run_chain(x, B, bufs)
-        return feats
+            self._run_blocks(x, B, bufs)
+        return bufs["feats"]
 
-    def _run_chain(self, x, B, bufs, offset_event=None):
-        a0, xres, h, qkv, ao, hid, feats = bufs
-        C, N = self.C, self.N
-        M = B * N
-        ops.patchify(x, a0, self.patch)
-        # patch_embed.proj as a GEMM, + bias, + pos_embed (row m uses pos[m % N]), fp32 residual stream
-        ops.gemm(a0, self.pe_w, xres, M=M, N=C, Kd=a0.shape[1], lda=a0.shape[1], ldw=a0.shape[1], ldc=C,
-                 bias=self.pe_b, rowbias=self.pos, rowbias_period=N, epilogue=EPI_OUT_F32)
+    def _run_blocks(self, x, B, bufs, fp8=False, observe=None, offset_event=None):
+        """The launch sequence of one batch: patch embed, the blocks, the final LayerNorm into bufs["feats"].
+        ``fp8``: LN and GELU write e4m3 (h8 / hid8) with the block's static scales, and qkv / fc1 / fc2 read the e4m3
+        weights with their column scales; with FP8_PROJ so do attention (ao8) and proj.  ``observe(block, point, t)`` is
+        called with each of the four _FP8_POINTS activations once it is enqueued (a calibration pass; it ends at the last
+        block, since nothing reads its feats)."""
+        xres, qkv = bufs["xres"], bufs["qkv"]
+        N, heads, hd = self.N, self.heads, self.hd
+        q8 = "8" if fp8 else ""
+        p8 = "8" if fp8 and FP8_PROJ else ""
+        h, hid, ao = bufs["h" + q8], bufs["hid" + q8], bufs["ao" + p8]
+        hm = (heads, hd) if self.headmajor else None
+        patch_embed(x, bufs["a0"], xres, self.patch, *self.pe)
         if offset_event is not None and not self.blocks:
             offset_event.record()
         for i, b in enumerate(self.blocks):
-            ops.layernorm(xres, b["n1w"], b["n1b"], b["eps1"], h)
+            s = b if fp8 else {}           # static scales and column scales go with e4m3 operands only
+            sp = s if p8 else {}
+            ops.layernorm(xres, b["n1w"], b["n1b"], b["eps1"], h, out_scale=s.get("s_h1"))
             if i == 0 and offset_event is not None:
                 offset_event.record()      # the other chain starts here: one patch-embed GEMM + LN behind
-            hm = (self.heads, self.hd) if self.headmajor else None
-            ops.linear(h, b["qkv_w"], b["qkv_b"], out=qkv, headmajor=hm)
-            ops.attention(qkv, ao, B, N, self.heads, self.hd, headmajor=self.headmajor)
-            ops.linear(ao, b["proj_w"], b["proj_b"], out=xres, residual=xres)
-            ops.layernorm(xres, b["n2w"], b["n2b"], b["eps2"], h)
-            ops.linear(h, b["fc1_w"], b["fc1_b"], out=hid, epilogue=EPI_GELU)
-            ops.linear(hid, b["fc2_w"], b["fc2_b"], out=xres, residual=xres)
-        ops.layernorm(xres, self.nw, self.nb, self.neps, feats)
+            if observe is not None:
+                observe(b, "h1", h)
+            ops.linear(h, b["qkv_w" + q8], b["qkv_b"], out=qkv, colscale=s.get("qkv_cs"), headmajor=hm)
+            ops.attention(qkv, ao, B, N, heads, hd, out_scale=sp.get("s_ao"), headmajor=self.headmajor)
+            if observe is not None:
+                observe(b, "ao", ao)
+            ops.linear(ao, b["proj_w" + p8], b["proj_b"], out=xres, residual=xres, colscale=sp.get("proj_cs"))
+            ops.layernorm(xres, b["n2w"], b["n2b"], b["eps2"], h, out_scale=s.get("s_h2"))
+            if observe is not None:
+                observe(b, "h2", h)
+            ops.linear(h, b["fc1_w" + q8], b["fc1_b"], out=hid, epilogue=EPI_GELU, colscale=s.get("fc1_cs"),
+                       out_scale=s.get("s_hid"))
+            if observe is not None:
+                observe(b, "hid", hid)
+            ops.linear(hid, b["fc2_w" + q8], b["fc2_b"], out=xres, residual=xres, colscale=s.get("fc2_cs"))
+        if observe is None:
+            ops.layernorm(xres, self.nw, self.nb, self.neps, bufs["feats"])
 
+    def _calibrate_fp8(self, x, B, bufs, margin: float = None):
+        """One bf16 pass over the batch (the row-layout walk with an observer) recording amax of the four quantised
+        activations of every block -> static scales margin * amax / 448, and the per-column dequantisation vectors
+        (activation scale x weight-row scale) of the fp8 GEMMs.  Repeated calls (calibrate over several batches) keep
+        the running maximum."""
+        margin = FP8_MARGIN if margin is None else margin
 
-FP8_MARGIN = 1.25      # head-room of the static activation scales over the calibration amax (e4m3 saturates at 448)
+        def observe(blk, point, t):
+            a = max(float(t.float().abs().max()), 1e-6, blk.get("amax_" + point, 0.0))
+            blk["amax_" + point] = a
+            s = blk["s_" + point] = a * margin / ops.FP8_MAX
+            lin = _FP8_POINTS[point]
+            blk[lin + "_cs"] = (blk[lin + "_sw"] * s).contiguous()
 
+        self._run_blocks(x, B, bufs, observe=observe)
+        self.fp8_calibrated = True
 
-def _vit_calibrate_fp8(self, x, B, bufs, margin: float = None):
-    """One bf16 pass over the batch recording amax of the four quantised activations of every block
-    (LN1 output, attention output, LN2 output, GELU output) -> static scales margin * amax / 448, and the per-column
-    dequantisation vectors (activation scale x weight-row scale) of the fp8 GEMMs.  Repeated calls
-    (VitPlan.calibrate over several batches) keep the running maximum."""
-    margin = FP8_MARGIN if margin is None else margin
-    a0, xres, h, qkv, ao, hid, feats = bufs
-    C, N = self.C, self.N
-    M = B * N
-    ops.patchify(x, a0, self.patch)
-    ops.gemm(a0, self.pe_w, xres, M=M, N=C, Kd=a0.shape[1], lda=a0.shape[1], ldw=a0.shape[1], ldc=C,
-             bias=self.pe_b, rowbias=self.pos, rowbias_period=N, epilogue=EPI_OUT_F32)
-    def amax(t, blk, key):
-        a = max(float(t.float().abs().max()), 1e-6, blk.get("amax_" + key, 0.0))
-        blk["amax_" + key] = a
-        return a * margin / ops.FP8_MAX
-
-    for b in self.blocks:
-        ops.layernorm(xres, b["n1w"], b["n1b"], b["eps1"], h)
-        b["s_h1"] = amax(h, b, "h1")
-        ops.linear(h, b["qkv_w"], b["qkv_b"], out=qkv)
-        ops.attention(qkv, ao, B, N, self.heads, self.hd)
-        b["s_ao"] = amax(ao, b, "ao")
-        ops.linear(ao, b["proj_w"], b["proj_b"], out=xres, residual=xres)
-        ops.layernorm(xres, b["n2w"], b["n2b"], b["eps2"], h)
-        b["s_h2"] = amax(h, b, "h2")
-        ops.linear(h, b["fc1_w"], b["fc1_b"], out=hid, epilogue=EPI_GELU)
-        b["s_hid"] = amax(hid, b, "hid")
-        ops.linear(hid, b["fc2_w"], b["fc2_b"], out=xres, residual=xres)
-        b["qkv_cs"] = (b["qkv_sw"] * b["s_h1"]).contiguous()
-        b["proj_cs"] = (b["proj_sw"] * b["s_ao"]).contiguous()
-        b["fc1_cs"] = (b["fc1_sw"] * b["s_h2"]).contiguous()
-        b["fc2_cs"] = (b["fc2_sw"] * b["s_hid"]).contiguous()
-    self.fp8_calibrated = True
-
-
-def _vit_run_chain_fp8(self, x, B, bufs):
-    a0, xres, h8, qkv, ao8, hid8, feats = bufs
-    C, N = self.C, self.N
-    M = B * N
-    ops.patchify(x, a0, self.patch)
-    ops.gemm(a0, self.pe_w, xres, M=M, N=C, Kd=a0.shape[1], lda=a0.shape[1], ldw=a0.shape[1], ldc=C,
-             bias=self.pe_b, rowbias=self.pos, rowbias_period=N, epilogue=EPI_OUT_F32)
-    for b in self.blocks:
-        ops.layernorm(xres, b["n1w"], b["n1b"], b["eps1"], h8, out_scale=b["s_h1"])
-        ops.linear(h8, b["qkv_w8"], b["qkv_b"], out=qkv, colscale=b["qkv_cs"])
-        if FP8_PROJ:
-            ops.attention(qkv, ao8, B, N, self.heads, self.hd, out_scale=b["s_ao"])
-            ops.linear(ao8, b["proj_w8"], b["proj_b"], out=xres, residual=xres, colscale=b["proj_cs"])
-        else:
-            ao = self.ws.get("ao", (M, C), self.dtype, self.device)
-            ops.attention(qkv, ao, B, N, self.heads, self.hd)
-            ops.linear(ao, b["proj_w"], b["proj_b"], out=xres, residual=xres)
-        ops.layernorm(xres, b["n2w"], b["n2b"], b["eps2"], h8, out_scale=b["s_h2"])
-        ops.linear(h8, b["fc1_w8"], b["fc1_b"], out=hid8, epilogue=EPI_GELU, colscale=b["fc1_cs"],
-                   out_scale=b["s_hid"])
-        ops.linear(hid8, b["fc2_w8"], b["fc2_b"], out=xres, residual=xres, colscale=b["fc2_cs"])
-    ops.layernorm(xres, self.nw, self.nb, self.neps, feats)
-
-
-
-
-
-def _vit_calibrate(self, batches, margin: float = None):
-    """Explicit fp8 calibration over representative batches (iterable of (B,3,H,W) device tensors): the static
-    activation scales become margin * (max |activation| over all batches) / 448.  Without it the first forward
-    calibrates on its own batch."""
-    if not self.fp8:
-        raise RuntimeError("calibrate() applies to the fp8 compute mode")
-    for b in self.blocks:
-        for k in [k for k in b if k.startswith("amax_")]:
-            del b[k]
-    with torch.cuda.device(self.device), torch.no_grad():
-        for x in batches:
-            x = x.detach().contiguous().float()
-            B = x.shape[0]
-            M = B * self.N
-            g = self.ws.get
-            bufs = (g("a0", (M, 3 * self.patch ** 2), self.dtype, self.device), g("xres", (M, self.C), torch.float32, self.device),
-                    g("h", (M, self.C), self.dtype, self.device), g("qkv", (M, 3 * self.C), self.dtype, self.device),
-                    g("ao", (M, self.C), self.dtype, self.device), g("hid", (M, self.hidden), self.dtype, self.device),
-                    g("feats", (M, self.C), self.dtype, self.device))
-            self._calibrate_fp8(x, B, bufs, margin)
-    return self
-
-
-VitPlan.calibrate = _vit_calibrate
-VitPlan._calibrate_fp8 = _vit_calibrate_fp8
-VitPlan._run_chain_fp8 = _vit_run_chain_fp8
+    def calibrate(self, batches, margin: float = None):
+        """Explicit fp8 calibration over representative batches (iterable of (B,3,H,W) device tensors): the static
+        activation scales become margin * (max |activation| over all batches) / 448.  Without it the first forward
+        calibrates on its own batch."""
+        if not self.fp8:
+            raise RuntimeError("calibrate() applies to the fp8 compute mode")
+        for b in self.blocks:
+            for k in [k for k in b if k.startswith("amax_")]:
+                del b[k]
+        with torch.cuda.device(self.device), torch.no_grad():
+            for x in batches:
+                x = x.detach().contiguous().float()
+                self._calibrate_fp8(x, x.shape[0], self._buffers(x.shape[0]), margin)
+        return self
 
 
 def build_vit_plan(vit, dtype, device):
@@ -320,100 +294,41 @@ def build_vit_plan(vit, dtype, device):
 AUX_NAMES = ("probability", "visibility", "oks", "error")
 
 
-class HeadPlan:
-    def __init__(self, head, dtype: torch.dtype, device):
+def final_heatmap_fits(cin: int, K: int, dtype: torch.dtype) -> bool:
+    """A 1x1 final layer runs as pp_final_heatmap when 64 padded input rows and the whole [K, cin] weight fit its LDS
+    budget; otherwise as a pp_gemm with the heatmap epilogue."""
+    es = 2 if dtype == torch.bfloat16 else 4
+    return 64 * (cin * es + 16) + K * cin * es <= 150 * 1024
+
+
+class HeadGeometry:
+    """The layer dimensions of a ProbMapHead and the gather / scatter tables that follow from them and (B, h, w):
+    what the eval plan and the training path (head_train.py) share.  deconvs / convs: one dict(k, cin, cout[, pad])
+    per layer; final: dict(k, pad, cin) or None (Identity); pools: the aux stages' (kh, kw)."""
+
+    def __init__(self, head, device):
         from torch import nn
-        self.dtype, self.device = dtype, device
-        self.K = head.out_channels
-        self.C = head.in_channels
-        self.temperature = float(head.temperature)
-        # normalize != None: Sparsemax over H*W, * normalize, clamp (head.py:237-245,526-532) as pp_sparsemax_rows on
-        # the unclamped logits; the third-party library is not in the reference checkout -> parity unpinned
-        self.normalize = None if head.normalize is None else float(head.normalize)
-        # --- heatmap branch: deconvs (+BN+ReLU), optional convs (+BN+ReLU), final conv
-        self.deconvs = []
-        cin = self.C
+        self.device = device
+        self.C = cin = head.in_channels
+        self.deconvs, self.convs = [], []
         if not isinstance(head.deconv_layers, nn.Identity):
-            layers = list(head.deconv_layers)
-            for i in range(0, len(layers), 3):
-                dc, bn = layers[i], layers[i + 1]
-                k = int(dc.kernel_size[0])
-                wf, bf = pack.fold_bn(dc.weight.detach().float().cpu(), None, bn.weight.detach().cpu(),
-                                      bn.bias.detach().cpu(), bn.running_mean.cpu(), bn.running_var.cpu(),
-                                      bn.eps, out_dim=1)
-                self.deconvs.append(dict(k=k, cin=cin, cout=dc.out_channels,
-                                         w=_dev(pack.pack_deconv_parities(wf, k), device, dtype),
-                                         b=_dev(bf, device, torch.float32)))
+            for dc in list(head.deconv_layers)[::3]:
+                self.deconvs.append(dict(k=int(dc.kernel_size[0]), cin=cin, cout=dc.out_channels))
                 cin = dc.out_channels
-        self.convs = []
         if not isinstance(head.conv_layers, nn.Identity):
-            layers = list(head.conv_layers)
-            for i in range(0, len(layers), 3):
-                cv, bn = layers[i], layers[i + 1]
-                wf, bf = pack.fold_bn(cv.weight.detach().float().cpu(),
-                                      None if cv.bias is None else cv.bias.detach().cpu(),
-                                      bn.weight.detach().cpu(), bn.bias.detach().cpu(), bn.running_mean.cpu(),
-                                      bn.running_var.cpu(), bn.eps)
+            for cv in list(head.conv_layers)[::3]:
                 self.convs.append(dict(k=int(cv.kernel_size[0]), pad=int(cv.padding[0]), cin=cin,
-                                       cout=cv.out_channels, w=_dev(pack.conv_taps_major(wf), device, dtype),
-                                       b=_dev(bf, device, torch.float32)))
+                                       cout=cv.out_channels))
                 cin = cv.out_channels
-        if isinstance(head.final_layer, nn.Identity):
-            # final_layer_kernel_size=None (head.py:234-235): the last conv / deconv layer's (ReLU'd) channels ARE the maps
-            if cin != self.K:
-                raise ValueError(f"final_layer_kernel_size=None: the heatmap branch ends with {cin} channels but the "
-                                 f"head has out_channels={self.K} (Codec.decode and the aux branches expect K maps)")
-            self.final = None
-        else:
-            fl = head.final_layer
-            self.final = dict(k=int(fl.kernel_size[0]), pad=int(fl.padding[0]), cin=cin,
-                              w=_dev(pack.conv_taps_major(fl.weight.detach().float().cpu()), device, dtype),
-                              b=_dev(fl.bias.detach().float(), device, torch.float32))
-        # the implicit-GEMM layers walk their input one K-tile (128 bytes of channels) at a time inside a tap: every layer
-        # INPUT width of the heatmap branch (and the aux branches' C) must be a whole number of K-tiles
-        gran = 64 if dtype == torch.bfloat16 else 32
-        widths = [self.C] + [d["cout"] for d in self.deconvs] + [c["cout"] for c in self.convs]
-        consumed = widths[: len(self.deconvs) + len(self.convs) + (1 if self.final is not None else 0)]
-        bad = [w for w in consumed if w % gran]
-        if bad:
-            raise ValueError(f"ProbMapHead on the HIP path ({dtype}): layer input widths {bad} are not multiples of {gran} "
-                             f"channels (in_channels / deconv_out_channels / conv_out_channels feeding another layer); "
-                             "the reference's own configurations use 256-channel layers")
-        # --- four aux branches: [conv3x3+BN, pool, relu] x n -> conv1x1 -> act
-        prob_layers = list(head.probability_layers)
-        n_stage = (len(prob_layers) - 2) // 4
+        fl = head.final_layer
+        self.final = None if isinstance(fl, nn.Identity) else dict(k=int(fl.kernel_size[0]), pad=int(fl.padding[0]),
+                                                                   cin=cin)
+        # four aux branches: [conv3x3+BN, pool, relu] x n -> conv1x1 -> act; all four pool alike
         self.pools = []
-        for i in range(n_stage):
-            ks = prob_layers[4 * i + 2].kernel_size
+        for pool in list(head.probability_layers)[2:-2:4]:
+            ks = pool.kernel_size
             self.pools.append((int(ks), int(ks)) if isinstance(ks, int) else (int(ks[0]), int(ks[1])))
-        n = len(self.pools)
-        C = self.C
-        stage_w = [[] for _ in range(n)]
-        stage_b = [[] for _ in range(n)]
-        tail_w, tail_b = [], []
-        for name in AUX_NAMES:
-            layers = list(getattr(head, name + "_layers"))
-            assert len(layers) == 4 * n + 2
-            for i in range(n):
-                cv, bn = layers[4 * i], layers[4 * i + 1]
-                wf, bf = pack.fold_bn(cv.weight.detach().float().cpu(), cv.bias.detach().cpu(),
-                                      bn.weight.detach().cpu(), bn.bias.detach().cpu(), bn.running_mean.cpu(),
-                                      bn.running_var.cpu(), bn.eps)
-                stage_w[i].append(pack.conv_taps_major(wf))
-                stage_b[i].append(bf)
-            last = layers[4 * n]
-            tail_w.append(last.weight.detach().float().cpu().reshape(self.K, C))
-            tail_b.append(last.bias.detach().float().cpu())
-        # stage 0 shares its input across branches -> one GEMM with N = 4C; later stages batch = 4
-        self.aux_w = [_dev(torch.cat(stage_w[0], 0), device, dtype)] + \
-                     [_dev(torch.stack(stage_w[i]), device, dtype) for i in range(1, n)]
-        self.aux_b = [_dev(torch.cat(stage_b[0], 0), device, torch.float32)] + \
-                     [_dev(torch.stack(stage_b[i]), device, torch.float32) for i in range(1, n)]
-        self.tail_w = _dev(torch.stack(tail_w), device, dtype)
-        self.tail_b = _dev(torch.stack(tail_b), device, torch.float32)
-        self.ws = _Workspace()
         self._tables: Dict[tuple, dict] = {}
-        self._aux_stream = None
 
     # gather/scatter tables depend on (B, h, w) only
     def _tables_for(self, B: int, h: int, w: int) -> dict:
@@ -455,6 +370,79 @@ class HeadPlan:
                 "branches must end at 1x1 (Codec.decode reshapes them to (B,1,K), reference codec.py:254-257)")
         self._tables[key] = t
         return t
+
+
+class HeadPlan(HeadGeometry):
+    def __init__(self, head, dtype: torch.dtype, device):
+        from torch import nn
+        super().__init__(head, device)
+        self.dtype = dtype
+        self.K = head.out_channels
+        self.temperature = float(head.temperature)
+        # normalize != None: Sparsemax over H*W, * normalize, clamp (head.py:237-245,526-532) as pp_sparsemax_rows on
+        # the unclamped logits; the third-party library is not in the reference checkout -> parity unpinned
+        self.normalize = None if head.normalize is None else float(head.normalize)
+        # --- heatmap branch: deconvs (+BN+ReLU), optional convs (+BN+ReLU), final conv
+        layers = [] if isinstance(head.deconv_layers, nn.Identity) else list(head.deconv_layers)
+        for d, dc, bn in zip(self.deconvs, layers[::3], layers[1::3]):
+            wf, bf = pack.fold_bn(dc.weight.detach().float().cpu(), None, bn.weight.detach().cpu(),
+                                  bn.bias.detach().cpu(), bn.running_mean.cpu(), bn.running_var.cpu(),
+                                  bn.eps, out_dim=1)
+            d.update(w=_dev(pack.pack_deconv_parities(wf, d["k"]), device, dtype), b=_dev(bf, device, torch.float32))
+        layers = [] if isinstance(head.conv_layers, nn.Identity) else list(head.conv_layers)
+        for c, cv, bn in zip(self.convs, layers[::3], layers[1::3]):
+            wf, bf = pack.fold_bn(cv.weight.detach().float().cpu(),
+                                  None if cv.bias is None else cv.bias.detach().cpu(),
+                                  bn.weight.detach().cpu(), bn.bias.detach().cpu(), bn.running_mean.cpu(),
+                                  bn.running_var.cpu(), bn.eps)
+            c.update(w=_dev(pack.conv_taps_major(wf), device, dtype), b=_dev(bf, device, torch.float32))
+        widths = [self.C] + [d["cout"] for d in self.deconvs] + [c["cout"] for c in self.convs]
+        if self.final is None:
+            # final_layer_kernel_size=None (head.py:234-235): the last conv / deconv layer's (ReLU'd) channels ARE the maps
+            if widths[-1] != self.K:
+                raise ValueError(f"final_layer_kernel_size=None: the heatmap branch ends with {widths[-1]} channels but "
+                                 f"the head has out_channels={self.K} (Codec.decode and the aux branches expect K maps)")
+        else:
+            fl = head.final_layer
+            self.final.update(w=_dev(pack.conv_taps_major(fl.weight.detach().float().cpu()), device, dtype),
+                              b=_dev(fl.bias.detach().float(), device, torch.float32))
+        # the implicit-GEMM layers walk their input one K-tile (128 bytes of channels) at a time inside a tap: every layer
+        # INPUT width of the heatmap branch (and the aux branches' C) must be a whole number of K-tiles
+        gran = 64 if dtype == torch.bfloat16 else 32
+        consumed = widths[: len(self.deconvs) + len(self.convs) + (1 if self.final is not None else 0)]
+        bad = [w for w in consumed if w % gran]
+        if bad:
+            raise ValueError(f"ProbMapHead on the HIP path ({dtype}): layer input widths {bad} are not multiples of {gran} "
+                             f"channels (in_channels / deconv_out_channels / conv_out_channels feeding another layer); "
+                             "the reference's own configurations use 256-channel layers")
+        # --- four aux branches: [conv3x3+BN, pool, relu] x n -> conv1x1 -> act
+        n = len(self.pools)
+        C = self.C
+        stage_w = [[] for _ in range(n)]
+        stage_b = [[] for _ in range(n)]
+        tail_w, tail_b = [], []
+        for name in AUX_NAMES:
+            layers = list(getattr(head, name + "_layers"))
+            assert len(layers) == 4 * n + 2
+            for i in range(n):
+                cv, bn = layers[4 * i], layers[4 * i + 1]
+                wf, bf = pack.fold_bn(cv.weight.detach().float().cpu(), cv.bias.detach().cpu(),
+                                      bn.weight.detach().cpu(), bn.bias.detach().cpu(), bn.running_mean.cpu(),
+                                      bn.running_var.cpu(), bn.eps)
+                stage_w[i].append(pack.conv_taps_major(wf))
+                stage_b[i].append(bf)
+            last = layers[4 * n]
+            tail_w.append(last.weight.detach().float().cpu().reshape(self.K, C))
+            tail_b.append(last.bias.detach().float().cpu())
+        # stage 0 shares its input across branches -> one GEMM with N = 4C; later stages batch = 4
+        self.aux_w = [_dev(torch.cat(stage_w[0], 0), device, dtype)] + \
+                     [_dev(torch.stack(stage_w[i]), device, dtype) for i in range(1, n)]
+        self.aux_b = [_dev(torch.cat(stage_b[0], 0), device, torch.float32)] + \
+                     [_dev(torch.stack(stage_b[i]), device, torch.float32) for i in range(1, n)]
+        self.tail_w = _dev(torch.stack(tail_w), device, dtype)
+        self.tail_b = _dev(torch.stack(tail_b), device, torch.float32)
+        self.ws = _Workspace()
+        self._aux_stream = None
 
     def forward(self, feats: torch.Tensor, B: int, h: int, w: int):
         """feats: channels-last rows [B*h*w, C] in the compute dtype.
@@ -560,7 +548,6 @@ class HeadPlan:
             x, cin = out, c["cout"]
         M = B * hh * ww
         assert heat.shape == (B, K, hh, ww)
-        es = 2 if dt == torch.bfloat16 else 4
         if f is None and not final_done:
             # no deconv, no conv, no final layer: the maps are the input features themselves (degenerate but constructible)
             nchw = torch.empty((B, K, hh, ww), dtype=torch.float32, device=dev)
@@ -568,12 +555,12 @@ class HeadPlan:
             heat.copy_(nchw / self.temperature)
             if clamp:
                 heat.clamp_(0, 1)
-        kk = f["k"] * f["k"] if f is not None else 0
         if fused_final or f is None:
             pass
-        elif f["k"] == 1 and 64 * (cin * es + 16) + K * cin * es <= 150 * 1024:
+        elif f["k"] == 1 and final_heatmap_fits(cin, K, dt):
             ops.final_heatmap(x, f["w"], f["b"], heat, B, hh * ww, cin, K, self.temperature, clamp=clamp)
         else:
+            kk = f["k"] * f["k"]
             ops.gemm(x, f["w"], heat, M=M, N=K, Kd=kk * cin, lda=cin, ldw=kk * cin, ldc=K, bias=f["b"],
                      rowoff=tb["final"], seg_len=cin, heatmap=(K, hh * ww, self.temperature, clamp))
         if not clamp:

@@ -5,7 +5,7 @@ batch mean and biased variance and updates its running statistics; the (de)convo
 f32 and keep them for the backward.  One once-differentiable ``torch.autograd.Function`` per head call; its backward
 launches only what the trainable parameters and ``x.requires_grad`` need, reads the upstream gradients on the device
 and does no host sync.  The weights are packed from the parameters on the device at every call (no host copy, no
-rebuild of the eval ``HeadPlan``); the gather / scatter tables are those of ``HeadPlan._tables_for``.
+rebuild of the eval ``HeadPlan``); the gather / scatter tables are ``engine.HeadGeometry``'s, as in eval.
 """
 from __future__ import annotations
 
@@ -57,28 +57,12 @@ def head_parameters(head) -> List[nn.Parameter]:
     return ps
 
 
-class _Geometry:
-    """What ``HeadPlan._tables_for`` reads, without HeadPlan's packed (BN-folded) weights."""
-    _tables_for = engine.HeadPlan._tables_for
+class _Geometry(engine.HeadGeometry):
+    """The head's layer dimensions and tables, plus what only the backward reads: the deconvolution's parity index and
+    a cache of its data-gradient tables."""
 
     def __init__(self, head, device):
-        self.device = device
-        self.C = head.in_channels
-        self.deconvs = []
-        cin = self.C
-        layers = list(head.deconv_layers)
-        for i in range(0, len(layers), 3):
-            dc = layers[i]
-            self.deconvs.append(dict(k=4, cin=cin, cout=dc.out_channels))
-            cin = dc.out_channels
-        self.convs = []
-        self.final = dict(k=1, pad=0, cin=cin)
-        prob = list(head.probability_layers)
-        self.pools = []
-        for i in range((len(prob) - 2) // 4):
-            ks = prob[4 * i + 2].kernel_size
-            self.pools.append((int(ks), int(ks)) if isinstance(ks, int) else (int(ks[0]), int(ks[1])))
-        self._tables: Dict[tuple, dict] = {}
+        super().__init__(head, device)
         self._extra: Dict[tuple, object] = {}
         self.KY, self.KX = (t.to(device) for t in pack.deconv_parity_index(4))
 
@@ -189,9 +173,8 @@ class _HeadTrainFn(torch.autograd.Function):
         fw = head.final_layer.weight.detach().reshape(K, cin).to(dt).contiguous()
         fb = head.final_layer.bias.detach().float().contiguous()
         v = torch.empty((B, K, HH, WW), dtype=torch.float32, device=dev)
-        es = 2 if dt == torch.bfloat16 else 4
         T = float(head.temperature)
-        if 64 * (cin * es + 16) + K * cin * es <= 150 * 1024:
+        if engine.final_heatmap_fits(cin, K, dt):
             ops.final_heatmap(xin, fw, fb, v, B, HW, cin, K, T, clamp=False)
         else:
             ops.gemm(xin, fw, v, M=B * HW, N=K, Kd=cin, lda=cin, ldw=cin, ldc=K, bias=fb, heatmap=(K, HW, T, False))

@@ -1,7 +1,7 @@
 """Training the ViT backbone on the HIP path (``ScratchViTBackbone(differentiable=True)`` in ``.train()`` mode).
 
-The forward runs the kernels of ``VitPlan._run_chain`` (pp_patchify, pp_gemm, pp_layernorm, pp_attention on the
-row-layout qkv) with three changes that the backward needs: every residual write goes to a new f32 buffer (the
+The forward runs the kernels of ``VitPlan._run_blocks`` (pp_patchify, pp_gemm, pp_layernorm, pp_attention on the
+row-layout qkv; the patch-embed step and the weight packing are engine.py's own) with three changes that the backward needs: every residual write goes to a new f32 buffer (the
 residual input stays intact), fc1 stores its f32 pre-activation and GELU runs as its own exact-erf kernel, and every
 activation the backward reads is kept in a per-call allocation (never in the plan's workspace, so two forwards
 before two backwards give correct gradients).  One once-differentiable ``torch.autograd.Function`` per call; its
@@ -22,6 +22,7 @@ nothing; a branch with p_i == 0 runs exactly the path above.
 """
 from __future__ import annotations
 
+from functools import partial
 from typing import List, Optional
 
 import numpy as np
@@ -29,6 +30,7 @@ import torch
 from torch import nn
 
 from . import _lib, engine, ops
+from .engine import _dev
 from .head_train import _wgrad
 from .ops import EPI_OUT_F32
 
@@ -112,17 +114,36 @@ def _drop_plan(vit, keep, B, device):
     return plan
 
 
-def _w(p, dt):
-    return p.detach().to(dt).contiguous()
-
-
 def _wt(p, dt):
     """W^T [in, out]: the pp_gemm weight of the data gradient dX = dY W."""
     return p.detach().t().to(dt).contiguous()
 
 
-def _f(p):
-    return p.detach().float().contiguous()
+def _branch(r, dp, B, N, dt, norm, body, last):
+    """One residual branch of a block, r [B*N, C] f32 -> (r + branch(r) in a new buffer, the activations its backward
+    reads): on all rows (dp None: rate 0), on the kept crops' rows, or (nothing kept) not at all.  norm = (gamma, beta,
+    eps); body(LN output, crops) -> (the last linear's input, activations to save); last = (weight, bias)."""
+    if dp is not None and not dp["k"]:
+        return r, {}
+    M, C = r.shape
+    dev, f32 = r.device, torch.float32
+    Bb = B if dp is None else dp["k"]
+    Mb = Bb * N
+    xin = r
+    if dp is not None:
+        xin = dp["x"] = torch.empty((Mb, C), dtype=f32, device=dev)
+        ops.crop_rows_gather(r, dp["idx"], B, N, C, xin)
+    ln = torch.empty((Mb, C), dtype=dt, device=dev)
+    ops.layernorm(xin, *norm, ln)
+    y, saved = body(ln, Bb)
+    out = torch.empty((M, C), dtype=f32, device=dev)
+    if dp is None:
+        ops.linear(y, *last, out=out, residual=r)
+    else:
+        br = torch.empty((Mb, C), dtype=f32, device=dev)
+        ops.linear(y, *last, out=br, out_dtype=f32)
+        ops.droppath_add(r, br, dp["slot"], B, Bb, N, C, dp["scale"], out)
+    return out, saved
 
 
 class _VitTrainFn(torch.autograd.Function):
@@ -135,73 +156,41 @@ class _VitTrainFn(torch.autograd.Function):
         if (H, W) != tuple(pe.img_size):
             raise AssertionError(f"Input size ({H}, {W}) doesn't match model {tuple(pe.img_size)}")
         p, C, N, heads = int(pe.patch_size[0]), vit.embed_dim, pe.num_patches, vit.num_heads
-        hd, M, K0 = C // heads, B * N, 3 * p * p
+        hd, M = C // heads, B * N
         f32 = torch.float32
         x = x.detach().contiguous().float()
-        a0 = torch.empty((M, K0), dtype=dt, device=dev)
-        ops.patchify(x, a0, p)
+        a0 = torch.empty((M, 3 * p * p), dtype=dt, device=dev)
         r = torch.empty((M, C), dtype=f32, device=dev)
-        ops.gemm(a0, _w(pe.proj.weight.reshape(C, K0), dt), r, M=M, N=C, Kd=K0, lda=K0, ldw=K0, ldc=C,
-                 bias=_f(pe.proj.bias), rowbias=_f(vit.pos_embed.reshape(N, C)), rowbias_period=N,
-                 epilogue=EPI_OUT_F32)
+        engine.patch_embed(x, a0, r, p, *engine.pack_embed(vit, dt))
+
+        def attention(w, ln1, Bb):         # w: the block's packed weights
+            qkv = torch.empty((Bb * N, 3 * C), dtype=dt, device=dev)
+            ops.linear(ln1, w["qkv_w"], w["qkv_b"], out=qkv)
+            ao = torch.empty((Bb * N, C), dtype=dt, device=dev)
+            ops.attention(qkv, ao, Bb, N, heads, hd)
+            return ao, dict(ln1=ln1, qkv=qkv, ao=ao)
+
+        def mlp(w, ln2, Bb):
+            hidden = w["fc1_w"].shape[0]
+            pre = torch.empty((Bb * N, hidden), dtype=f32, device=dev)
+            ops.linear(ln2, w["fc1_w"], w["fc1_b"], out=pre, out_dtype=f32)
+            hid = torch.empty((Bb * N, hidden), dtype=dt, device=dev)
+            ops.gelu_forward(pre, hid)
+            return hid, dict(ln2=ln2, pre=pre, hid=hid)
+
         drop = [(None, None)] * len(vit.blocks) if keep is None else _drop_plan(vit, keep, B, dev)
         res, blocks = [r], []
         for blk, (dpa, dpm) in zip(vit.blocks, drop):
-            hidden = blk.mlp.fc1.out_features
-            s = dict(dpa=dpa, dpm=dpm)
-            # ---- attention branch: on all rows (rate 0), on the kept crops' rows, or not at all
-            if dpa is None or dpa["k"]:
-                Bb = B if dpa is None else dpa["k"]
-                Mb = Bb * N
-                xa = r
-                if dpa is not None:
-                    xa = dpa["x"] = torch.empty((Mb, C), dtype=f32, device=dev)
-                    ops.crop_rows_gather(r, dpa["idx"], B, N, C, xa)
-                ln1 = torch.empty((Mb, C), dtype=dt, device=dev)
-                ops.layernorm(xa, _f(blk.norm1.weight), _f(blk.norm1.bias), blk.norm1.eps, ln1)
-                qkv = torch.empty((Mb, 3 * C), dtype=dt, device=dev)
-                ops.linear(ln1, _w(blk.attn.qkv.weight, dt), _f(blk.attn.qkv.bias), out=qkv)
-                ao = torch.empty((Mb, C), dtype=dt, device=dev)
-                ops.attention(qkv, ao, Bb, N, heads, hd)
-                r1 = torch.empty((M, C), dtype=f32, device=dev)
-                if dpa is None:
-                    ops.linear(ao, _w(blk.attn.proj.weight, dt), _f(blk.attn.proj.bias), out=r1, residual=r)
-                else:
-                    br = torch.empty((Mb, C), dtype=f32, device=dev)
-                    ops.linear(ao, _w(blk.attn.proj.weight, dt), _f(blk.attn.proj.bias), out=br, out_dtype=f32)
-                    ops.droppath_add(r, br, dpa["slot"], B, Bb, N, C, dpa["scale"], r1)
-                s.update(ln1=ln1, qkv=qkv, ao=ao)
-            else:
-                r1 = r
-            # ---- MLP branch
-            if dpm is None or dpm["k"]:
-                Bb = B if dpm is None else dpm["k"]
-                Mb = Bb * N
-                xm = r1
-                if dpm is not None:
-                    xm = dpm["x"] = torch.empty((Mb, C), dtype=f32, device=dev)
-                    ops.crop_rows_gather(r1, dpm["idx"], B, N, C, xm)
-                ln2 = torch.empty((Mb, C), dtype=dt, device=dev)
-                ops.layernorm(xm, _f(blk.norm2.weight), _f(blk.norm2.bias), blk.norm2.eps, ln2)
-                pre = torch.empty((Mb, hidden), dtype=f32, device=dev)
-                ops.linear(ln2, _w(blk.mlp.fc1.weight, dt), _f(blk.mlp.fc1.bias), out=pre, out_dtype=f32)
-                hid = torch.empty((Mb, hidden), dtype=dt, device=dev)
-                ops.gelu_forward(pre, hid)
-                r2 = torch.empty((M, C), dtype=f32, device=dev)
-                if dpm is None:
-                    ops.linear(hid, _w(blk.mlp.fc2.weight, dt), _f(blk.mlp.fc2.bias), out=r2, residual=r1)
-                else:
-                    br = torch.empty((Mb, C), dtype=f32, device=dev)
-                    ops.linear(hid, _w(blk.mlp.fc2.weight, dt), _f(blk.mlp.fc2.bias), out=br, out_dtype=f32)
-                    ops.droppath_add(r1, br, dpm["slot"], B, Bb, N, C, dpm["scale"], r2)
-                s.update(ln2=ln2, pre=pre, hid=hid)
-            else:
-                r2 = r1
-            blocks.append(s)
+            w = engine.pack_block(blk, dt)
+            r1, sa = _branch(r, dpa, B, N, dt, (w["n1w"], w["n1b"], w["eps1"]), partial(attention, w),
+                             (w["proj_w"], w["proj_b"]))
+            r2, sm = _branch(r1, dpm, B, N, dt, (w["n2w"], w["n2b"], w["eps2"]), partial(mlp, w),
+                             (w["fc2_w"], w["fc2_b"]))
+            blocks.append(dict(sa, **sm, dpa=dpa, dpm=dpm))
             res += [r1, r2]
             r = r2
         feats = torch.empty((M, C), dtype=dt, device=dev)
-        ops.layernorm(r, _f(vit.norm.weight), _f(vit.norm.bias), vit.norm.eps, feats)
+        ops.layernorm(r, _dev(vit.norm.weight, None, f32), _dev(vit.norm.bias, None, f32), vit.norm.eps, feats)
         ctx.vit = vit
         ctx.save_for_backward(*params)
         ctx.saved = dict(B=B, N=N, a0=a0, res=res, blocks=blocks, nchw=nchw)
@@ -264,7 +253,7 @@ class _VitTrainFn(torch.autograd.Function):
                 out, out_c = dR, dRc
             else:
                 out, out_c, accumulate = torch.empty_like(x), torch.empty(x.shape, dtype=dt, device=dev), False
-            ops.layernorm_backward(x, _f(ln.weight), ln.eps, dy, out, out_c, accumulate,
+            ops.layernorm_backward(x, _dev(ln.weight, None, f32), ln.eps, dy, out, out_c, accumulate,
                                    dgamma=None if dgb is None else dgb[0], dbeta=None if dgb is None else dgb[1])
             if dp is not None:
                 ops.crop_rows_scatter_add(out, dp["idx"], B, N, C, dR, dRc)
@@ -272,69 +261,59 @@ class _VitTrainFn(torch.autograd.Function):
                 put(i, dgb[0])
                 put(i + 1, dgb[1])
 
-        def branch_grad(dp):
-            """(rows, crops, the branch's output gradient in the compute dtype): dRc itself, or the kept crops' rows
-            of dR times 1 / (1 - p)."""
-            if dp is None:
-                return M, B, dRc
-            dY = torch.empty((dp["k"] * N, C), dtype=dt, device=dev)
-            ops.crop_rows_gather(dR, dp["idx"], B, N, C, dY, dp["scale"])
-            return dp["k"] * N, dp["k"], dY
-
-        def mlp_backward(bi, base, blk, s):
-            """False: nothing below needs a gradient."""
-            dp = s["dpm"]
-            hidden = blk.mlp.fc1.out_features
+        def branch_backward(lo, blk, s, dp, ln, x, a_last, body):
+            """The backward of one residual branch whose six parameters start at index lo (LayerNorm, first linear at
+            lo + 2, last linear at lo + 4): x is the branch's input residual, a_last the last linear's input;
+            body(lo, blk, s, dY, rows, crops) takes the branch's output gradient to the LayerNorm's output gradient, or
+            returns None when nothing below the first linear needs one.  False: nothing below the branch needs a
+            gradient."""
             if dp is not None and not dp["k"]:
-                put_zeros(base + 6, base + 12)
-                return below(base + 6)
-            Mb, _, dY = branch_grad(dp)
-            # fc2 (+ residual): its output gradient is dR
-            linear_wgrad(base + 10, dY, s["hid"], C, hidden, Mb)
-            if not below(base + 10):
+                put_zeros(lo, lo + 6)
+                return below(lo)
+            if dp is None:          # the residual gradient itself, or the kept crops' rows of it times 1 / (1 - p)
+                Mb, Bb, dY = M, B, dRc
+            else:
+                Mb, Bb = dp["k"] * N, dp["k"]
+                dY = torch.empty((Mb, C), dtype=dt, device=dev)
+                ops.crop_rows_gather(dR, dp["idx"], B, N, C, dY, dp["scale"])
+            linear_wgrad(lo + 4, dY, a_last, C, a_last.shape[1], Mb)
+            if not below(lo + 4):
                 return False
+            dL = body(lo, blk, s, dY, Mb, Bb)
+            if dL is None:
+                return False
+            ln_backward(lo, ln, x if dp is None else dp["x"], dL, True, dp)
+            return below(lo)
+
+        def mlp_backward(lo, blk, s, dY, Mb, Bb):
+            hidden = blk.mlp.fc1.out_features
             dH = torch.empty((Mb, hidden), dtype=f32, device=dev)
             ops.gemm(dY, _wt(blk.mlp.fc2.weight, dt), dH, M=Mb, N=hidden, Kd=C, lda=C, ldw=C, ldc=hidden,
                      epilogue=EPI_OUT_F32)
             dPre = torch.empty((Mb, hidden), dtype=dt, device=dev)
             ops.gelu_backward(s["pre"], dH, dPre)
             del dH
-            # fc1
-            linear_wgrad(base + 8, dPre, s["ln2"], hidden, C, Mb)
-            if not below(base + 8):
-                return False
+            linear_wgrad(lo + 2, dPre, s["ln2"], hidden, C, Mb)
+            if not below(lo + 2):
+                return None
             dL = torch.empty((Mb, C), dtype=f32, device=dev)
             ops.gemm(dPre, _wt(blk.mlp.fc1.weight, dt), dL, M=Mb, N=C, Kd=hidden, lda=hidden, ldw=hidden, ldc=C,
                      epilogue=EPI_OUT_F32)
-            del dPre
-            ln_backward(base + 6, blk.norm2, res[2 * bi + 1] if dp is None else dp["x"], dL, True, dp)
-            return below(base + 6)
+            return dL
 
-        def attn_backward(bi, base, blk, s):
-            dp = s["dpa"]
-            if dp is not None and not dp["k"]:
-                put_zeros(base, base + 6)
-                return below(base)
-            Mb, Bb, dY = branch_grad(dp)
-            # proj (+ residual)
-            linear_wgrad(base + 4, dY, s["ao"], C, C, Mb)
-            if not below(base + 4):
-                return False
+        def attn_backward(lo, blk, s, dY, Mb, Bb):
             dO = torch.empty((Mb, C), dtype=dt, device=dev)
             ops.gemm(dY, _wt(blk.attn.proj.weight, dt), dO, M=Mb, N=C, Kd=C, lda=C, ldw=C, ldc=C)
             dqkv = torch.empty((Mb, 3 * C), dtype=dt, device=dev)
             ops.attention_backward(s["qkv"], s["ao"], dO, dqkv, Bb, N, heads, hd)
             del dO
-            # qkv
-            linear_wgrad(base + 2, dqkv, s["ln1"], 3 * C, C, Mb)
-            if not below(base + 2):
-                return False
+            linear_wgrad(lo + 2, dqkv, s["ln1"], 3 * C, C, Mb)
+            if not below(lo + 2):
+                return None
             dL = torch.empty((Mb, C), dtype=f32, device=dev)
             ops.gemm(dqkv, _wt(blk.attn.qkv.weight, dt), dL, M=Mb, N=C, Kd=3 * C, lda=3 * C, ldw=3 * C, ldc=C,
                      epilogue=EPI_OUT_F32)
-            del dqkv
-            ln_backward(base, blk.norm1, res[2 * bi] if dp is None else dp["x"], dL, True, dp)
-            return below(base)
+            return dL
 
         # ---- final LayerNorm: dR (f32) and dR_c (compute dtype) = the residual stream's gradient
         if S["nchw"]:
@@ -351,7 +330,9 @@ class _VitTrainFn(torch.autograd.Function):
                 break
             base = 3 + PER_BLOCK * bi
             blk, s = vit.blocks[bi], S["blocks"][bi]
-            reached_embed = mlp_backward(bi, base, blk, s) and attn_backward(bi, base, blk, s)
+            reached_embed = (
+                branch_backward(base + 6, blk, s, s["dpm"], blk.norm2, res[2 * bi + 1], s.get("hid"), mlp_backward)
+                and branch_backward(base, blk, s, s["dpa"], blk.norm1, res[2 * bi], s.get("ao"), attn_backward))
         if reached_embed:
             K0 = S["a0"].shape[1]
             if wants(0) or wants(1):
