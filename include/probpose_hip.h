@@ -646,6 +646,33 @@ int pp_grad_norm_finish(const double *partials, int n_chunks, int clip, double m
                         void *stream);
 int pp_adamw_step(const void *table, int n_chunks, const void *record, int skip_nonfinite, void *stream);
 
+/* ------------------------------------------------------------------------
+ * ModelEma (probpose_pytorch_amd/ema.py): the exponential moving average of all state tensors of a model in one
+ * launch, no host sync, no atomics.  All tensors contiguous and 4-byte aligned.
+ *
+ * The device table (8-byte aligned) that the kernel reads:
+ *   header  32 B  {uint32 magic, int32 n_tensors, n_chunks, chunk_elems, 16 B zero}
+ *   tensors n_tensors x 32 B {const void *src, void *dst; int64 count; int32 kind, pad}
+ *   chunks  n_chunks x 8 B   {int32 tensor, chunk within the tensor}: one workgroup per chunk of at most
+ *                            PP_OPTIM_CHUNK elements of one tensor
+ * kind PP_EMA_LERP_F32:   dst = (float)((double)dst + weight * ((double)src - (double)dst)), count in float32
+ *                         elements, evaluated in float64 and rounded once at the store
+ * kind PP_EMA_COPY_WORDS: dst = src as 4-byte words, count in words (non-float state, e.g. BatchNorm's int64
+ *                         num_batches_tracked: 2 words)
+ * The table is static: it depends on the addresses, counts and kinds only, so it is uploaded once.
+ * pp_ema_table_bytes: the table's size for these counts, -1 (and pp_last_error) on bad arguments.
+ * pp_ema_table_build: checks every argument on the host (null and misaligned pointers, counts <= 0, kinds, a dst
+ *   range that overlaps any src range or another dst range) and packs the table into HOST memory `table`.
+ * pp_ema_update: one launch over n_chunks workgroups; weight = 1 - decay of this update, in [0, 1].  A table whose
+ *   first word is not the magic word is left alone by every workgroup.
+ * ---------------------------------------------------------------------- */
+#define PP_EMA_LERP_F32 0
+#define PP_EMA_COPY_WORDS 1
+long long pp_ema_table_bytes(int n_tensors, const long long *counts);
+int pp_ema_table_build(int n_tensors, const void *const *src, const void *const *dst, const long long *counts,
+                       const int *kinds, void *table, int *n_chunks);
+int pp_ema_update(const void *table, int n_chunks, double weight, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -133,7 +133,11 @@ _SIGNATURES = {
     "pp_grad_sqnorm_partials": (C.c_int, [_vp, _i, _vp, _vp]),
     "pp_grad_norm_finish": (C.c_int, [_vp, _i, _i, _d, _i, _vp, _vp]),
     "pp_adamw_step": (C.c_int, [_vp, _i, _vp, _i, _vp]),
+    "pp_ema_table_bytes": (C.c_longlong, [_i, _vp]),
+    "pp_ema_table_build": (C.c_int, [_i] + [_vp] * 5 + [C.POINTER(C.c_int)]),
+    "pp_ema_update": (C.c_int, [_vp, _i, _d, _vp]),
 }
+PP_EMA_LERP_F32, PP_EMA_COPY_WORDS = 0, 1
 EXPORTS = tuple(_SIGNATURES)
 
 
