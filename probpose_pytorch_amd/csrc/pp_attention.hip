@@ -55,24 +55,20 @@ typedef float att_f32x2 __attribute__((ext_vector_type(2)));
 
 __device__ __attribute__((aligned(256))) unsigned char g_att_zero[1024];
 
-__device__ __forceinline__ void att_glds16(const void *gsrc, unsigned lds_off_uniform) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(gsrc), "s"(lds_off_uniform)
-      : "memory");
+// accumulator init of a score tile whose lane holds keys key_lo .. key_lo + 3: keys >= N (zero rows in LDS) start at -inf,
+// so their scores stay -inf and their weights 0
+__device__ __forceinline__ f32x4 att_mask_init(int key_lo, int N) {
+  return f32x4{key_lo + 0 < N ? 0.f : -__builtin_inff(), key_lo + 1 < N ? 0.f : -__builtin_inff(),
+               key_lo + 2 < N ? 0.f : -__builtin_inff(), key_lo + 3 < N ? 0.f : -__builtin_inff()};
 }
 
-// OCP e4m3, saturating at +-448 (fp8 mode: the attention output feeds the fp8 proj GEMM)
-__device__ __forceinline__ unsigned att_pack_fp8x4(float a, float b, float c, float d) {
-  a = __builtin_amdgcn_fmed3f(a, -448.0f, 448.0f);
-  b = __builtin_amdgcn_fmed3f(b, -448.0f, 448.0f);
-  c = __builtin_amdgcn_fmed3f(c, -448.0f, 448.0f);
-  d = __builtin_amdgcn_fmed3f(d, -448.0f, 448.0f);
-  int w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
-  w = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);
-  return (unsigned)w;
+// the e4m3 store of query tile t, 4 bytes per lane (a lane holds dims 16 dt + 4 g .. + 3 of its query per dim tile): orow8 is the query's head row of an e4m3 byte tensor [B*N, C], sc = inv_l * fp8_inv_scale
+template <int DT, int QT>
+__device__ __forceinline__ void att_store_fp8(unsigned char *orow8, const f32x4 (&oacc)[DT][QT], int t, float sc, int g) {
+#pragma unroll
+  for (int dt = 0; dt < DT; ++dt)
+    *reinterpret_cast<unsigned *>(orow8 + dt * 16 + g * 4) =
+        pack_fp8x4(oacc[dt][t][0] * sc, oacc[dt][t][1] * sc, oacc[dt][t][2] * sc, oacc[dt][t][3] * sc);
 }
 
 template <int PENDING>
@@ -120,7 +116,7 @@ __global__ __launch_bounds__(256, 3) void attention_mfma_kernel(const bf16_t *__
     const int lchunk = G::swz(r, pchunk);
     const void *src = (FULL || r < N) ? (const void *)(base + (size_t)r * ld + (1 + mat) * C + lchunk * 8)
                                       : (const void *)(g_att_zero + lane * 16);
-    att_glds16(src, __builtin_amdgcn_readfirstlane(lds0 + mat * (AT_NMAX * AT_KROW) + piece * 1024));
+    glds16(src, __builtin_amdgcn_readfirstlane(lds0 + mat * (AT_NMAX * AT_KROW) + piece * 1024));
   };
   // ---- Q fragments first (B operand, lane (col q = lrow, g) holds Q[q][32s + 8g .. +7]).  Ordinary loads, and the
   // OLDEST memory operations of the wave: the waits the compiler places for them count only these six, which with
@@ -161,11 +157,7 @@ __global__ __launch_bounds__(256, 3) void attention_mfma_kernel(const bf16_t *__
     f32x4 sacc[KB_TILES][AT_QT];
 #pragma unroll
     for (int kt = 0; kt < KB_TILES; ++kt) {
-      // keys >= N (zero rows in LDS) start at -inf, so their scores stay -inf and their weights 0
-      const int key_lo = (kb * KB_TILES + kt) * 16 + g * 4;
-      const f32x4 init = FULL ? f32x4{0.f, 0.f, 0.f, 0.f}
-                              : f32x4{key_lo + 0 < N ? 0.f : -__builtin_inff(), key_lo + 1 < N ? 0.f : -__builtin_inff(),
-                                      key_lo + 2 < N ? 0.f : -__builtin_inff(), key_lo + 3 < N ? 0.f : -__builtin_inff()};
+      const f32x4 init = FULL ? f32x4{0.f, 0.f, 0.f, 0.f} : att_mask_init((kb * KB_TILES + kt) * 16 + g * 4, N);
 #pragma unroll
       for (int t = 0; t < AT_QT; ++t) sacc[kt][t] = init;
       const int r = (kb * KB_TILES + kt) * 16 + lrow;
@@ -280,10 +272,7 @@ __global__ __launch_bounds__(256, 3) void attention_mfma_kernel(const bf16_t *__
     if (fp8_inv_scale > 0.f) {   // out is an e4m3 byte tensor [B*N, C]
       unsigned char *orow8 = reinterpret_cast<unsigned char *>(out) + ((size_t)b * N + q) * C + h * AT_HD;
       const float sc = inv_l[t] * fp8_inv_scale;
-#pragma unroll
-      for (int dt = 0; dt < G::DT; ++dt)
-        *reinterpret_cast<unsigned *>(orow8 + dt * 16 + g * 4) =
-            att_pack_fp8x4(oacc[dt][t][0] * sc, oacc[dt][t][1] * sc, oacc[dt][t][2] * sc, oacc[dt][t][3] * sc);
+      att_store_fp8(orow8, oacc, t, sc, g);
       continue;
     }
     bf16_t *orow = out + ((size_t)b * N + q) * C + h * AT_HD;
@@ -404,8 +393,8 @@ __global__ __launch_bounds__(NW * 64, 3) void attention_stream_kernel(const bf16
         const bf16_t *src = base + (size_t)key * ld + G::swz(row, pchunk) * 8;
         const unsigned dst = __builtin_amdgcn_readfirstlane(slot + pc * 1024);
         const void *zsrc = g_att_zero + lane * 16;
-        att_glds16(key < N ? (const void *)(src + kofs) : zsrc, dst);
-        att_glds16(key < N ? (const void *)(src + vofs) : zsrc, dst + BLK_BYTES);
+        glds16(key < N ? (const void *)(src + kofs) : zsrc, dst);
+        glds16(key < N ? (const void *)(src + vofs) : zsrc, dst + BLK_BYTES);
       }
     }
   };
@@ -422,9 +411,7 @@ __global__ __launch_bounds__(NW * 64, 3) void attention_stream_kernel(const bf16
     f32x4 sacc[KB_TILES][ST_QT];
 #pragma unroll
     for (int kt = 0; kt < KB_TILES; ++kt) {
-      const int key_lo = kb * ST_KB + kt * 16 + g * 4;
-      const f32x4 init = f32x4{key_lo + 0 < N ? 0.f : -__builtin_inff(), key_lo + 1 < N ? 0.f : -__builtin_inff(),
-                               key_lo + 2 < N ? 0.f : -__builtin_inff(), key_lo + 3 < N ? 0.f : -__builtin_inff()};
+      const f32x4 init = att_mask_init(kb * ST_KB + kt * 16 + g * 4, N);
 #pragma unroll
       for (int t = 0; t < ST_QT; ++t) sacc[kt][t] = init;
       const int r = kt * 16 + lrow;
@@ -521,10 +508,7 @@ __global__ __launch_bounds__(NW * 64, 3) void attention_stream_kernel(const bf16
       if (q >= N) continue;
       unsigned char *orow8 = reinterpret_cast<unsigned char *>(out) + ((size_t)b * N + q) * C + h * HD;
       const float sc = inv_l * fp8_inv_scale;
-#pragma unroll
-      for (int dt = 0; dt < G::DT; ++dt)
-        *reinterpret_cast<unsigned *>(orow8 + dt * 16 + g * 4) =
-            att_pack_fp8x4(oacc[dt][t][0] * sc, oacc[dt][t][1] * sc, oacc[dt][t][2] * sc, oacc[dt][t][3] * sc);
+      att_store_fp8(orow8, oacc, t, sc, g);
       continue;
     }
     if constexpr (G::DT < 4) {      // head_dim 32: one pair of dim tiles only; the 8-byte form stays (the wide form returned

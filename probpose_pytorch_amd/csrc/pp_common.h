@@ -53,6 +53,33 @@ __device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {
   return r;
 }
 
+// OCP e4m3 (gfx950): 4 floats -> 4 bytes, round-to-nearest-even, saturating at +-448 (NaN stays NaN).  The fp8 mode's
+// producers: the GEMM epilogue, LayerNorm (value * static per-tensor scale) and attention (its output feeds the fp8 proj
+// GEMM).
+__device__ __forceinline__ unsigned pack_fp8x4(float a, float b, float c, float d) {
+  a = __builtin_amdgcn_fmed3f(a, -448.0f, 448.0f);
+  b = __builtin_amdgcn_fmed3f(b, -448.0f, 448.0f);
+  c = __builtin_amdgcn_fmed3f(c, -448.0f, 448.0f);
+  d = __builtin_amdgcn_fmed3f(d, -448.0f, 448.0f);
+  int w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
+  w = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);
+  return (unsigned)w;
+}
+
+// LDS-DMA of 16 B per lane: LDS destination = wave-uniform byte offset (M0) + lane * 16.  Issued
+// from inline asm on purpose: hipcc cannot tell that the DMA into buffer t+1 never aliases the
+// ds_reads of buffer t and would drain vmcnt(0) in front of every fragment read, serialising the
+// prefetch behind the MFMAs.  The asm DMA is invisible to its wait-count bookkeeping; completion is
+// enforced by the caller's explicit s_waitcnt vmcnt + barrier.
+__device__ __forceinline__ void glds16(const void *gsrc, unsigned lds_off_uniform) {
+  unsigned keep;
+  asm volatile(
+      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+      : "=&s"(keep)
+      : "v"(gsrc), "s"(lds_off_uniform)
+      : "memory");
+}
+
 template <typename T> struct Store;
 template <> struct Store<float> {
   static __device__ __forceinline__ float ld(const float *p) { return *p; }
@@ -64,6 +91,11 @@ template <> struct Store<bf16_t> {
 };
 
 __device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;

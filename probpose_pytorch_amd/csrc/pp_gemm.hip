@@ -49,17 +49,7 @@ __device__ __attribute__((aligned(256))) unsigned char g_zero_page[ZERO_REGION];
 
 
 
-// OCP e4m3 (gfx950): 4 floats -> 4 bytes, round-to-nearest-even, saturating at +-448 (NaN stays NaN)
-typedef unsigned char fp8_t;
-__device__ __forceinline__ unsigned pack_fp8x4(float a, float b, float c, float d) {
-  a = __builtin_amdgcn_fmed3f(a, -448.0f, 448.0f);
-  b = __builtin_amdgcn_fmed3f(b, -448.0f, 448.0f);
-  c = __builtin_amdgcn_fmed3f(c, -448.0f, 448.0f);
-  d = __builtin_amdgcn_fmed3f(d, -448.0f, 448.0f);
-  int w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
-  w = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);
-  return (unsigned)w;
-}
+typedef unsigned char fp8_t;   // OCP e4m3 storage (pack_fp8x4, pp_common.h)
 
 // WGM x WGN waves per workgroup; STAGES LDS buffers (prefetch distance STAGES-1, counted vmcnt).
 // GATHER: A rows addressed through the row-offset table (implicit convolution).  VEC: N and ldc are

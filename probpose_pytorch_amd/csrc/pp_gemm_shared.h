@@ -1,5 +1,5 @@
 // Shared by the GEMM translation units (pp_gemm.hip, pp_gemm_quad.hip): launch parameters and the small device
-// helpers every kernel form uses (counted waits, LDS-DMA issue, GELU).  Device code only; no state.
+// helpers every kernel form uses (counted waits, GELU; the LDS-DMA issue glds16 is in pp_common.h).  Device code only; no state.
 #pragma once
 #include "pp_common.h"
 
@@ -40,20 +40,6 @@ struct GemmParams {
   const char *final_w;     // PP_EPI_FUSE_FINAL: [hm_K, N] storage-dtype weights of the 1x1 heatmap layer
   const float *final_b;    // [hm_K]
 };
-
-// LDS-DMA of 16 B per lane: LDS destination = wave-uniform byte offset (M0) + lane * 16.  Issued
-// from inline asm on purpose: hipcc cannot tell that the DMA into buffer t+1 never aliases the
-// ds_reads of buffer t and would drain vmcnt(0) in front of every fragment read, serialising the
-// prefetch behind the MFMAs.  The asm DMA is invisible to its wait-count bookkeeping; completion is
-// enforced by the explicit s_waitcnt vmcnt(0) + barrier that ends each K-step.
-__device__ __forceinline__ void glds16(const void *gsrc, unsigned lds_off_uniform) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(gsrc), "s"(lds_off_uniform)
-      : "memory");
-}
 
 __device__ __forceinline__ unsigned lds_offset_of(const void *p) {
   return (unsigned)(size_t)(__attribute__((address_space(3))) const char *)p;

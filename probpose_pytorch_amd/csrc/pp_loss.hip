@@ -39,7 +39,7 @@ __device__ __forceinline__ float nan_max(float m, float v) { return (v > m || v 
 template <int WAVES>
 __device__ __forceinline__ float block_sum_f(float v, float *lds) {
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);   // not wave_sum: that call moves oks_heatmap_loss_kernel's schedule
   __syncthreads();
   if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
   __syncthreads();
@@ -50,8 +50,7 @@ __device__ __forceinline__ float block_sum_f(float v, float *lds) {
 
 template <int WAVES>
 __device__ __forceinline__ double block_sum_d(double v, double *lds) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  v = wave_sum(v);
   __syncthreads();
   if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
   __syncthreads();

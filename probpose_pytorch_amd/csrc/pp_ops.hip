@@ -12,16 +12,14 @@ namespace pp {
 // LayerNorm: one wave per row, the row held in registers (C <= 2048) so HBM/L2
 // is read once; fp32 statistics (two-pass, like torch's RowwiseMoments result).
 // ---------------------------------------------------------------------------
-// T = unsigned char: the output is OCP e4m3 of value * qscale (static per-tensor scale), saturating at 448.
-__device__ __forceinline__ unsigned ln_pack_fp8x4(float a, float b, float c, float d) {
-  a = __builtin_amdgcn_fmed3f(a, -448.0f, 448.0f);
-  b = __builtin_amdgcn_fmed3f(b, -448.0f, 448.0f);
-  c = __builtin_amdgcn_fmed3f(c, -448.0f, 448.0f);
-  d = __builtin_amdgcn_fmed3f(d, -448.0f, 448.0f);
-  int w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
-  w = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);
-  return (unsigned)w;
+// The statistics of both kernels on one float4 of a row, written once so that the multi-row form's mean and rstd are
+// bit-identical to the one-row form's by construction: the sum and the centred squares in a fixed order.
+__device__ __forceinline__ float ln_sum4(float4 v) { return (v.x + v.y) + (v.z + v.w); }
+__device__ __forceinline__ float ln_sqsum4(float4 v, float mean) {
+  const float a = v.x - mean, b = v.y - mean, cc = v.z - mean, d = v.w - mean;
+  return (a * a + b * b) + (cc * cc + d * d);
 }
+// T = unsigned char: the output is OCP e4m3 of value * qscale (static per-tensor scale), saturating at 448.
 template <typename T>
 __global__ __launch_bounds__(256) void layernorm_kernel(const float *__restrict__ x,
                                                         const float *__restrict__ gamma,
@@ -41,7 +39,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float *__restrict_
       const int c = (i * 64 + lane) * 4;
       if (c < C) {
         v[i] = *reinterpret_cast<const float4 *>(xr + c);
-        s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
+        s += ln_sum4(v[i]);
       }
     }
     const float mean = wave_sum(s) / (float)C;
@@ -50,8 +48,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float *__restrict_
     for (int i = 0; i < MAXV; ++i) {
       const int c = (i * 64 + lane) * 4;
       if (c < C) {
-        const float a = v[i].x - mean, b = v[i].y - mean, cc = v[i].z - mean, d = v[i].w - mean;
-        q += (a * a + b * b) + (cc * cc + d * d);
+        q += ln_sqsum4(v[i], mean);
       }
     }
     const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)C + eps);
@@ -66,7 +63,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float *__restrict_
         if constexpr (sizeof(T) == 4) {
           *reinterpret_cast<float4 *>(orow + c) = make_float4(o0, o1, o2, o3);
         } else if constexpr (sizeof(T) == 1) {
-          *reinterpret_cast<unsigned *>(orow + c) = ln_pack_fp8x4(o0 * qscale, o1 * qscale, o2 * qscale, o3 * qscale);
+          *reinterpret_cast<unsigned *>(orow + c) = pack_fp8x4(o0 * qscale, o1 * qscale, o2 * qscale, o3 * qscale);
         } else {
           ushort4 pk;
           pk.x = f32_to_bf16(o0); pk.y = f32_to_bf16(o1); pk.z = f32_to_bf16(o2); pk.w = f32_to_bf16(o3);
@@ -127,7 +124,7 @@ __global__ __launch_bounds__(256) void layernorm_rows_kernel(const float *__rest
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
       const int c = (i * 64 + lane) * 4;
-      if (c < C) s += (v[r][i].x + v[r][i].y) + (v[r][i].z + v[r][i].w);
+      if (c < C) s += ln_sum4(v[r][i]);
     }
     const float mean = wave_sum(s) / (float)C;
     float q = 0.f;
@@ -135,8 +132,7 @@ __global__ __launch_bounds__(256) void layernorm_rows_kernel(const float *__rest
     for (int i = 0; i < NV; ++i) {
       const int c = (i * 64 + lane) * 4;
       if (c < C) {
-        const float a = v[r][i].x - mean, b = v[r][i].y - mean, cc = v[r][i].z - mean, d = v[r][i].w - mean;
-        q += (a * a + b * b) + (cc * cc + d * d);
+        q += ln_sqsum4(v[r][i], mean);
       }
     }
     const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)C + eps);
@@ -151,7 +147,7 @@ __global__ __launch_bounds__(256) void layernorm_rows_kernel(const float *__rest
         if constexpr (sizeof(T) == 4) {
           *reinterpret_cast<float4 *>(orow + c) = make_float4(o0, o1, o2, o3);
         } else if constexpr (sizeof(T) == 1) {
-          *reinterpret_cast<unsigned *>(orow + c) = ln_pack_fp8x4(o0 * qscale, o1 * qscale, o2 * qscale, o3 * qscale);
+          *reinterpret_cast<unsigned *>(orow + c) = pack_fp8x4(o0 * qscale, o1 * qscale, o2 * qscale, o3 * qscale);
         } else {
           ushort4 pk;
           pk.x = f32_to_bf16(o0); pk.y = f32_to_bf16(o1); pk.z = f32_to_bf16(o2); pk.w = f32_to_bf16(o3);

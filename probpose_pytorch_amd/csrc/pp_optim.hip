@@ -73,12 +73,6 @@ __host__ __device__ inline OptView view_of(const void *table, int n_groups, int 
   return w;
 }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(256) void grad_sqnorm_partials_kernel(const void *__restrict__ table,
                                                                    double *__restrict__ partials) {
   const OptHeader *hdr = reinterpret_cast<const OptHeader *>(table);
@@ -104,7 +98,7 @@ __global__ __launch_bounds__(256) void grad_sqnorm_partials_kernel(const void *_
   } else {
     for (int i = threadIdx.x; i < cnt; i += 256) acc += (double)g[i] * (double)g[i];
   }
-  acc = wave_sum_f64(acc);
+  acc = wave_sum(acc);
   __shared__ double ws[4];
   if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = acc;
   __syncthreads();
@@ -116,7 +110,7 @@ __global__ __launch_bounds__(1024) void grad_norm_finish_kernel(const double *__
                                                                 OptRecord *__restrict__ rec) {
   double acc = 0.0;
   for (int i = threadIdx.x; i < n; i += 1024) acc += partials[i];
-  acc = wave_sum_f64(acc);
+  acc = wave_sum(acc);
   __shared__ double ws[16];
   if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = acc;
   __syncthreads();

@@ -41,7 +41,7 @@ def ops(built_lib):
 # ---------------------------------------------------------------------------------------------------------------
 def attention_form(N, hd, qkv_dtype, out_dtype, headmajor=False, qkv_mod16=0, out_mod16=0, B=1, heads=1):
     """The kernel instantiation a call runs: attention_dispatch, launch_stream and pp_attention_headmajor
-    (pp_attention.hip:664-746) restated.  None: the call is refused."""
+    (pp_attention.hip) restated.  None: the call is refused."""
     fp8 = out_dtype == FP8
 
     def stream():
@@ -316,7 +316,7 @@ def test_attention_random_within_bound(ops, c, qscale):
 # LayerNorm
 # ---------------------------------------------------------------------------------------------------------------
 def layernorm_form(rows, C, out_dtype):
-    """The kernel a call runs: pp_layernorm / pp_layernorm_fp8 and layernorm_rows_launch (pp_ops.hip:165-188, 619-651)
+    """The kernel a call runs: pp_layernorm / pp_layernorm_fp8 and layernorm_rows_launch (pp_ops.hip)
     restated."""
     if C % 4 == 0 and 512 < C <= 1280 and rows >= 2048:
         want = (rows + 4095) // 4096
