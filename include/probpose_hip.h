@@ -673,6 +673,48 @@ int pp_ema_table_build(int n_tensors, const void *const *src, const void *const 
                        const int *kinds, void *table, int *n_chunks);
 int pp_ema_update(const void *table, int n_chunks, double weight, void *stream);
 
+/* ------------------------------------------------------------------------
+ * CocoKeypointEval (probpose_pytorch_amd/cocoeval.py): COCO keypoint AP / AR on the device.  Everything is float64;
+ * no host sync, no float atomics, the same bits on every call.
+ *
+ * A ragged batch of n_img images is one int64 array of 3 (n_img + 1) CSR offsets [det_off | gt_off | oks_off]:
+ * image i owns detections det_off[i] .. det_off[i+1] (already in descending score order, cut to max_dets), ground
+ * truths gt_off[i] .. gt_off[i+1], and its row-major D_i x G_i OKS matrix starts at oks_off[i].  `host_offs` is the
+ * copy in HOST memory that the entry points check before any launch (start at 0, monotone, oks_off the running sum of
+ * D_i G_i, ending at Dtot / Gtot / oks_total); `offs` is the same array in device memory.  D_i = 0 and G_i = 0 are
+ * legal, so is n_img = 0 (nothing is launched).
+ *
+ * pp_cocoeval_oks: oks[oks_off[i] + d G_i + g] = OKS(detection d, ground truth g) of every image in one launch.
+ *   det_kpts [Dtot, K, 2] (x, y), gt_kpts [Gtot, K, 3] (x, y, v), gt_bbox [Gtot, 4] xywh, gt_area [Gtot],
+ *   vars [K] = (2 sigma_k)^2, gt_flags [Gtot] bytes (below).  Over the keypoints with v > 0:
+ *   e = (dx^2 + dy^2) / vars / (area + DBL_EPSILON) / 2, OKS = mean(exp(-e)); a ground truth flagged NO_VISIBLE is
+ *   scored over all K keypoints by the distance to its box grown by its own size on every side.
+ * pp_cocoeval_match: the greedy matching of all (image, area range, threshold) triples in one launch.
+ *   area_ranges [A, 2] (lo, hi), thr [T], det_area [Dtot].  A ground truth is ignored in a range when it is CROWD or
+ *   NO_VISIBLE or its area is outside [lo, hi].  Per detection, in order: the best still-free ground truth with
+ *   OKS >= min(thr, 1 - 1e-10), non-ignored ones before ignored ones, the later one on equal OKS; crowd ground truths
+ *   stay free.  dt_matched / dt_ignore [A, T, Dtot] bytes (an unmatched detection is ignored when its own area is
+ *   outside the range), npig [A] int32 = non-ignored ground truths, gt_matched [A, T, Gtot] bytes (workspace; on
+ *   return: which ground truths were taken).
+ * pp_cocoeval_accumulate: per (area range, threshold), over the detections in `order` ([Dtot] int64, the stable
+ *   descending score order over all images): tp / fp over the non-ignored ones, precision tp / (tp + fp + eps) made
+ *   non-increasing from the right, sampled at the first position whose recall tp / npig reaches rec_thr[r].
+ *   precision [T, R, A], recall [T, A]; -1 where npig[a] = 0.  ws_env [A, T, Dtot] float64 and ws_tp [A, T, Dtot]
+ *   int32 are workspace.
+ * ---------------------------------------------------------------------- */
+#define PP_COCO_GT_CROWD 1
+#define PP_COCO_GT_NO_VISIBLE 2
+int pp_cocoeval_oks(int n_img, int K, long long Dtot, long long Gtot, long long oks_total, const long long *host_offs,
+                    const void *offs, const void *det_kpts, const void *gt_kpts, const void *gt_bbox,
+                    const void *gt_area, const void *gt_flags, const void *vars, void *oks, void *stream);
+int pp_cocoeval_match(int n_img, int A, int T, long long Dtot, long long Gtot, long long oks_total,
+                      const long long *host_offs, const void *offs, const void *oks, const void *gt_flags,
+                      const void *gt_area, const void *det_area, const void *area_ranges, const void *thr,
+                      void *gt_matched, void *dt_matched, void *dt_ignore, void *npig, void *stream);
+int pp_cocoeval_accumulate(long long Dtot, int A, int T, int R, const void *order, const void *dt_matched,
+                           const void *dt_ignore, const void *npig, const void *rec_thr, void *ws_env, void *ws_tp,
+                           void *precision, void *recall, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

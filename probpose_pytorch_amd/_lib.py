@@ -136,8 +136,12 @@ _SIGNATURES = {
     "pp_ema_table_bytes": (C.c_longlong, [_i, _vp]),
     "pp_ema_table_build": (C.c_int, [_i] + [_vp] * 5 + [C.POINTER(C.c_int)]),
     "pp_ema_update": (C.c_int, [_vp, _i, _d, _vp]),
+    "pp_cocoeval_oks": (C.c_int, [_i, _i] + [C.c_longlong] * 3 + [_vp] * 10),
+    "pp_cocoeval_match": (C.c_int, [_i, _i, _i] + [C.c_longlong] * 3 + [_vp] * 13),
+    "pp_cocoeval_accumulate": (C.c_int, [C.c_longlong, _i, _i, _i] + [_vp] * 10),
 }
 PP_EMA_LERP_F32, PP_EMA_COPY_WORDS = 0, 1
+PP_COCO_GT_CROWD, PP_COCO_GT_NO_VISIBLE = 1, 2
 EXPORTS = tuple(_SIGNATURES)
 
 
