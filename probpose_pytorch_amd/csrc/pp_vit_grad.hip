@@ -164,9 +164,13 @@ __global__ __launch_bounds__(256) void gelu_kernel(const float *__restrict__ x, 
 // (a) dq kernel, per (crop, head, query block): one query row per thread (head_dim 64: two lanes per row, 32 dims
 //     each, the dot products joined by one lane exchange); keys stream through LDS; the row's log-sum-exp is
 //     recomputed (pass 1), then dQ accumulates in registers (pass 2); lse and D go to the workspace.
-// (b) dk / dv kernel, per (crop, head, key block): one key row per thread; the queries (pre-scaled), dO, lse and D
+// (b) dk / dv kernel, per (crop, head, key block): one key row per thread; the queries, dO, lse and D
 //     stream through LDS; P and dS are recomputed from the saved statistics.
 // Every sum runs in key / query order: no atomics, deterministic.
+// The score s_ij is the argument of an exponential: an absolute error t of it is a relative error t of P_ij, and an f32
+// chain over hd products of a score of size 50 (peaked rows) is off by 100 u and more.  So the score alone is summed as
+// a compensated dot product (Ogita, Rump, Oishi: Dot2, the result as if accumulated in twice the precision) of the
+// unscaled q and k and then scaled by hd^-1/2 held as two floats: it carries one rounding of its own size.
 // ============================================================================================================
 constexpr int AB_THREADS = 128;
 constexpr int AB_CHUNK = 64;      // rows per LDS chunk
@@ -177,11 +181,50 @@ __device__ __forceinline__ float ab_join(float v) {
   return v;
 }
 
+// hi + lo += a b, exactly but for second-order terms (TwoProduct by fma, Knuth's TwoSum; -ffp-contract=off)
+__device__ __forceinline__ void ab_dot2(float a, float b, float &hi, float &lo) {
+  const float p = a * b;
+  const float ep = fmaf(a, b, -p);
+  const float t = hi + p;
+  const float z = t - hi;
+  const float es = (hi - (t - z)) + (p - z);
+  hi = t;
+  lo += ep + es;
+}
+
+// the 32 dims of a lane: q in registers against a row of 8 float4
+__device__ __forceinline__ void ab_dot2_row(const float (&q)[32], const float4 *kr, float &hi, float &lo) {
+  hi = 0.f;
+  lo = 0.f;
+#pragma unroll
+  for (int d4 = 0; d4 < 8; ++d4) {
+    const float4 kv = kr[d4];
+    ab_dot2(q[4 * d4], kv.x, hi, lo); ab_dot2(q[4 * d4 + 1], kv.y, hi, lo);
+    ab_dot2(q[4 * d4 + 2], kv.z, hi, lo); ab_dot2(q[4 * d4 + 3], kv.w, hi, lo);
+  }
+}
+
+// scale (sc_hi + sc_lo) times the dot product hi + lo, the two half rows of head_dim 64 joined first (TwoSum's error
+// term is exact, so both lanes of a pair hold the same bits)
+template <int SPLIT>
+__device__ __forceinline__ float ab_score(float hi, float lo, float sc_hi, float sc_lo) {
+  if constexpr (SPLIT == 2) {
+    const float h2 = __shfl_xor(hi, 1, 64), l2 = __shfl_xor(lo, 1, 64);
+    const float t = hi + h2;
+    const float z = t - hi;
+    lo = ((hi - (t - z)) + (h2 - z)) + (lo + l2);
+    hi = t;
+  }
+  const float p = hi * sc_hi;
+  const float e = fmaf(hi, sc_hi, -p);
+  return p + (e + (hi * sc_lo + lo * sc_hi));
+}
+
 template <typename T, int HD>
 __global__ __launch_bounds__(AB_THREADS) void attn_bwd_dq_kernel(const T *__restrict__ qkv, const T *__restrict__ o,
                                                                  const T *__restrict__ dout, T *__restrict__ dqkv,
                                                                  float *__restrict__ ws, int N, int heads,
-                                                                 float scale) {
+                                                                 float scale, float scale_lo) {
   constexpr int SPLIT = HD / 32, ROWS = AB_THREADS / SPLIT;
   __shared__ __attribute__((aligned(16))) float Ks[AB_CHUNK * HD];
   __shared__ __attribute__((aligned(16))) float Vs[AB_CHUNK * HD];
@@ -197,7 +240,7 @@ __global__ __launch_bounds__(AB_THREADS) void attn_bwd_dq_kernel(const T *__rest
 #pragma unroll
   for (int d = 0; d < 32; ++d) {
     const long long orow = ((long long)b * N + i) * C + h * HD + d0 + d;
-    q[d] = active ? Store<T>::ld(base + (long long)i * ld + h * HD + d0 + d) * scale : 0.f;
+    q[d] = active ? Store<T>::ld(base + (long long)i * ld + h * HD + d0 + d) : 0.f;
     dob[d] = active ? Store<T>::ld(dout + orow) : 0.f;
     Dp = fmaf(dob[d], active ? Store<T>::ld(o + orow) : 0.f, Dp);
     dq[d] = 0.f;
@@ -214,15 +257,9 @@ __global__ __launch_bounds__(AB_THREADS) void attn_bwd_dq_kernel(const T *__rest
     }
     __syncthreads();
     for (int j = 0; j < kc; ++j) {
-      const float4 *kr = reinterpret_cast<const float4 *>(Ks + j * HD + d0);
-      float a = 0.f;
-#pragma unroll
-      for (int d4 = 0; d4 < 8; ++d4) {
-        const float4 kv = kr[d4];
-        a = fmaf(q[4 * d4], kv.x, a); a = fmaf(q[4 * d4 + 1], kv.y, a);
-        a = fmaf(q[4 * d4 + 2], kv.z, a); a = fmaf(q[4 * d4 + 3], kv.w, a);
-      }
-      const float sc = ab_join<SPLIT>(a);
+      float a, al;
+      ab_dot2_row(q, reinterpret_cast<const float4 *>(Ks + j * HD + d0), a, al);
+      const float sc = ab_score<SPLIT>(a, al, scale, scale_lo);
       const float mn = fmaxf(m, sc);
       l = l * expf(m - mn) + expf(sc - mn);
       m = mn;
@@ -243,16 +280,15 @@ __global__ __launch_bounds__(AB_THREADS) void attn_bwd_dq_kernel(const T *__rest
     for (int j = 0; j < kc; ++j) {
       const float4 *kr = reinterpret_cast<const float4 *>(Ks + j * HD + d0);
       const float4 *vr = reinterpret_cast<const float4 *>(Vs + j * HD + d0);
-      float a = 0.f, dp = 0.f;
+      float a, al, dp = 0.f;
+      ab_dot2_row(q, kr, a, al);
 #pragma unroll
       for (int d4 = 0; d4 < 8; ++d4) {
-        const float4 kv = kr[d4], vv = vr[d4];
-        a = fmaf(q[4 * d4], kv.x, a); a = fmaf(q[4 * d4 + 1], kv.y, a);
-        a = fmaf(q[4 * d4 + 2], kv.z, a); a = fmaf(q[4 * d4 + 3], kv.w, a);
+        const float4 vv = vr[d4];
         dp = fmaf(dob[4 * d4], vv.x, dp); dp = fmaf(dob[4 * d4 + 1], vv.y, dp);
         dp = fmaf(dob[4 * d4 + 2], vv.z, dp); dp = fmaf(dob[4 * d4 + 3], vv.w, dp);
       }
-      const float p = expf(ab_join<SPLIT>(a) - lse);
+      const float p = expf(ab_score<SPLIT>(a, al, scale, scale_lo) - lse);
       const float ds = p * (ab_join<SPLIT>(dp) - D);
 #pragma unroll
       for (int d4 = 0; d4 < 8; ++d4) {
@@ -276,7 +312,7 @@ __global__ __launch_bounds__(AB_THREADS) void attn_bwd_dq_kernel(const T *__rest
 template <typename T, int HD>
 __global__ __launch_bounds__(AB_THREADS) void attn_bwd_dkv_kernel(const T *__restrict__ qkv, const T *__restrict__ dout,
                                                                   T *__restrict__ dqkv, const float *__restrict__ ws,
-                                                                  int N, int heads, float scale) {
+                                                                  int N, int heads, float scale, float scale_lo) {
   constexpr int SPLIT = HD / 32, ROWS = AB_THREADS / SPLIT;
   __shared__ __attribute__((aligned(16))) float Qs[AB_CHUNK * HD];
   __shared__ __attribute__((aligned(16))) float Gs[AB_CHUNK * HD];
@@ -303,7 +339,7 @@ __global__ __launch_bounds__(AB_THREADS) void attn_bwd_dkv_kernel(const T *__res
     __syncthreads();
     for (int e = threadIdx.x; e < qc * HD; e += AB_THREADS) {
       const int ii = e / HD, d = e - ii * HD;
-      Qs[e] = Store<T>::ld(base + (long long)(i0 + ii) * ld + h * HD + d) * scale;
+      Qs[e] = Store<T>::ld(base + (long long)(i0 + ii) * ld + h * HD + d);
       Gs[e] = Store<T>::ld(dout + ((long long)b * N + i0 + ii) * C + h * HD + d);
     }
     for (int e = threadIdx.x; e < qc; e += AB_THREADS) {
@@ -314,16 +350,15 @@ __global__ __launch_bounds__(AB_THREADS) void attn_bwd_dkv_kernel(const T *__res
     for (int ii = 0; ii < qc; ++ii) {
       const float4 *qr = reinterpret_cast<const float4 *>(Qs + ii * HD + d0);
       const float4 *gr = reinterpret_cast<const float4 *>(Gs + ii * HD + d0);
-      float a = 0.f, dp = 0.f;
+      float a, al, dp = 0.f;
+      ab_dot2_row(k, qr, a, al);          // the products and their order are the dq kernel's: the same bits
 #pragma unroll
       for (int d4 = 0; d4 < 8; ++d4) {
-        const float4 qv = qr[d4], gv = gr[d4];
-        a = fmaf(qv.x, k[4 * d4], a); a = fmaf(qv.y, k[4 * d4 + 1], a);
-        a = fmaf(qv.z, k[4 * d4 + 2], a); a = fmaf(qv.w, k[4 * d4 + 3], a);
+        const float4 gv = gr[d4];
         dp = fmaf(gv.x, v[4 * d4], dp); dp = fmaf(gv.y, v[4 * d4 + 1], dp);
         dp = fmaf(gv.z, v[4 * d4 + 2], dp); dp = fmaf(gv.w, v[4 * d4 + 3], dp);
       }
-      const float p = expf(ab_join<SPLIT>(a) - Ls[ii]);
+      const float p = expf(ab_score<SPLIT>(a, al, scale, scale_lo) - Ls[ii]);
       const float ds = p * (ab_join<SPLIT>(dp) - Dd[ii]);
 #pragma unroll
       for (int d4 = 0; d4 < 8; ++d4) {
@@ -339,7 +374,7 @@ __global__ __launch_bounds__(AB_THREADS) void attn_bwd_dkv_kernel(const T *__res
     T *out = dqkv + ((long long)b * N + j) * ld + h * HD + d0;
 #pragma unroll
     for (int d = 0; d < 32; ++d) {
-      Store<T>::st(out + C + d, dk[d]);
+      Store<T>::st(out + C + d, dk[d] * scale);
       Store<T>::st(out + 2 * C + d, dv[d]);
     }
   }
@@ -350,12 +385,13 @@ static int attn_bwd_launch(const void *qkv, const void *o, const void *dout, voi
                            float *ws, hipStream_t s) {
   constexpr int ROWS = AB_THREADS / (HD / 32);
   const float scale = 1.0f / sqrtf((float)HD);
+  const float scale_lo = (float)(1.0 / sqrt((double)HD) - (double)scale);
   const dim3 grid(B * heads, cdiv(N, ROWS));
   hipLaunchKernelGGL((attn_bwd_dq_kernel<T, HD>), grid, dim3(AB_THREADS), 0, s, (const T *)qkv, (const T *)o,
-                     (const T *)dout, (T *)dqkv, ws, N, heads, scale);
+                     (const T *)dout, (T *)dqkv, ws, N, heads, scale, scale_lo);
   PP_CHECK_LAUNCH("attn_bwd_dq_kernel");
   hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, HD>), grid, dim3(AB_THREADS), 0, s, (const T *)qkv, (const T *)dout,
-                     (T *)dqkv, (const float *)ws, N, heads, scale);
+                     (T *)dqkv, (const float *)ws, N, heads, scale, scale_lo);
   PP_CHECK_LAUNCH("attn_bwd_dkv_kernel");
   return 0;
 }
