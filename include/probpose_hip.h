@@ -715,6 +715,43 @@ int pp_cocoeval_accumulate(long long Dtot, int A, int T, int R, const void *orde
                            const void *dt_ignore, const void *npig, const void *rec_thr, void *ws_env, void *ws_tp,
                            void *precision, void *recall, void *stream);
 
+/* ------------------------------------------------------------------------
+ * PoseNMS (probpose_pytorch_amd/posenms.py): instance rescoring and OKS-NMS of decoded poses, the stage between
+ * Codec.decode and CocoKeypointEval.  Everything is float64; no host sync, no atomics, plain vector stores, the same
+ * bits on every call.
+ *
+ * pp_posenms_rescore: out[i] = box_scores[i] * mean, one lane per detection.  mean = (sum of the kpt_scores[i, k] >
+ *   kpt_thr, added in ascending k) / (their number n); n = 0 gives mean 0.  kpt_scores [M, K], box_scores [M],
+ *   out [M].  M = 0 launches nothing.
+ *
+ * pp_posenms: NMS of every image of a ragged batch in one launch.  `host_off` / `off` are the n_img + 1 int64 CSR
+ *   offsets of the detections, in HOST memory (checked before any launch: start at 0, monotone, ending at Dtot, no
+ *   image above PP_POSENMS_MAX_DETS) and in device memory (what the kernel reads).  Image i owns detections
+ *   off[i] .. off[i+1], ALREADY in descending score order, equal scores in the order they were given.
+ *   kpts [Dtot, K, 2] (x, y), vis [Dtot, K] or NULL, area [Dtot], scores [Dtot], vars [K] = (2 sigma_k)^2.
+ *   OKS(a, b) = mean over the keypoints that count of exp(-e_k),
+ *   e_k = (dx^2 + dy^2) / vars[k] / ((area_a + area_b) / 2 + DBL_EPSILON) / 2; with vis == NULL every keypoint counts,
+ *   otherwise those with vis_a[k] > vis_thr and vis_b[k] > vis_thr; none counting gives OKS 0.
+ *   PP_POSENMS_HARD: walk the order; a detection not yet suppressed is kept and suppresses every later live one whose
+ *     OKS with it is > oks_thr.  out_scores = scores.  max_dets is not used (it must still be positive).
+ *   PP_POSENMS_SOFT_GAUSSIAN / PP_POSENMS_SOFT_LINEAR: until nothing is live or max_dets are kept: the live detection
+ *     with the largest current score (the earliest on equal scores) is kept with that score, and every other live
+ *     detection's score is multiplied by exp(-OKS^2 / oks_thr), or by (1 - OKS) where OKS >= oks_thr.
+ *   out_scores [Dtot] (the current scores at the end), keep [Dtot] bytes (1 = kept), counts [n_img] int32 = kept per
+ *   image.  n_img = 0 or Dtot = 0 launches nothing.
+ * Both refuse on the host, with pp_last_error, before any launch: null pointers, K <= 0, oks_thr outside (0, 1], an
+ * unknown mode, max_dets <= 0, bad offsets.
+ * ---------------------------------------------------------------------- */
+#define PP_POSENMS_HARD 0
+#define PP_POSENMS_SOFT_GAUSSIAN 1
+#define PP_POSENMS_SOFT_LINEAR 2
+#define PP_POSENMS_MAX_DETS 4096
+int pp_posenms_rescore(long long M, int K, const void *kpt_scores, const void *box_scores, double kpt_thr, void *out,
+                       void *stream);
+int pp_posenms(int n_img, int K, long long Dtot, const long long *host_off, const void *off, const void *kpts,
+               const void *vis, const void *area, const void *scores, const void *vars, int mode, double oks_thr,
+               double vis_thr, int max_dets, void *out_scores, void *keep, void *counts, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,7 +13,7 @@ from .codec import ArgMaxProbMap, Codec, ProbMap  # noqa: F401
 from .heatmap import get_heatmap_expected_value  # noqa: F401
 
 __all__ = ["to_numpy", "Codec", "ProbMap", "ArgMaxProbMap", "get_heatmap_expected_value", "FusedAdamW",
-           "Augment", "ModelEma", "ema_update_", "CocoKeypointEval"]
+           "Augment", "ModelEma", "ema_update_", "CocoKeypointEval", "PoseNMS", "rescore_instances"]
 
 
 def __getattr__(name):  # lazy: the nn.Module side pulls in the engine
@@ -35,6 +35,9 @@ def __getattr__(name):  # lazy: the nn.Module side pulls in the engine
     if name == "CocoKeypointEval":
         from .cocoeval import CocoKeypointEval
         return CocoKeypointEval
+    if name in ("PoseNMS", "rescore_instances"):
+        from . import posenms
+        return getattr(posenms, name)
     if name == "Augment":
         from .dataset import Augment
         return Augment

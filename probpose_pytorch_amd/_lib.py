@@ -139,9 +139,13 @@ _SIGNATURES = {
     "pp_cocoeval_oks": (C.c_int, [_i, _i] + [C.c_longlong] * 3 + [_vp] * 10),
     "pp_cocoeval_match": (C.c_int, [_i, _i, _i] + [C.c_longlong] * 3 + [_vp] * 13),
     "pp_cocoeval_accumulate": (C.c_int, [C.c_longlong, _i, _i, _i] + [_vp] * 10),
+    "pp_posenms_rescore": (C.c_int, [C.c_longlong, _i, _vp, _vp, _d, _vp, _vp]),
+    "pp_posenms": (C.c_int, [_i, _i, C.c_longlong] + [_vp] * 7 + [_i, _d, _d, _i] + [_vp] * 4),
 }
 PP_EMA_LERP_F32, PP_EMA_COPY_WORDS = 0, 1
 PP_COCO_GT_CROWD, PP_COCO_GT_NO_VISIBLE = 1, 2
+PP_POSENMS_HARD, PP_POSENMS_SOFT_GAUSSIAN, PP_POSENMS_SOFT_LINEAR = 0, 1, 2
+PP_POSENMS_MAX_DETS = 4096
 EXPORTS = tuple(_SIGNATURES)
 
 

@@ -12,7 +12,10 @@ function, ``run_inference``: ``Codec(ProbMap(input_size, heatmap_size, sigmas))`
 * image I/O needs PIL; without ``--image`` a seeded synthetic crop is used;
 * ``--flip-test`` averages the outputs with those of the mirrored crop (``ProbPoseModel.set_flip_test``), the way the
   accuracy of top-down estimators is usually reported; ``--flip-pairs "1-2,3-4,..."`` names the left/right keypoint
-  pairs (default for 17 keypoints: COCO's 1-2, 3-4, ..., 15-16).
+  pairs (default for 17 keypoints: COCO's 1-2, 3-4, ..., 15-16);
+* ``--boxes "x,y,w,h[,score];..."`` runs the box path (``run_inference_on_boxes``) on the full-size ``--image``, and
+  ``--nms {hard,soft_gaussian,soft_linear}`` / ``--nms-thr`` rescore and suppress the boxes' duplicate poses after
+  decode (``posenms.PoseNMS``); both are off by default.
 """
 from __future__ import annotations
 
@@ -63,11 +66,16 @@ def run_inference(model: ProbPoseModel, codec: Codec, image_tensor: torch.Tensor
     return output, codec.decode(output)
 
 
-def run_inference_on_boxes(model: ProbPoseModel, codec: Codec, frame: torch.Tensor, boxes_xywh):
+def run_inference_on_boxes(model: ProbPoseModel, codec: Codec, frame: torch.Tensor, boxes_xywh, nms=None,
+                           box_scores=None):
     """Whole per-frame path on the GPU: ``frame`` (H, W, 3) uint8 RGB on the device and person boxes
     [x, y, w, h] -> crops (dataset.py:71-90 semantics, frontend.crop_resize) -> forward -> decode.
     Returns (raw 5-tuple, decoded predictions, keypoints in FRAME pixels (n, K, 2) float64): the inverse of
-    the keypoint rescale of dataset.py:87-89, ``kpt / input_size * box_wh + box_xy``."""
+    the keypoint rescale of dataset.py:87-89, ``kpt / input_size * box_wh + box_xy``.
+
+    With ``nms`` (a ``posenms.PoseNMS``) a fourth value follows: the ``PoseNMSResult`` of the frame's poses, rescored
+    by ``box_scores`` [n] (default: ones) times the mean confident keypoint score and suppressed by OKS, with the box
+    areas w * h as the scale; the three other values are what they are without it."""
     from . import frontend
     input_size = codec.probmap.input_size
     crops = frontend.crop_resize(frame, boxes_xywh, input_size)
@@ -76,7 +84,15 @@ def run_inference_on_boxes(model: ProbPoseModel, codec: Codec, frame: torch.Tens
     kpts = np.asarray(preds[0][0], dtype=np.float64)
     in_wh = np.asarray(input_size, dtype=np.float64)
     frame_kpts = kpts / in_wh * b[:, None, 2:4] + b[:, None, 0:2]
-    return output, preds, frame_kpts
+    if nms is None:
+        return output, preds, frame_kpts
+    n = b.shape[0]
+    scores = np.ones(n) if box_scores is None else np.asarray(box_scores, dtype=np.float64).reshape(n)
+    dev = frame.device
+    result = nms(np.zeros(n, dtype=np.int64), torch.from_numpy(frame_kpts).to(dev), torch.from_numpy(scores).to(dev),
+                 torch.from_numpy(b[:, 2] * b[:, 3]).to(dev),
+                 kpt_scores=torch.from_numpy(np.ascontiguousarray(preds[0][1])).to(dev))
+    return output, preds, frame_kpts, result
 
 
 def load_image(path: Path, input_size) -> torch.Tensor:
@@ -119,6 +135,28 @@ def resolve_flip_pairs(parser, args):
     return pairs
 
 
+def parse_boxes(text: str):
+    """"x,y,w,h[,score];..." -> (boxes [n, 4], scores [n]; a box without score gets 1)."""
+    boxes, scores = [], []
+    for part in text.split(";"):
+        if not part.strip():
+            continue
+        v = [float(t) for t in part.split(",")]
+        if len(v) not in (4, 5) or v[2] <= 0 or v[3] <= 0:
+            raise ValueError(f"{part!r} is not x,y,w,h[,score] with positive w, h")
+        boxes.append(v[:4])
+        scores.append(v[4] if len(v) == 5 else 1.0)
+    if not boxes:
+        raise ValueError("no box given")
+    return np.asarray(boxes, dtype=np.float64), np.asarray(scores, dtype=np.float64)
+
+
+def load_frame(path: Path) -> torch.Tensor:
+    """The image at its own size as (H, W, 3) uint8 RGB: what the box path crops from."""
+    import PIL.Image
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(PIL.Image.open(path).convert("RGB"), dtype=np.uint8)))
+
+
 def main(argv=None):
     p = argparse.ArgumentParser(description="Inference script for ProbPose (MI355X-native path)")
     p.add_argument("--model", type=Path, default=None, help="state_dict checkpoint (omit: seeded synthetic weights)")
@@ -135,8 +173,23 @@ def main(argv=None):
     p.add_argument("--flip-test", action="store_true", help="average with the outputs of the mirrored crop")
     p.add_argument("--flip-pairs", type=str, default=None,
                    help='left/right keypoint pairs "1-2,3-4,..." (default for 17 keypoints: the COCO pairs)')
+    p.add_argument("--boxes", type=str, default=None,
+                   help='person boxes "x,y,w,h[,score];..." in pixels of --image at its own size: the box path')
+    p.add_argument("--nms", type=str, default=None, choices=["hard", "soft_gaussian", "soft_linear"],
+                   help="with --boxes: rescore the poses and suppress duplicates by OKS after decode (default: off)")
+    p.add_argument("--nms-thr", type=float, default=0.9, help="OKS threshold of --nms")
     args = p.parse_args(argv)
     flip_pairs = resolve_flip_pairs(p, args)
+    boxes = None
+    if args.boxes is not None:
+        try:
+            boxes = parse_boxes(args.boxes)
+        except ValueError as e:
+            p.error(f"--boxes: {e}")
+    if args.nms is not None and boxes is None:
+        p.error("--nms needs --boxes (it applies to the box path)")
+    if not 0.0 < args.nms_thr <= 1.0:
+        p.error(f"--nms-thr: {args.nms_thr} is outside (0, 1]")
     input_size = tuple(map(int, args.input_size.split(",")))
     model, heatmap_size = build_model(input_size, args.num_keypoints, args.backbone)
     if args.model is not None:
@@ -151,6 +204,8 @@ def main(argv=None):
         model.set_compute_dtype(torch.bfloat16)
     model.set_flip_test(flip_pairs)
     codec = Codec(ProbMap(input_size, heatmap_size, np.array([args.sigma] * args.num_keypoints)))
+    if boxes is not None:
+        return _main_boxes(args, model, codec, boxes)
     if args.image is not None:
         x = load_image(args.image, input_size)
     else:
@@ -170,6 +225,27 @@ def main(argv=None):
     print("OKS:", preds[3])
     print("Errors:", preds[4])
     return preds
+
+
+def _main_boxes(args, model, codec, boxes):
+    """The box path of the command line: full-size frame, one crop per box, optional NMS of the poses."""
+    if args.image is not None:
+        frame = load_frame(args.image)
+    else:       # a seeded synthetic frame that holds every box
+        h, w = int(np.ceil((boxes[0][:, 1] + boxes[0][:, 3]).max())) + 1, int(np.ceil((boxes[0][:, 0]
+                                                                                       + boxes[0][:, 2]).max())) + 1
+        frame = torch.from_numpy(np.random.default_rng(1234).integers(0, 256, (h, w, 3), dtype=np.uint8))
+    print("Frame shape:", tuple(frame.shape), "boxes:", boxes[0].shape[0])
+    nms = None
+    if args.nms is not None:
+        from .posenms import PoseNMS
+        nms = PoseNMS(np.array([args.sigma] * args.num_keypoints), mode=args.nms, oks_thr=args.nms_thr)
+    out = run_inference_on_boxes(model, codec, frame.to("cuda"), boxes[0], nms=nms, box_scores=boxes[1])
+    print("Keypoints (frame pixels):", out[2])
+    if nms is not None:
+        print("Kept:", out[3].keep.cpu().numpy())
+        print("Scores:", out[3].scores.cpu().numpy())
+    return out
 
 
 if __name__ == "__main__":

@@ -1,0 +1,238 @@
+"""Instance rescoring and OKS-NMS of decoded poses on the GPU: the stage between ``Codec.decode`` and
+``CocoKeypointEval.add_detections`` of every top-down evaluation protocol.
+
+A person detector emits several overlapping boxes per person; the duplicate poses would count as false positives.
+``rescore_instances`` makes an instance's score its box score times the mean of its confident keypoint scores;
+``PoseNMS`` suppresses the duplicates per image, by hard OKS-NMS or by soft OKS-NMS, with the two launches of
+csrc/pp_posenms.hip:
+
+  pp_posenms_rescore   one lane per detection
+  pp_posenms           one wave per image; lane j % 64 owns detection j's live flag and current score
+
+Between them run torch device ops that do not synchronise: casts to float64, two stable sorts (descending score, then
+image: every image's detections end up in score order, equal scores in the order they were given) and gathers.
+
+Rules (restated in tests/posenms_reference.py, the gauge this module is tested against), float64 throughout:
+* rescoring: n = the keypoints with score > kpt_thr, score = box_score * (their sum in ascending k / n), 0 with n = 0;
+* OKS of detections a, b of one image: the mean over the keypoints that count of exp(-e_k), e_k = (dx^2 + dy^2) /
+  (2 sigma_k)^2 / ((area_a + area_b) / 2 + eps) / 2; with ``vis_thr`` None every keypoint counts, otherwise those whose
+  visibility is above it in both; none counting gives 0;
+* detections of an image are visited by descending score, equal scores in the order they were given;
+* hard: a detection not yet suppressed is kept and suppresses every later live one whose OKS with it is > oks_thr;
+  scores are unchanged;
+* soft_gaussian / soft_linear: until nothing is live or ``max_dets`` are kept, the live detection with the largest
+  current score (the earliest on equal scores) is kept with that score and every other live detection's score is
+  multiplied by exp(-OKS^2 / oks_thr), or by (1 - OKS) where OKS >= oks_thr; detections never picked are not kept and
+  return their current score.
+
+There is no CPU fallback: without a GPU the calls raise ``_lib.HipExtensionError``.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import _lib
+from .cocoeval import _host
+
+MODES = {"hard": _lib.PP_POSENMS_HARD, "soft_gaussian": _lib.PP_POSENMS_SOFT_GAUSSIAN,
+         "soft_linear": _lib.PP_POSENMS_SOFT_LINEAR}
+MAX_DETS_PER_IMAGE = _lib.PP_POSENMS_MAX_DETS
+
+
+def _room(t: torch.Tensor) -> torch.Tensor:
+    """A tensor the library can take the address of: an empty one gets one element of room."""
+    return t if t.numel() else torch.zeros(1, dtype=t.dtype, device=t.device)
+
+
+def _device_f64(named) -> list:
+    """The named inputs as contiguous float64 device tensors.  Refuses host arrays, mixed placement, non-float
+    dtypes and non-finite values (one boolean per input is read back, as CocoKeypointEval.add_detections does)."""
+    names = " / ".join(n for n, _ in named)
+    dev = [isinstance(a, torch.Tensor) and a.is_cuda for _, a in named]
+    if any(dev) and not all(dev):
+        raise ValueError(f"{names}: either all device tensors or all host arrays")
+    if not all(dev):
+        _lib.require_device()
+        raise _lib.HipExtensionError(f"{names}: expected tensors on the GPU (cuda/HIP device); there is no CPU "
+                                     "fallback")
+    for n, a in named:
+        if not a.dtype.is_floating_point:
+            raise ValueError(f"{n}: expected a float dtype, got {a.dtype}")
+    out = [a.detach().to(torch.float64).contiguous() for _, a in named]
+    finite = torch.stack([torch.isfinite(t).all() for t in out]).cpu().numpy()
+    for (n, _), ok in zip(named, finite):
+        if not bool(ok):
+            raise ValueError(f"{n}: non-finite values")
+    return out
+
+
+def _first_seen(ids: np.ndarray):
+    """(the distinct ids in the order they first appear, every id's position in that list [M] int64)."""
+    if ids.dtype != object:
+        uniq, first, inverse = np.unique(ids, return_index=True, return_inverse=True)
+        by_first = np.argsort(first, kind="stable")
+        rank = np.empty(by_first.size, dtype=np.int64)
+        rank[by_first] = np.arange(by_first.size, dtype=np.int64)
+        return uniq[by_first].tolist(), rank[inverse.reshape(-1)]
+    index = {}
+    for i in ids.tolist():
+        if i not in index:
+            index[i] = len(index)
+    return list(index), np.fromiter((index[i] for i in ids.tolist()), dtype=np.int64, count=ids.shape[0])
+
+
+def _rescore(ks: torch.Tensor, bs: torch.Tensor, kpt_thr: float) -> torch.Tensor:
+    M, K = ks.shape
+    out = torch.empty(M, dtype=torch.float64, device=ks.device)
+    _lib.check(_lib.lib().pp_posenms_rescore(M, K, _lib.ptr(_room(ks)), _lib.ptr(_room(bs)), float(kpt_thr),
+                                             _lib.ptr(_room(out)), _lib.stream_ptr()), "pp_posenms_rescore")
+    return out
+
+
+def rescore_instances(kpt_scores, box_scores, kpt_thr: float = 0.2) -> torch.Tensor:
+    """box_scores [M] times the mean of the kpt_scores [M, K] above ``kpt_thr``: a device float64 tensor [M].  An
+    instance with no keypoint above the threshold scores 0.  The inputs are device tensors of any float dtype."""
+    shape, bshape = tuple(kpt_scores.shape), tuple(box_scores.shape)
+    if len(shape) != 2 or shape[1] == 0:
+        raise ValueError(f"kpt_scores: expected [M, K] with K > 0, got {shape}")
+    if bshape != (shape[0],):
+        raise ValueError(f"box_scores: expected [{shape[0]}], got {bshape}")
+    if not np.isfinite(kpt_thr):
+        raise ValueError(f"kpt_thr: {kpt_thr} is not finite")
+    ks, bs = _device_f64((("kpt_scores", kpt_scores), ("box_scores", box_scores)))
+    return _rescore(ks, bs, kpt_thr)
+
+
+class PoseNMSResult:
+    """What ``PoseNMS.__call__`` returns, in the order the detections were given: ``keep`` [M] bool and ``scores``
+    [M] float64 on the device, ``counts`` [n_img] int32 on the device (kept per image) and ``image_ids`` (host list),
+    both in first-seen image order."""
+    __slots__ = ("keep", "scores", "counts", "image_ids", "_staged")
+
+    def __init__(self, keep, scores, counts, image_ids, staged):
+        self.keep, self.scores, self.counts, self.image_ids, self._staged = keep, scores, counts, image_ids, staged
+
+    def __repr__(self):
+        return f"PoseNMSResult({self.keep.shape[0]} detections of {len(self.image_ids)} images)"
+
+
+class PoseNMS:
+    """OKS-NMS of the decoded poses of a batch, per image.
+
+    ``sigmas`` [K] are the per-keypoint constants; ``mode`` is "hard", "soft_gaussian" or "soft_linear";
+    ``oks_thr`` in (0, 1]; ``vis_thr`` None lets every keypoint count in the OKS; ``kpt_thr`` is the rescoring
+    threshold; ``max_dets`` bounds what the soft modes keep per image (hard mode does not use it)."""
+
+    def __init__(self, sigmas, *, mode: str = "hard", oks_thr: float = 0.9, vis_thr=None, kpt_thr: float = 0.2,
+                 max_dets: int = 20):
+        self.sigmas = _host(sigmas, "sigmas", np.float64).reshape(-1)
+        if self.sigmas.size == 0 or not np.all(np.isfinite(self.sigmas)) or np.any(self.sigmas <= 0):
+            raise ValueError("sigmas: need K > 0 finite positive values")
+        self.K = int(self.sigmas.size)
+        if mode not in MODES:
+            raise ValueError(f"mode: {mode!r} is not one of {tuple(MODES)}")
+        if not 0.0 < float(oks_thr) <= 1.0:
+            raise ValueError(f"oks_thr: {oks_thr} is outside (0, 1]")
+        if vis_thr is not None and not np.isfinite(vis_thr):
+            raise ValueError(f"vis_thr: {vis_thr} is not finite")
+        if not np.isfinite(kpt_thr):
+            raise ValueError(f"kpt_thr: {kpt_thr} is not finite")
+        if int(max_dets) <= 0:
+            raise ValueError(f"max_dets: {max_dets} is not positive")
+        self.mode, self.oks_thr, self.kpt_thr = mode, float(oks_thr), float(kpt_thr)
+        self.vis_thr = None if vis_thr is None else float(vis_thr)
+        self.max_dets = int(max_dets)
+
+    def _launch(self, n_img, off, off_dev, kp_s, vis_s, ar_s, sc_s, variances):
+        """pp_posenms on a batch in visiting order: (scores [M] float64, keep [M] uint8, counts [n_img] int32)."""
+        M, dev = int(off[-1]), kp_s.device
+        out_s = torch.empty(M, dtype=torch.float64, device=dev)
+        keep_s = torch.empty(M, dtype=torch.uint8, device=dev)
+        counts = torch.zeros(n_img, dtype=torch.int32, device=dev)
+        hold = [_room(t) for t in (kp_s, ar_s, sc_s, out_s, keep_s, counts)]
+        vis_hold = None if vis_s is None else _room(vis_s)
+        _lib.check(_lib.lib().pp_posenms(
+            n_img, self.K, M, off.ctypes.data, _lib.ptr(off_dev), _lib.ptr(hold[0]), _lib.ptr(vis_hold),
+            _lib.ptr(hold[1]), _lib.ptr(hold[2]), _lib.ptr(variances), MODES[self.mode], self.oks_thr,
+            0.0 if self.vis_thr is None else self.vis_thr, self.max_dets, _lib.ptr(hold[3]), _lib.ptr(hold[4]),
+            _lib.ptr(hold[5]), _lib.stream_ptr()), "pp_posenms")
+        return out_s, keep_s, counts
+
+    def __call__(self, image_ids, keypoints, box_scores, areas, kpt_scores=None) -> PoseNMSResult:
+        """M detections: image_ids [M], keypoints [M, K, 2|3], box_scores [M], areas [M], kpt_scores [M, K] or None.
+
+        The image ids are bookkeeping of the host (they decide the ragged layout), so a tensor of ids is read here,
+        once; the other inputs are device tensors of any float dtype and stay on the device.  With ``kpt_scores`` the
+        instances are rescored first (``rescore_instances``) and ``kpt_scores`` is the per-keypoint visibility that
+        ``vis_thr`` reads; without it ``box_scores`` are the scores and a third keypoint column, if there is one, is
+        the visibility.
+
+        Apart from the finiteness booleans of the inputs nothing is read back and nothing waits for the device: the
+        result's tensors are still being computed when this returns.  Boolean indexing by ``keep``
+        (``keypoints[res.keep]``) is the caller's one readback, since the number of survivors decides a shape."""
+        ids = image_ids.detach().cpu().numpy() if isinstance(image_ids, torch.Tensor) else np.asarray(image_ids)
+        if ids.ndim != 1:
+            raise ValueError(f"image_ids: expected [M], got {ids.shape}")
+        M, K = int(ids.shape[0]), self.K
+        named = [("keypoints", keypoints), ("box_scores", box_scores), ("areas", areas)]
+        if kpt_scores is not None:
+            named.append(("kpt_scores", kpt_scores))
+        named = [(n, a if isinstance(a, torch.Tensor) else np.asarray(a)) for n, a in named]
+        shape = tuple(named[0][1].shape)
+        if len(shape) != 3 or shape[0] != M or shape[1] != K or shape[2] not in (2, 3):
+            raise ValueError(f"keypoints: expected [{M}, {K}, 2|3] (K = len(sigmas)), got {shape}")
+        for n, a in named[1:3]:
+            if tuple(a.shape) != (M,):
+                raise ValueError(f"{n}: expected [{M}], got {tuple(a.shape)}")
+        if kpt_scores is not None and tuple(named[3][1].shape) != (M, K):
+            raise ValueError(f"kpt_scores: expected [{M}, {K}], got {tuple(named[3][1].shape)}")
+        if self.vis_thr is not None and kpt_scores is None and shape[2] != 3:
+            raise ValueError("vis_thr: needs visibilities, kpt_scores or a third keypoint column")
+
+        # the ragged layout: host arithmetic on the image ids
+        image_list, pos = _first_seen(ids)
+        n_img = len(image_list)
+        d_cnt = np.bincount(pos, minlength=n_img).astype(np.int64) if n_img else np.zeros(0, dtype=np.int64)
+        if n_img and int(d_cnt.max()) > MAX_DETS_PER_IMAGE:
+            worst = int(d_cnt.argmax())
+            raise ValueError(f"image_ids: image {image_list[worst]!r} has {int(d_cnt[worst])} detections, more than "
+                             f"the {MAX_DETS_PER_IMAGE} that PoseNMS handles per image")
+        off = np.zeros(n_img + 1, dtype=np.int64)
+        off[1:] = np.cumsum(d_cnt)
+
+        tensors = _device_f64(named)
+        kp3, bs, ar = tensors[:3]
+        dev = kp3.device
+        if kpt_scores is not None:
+            sc = _rescore(tensors[3], bs, self.kpt_thr)
+            vis = tensors[3] if self.vis_thr is not None else None
+        else:
+            sc = bs
+            vis = kp3[..., 2] if self.vis_thr is not None else None
+
+        staged = []
+
+        def up(a: np.ndarray) -> torch.Tensor:
+            """To the device without a synchronising copy: through a pinned buffer."""
+            if a.size == 0:
+                return torch.zeros(a.shape, dtype=torch.from_numpy(a).dtype, device=dev)
+            t = torch.from_numpy(np.ascontiguousarray(a)).pin_memory()
+            staged.append(t)
+            return t.to(device=dev, non_blocking=True)
+
+        # descending score, then image: two stable sorts leave every image's detections in score order, equal scores
+        # in the order they were given
+        by_score = torch.sort(sc, descending=True, stable=True).indices
+        by_image = torch.sort(up(pos)[by_score], stable=True).indices
+        perm = by_score[by_image]
+        kp_s = kp3[..., :2][perm].contiguous()
+        vis_s = None if vis is None else vis[perm].contiguous()
+        ar_s, sc_s = ar[perm].contiguous(), sc[perm].contiguous()
+        variances, off_dev = up((self.sigmas * 2) ** 2), up(off)
+        out_s, keep_s, counts = self._launch(n_img, off, off_dev, kp_s, vis_s, ar_s, sc_s, variances)
+        keep = torch.empty(M, dtype=torch.bool, device=dev)
+        scores = torch.empty(M, dtype=torch.float64, device=dev)
+        keep[perm] = keep_s.to(torch.bool)
+        scores[perm] = out_s
+        return PoseNMSResult(keep, scores, counts, image_list, staged)
