@@ -5,6 +5,9 @@ import ctypes as C
 import os
 import threading
 
+import numpy as np
+import torch
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libprobpose_hip.so")
 
@@ -174,9 +177,31 @@ def check(rc: int, what: str = "") -> None:
         raise HipExtensionError(f"{what or 'libprobpose_hip'} failed ({rc}): {msg}")
 
 
+# the int-returning entries whose value is an answer, not a status
+_INT_VALUES = ("pp_version", "pp_device_ok")
+
+
+def call(name: str, *args):
+    """``name(*args)`` in the library: tensors and numpy arrays go as their addresses, None as a null pointer, the rest
+    as given (ctypes checks it against ``_SIGNATURES``).  Raises for a non-zero status and for a negative size;
+    otherwise returns the value."""
+    r = getattr(lib(), name)(*[C.c_void_p(a.data_ptr()) if isinstance(a, torch.Tensor) else
+                               C.c_void_p(a.ctypes.data) if isinstance(a, np.ndarray) else a for a in args])
+    if name.endswith(("_bytes", "_floats")):
+        if r < 0:
+            check(r, name)
+    elif _SIGNATURES[name][0] is C.c_int and name not in _INT_VALUES:
+        check(r, name)
+    return r
+
+
+def launch(name: str, *args):
+    """``call`` for the entries that enqueue work: torch's current stream is the last argument."""
+    return call(name, *args, stream_ptr())
+
+
 def require_device(t=None) -> None:
     """The product path is HIP-only: refuse CPU tensors / missing GPU."""
-    import torch
     if not torch.cuda.is_available():
         raise HipExtensionError("no HIP device visible: the ProbPose hot path has no CPU fallback")
     if t is not None and not t.is_cuda:
@@ -188,5 +213,4 @@ def ptr(t):
 
 
 def stream_ptr():
-    import torch
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)

@@ -26,11 +26,13 @@ There is no CPU fallback: without a GPU ``evaluate()`` raises ``_lib.HipExtensio
 from __future__ import annotations
 
 import json
+from functools import partial
 
 import numpy as np
 import torch
 
 from . import _lib
+from ._buffers import host_array as _host, room, upload
 
 STATS = ("AP", "AP50", "AP75", "APm", "APl", "AR", "AR50", "AR75", "ARm", "ARl")
 _AREA_RANGES = ((0.0, 1e10), (32.0 ** 2, 96.0 ** 2), (96.0 ** 2, 1e10))
@@ -40,15 +42,6 @@ def _mean_present(a: np.ndarray) -> float:
     a = np.asarray(a, dtype=np.float64).reshape(-1)
     a = a[a > -1]
     return float(a.mean()) if a.size else -1.0
-
-
-def _host(x, name: str, dtype) -> np.ndarray:
-    if isinstance(x, torch.Tensor):
-        x = x.detach().cpu().numpy()
-    try:
-        return np.ascontiguousarray(np.asarray(x), dtype=dtype)
-    except (TypeError, ValueError) as e:
-        raise ValueError(f"{name}: cannot be read as {np.dtype(dtype).name} ({e})") from None
 
 
 class CocoKeypointEval:
@@ -236,22 +229,11 @@ class CocoKeypointEval:
         Dtot = int(offs[0, -1])
 
         staged = []                 # pinned host copies, alive until the results are back
-
-        def up(a, dtype=None):
-            """To the device without a synchronising copy: host data goes through a pinned buffer."""
-            if isinstance(a, torch.Tensor) and a.is_cuda:
-                return a.to(dtype=dtype or a.dtype).contiguous()
-            t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
-            if t.numel() == 0:
-                return torch.zeros(t.shape, dtype=dtype or t.dtype, device=dev)
-            t = t.to(dtype=dtype or t.dtype).contiguous().pin_memory()
-            staged.append(t)
-            return t.to(device=dev, non_blocking=True)
-
+        up = partial(upload, device=dev, keep=staged)
         if pos.size:
-            kp = torch.cat([up(d[1], torch.float64) for d in self._dets])
-            sc = torch.cat([up(d[2], torch.float64) for d in self._dets])
-            ar = torch.cat([up(d[3], torch.float64) for d in self._dets])
+            kp = torch.cat([up(d[1], dtype=torch.float64) for d in self._dets])
+            sc = torch.cat([up(d[2], dtype=torch.float64) for d in self._dets])
+            ar = torch.cat([up(d[3], dtype=torch.float64) for d in self._dets])
             # descending score, then image: two stable sorts leave every image's detections in score order, equal
             # scores in the order they were added
             by_score = torch.sort(sc, descending=True, stable=True).indices
@@ -267,62 +249,41 @@ class CocoKeypointEval:
             ar = torch.zeros(0, dtype=torch.float64, device=dev)
         return dict(n_img=n_img, offs_host=offs, offs=up(offs), staged=staged, Dtot=Dtot, Gtot=int(offs[1, -1]),
                     oks_total=int(offs[2, -1]), dt_kpts=kp, dt_score=sc, dt_area=ar, gt_kpts=up(gt_kp),
-                    gt_bbox=up(gt_bb),
-                    gt_area=up(gt_ar), gt_flags=up(gt_flags))
-
-    @staticmethod
-    def _room(t: torch.Tensor) -> torch.Tensor:
-        """A tensor the library can take the address of: an empty one gets one element of room."""
-        return t if t.numel() else torch.zeros(1, dtype=t.dtype, device=t.device)
-
-    @staticmethod
-    def _constant(b, a: np.ndarray) -> torch.Tensor:
-        t = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64).copy()).pin_memory()
-        b["staged"].append(t)
-        return t.to(device="cuda", non_blocking=True)
+                    gt_bbox=up(gt_bb), gt_area=up(gt_ar), gt_flags=up(gt_flags))
 
     def _oks(self, b) -> torch.Tensor:
-        L = _lib.lib()
         oks = torch.empty(max(b["oks_total"], 1), dtype=torch.float64, device="cuda")
-        variances = self._constant(b, (self.sigmas * 2) ** 2)
-        room = self._room
+        variances = upload((self.sigmas * 2) ** 2, "cuda", b["staged"], torch.float64)
         keep = [room(b[k]) for k in ("dt_kpts", "gt_kpts", "gt_bbox", "gt_area", "gt_flags")]
-        _lib.check(L.pp_cocoeval_oks(b["n_img"], self.K, b["Dtot"], b["Gtot"], b["oks_total"],
-                                     b["offs_host"].ctypes.data, _lib.ptr(b["offs"]), *[_lib.ptr(t) for t in keep],
-                                     _lib.ptr(variances), _lib.ptr(oks), _lib.stream_ptr()), "pp_cocoeval_oks")
+        _lib.launch("pp_cocoeval_oks", b["n_img"], self.K, b["Dtot"], b["Gtot"], b["oks_total"], b["offs_host"],
+                    b["offs"], *keep, variances, oks)
         b["_keep_oks"] = (keep, variances)      # referenced until the results are back
         return oks
 
     def _match(self, b, oks):
-        L = _lib.lib()
         A, T = self.area_ranges.shape[0], self.oks_thresholds.size
-        ranges, thr = self._constant(b, self.area_ranges), self._constant(b, self.oks_thresholds)
+        ranges = upload(self.area_ranges, "cuda", b["staged"], torch.float64)
+        thr = upload(self.oks_thresholds, "cuda", b["staged"], torch.float64)
         gt_matched = torch.empty(max(A * T * b["Gtot"], 1), dtype=torch.uint8, device="cuda")
         dt_matched = torch.empty(max(A * T * b["Dtot"], 1), dtype=torch.uint8, device="cuda")
         dt_ignore = torch.empty(max(A * T * b["Dtot"], 1), dtype=torch.uint8, device="cuda")
         npig = torch.empty(A, dtype=torch.int32, device="cuda")
-        keep = [self._room(b[k]) for k in ("gt_flags", "gt_area", "dt_area")]
-        _lib.check(L.pp_cocoeval_match(b["n_img"], A, T, b["Dtot"], b["Gtot"], b["oks_total"],
-                                       b["offs_host"].ctypes.data, _lib.ptr(b["offs"]), _lib.ptr(oks),
-                                       *[_lib.ptr(t) for t in keep], _lib.ptr(ranges), _lib.ptr(thr),
-                                       _lib.ptr(gt_matched), _lib.ptr(dt_matched), _lib.ptr(dt_ignore), _lib.ptr(npig),
-                                       _lib.stream_ptr()), "pp_cocoeval_match")
+        keep = [room(b[k]) for k in ("gt_flags", "gt_area", "dt_area")]
+        _lib.launch("pp_cocoeval_match", b["n_img"], A, T, b["Dtot"], b["Gtot"], b["oks_total"], b["offs_host"],
+                    b["offs"], oks, *keep, ranges, thr, gt_matched, dt_matched, dt_ignore, npig)
         b["_keep_match"] = (keep, ranges, thr)
         return gt_matched, dt_matched, dt_ignore, npig
 
     def _accumulate(self, b, dt_matched, dt_ignore, npig) -> torch.Tensor:
-        L = _lib.lib()
         A, T, R = self.area_ranges.shape[0], self.oks_thresholds.size, self.recall_thresholds.size
-        order = self._room(torch.sort(b["dt_score"], descending=True, stable=True).indices)
-        rec = self._constant(b, self.recall_thresholds)
+        order = room(torch.sort(b["dt_score"], descending=True, stable=True).indices)
+        rec = upload(self.recall_thresholds, "cuda", b["staged"], torch.float64)
         ws_env = torch.empty(max(A * T * b["Dtot"], 1), dtype=torch.float64, device="cuda")
         ws_tp = torch.empty(max(A * T * b["Dtot"], 1), dtype=torch.int32, device="cuda")
         out = torch.empty(T * R * A + T * A, dtype=torch.float64, device="cuda")
         precision, recall = out[:T * R * A], out[T * R * A:]
-        _lib.check(L.pp_cocoeval_accumulate(b["Dtot"], A, T, R, _lib.ptr(order), _lib.ptr(dt_matched),
-                                            _lib.ptr(dt_ignore), _lib.ptr(npig), _lib.ptr(rec), _lib.ptr(ws_env),
-                                            _lib.ptr(ws_tp), _lib.ptr(precision), _lib.ptr(recall),
-                                            _lib.stream_ptr()), "pp_cocoeval_accumulate")
+        _lib.launch("pp_cocoeval_accumulate", b["Dtot"], A, T, R, order, dt_matched, dt_ignore, npig, rec, ws_env,
+                    ws_tp, precision, recall)
         b["_keep_acc"] = (order, rec, ws_env, ws_tp)
         return out
 

@@ -97,9 +97,7 @@ class ProbMap:
         heat = torch.empty((B, K, H, W), dtype=torch.float32, device=dev)
         wts = torch.empty((B, K), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            rc = _lib.lib().pp_encode_probmaps(_lib.ptr(kpts_hm), _lib.ptr(visible), _lib.ptr(d_s), B, K, H, W,
-                                               _lib.ptr(heat), _lib.ptr(wts), _lib.stream_ptr())
-        _lib.check(rc, "pp_encode_probmaps")
+            _lib.launch("pp_encode_probmaps", kpts_hm, visible, d_s, B, K, H, W, heat, wts)
         return heat, wts
 
     def encode_device(self, keypoints, keypoints_visible=None):
@@ -170,10 +168,8 @@ class ArgMaxProbMap(ProbMap):
         scores = torch.empty((B, K), dtype=torch.float32, device=hm.device)
         locs = torch.empty((B, K, 2), dtype=torch.float32, device=hm.device)
         with torch.cuda.device(hm.device):
-            rc = _lib.lib().pp_dark_decode_f32(_lib.ptr(hm), B, K, H, W, taps.ctypes.data, taps.shape[0],
-                                               float(self.input_size[0]), float(self.input_size[1]), _lib.ptr(kpts),
-                                               _lib.ptr(scores), _lib.ptr(locs), _lib.stream_ptr())
-        _lib.check(rc, "pp_dark_decode_f32")
+            _lib.launch("pp_dark_decode_f32", hm, B, K, H, W, taps, taps.shape[0], float(self.input_size[0]),
+                        float(self.input_size[1]), kpts, scores, locs)
         out = dict(kpts=kpts, scores=scores, locs=locs)
         if aux is not None:       # Codec.decode's pass-through of the four scalar heads (codec.py:254-261)
             a = [t.reshape(B, K).float() for t in aux]

@@ -21,7 +21,6 @@ one and two by ``pp_augment_warp`` (bilinear) and ``pp_dataset_ground_truth_affi
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 from dataclasses import dataclass
 from pathlib import Path
@@ -33,6 +32,7 @@ import torch
 from torch.utils.data import DataLoader, Dataset, get_worker_info
 
 from . import _lib, frontend
+from ._buffers import PinnedStaging
 from .flip import pair_permutation
 
 _REGION_ALIGN = 16          # byte alignment of a region in the packed buffer (a multiple of frontend.SRC_ALIGN)
@@ -212,12 +212,12 @@ class YOLOPoseDataset(Dataset):
         self.augment = augment
         self.epoch = 0
         self.annotations = parse_annotations(Path(root) / split, target_single_class)
-        self._staging = []           # [(pinned host buffer, event after its last copy)]
+        self._staging = PinnedStaging()
         self._perm = None            # (K, device, host int32 [K], device int32 [K]) of the flip permutation
 
     def __getstate__(self):          # workers started by spawn get a copy: without the pinned buffers and their events
         state = dict(self.__dict__)
-        state["_staging"] = []
+        state["_staging"] = PinnedStaging()
         state["_perm"] = None
         return state
 
@@ -256,16 +256,6 @@ class YOLOPoseDataset(Dataset):
         return np.ascontiguousarray(region), np.array(ann["keypoints"], dtype=np.float32).reshape(-1, 3), bbox
 
     # ---- batch assembly on the device --------------------------------------------------------------------------
-    def _staging_buffer(self, nbytes: int):
-        """A pinned host buffer that no earlier asynchronous copy can still be reading: one whose event has completed,
-        or a new one.  Never waits."""
-        for slot in self._staging:
-            if slot[0].numel() >= nbytes and slot[1].query():
-                return slot
-        slot = [torch.empty(max(nbytes, 4096), dtype=torch.uint8, pin_memory=True), torch.cuda.Event()]
-        self._staging.append(slot)
-        return slot
-
     def collate(self, samples):
         """``collate_fn`` of the loader: samples of ``__getitem__`` -> (img (B, 3, h, w) f32 in [0, 1], gt dict of
         heatmaps (B, K, H, W) f32, in_image / keypoints_visible (B, 1, K) bool, keypoints_visibility (B, 1, K) f32) on
@@ -291,31 +281,41 @@ class YOLOPoseDataset(Dataset):
             return self._launch_augmented(*self._upload_augmented(samples))
         return self._launch(*self._upload(samples))
 
-    def _upload(self, samples):
-        """Host half of ``collate``: pack, build the plan, issue the two copies.  Returns what ``_launch`` takes."""
+    def _pack(self, samples, fields):
+        """What both uploads start with: check the samples (tuples of ``fields`` entries), pack the regions back to
+        back and issue copy 1, the pixels.  Returns (B, K, shapes, offs, total, d_src)."""
         _lib.require_device()
         B = len(samples)
         if B == 0:
             raise ValueError("YOLOPoseDataset.collate: an empty batch")
-        pm = self.codec.probmap
-        in_w, in_h = int(pm.input_size[0]), int(pm.input_size[1])
         K = int(samples[0][1].shape[0])
-        for region, kps, _ in samples:
+        for s in samples:
+            region, kps = s[0], s[1]
+            if len(s) != fields:
+                raise ValueError("YOLOPoseDataset.collate: augmented and un-augmented samples in one batch")
             if region.dtype != np.uint8 or region.ndim != 3 or region.shape[2] != 3 or region.size == 0:
                 raise ValueError(f"YOLOPoseDataset.collate: a region of shape {region.shape}, dtype {region.dtype}")
             if kps.shape != (K, 3):
                 raise ValueError(f"YOLOPoseDataset.collate: keypoints of shapes {(K, 3)} and {kps.shape} in one batch")
-        dev = torch.device("cuda", torch.cuda.current_device())
         shapes = [s[0].shape[:2] for s in samples]
         offs, total = self.pack_layout(shapes)
-        # copy 1: the pixels
-        slot = self._staging_buffer(total)
+        slot = self._staging.take(total)
         host = slot[0].numpy()
-        for (region, _, _), off in zip(samples, offs):
-            host[off:off + region.size] = region.reshape(-1)
-        d_src = torch.empty(total, dtype=torch.uint8, device=dev)
+        for s, off in zip(samples, offs):
+            host[off:off + s[0].size] = s[0].reshape(-1)
+        d_src = torch.empty(total, dtype=torch.uint8, device=torch.device("cuda", torch.cuda.current_device()))
         d_src.copy_(slot[0][:total], non_blocking=True)
         slot[1].record()
+        return B, K, shapes, offs, total, d_src
+
+    def _input_size(self):
+        pm = self.codec.probmap
+        return int(pm.input_size[0]), int(pm.input_size[1])
+
+    def _upload(self, samples):
+        """Host half of ``collate``: pack, build the plan, issue the two copies.  Returns what ``_launch`` takes."""
+        B, K, shapes, offs, total, d_src = self._pack(samples, 3)
+        in_w, in_h = self._input_size()
         # copy 2: the plan, then the boxes (f64) and the raw keypoints (f32); built while copy 1 runs
         boxes = np.array([[0, 0, w, h] for h, w in shapes], dtype=np.int32)
         sources = np.array([[off, w, h, 3 * w] for off, (h, w) in zip(offs, shapes)], dtype=np.int64)
@@ -323,38 +323,37 @@ class YOLOPoseDataset(Dataset):
         box_off = -(-plan_bytes // 8) * 8
         kp_off = box_off + 32 * B
         meta_bytes = kp_off + 12 * B * K
-        slot = self._staging_buffer(meta_bytes)
+        slot = self._staging.take(meta_bytes)
         n_blocks, lds = frontend.multi_plan_build(boxes, sources, total, (in_w, in_h), slot[0].data_ptr())
         host = slot[0].numpy()
         host[box_off:kp_off].view(np.float64).reshape(B, 4)[:] = [s[2] for s in samples]
         host[kp_off:meta_bytes].view(np.float32).reshape(B, K, 3)[:] = [s[1] for s in samples]
-        d_meta = torch.empty(meta_bytes, dtype=torch.uint8, device=dev)
+        d_meta = torch.empty(meta_bytes, dtype=torch.uint8, device=d_src.device)
         d_meta.copy_(slot[0][:meta_bytes], non_blocking=True)
         slot[1].record()
         return d_src, d_meta, B, K, n_blocks, lds, box_off, kp_off
 
-    def _launch(self, d_src, d_meta, B, K, n_blocks, lds, box_off, kp_off):
-        """Device half of ``collate``: the three launches on the uploaded buffers."""
+    def _ground_truth(self, img, B, K, entry, *args):
+        """What both launches end with: the keypoint kernel ``entry(*args, B, K, input size, scale, outputs)``, then
+        the maps.  Returns collate's (img, gt dict)."""
         pm = self.codec.probmap
-        in_w, in_h = int(pm.input_size[0]), int(pm.input_size[1])
-        dev = d_src.device
-        # launch 1: crops
-        img = frontend.crop_resize_multi(d_src, d_meta, B, n_blocks, lds, (in_w, in_h))
-        # launch 2: keypoints and flags
+        dev = img.device
         f32 = torch.empty((6, B, K), dtype=torch.float32, device=dev)    # crop xy (2), heatmap xy (2), encode vis, visibility
         flags = torch.empty((2, B, 1, K), dtype=torch.bool, device=dev)  # in_image, keypoints_visible
         kp_crop, kp_hm = f32[0:2].view(B, K, 2), f32[2:4].view(B, K, 2)
         sx, sy = (float(v) for v in np.asarray(pm.scale_factor, dtype=np.float32))
         with torch.cuda.device(dev):
-            rc = _lib.lib().pp_dataset_ground_truth(d_meta.data_ptr() + kp_off, d_meta.data_ptr() + box_off, B, K,
-                                                    in_w, in_h, sx, sy, _lib.ptr(kp_crop), _lib.ptr(kp_hm),
-                                                    _lib.ptr(f32[4]), _lib.ptr(flags[0]), _lib.ptr(flags[1]),
-                                                    _lib.ptr(f32[5]), _lib.stream_ptr())
-        _lib.check(rc, "pp_dataset_ground_truth")
-        # launch 3: the maps
+            _lib.launch(entry, *args, B, K, *self._input_size(), sx, sy, kp_crop, kp_hm, f32[4], flags[0], flags[1],
+                        f32[5])
         heat, _ = pm.encode_device_tensors(kp_hm, f32[4])
         return img, dict(heatmaps=heat, in_image=flags[0], keypoints_visible=flags[1],
                          keypoints_visibility=f32[5].view(B, 1, K))
+
+    def _launch(self, d_src, d_meta, B, K, n_blocks, lds, box_off, kp_off):
+        """Device half of ``collate``: the three launches on the uploaded buffers (crops; keypoints and flags; maps)."""
+        img = frontend.crop_resize_multi(d_src, d_meta, B, n_blocks, lds, self._input_size())
+        meta = d_meta.data_ptr()
+        return self._ground_truth(img, B, K, "pp_dataset_ground_truth", meta + kp_off, meta + box_off)
 
     # ---- the augmented batch: the same two copies, then warp, keypoints, maps ---------------------------------------
     def _permutation(self, K, dev):
@@ -370,37 +369,15 @@ class YOLOPoseDataset(Dataset):
         _lib.require_device()
         if self.augment is None:
             raise ValueError("YOLOPoseDataset.collate: augmented samples, but the dataset has augment=None")
-        B = len(samples)
-        pm = self.codec.probmap
-        in_w, in_h = int(pm.input_size[0]), int(pm.input_size[1])
-        K = int(samples[0][1].shape[0])
-        for s in samples:
-            region, kps = s[0], s[1]
-            if len(s) != 5:
-                raise ValueError("YOLOPoseDataset.collate: augmented and un-augmented samples in one batch")
-            if region.dtype != np.uint8 or region.ndim != 3 or region.shape[2] != 3 or region.size == 0:
-                raise ValueError(f"YOLOPoseDataset.collate: a region of shape {region.shape}, dtype {region.dtype}")
-            if kps.shape != (K, 3):
-                raise ValueError(f"YOLOPoseDataset.collate: keypoints of shapes {(K, 3)} and {kps.shape} in one batch")
-        dev = torch.device("cuda", torch.cuda.current_device())
-        perm, d_perm = self._permutation(K, dev)
-        shapes = [s[0].shape[:2] for s in samples]
-        offs, total = self.pack_layout(shapes)
-        # copy 1: the pixels
-        slot = self._staging_buffer(total)
-        host = slot[0].numpy()
-        for s, off in zip(samples, offs):
-            host[off:off + s[0].size] = s[0].reshape(-1)
-        d_src = torch.empty(total, dtype=torch.uint8, device=dev)
-        d_src.copy_(slot[0][:total], non_blocking=True)
-        slot[1].record()
+        B, K, shapes, offs, total, d_src = self._pack(samples, 5)
+        perm, d_perm = self._permutation(K, d_src.device)
         # copy 2: [B x 4 i64 source records][B x 8 f64 pixel matrix, c, b][B x 8 f32 keypoint matrix, flip, 0][keypoints]
         params = np.stack([s[4] for s in samples])
         pixel, keypoint = augment_matrices(np.stack([s[2] for s in samples]), np.stack([s[3] for s in samples]),
-                                           params, (in_w, in_h))
+                                           params, self._input_size())
         warp_off, aff_off, kp_off = 32 * B, 96 * B, 128 * B
         meta_bytes = kp_off + 12 * B * K
-        slot = self._staging_buffer(meta_bytes)
+        slot = self._staging.take(meta_bytes)
         host = slot[0].numpy()
         host[:warp_off].view(np.int64).reshape(B, 4)[:] = [[off, w, h, 3 * w] for off, (h, w) in zip(offs, shapes)]
         warp = host[warp_off:aff_off].view(np.float64).reshape(B, 8)
@@ -409,37 +386,20 @@ class YOLOPoseDataset(Dataset):
         aff[:, :6], aff[:, 6], aff[:, 7] = keypoint.reshape(B, 6), params[:, 0], 0.0
         host[kp_off:meta_bytes].view(np.float32).reshape(B, K, 3)[:] = [s[1] for s in samples]
         base = slot[0].data_ptr()
-        _lib.check(_lib.lib().pp_augment_check(B, C.c_void_p(base), total, C.c_void_p(base + warp_off),
-                                               C.c_void_p(base + aff_off), K, perm.ctypes.data_as(C.c_void_p)),
-                   "pp_augment_check")
-        d_meta = torch.empty(meta_bytes, dtype=torch.uint8, device=dev)
+        _lib.call("pp_augment_check", B, base, total, base + warp_off, base + aff_off, K, perm)
+        d_meta = torch.empty(meta_bytes, dtype=torch.uint8, device=d_src.device)
         d_meta.copy_(slot[0][:meta_bytes], non_blocking=True)
         slot[1].record()
         return d_src, d_meta, d_perm, B, K
 
     def _launch_augmented(self, d_src, d_meta, d_perm, B, K):
         """Device half of the augmented ``collate``: warp, keypoints and flags, maps."""
-        pm = self.codec.probmap
-        in_w, in_h = int(pm.input_size[0]), int(pm.input_size[1])
-        dev = d_src.device
-        L, meta = _lib.lib(), d_meta.data_ptr()
-        img = torch.empty((B, 3, in_h, in_w), dtype=torch.float32, device=dev)
-        f32 = torch.empty((6, B, K), dtype=torch.float32, device=dev)    # as _launch
-        flags = torch.empty((2, B, 1, K), dtype=torch.bool, device=dev)
-        kp_crop, kp_hm = f32[0:2].view(B, K, 2), f32[2:4].view(B, K, 2)
-        sx, sy = (float(v) for v in np.asarray(pm.scale_factor, dtype=np.float32))
-        with torch.cuda.device(dev):
-            rc = L.pp_augment_warp(_lib.ptr(d_src), meta, meta + 32 * B, B, in_w, in_h, _lib.ptr(img),
-                                   _lib.stream_ptr())
-            _lib.check(rc, "pp_augment_warp")
-            rc = L.pp_dataset_ground_truth_affine(meta + 128 * B, meta + 96 * B, _lib.ptr(d_perm), B, K, in_w, in_h,
-                                                  sx, sy, _lib.ptr(kp_crop), _lib.ptr(kp_hm), _lib.ptr(f32[4]),
-                                                  _lib.ptr(flags[0]), _lib.ptr(flags[1]), _lib.ptr(f32[5]),
-                                                  _lib.stream_ptr())
-            _lib.check(rc, "pp_dataset_ground_truth_affine")
-        heat, _ = pm.encode_device_tensors(kp_hm, f32[4])
-        return img, dict(heatmaps=heat, in_image=flags[0], keypoints_visible=flags[1],
-                         keypoints_visibility=f32[5].view(B, 1, K))
+        in_w, in_h = self._input_size()
+        meta = d_meta.data_ptr()
+        img = torch.empty((B, 3, in_h, in_w), dtype=torch.float32, device=d_src.device)
+        with torch.cuda.device(d_src.device):
+            _lib.launch("pp_augment_warp", d_src, meta, meta + 32 * B, B, in_w, in_h, img)
+        return self._ground_truth(img, B, K, "pp_dataset_ground_truth_affine", meta + 128 * B, meta + 96 * B, d_perm)
 
     def loader(self, batch_size, shuffle=False, num_workers=0, **kw):
         """A DataLoader over this dataset whose batches are ``collate``'s.  The workers do file reading, decoding and

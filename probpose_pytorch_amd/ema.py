@@ -14,7 +14,6 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from collections import OrderedDict
 from copy import deepcopy
 from typing import Any, Dict, Optional, Sequence, Tuple
 
@@ -22,9 +21,9 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._buffers import CaptureCache
 
-_PLAN_CACHE_SIZE = 16
-_plans: "OrderedDict[tuple, _Plan]" = OrderedDict()
+_plans = CaptureCache(16)       # key -> _Plan: the device table and its pinned host copy live and die together
 
 
 class _Plan:
@@ -44,8 +43,7 @@ class _Plan:
             stream = torch.cuda.current_stream()
             if stream != self.stream:   # the upload was queued on another stream: wait for it on the device
                 stream.wait_event(self.uploaded)
-            _lib.check(_lib.lib().pp_ema_update(_lib.ptr(self.table), self.n_chunks, float(weight),
-                                                _lib.stream_ptr()), "pp_ema_update")
+            _lib.launch("pp_ema_update", self.table, self.n_chunks, float(weight))
 
 
 def _kind_of(t: torch.Tensor, what: str) -> int:
@@ -105,38 +103,31 @@ def _plan_for(dsts: Sequence[torch.Tensor], srcs: Sequence[torch.Tensor]) -> Tup
             continue
         seen.add(row)
         rows.append((*row, i))
-    key = (str(device), tuple(r[:4] for r in rows))
     written = [r[4] for r in rows]
-    plan = _plans.get(key)
-    if plan is not None:
-        _plans.move_to_end(key)
-        return plan, written
-    _check_disjoint([(s, d, nbytes, i) for s, d, nbytes, _, i in rows])
-    for d in dsts:
-        _lib.require_device(d)
+
+    def build():
+        _check_disjoint([(s, d, nbytes, i) for s, d, nbytes, _, i in rows])
+        for d in dsts:
+            _lib.require_device(d)
+        n = len(rows)
+        src = np.fromiter((r[0] for r in rows), dtype=np.uint64, count=n)
+        dst = np.fromiter((r[1] for r in rows), dtype=np.uint64, count=n)
+        counts = np.fromiter((r[2] // 4 for r in rows), dtype=np.int64, count=n)
+        kinds = np.fromiter((r[3] for r in rows), dtype=np.int32, count=n)
+        nbytes = int(_lib.call("pp_ema_table_bytes", n, counts))
+        with torch.cuda.device(device):
+            host = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+            n_chunks = C.c_int(0)
+            _lib.call("pp_ema_table_build", n, src, dst, counts, kinds, host, C.byref(n_chunks))
+            table = torch.empty(nbytes, dtype=torch.uint8, device=device)
+            table.copy_(host, non_blocking=True)
+            return _Plan(device, table, host, int(n_chunks.value))
+
     if not rows:                        # nothing but zero-element tensors
+        for d in dsts:
+            _lib.require_device(d)
         return None, written
-    n = len(rows)
-    L = _lib.lib()
-    src = np.fromiter((r[0] for r in rows), dtype=np.uint64, count=n)
-    dst = np.fromiter((r[1] for r in rows), dtype=np.uint64, count=n)
-    counts = np.fromiter((r[2] // 4 for r in rows), dtype=np.int64, count=n)
-    kinds = np.fromiter((r[3] for r in rows), dtype=np.int32, count=n)
-    nbytes = int(L.pp_ema_table_bytes(n, counts.ctypes.data))
-    if nbytes < 0:
-        _lib.check(1, "pp_ema_table_bytes")
-    with torch.cuda.device(device):
-        host = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
-        n_chunks = C.c_int(0)
-        _lib.check(L.pp_ema_table_build(n, src.ctypes.data, dst.ctypes.data, counts.ctypes.data, kinds.ctypes.data,
-                                        host.data_ptr(), C.byref(n_chunks)), "pp_ema_table_build")
-        table = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        table.copy_(host, non_blocking=True)
-        plan = _Plan(device, table, host, int(n_chunks.value))
-    _plans[key] = plan
-    while len(_plans) > _PLAN_CACHE_SIZE:
-        _plans.popitem(last=False)
-    return plan, written
+    return _plans.get((str(device), tuple(r[:4] for r in rows)), build), written
 
 
 def _run(plan: Optional[_Plan], written, dsts: Sequence[torch.Tensor], weight: float) -> None:

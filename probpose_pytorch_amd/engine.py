@@ -16,6 +16,7 @@ from typing import Dict, Optional, Sequence, Tuple
 import torch
 
 from . import _lib, ops, pack
+from ._buffers import CaptureCache
 from .ops import EPI_GELU, EPI_OUT_F32, EPI_RELU
 
 _PLANS: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()
@@ -65,27 +66,16 @@ def _dev(t: torch.Tensor, device, dtype=None):
 class _Workspace:
     """Named scratch tensors.  Every buffer is row-major [rows, ...]: one allocation per name serves every batch
     size up to the largest seen (smaller batches get the leading rows: contiguous views at a stable address, so
-    captured graphs stay valid).  A larger batch allocates a new buffer; the old one is kept alive (a graph captured
-    at the old size still points into it) but is no longer handed out."""
+    captured graphs stay valid).  A larger batch allocates a new buffer; the cache keeps the old one alive if a
+    captured graph points into it, but it is no longer handed out."""
 
     def __init__(self):
-        self._bufs: Dict[tuple, torch.Tensor] = {}
-        self._in_graph = set()        # keys handed out while a graph was being captured
-        self._retired = []
+        self._bufs = CaptureCache()
 
     def get(self, name: str, shape, dtype, device) -> torch.Tensor:
         shape = tuple(shape)
-        key = (name, shape[1:], dtype)
-        t = self._bufs.get(key)
-        capturing = torch.cuda.is_current_stream_capturing()
-        if t is None or t.shape[0] < shape[0]:
-            if t is not None and key in self._in_graph:
-                self._retired.append(t)      # a captured graph points into it; buffers no graph has seen are freed
-                self._in_graph.discard(key)
-            t = torch.empty(shape, dtype=dtype, device=device)
-            self._bufs[key] = t
-        if capturing:
-            self._in_graph.add(key)
+        t = self._bufs.get((name, shape[1:], dtype), lambda: torch.empty(shape, dtype=dtype, device=device),
+                           lambda t: t.shape[0] >= shape[0])
         return t[: shape[0]]
 
 
@@ -328,25 +318,15 @@ class HeadGeometry:
         for pool in list(head.probability_layers)[2:-2:4]:
             ks = pool.kernel_size
             self.pools.append((int(ks), int(ks)) if isinstance(ks, int) else (int(ks[0]), int(ks[1])))
-        self._tables: Dict[tuple, dict] = {}
+        self._tables = CaptureCache(8)      # batch sizes vary per frame in inference; captured entries stay
 
     # gather/scatter tables depend on (B, h, w) only
     def _tables_for(self, B: int, h: int, w: int) -> dict:
-        key = (B, h, w)
-        capturing = torch.cuda.is_current_stream_capturing()
-        t = self._tables.get(key)
-        if t is not None:
-            self._tables[key] = self._tables.pop(key)          # most recently used last
-            t["pinned"] = t["pinned"] or capturing
-            return t
-        # bounded: batch sizes vary per frame in inference.  The tables are device tensors whose ADDRESSES a captured
-        # graph has baked in, so an entry that was handed out during a capture is pinned and never evicted (a replay
-        # would otherwise gather through freed memory); only eager-only entries age out.
-        evictable = [k for k, v in self._tables.items() if not v["pinned"]]
-        while len(evictable) >= 8:
-            self._tables.pop(evictable.pop(0))
+        return self._tables.get((B, h, w), lambda: self._build_tables(B, h, w))
+
+    def _build_tables(self, B: int, h: int, w: int) -> dict:
         dev = self.device
-        t = dict(deconv=[], conv=[], aux=[], pinned=capturing)
+        t = dict(deconv=[], conv=[], aux=[])
         hh, ww = h, w
         for d in self.deconvs:
             ro, rm = pack.deconv_tables(B, hh, ww, d["k"], d["cin"])
@@ -368,7 +348,6 @@ class HeadGeometry:
             raise ValueError(
                 f"alt_head_kernel_sizes {self.pools} reduce a {h}x{w} feature map to {ah}x{aw}; the aux "
                 "branches must end at 1x1 (Codec.decode reshapes them to (B,1,K), reference codec.py:254-257)")
-        self._tables[key] = t
         return t
 
 

@@ -33,18 +33,13 @@ class FrontendPlan:
     """Host-built tables for one set of boxes and one output size (reusable across frames)."""
 
     def __init__(self, boxes_xyxy: np.ndarray, input_size: Sequence[int], device):
-        L = _lib.lib()
         self.boxes = np.ascontiguousarray(boxes_xyxy, dtype=np.int32).reshape(-1, 4)
         self.n = int(self.boxes.shape[0])
         self.out_w, self.out_h = int(input_size[0]), int(input_size[1])
-        bp = self.boxes.ctypes.data_as(C.c_void_p)
-        nbytes = L.pp_frontend_plan_bytes(self.n, bp, self.out_w, self.out_h)
-        if nbytes < 0:
-            _lib.check(-1, "pp_frontend_plan_bytes")
+        nbytes = _lib.call("pp_frontend_plan_bytes", self.n, self.boxes, self.out_w, self.out_h)
         host = np.empty((max(int(nbytes), 4) // 4,), dtype=np.int32)
         nb, lds = C.c_int(0), C.c_longlong(0)
-        _lib.check(L.pp_frontend_plan_build(self.n, bp, self.out_w, self.out_h, host.ctypes.data_as(C.c_void_p),
-                                            C.byref(nb), C.byref(lds)), "pp_frontend_plan_build")
+        _lib.call("pp_frontend_plan_build", self.n, self.boxes, self.out_w, self.out_h, host, C.byref(nb), C.byref(lds))
         self.host = host
         self.n_blocks, self.lds_bytes = int(nb.value), int(lds.value)
         self.dev = torch.from_numpy(host).to(device) if device is not None else None
@@ -65,11 +60,8 @@ def crop_resize(image: torch.Tensor, boxes_xywh, input_size: Sequence[int], plan
     if plan.n == 0:
         return out
     with torch.cuda.device(image.device):
-        rc = _lib.lib().pp_frontend_crop_resize(_lib.ptr(image), int(image.shape[1]), int(image.shape[0]),
-                                                int(image.stride(0)), _lib.ptr(plan.dev), plan.n, plan.n_blocks,
-                                                plan.lds_bytes, plan.out_w, plan.out_h, _lib.ptr(out),
-                                                _lib.stream_ptr())
-    _lib.check(rc, "pp_frontend_crop_resize")
+        _lib.launch("pp_frontend_crop_resize", image, int(image.shape[1]), int(image.shape[0]), int(image.stride(0)),
+                    plan.dev, plan.n, plan.n_blocks, plan.lds_bytes, plan.out_w, plan.out_h, out)
     return out
 
 
@@ -79,11 +71,8 @@ SRC_ALIGN, SRC_PAD = 4, 4     # PP_FRONTEND_SRC_ALIGN / PP_FRONTEND_SRC_PAD of i
 def multi_plan_bytes(boxes_xyxy: np.ndarray, input_size: Sequence[int]) -> int:
     """Bytes of the multi-source plan for these integer boxes (host only)."""
     boxes = np.ascontiguousarray(boxes_xyxy, dtype=np.int32).reshape(-1, 4)
-    nbytes = _lib.lib().pp_frontend_multi_plan_bytes(int(boxes.shape[0]), boxes.ctypes.data_as(C.c_void_p),
-                                                     int(input_size[0]), int(input_size[1]))
-    if nbytes < 0:
-        _lib.check(-1, "pp_frontend_multi_plan_bytes")
-    return int(nbytes)
+    return int(_lib.call("pp_frontend_multi_plan_bytes", int(boxes.shape[0]), boxes, int(input_size[0]),
+                         int(input_size[1])))
 
 
 def multi_plan_build(boxes_xyxy: np.ndarray, sources: np.ndarray, src_bytes: int, input_size: Sequence[int],
@@ -98,10 +87,8 @@ def multi_plan_build(boxes_xyxy: np.ndarray, sources: np.ndarray, src_bytes: int
     if src.shape[0] != boxes.shape[0]:
         raise ValueError(f"{boxes.shape[0]} boxes but {src.shape[0]} source records")
     nb, lds = C.c_int(0), C.c_longlong(0)
-    _lib.check(_lib.lib().pp_frontend_multi_plan_build(int(boxes.shape[0]), boxes.ctypes.data_as(C.c_void_p),
-                                                       src.ctypes.data_as(C.c_void_p), int(src_bytes),
-                                                       int(input_size[0]), int(input_size[1]), C.c_void_p(plan_ptr),
-                                                       C.byref(nb), C.byref(lds)), "pp_frontend_multi_plan_build")
+    _lib.call("pp_frontend_multi_plan_build", int(boxes.shape[0]), boxes, src, int(src_bytes), int(input_size[0]),
+              int(input_size[1]), plan_ptr, C.byref(nb), C.byref(lds))
     return int(nb.value), int(lds.value)
 
 
@@ -119,9 +106,7 @@ def crop_resize_multi(src: torch.Tensor, plan_dev: torch.Tensor, n: int, n_block
     if n == 0:
         return out
     with torch.cuda.device(src.device):
-        rc = _lib.lib().pp_frontend_crop_resize_multi(_lib.ptr(src), _lib.ptr(plan_dev), n, n_blocks, lds_bytes,
-                                                      out_w, out_h, _lib.ptr(out), _lib.stream_ptr())
-    _lib.check(rc, "pp_frontend_crop_resize_multi")
+        _lib.launch("pp_frontend_crop_resize_multi", src, plan_dev, n, n_blocks, lds_bytes, out_w, out_h, out)
     return out
 
 

@@ -10,8 +10,9 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._buffers import CaptureCache
 
-_TAP_CACHE: dict = {}
+_TAP_CACHE = CaptureCache(64)
 
 
 def oks_tap_table(K: int, H: int, W: int, sigmas) -> tuple[np.ndarray, np.ndarray]:
@@ -43,15 +44,12 @@ def oks_tap_table(K: int, H: int, W: int, sigmas) -> tuple[np.ndarray, np.ndarra
 
 def _device_taps(K, H, W, sigmas, device):
     sig = np.asarray(sigmas)
-    key = (K, H, W, sig.dtype.str, sig.tobytes(), str(device))
-    hit = _TAP_CACHE.get(key)
-    if hit is None:
+
+    def make():
         taps, radius = oks_tap_table(K, H, W, sig)
-        hit = (torch.from_numpy(taps).to(device), torch.from_numpy(radius).to(device))
-        if len(_TAP_CACHE) > 64:
-            _TAP_CACHE.clear()
-        _TAP_CACHE[key] = hit
-    return hit
+        return torch.from_numpy(taps).to(device), torch.from_numpy(radius).to(device)
+
+    return _TAP_CACHE.get((K, H, W, sig.dtype.str, sig.tobytes(), str(device)), make)
 
 
 # which implementation pp_decode_f32 runs: 0 = the default per map size; _lib.DECODE_* force another one (A/B tools and
@@ -60,20 +58,15 @@ DECODE_FLAGS = 0
 
 # zeroed hand-over lists of the wave-per-map path, one per (device, stream): allocated and zeroed once, every call
 # leaves their counters zeroed (include/probpose_hip.h), the address stays stable for graph replay
-_DECODE_WS: dict = {}
+_DECODE_WS = CaptureCache(16)
 
 
 def _decode_workspace(nbytes: int, dev):
     if nbytes <= 0:
         return None
-    key = (str(dev), int(torch.cuda.current_stream(dev).cuda_stream))
-    t = _DECODE_WS.get(key)
-    if t is None or t.numel() < nbytes:
-        if len(_DECODE_WS) > 16:
-            _DECODE_WS.clear()
-        t = torch.zeros((max(nbytes, 1 << 16),), dtype=torch.uint8, device=dev)
-        _DECODE_WS[key] = t
-    return t
+    return _DECODE_WS.get((str(dev), int(torch.cuda.current_stream(dev).cuda_stream)),
+                          lambda: torch.zeros((max(nbytes, 1 << 16),), dtype=torch.uint8, device=dev),
+                          lambda t: t.numel() >= nbytes)
 
 
 def decode_on_device(heatmaps: torch.Tensor, sigmas, *, den=None, input_size=None,
@@ -86,7 +79,6 @@ def decode_on_device(heatmaps: torch.Tensor, sigmas, *, den=None, input_size=Non
     with ``want_conv`` the convolved maps (B,K,H,W) f32.
     """
     _lib.require_device(heatmaps)
-    L = _lib.lib()
     if heatmaps.dtype != torch.float32:
         heatmaps = heatmaps.float()
     heatmaps = heatmaps.contiguous()
@@ -115,20 +107,16 @@ def decode_on_device(heatmaps: torch.Tensor, sigmas, *, den=None, input_size=Non
             out["packed"] = torch.empty((B, K, 7), dtype=torch.float64, device=dev)
     if want_conv:
         out["conv"] = torch.empty_like(heatmaps)
-    ws_bytes = L.pp_decode_workspace_bytes(B, K, H, W)
+    ws_bytes = _lib.call("pp_decode_workspace_bytes", B, K, H, W)
     if (H, W) in ((64, 48), (96, 72)):
         ws = _decode_workspace(ws_bytes, dev)                # the self-resetting hand-over list: zeroed once, kept
     else:
         ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev) if ws_bytes else None
     from . import ops as _ops
     with torch.cuda.device(dev):
-        rc = _ops._timed("decode", float(B * K * (H * W * 4 + 16 + 28)), lambda: L.pp_decode_f32(
-            _lib.ptr(heatmaps), _lib.ptr(a[0]), _lib.ptr(a[1]), _lib.ptr(a[2]), _lib.ptr(a[3]),
-            B, K, H, W, _lib.ptr(taps), _lib.ptr(radius), den_x, den_y, in_w, in_h,
-            _lib.ptr(out.get("kpts")), _lib.ptr(out["scores"]), _lib.ptr(out["locs"]),
-            _lib.ptr(out.get("aux")), _lib.ptr(out.get("err")), _lib.ptr(out.get("conv")),
-            _lib.ptr(out.get("packed")), _lib.ptr(ws), int(DECODE_FLAGS), _lib.stream_ptr()))
-    _lib.check(rc, "pp_decode_f32")
+        _ops._run("decode", float(B * K * (H * W * 4 + 16 + 28)), "pp_decode_f32", heatmaps, *a, B, K, H, W, taps,
+                  radius, den_x, den_y, in_w, in_h, out.get("kpts"), out["scores"], out["locs"], out.get("aux"),
+                  out.get("err"), out.get("conv"), out.get("packed"), ws, int(DECODE_FLAGS))
     return out
 
 

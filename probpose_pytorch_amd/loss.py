@@ -94,12 +94,9 @@ def _oks_heatmap_loss(output, target, weights, mask, skip_empty, oks_type, sw, g
     parts = torch.empty((B * K * 5,), dtype=torch.float32, device=dev)
     ow = 1.0 - sw - gw
     with torch.cuda.device(dev):
-        rc = _lib.lib().pp_oks_heatmap_loss(
-            _lib.ptr(output), _lib.ptr(target), _lib.ptr(weights), per_pixel_weights, _lib.ptr(mask), mask_sb,
-            mask_sk, int(bool(skip_empty)), _OKS_TYPES[oks_type], float(sw), float(ow), float(gw), float(lw),
-            B, K, H, W, _lib.ptr(per_pixel_out), _lib.ptr(per_keypoint_out), _lib.ptr(parts), _lib.ptr(scalars),
-            _lib.stream_ptr())
-    _lib.check(rc, "pp_oks_heatmap_loss")
+        _lib.launch("pp_oks_heatmap_loss", output, target, weights, per_pixel_weights, mask, mask_sb, mask_sk,
+                    int(bool(skip_empty)), _OKS_TYPES[oks_type], float(sw), float(ow), float(gw), float(lw),
+                    B, K, H, W, per_pixel_out, per_keypoint_out, parts, scalars)
     return parts
 
 
@@ -121,12 +118,10 @@ def _oks_heatmap_loss_backward(output, target, weights, mask, skip_empty, oks_ty
         strides[:grad.ndim] = grad.stride()
     grad_output = torch.empty((B, K, H, W), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        rc = _lib.lib().pp_oks_heatmap_loss_backward(
-            _lib.ptr(output), _lib.ptr(target), _lib.ptr(weights), int(weights is not None and weights.ndim == 4),
-            _lib.ptr(mask), mask_sb, mask_sk, int(bool(skip_empty)), _OKS_TYPES[oks_type], float(sw),
-            float(1.0 - sw - gw), float(gw), float(lw), reduction, _lib.ptr(grad), *strides, B, K, H, W,
-            _lib.ptr(grad_output), _lib.stream_ptr())
-    _lib.check(rc, "pp_oks_heatmap_loss_backward")
+        _lib.launch("pp_oks_heatmap_loss_backward", output, target, weights,
+                    int(weights is not None and weights.ndim == 4), mask, mask_sb, mask_sk, int(bool(skip_empty)),
+                    _OKS_TYPES[oks_type], float(sw), float(1.0 - sw - gw), float(gw), float(lw), reduction, grad,
+                    *strides, B, K, H, W, grad_output)
     return grad_output
 
 
@@ -386,11 +381,8 @@ class _ProbPoseLossFn(torch.autograd.Function):
             d = torch.empty((4, B * K), dtype=torch.float32, device=hm.device)
             u = [_upstream(g, ()).contiguous() for g in (g_prob, g_vis, g_oks, g_err)]
             with torch.cuda.device(hm.device):
-                rc = _lib.lib().pp_probpose_loss_grads(
-                    *[_lib.ptr(t) for t in (dt_prob, dt_vis, dt_oks, dt_err, gt_oks, gt_err, masks[0], masks[1],
-                                            masks[2], *u)], B, K, *[_lib.ptr(d[i]) for i in range(4)],
-                    _lib.stream_ptr())
-            _lib.check(rc, "pp_probpose_loss_grads")
+                _lib.launch("pp_probpose_loss_grads", dt_prob, dt_vis, dt_oks, dt_err, gt_oks, gt_err, *masks[:3], *u,
+                            B, K, *d)
             for i in range(4):
                 if need[1 + i]:
                     grads[1 + i] = _grad_as(d[i], ctx.like[1 + i])
@@ -473,12 +465,8 @@ class ProbPoseLoss(nn.Module):
         oks_area = (W * H) * 0.53 + np.spacing(1)    # bbox [0, 0, H, W] from heatmap_size=(W, H) (loss.py:395, :609-620)
         var = self._device_variance(C, dev)
         with torch.cuda.device(dev):
-            rc = _lib.lib().pp_probpose_loss_terms(
-                _lib.ptr(gt_kpts), _lib.ptr(dt_kpts), _lib.ptr(masks[0]), _lib.ptr(masks[1]), _lib.ptr(masks[2]),
-                *[_lib.ptr(t) for t in heads], _lib.ptr(var), float(oks_area), B, C, int(bool(self.freeze_error)),
-                _lib.ptr(gt_oks), _lib.ptr(gt_err), _lib.ptr(vis_weight), _lib.ptr(oks_weight), _lib.ptr(res[3:]),
-                _lib.stream_ptr())
-        _lib.check(rc, "pp_probpose_loss_terms")
+            _lib.launch("pp_probpose_loss_terms", gt_kpts, dt_kpts, *masks[:3], *heads, var, float(oks_area), B, C,
+                        int(bool(self.freeze_error)), gt_oks, gt_err, vis_weight, oks_weight, res[3:])
         return dict(hm=hm, gt_hm=gt_hm, kw=kw, heads=heads, gt_kpts=gt_kpts, dt_kpts=dt_kpts, gt_oks=gt_oks,
                     gt_err=gt_err, vis_weight=vis_weight, oks_weight=oks_weight, res=res, probs=probs,
                     annotated=annotated, vis=vis, masks=masks, heat_w=heat_weights)

@@ -46,8 +46,7 @@ def _argmax_device(heatmaps):
     t = t.to(device="cuda", dtype=torch.float32).contiguous()
     locs = torch.empty((B, K, 2), dtype=torch.float32, device="cuda")
     vals = torch.empty((B, K), dtype=torch.float32, device="cuda")
-    _lib.check(_lib.lib().pp_heatmap_argmax(_lib.ptr(t), B * K, H, W, _lib.ptr(locs), _lib.ptr(vals),
-                                            _lib.stream_ptr()), "pp_heatmap_argmax")
+    _lib.launch("pp_heatmap_argmax", t, B * K, H, W, locs, vals)
     return locs, vals, squeeze
 
 
@@ -83,9 +82,7 @@ def pck_counts(pred, gt, mask, thr, norm_factor, return_distances: bool = False)
     # goes back to the caching allocator and is handed to the next allocation before the kernel has run
     nf_dev = _as_device(nf64, torch.float64)
     skip_dev = _as_device(skip, torch.bool).view(torch.uint8)
-    _lib.check(_lib.lib().pp_pck_counts(_lib.ptr(p), _lib.ptr(g), 0 if is_f32 else 1, _lib.ptr(m), _lib.ptr(nf_dev),
-                                        _lib.ptr(skip_dev), thr_eff, N, K, _lib.ptr(counts), _lib.ptr(dist),
-                                        _lib.stream_ptr()), "pp_pck_counts")
+    _lib.launch("pp_pck_counts", p, g, 0 if is_f32 else 1, m, nf_dev, skip_dev, thr_eff, N, K, counts, dist)
     c = counts.cpu().numpy().astype(np.int64)
     del nf_dev, skip_dev
     return (c[0], c[1], dist.cpu().numpy()) if return_distances else (c[0], c[1])

@@ -39,6 +39,11 @@ def _timed(name, work, fn, info=""):
     return r
 
 
+def _run(label, work, name, *args, info=""):
+    """One launch of the library entry ``name`` on the current stream, under ``label`` in the profile."""
+    return _timed(label, work, lambda: _lib.launch(name, *args), info)
+
+
 def dtype_code(dt: torch.dtype) -> int:
     try:
         return _DT[dt]
@@ -170,10 +175,8 @@ def gemm(A, W, out, *, M, N, Kd, lda, ldw, ldc, bias=None, residual=None, rowbia
             best = _tune(a, key, out, residual)
         if best:
             a.tile = best
-    rc = _timed("gemm", 2.0 * M * N * Kd * batch * max(1, splitk),
-                lambda: _lib.lib().pp_gemm(C.byref(a), _lib.stream_ptr()),
-                f"M={M} N={N} K={Kd} batch={batch} splitk={splitk} gather={rowoff is not None} epi={epilogue}")
-    _lib.check(rc, "pp_gemm")
+    _run("gemm", 2.0 * M * N * Kd * batch * max(1, splitk), "pp_gemm", C.byref(a),
+         info=f"M={M} N={N} K={Kd} batch={batch} splitk={splitk} gather={rowoff is not None} epi={epilogue}")
     return out
 
 
@@ -203,93 +206,70 @@ def quantize_rows_fp8(w: torch.Tensor):
 def layernorm(x, gamma, beta, eps, out, out_scale=None):
     rows, Cc = x.shape
     if out.dtype == FP8:     # static per-tensor scale: out = e4m3(LN(x) / out_scale)
-        rc = _timed("layernorm", float(rows * Cc * 5),
-                    lambda: _lib.lib().pp_layernorm_fp8(_p(x), _p(gamma), _p(beta), float(eps), rows, Cc, _p(out),
-                                                        1.0 / float(out_scale), _lib.stream_ptr()))
-        _lib.check(rc, "pp_layernorm_fp8")
-        return out
-    rc = _timed("layernorm", float(rows * Cc * (4 + out.element_size())),
-                lambda: _lib.lib().pp_layernorm(_p(x), _p(gamma), _p(beta), float(eps), rows, Cc, _p(out),
-                                                dtype_code(out.dtype), _lib.stream_ptr()))
-    _lib.check(rc, "pp_layernorm")
+        _run("layernorm", float(rows * Cc * 5), "pp_layernorm_fp8", x, gamma, beta, float(eps), rows, Cc, out,
+             1.0 / float(out_scale))
+    else:
+        _run("layernorm", float(rows * Cc * (4 + out.element_size())), "pp_layernorm", x, gamma, beta, float(eps),
+             rows, Cc, out, dtype_code(out.dtype))
     return out
 
 
 def attention(qkv, out, B, N, heads, hd, out_scale=None, headmajor=False):
+    work = 4.0 * B * heads * N * N * hd
     if headmajor:            # qkv [3][heads][B*N][hd] as linear(..., headmajor=(heads, hd)) wrote it
-        rc = _timed("attention", 4.0 * B * heads * N * N * hd,
-                    lambda: _lib.lib().pp_attention_headmajor(_p(qkv), _p(out), B, N, heads, hd, _lib.stream_ptr()))
-        _lib.check(rc, "pp_attention_headmajor")
-        return out
-    if out.dtype == FP8:     # e4m3 output with a static per-tensor scale (fp8 mode)
-        rc = _timed("attention", 4.0 * B * heads * N * N * hd,
-                    lambda: _lib.lib().pp_attention_fp8out(_p(qkv), _p(out), B, N, heads, hd, 1.0 / float(out_scale),
-                                                           _lib.stream_ptr()))
-        _lib.check(rc, "pp_attention_fp8out")
-        return out
-    rc = _timed("attention", 4.0 * B * heads * N * N * hd,
-                lambda: _lib.lib().pp_attention(_p(qkv), _p(out), B, N, heads, hd, dtype_code(qkv.dtype),
-                                                _lib.stream_ptr()))
-    _lib.check(rc, "pp_attention")
+        _run("attention", work, "pp_attention_headmajor", qkv, out, B, N, heads, hd)
+    elif out.dtype == FP8:   # e4m3 output with a static per-tensor scale (fp8 mode)
+        _run("attention", work, "pp_attention_fp8out", qkv, out, B, N, heads, hd, 1.0 / float(out_scale))
+    else:
+        _run("attention", work, "pp_attention", qkv, out, B, N, heads, hd, dtype_code(qkv.dtype))
     return out
 
 
 def patchify(x, out, patch):
     B, _, H, W = x.shape
-    _lib.check(_lib.lib().pp_patchify(_p(x), _p(out), B, H, W, patch, dtype_code(out.dtype),
-                                      _lib.stream_ptr()), "pp_patchify")
+    _lib.launch("pp_patchify", x, out, B, H, W, patch, dtype_code(out.dtype))
     return out
 
 
 def maxpool_relu(x, out, B, h, w, Cc, kh, kw):
-    _lib.check(_lib.lib().pp_maxpool_relu(_p(x), _p(out), B, h, w, Cc, kh, kw, dtype_code(x.dtype),
-                                          _lib.stream_ptr()), "pp_maxpool_relu")
+    _lib.launch("pp_maxpool_relu", x, out, B, h, w, Cc, kh, kw, dtype_code(x.dtype))
     return out
 
 
 def maxpool_relu_sum(parts, bias, out, B, h, w, Cc, kh, kw):
     """parts [S, B*h*w, Cc] f32 split-K partials -> out = ReLU(MaxPool(sum_s parts[s] + bias))."""
-    S = parts.shape[0]
-    _lib.check(_lib.lib().pp_maxpool_relu_sum(_p(parts), S, parts.stride(0), _p(bias), _p(out), B, h, w, Cc, kh, kw,
-                                              dtype_code(out.dtype), _lib.stream_ptr()), "pp_maxpool_relu_sum")
+    _lib.launch("pp_maxpool_relu_sum", parts, parts.shape[0], parts.stride(0), bias, out, B, h, w, Cc, kh, kw,
+                dtype_code(out.dtype))
     return out
 
 
 def final_heatmap(x, w, bias, out, B, HW, Cin, K, temperature, clamp=True):
     """clamp=False: the unclamped logits z / T that the Sparsemax normalisation takes (head.py:526-528)."""
-    fn = _lib.lib().pp_final_heatmap if clamp else _lib.lib().pp_final_logits
-    rc = _timed("final_heatmap", float(B * HW * (Cin * x.element_size() + 4 * K)),
-                lambda: fn(_p(x), _p(w), _p(bias), _p(out), B, HW, Cin, K, float(temperature), dtype_code(w.dtype),
-                           _lib.stream_ptr()))
-    _lib.check(rc, "pp_final_heatmap" if clamp else "pp_final_logits")
+    _run("final_heatmap", float(B * HW * (Cin * x.element_size() + 4 * K)),
+         "pp_final_heatmap" if clamp else "pp_final_logits", x, w, bias, out, B, HW, Cin, K, float(temperature),
+         dtype_code(w.dtype))
     return out
 
 
 def sparsemax_rows(x, scale):
     """In place on x [..., n] f32 contiguous: clamp(sparsemax(x, dim=-1) * scale, 0, 1)  (head.py:528-531)."""
     n = x.shape[-1]
-    rows = x.numel() // n
-    rc = _timed("sparsemax", float(x.numel() * 8),
-                lambda: _lib.lib().pp_sparsemax_rows(_p(x), rows, n, float(scale), _lib.stream_ptr()))
-    _lib.check(rc, "pp_sparsemax_rows")
+    _run("sparsemax", float(x.numel() * 8), "pp_sparsemax_rows", x, x.numel() // n, n, float(scale))
     return x
 
 
 def aux_tail(x, w, bias, out, B, Cc, K):
-    _lib.check(_lib.lib().pp_aux_tail(_p(x), _p(w), _p(bias), _p(out), B, Cc, K, dtype_code(w.dtype),
-                                      _lib.stream_ptr()), "pp_aux_tail")
+    _lib.launch("pp_aux_tail", x, w, bias, out, B, Cc, K, dtype_code(w.dtype))
     return out
 
 
 def tokens_to_nchw(x, out, B, N, Cc):
-    _lib.check(_lib.lib().pp_tokens_to_nchw(_p(x), _p(out), B, N, Cc, dtype_code(x.dtype),
-                                            _lib.stream_ptr()), "pp_tokens_to_nchw")
+    _lib.launch("pp_tokens_to_nchw", x, out, B, N, Cc, dtype_code(x.dtype))
     return out
 
 
 def nchw_to_tokens(x, out, B, Cc, HW):
-    _lib.check(_lib.lib().pp_nchw_to_tokens(_p(x), _p(out), B, Cc, HW, dtype_code(out.dtype),
-                                            _lib.stream_ptr()), "pp_nchw_to_tokens")
+    _lib.launch("pp_nchw_to_tokens", x, out, B, Cc, HW, dtype_code(out.dtype))
     return out
 
 
@@ -297,9 +277,7 @@ def nchw_to_tokens(x, out, B, Cc, HW):
 def hflip_pair(x, out):
     """x [B,C,H,W] f32 -> out [2B,C,H,W] f32: the batch followed by its mirror image (columns reversed)."""
     B, Cc, H, W = x.shape
-    rc = _timed("hflip_pair", float(x.numel() * 12),
-                lambda: _lib.lib().pp_hflip_pair(_p(x), _p(out), B, Cc, H, W, _lib.stream_ptr()))
-    _lib.check(rc, "pp_hflip_pair")
+    _run("hflip_pair", float(x.numel() * 12), "pp_hflip_pair", x, out, B, Cc, H, W)
     return out
 
 
@@ -307,16 +285,14 @@ def flip_merge(heat2, aux2, perm, heat_out, aux_out):
     """heat2 [2B,K,H,W], aux2 [4,2B,K] f32, perm [K] int32 -> heat_out [B,K,H,W], aux_out [4,B,K]: the average of the
     straight half and the un-mirrored, left/right-swapped second half (pp_flip_merge in include/probpose_hip.h)."""
     B, K, H, W = heat_out.shape
-    rc = _timed("flip_merge", float((heat_out.numel() + aux_out.numel()) * 12),
-                lambda: _lib.lib().pp_flip_merge(_p(heat2), _p(aux2), _p(perm), B, K, H, W, _p(heat_out), _p(aux_out),
-                                                 _lib.stream_ptr()))
-    _lib.check(rc, "pp_flip_merge")
+    _run("flip_merge", float((heat_out.numel() + aux_out.numel()) * 12), "pp_flip_merge", heat2, aux2, perm, B, K, H,
+         W, heat_out, aux_out)
     return heat_out, aux_out
 
 
 # ---- training ProbMapHead (pp_head_grad.hip) ------------------------------------------------------------------
 def wgrad_workspace_floats(M, N, Kd, batch=1) -> int:
-    return int(_lib.lib().pp_wgrad_workspace_floats(M, N, Kd, batch))
+    return int(_lib.call("pp_wgrad_workspace_floats", M, N, Kd, batch))
 
 
 def wgrad(dY, A, dW, *, M, N, Kd, ldd, lda=0, rowoff=None, seg_len=0, dy_rowmap=None, dB=None, batch=1, lddw=None,
@@ -335,38 +311,28 @@ def wgrad(dY, A, dW, *, M, N, Kd, ldd, lda=0, rowoff=None, seg_len=0, dy_rowmap=
     need = wgrad_workspace_floats(M, N, Kd, batch)
     if need and (parts is None or parts.numel() < need or parts.dtype != torch.float32):
         raise ValueError(f"wgrad: this shape needs a float32 parts workspace of {need} elements")
-    rc = _timed("wgrad", 2.0 * M * N * Kd * batch, lambda: _lib.lib().pp_wgrad_gemm(C.byref(a), _lib.stream_ptr()),
-                f"M={M} N={N} K={Kd} batch={batch}")
-    _lib.check(rc, "pp_wgrad_gemm")
+    _run("wgrad", 2.0 * M * N * Kd * batch, "pp_wgrad_gemm", C.byref(a), info=f"M={M} N={N} K={Kd} batch={batch}")
     return dW
 
 
 def bn_workspace_bytes(M, Cc) -> int:
-    return int(_lib.lib().pp_bn_workspace_bytes(M, Cc))
+    return int(_lib.call("pp_bn_workspace_bytes", M, Cc))
 
 
 def bn_train_stats(y, M, Cc, gamma, beta, eps, momentum, running_mean, running_var, mean, rstd, scale, shift, ws):
-    rc = _timed("bn_stats", float(M * Cc * 4),
-                lambda: _lib.lib().pp_bn_train_stats(_p(y), y.stride(0), M, Cc, _p(gamma), _p(beta), float(eps),
-                                                     float(momentum), _p(running_mean), _p(running_var), _p(mean),
-                                                     _p(rstd), _p(scale), _p(shift), _p(ws), _lib.stream_ptr()))
-    _lib.check(rc, "pp_bn_train_stats")
+    _run("bn_stats", float(M * Cc * 4), "pp_bn_train_stats", y, y.stride(0), M, Cc, gamma, beta, float(eps),
+         float(momentum), running_mean, running_var, mean, rstd, scale, shift, ws)
 
 
 def bn_apply_relu(y, M, Cc, scale, shift, out, relu=True):
-    rc = _timed("bn_apply", float(M * Cc * (4 + out.element_size())),
-                lambda: _lib.lib().pp_bn_apply_relu(_p(y), y.stride(0), M, Cc, _p(scale), _p(shift), _p(out),
-                                                    out.stride(0), int(relu), dtype_code(out.dtype),
-                                                    _lib.stream_ptr()))
-    _lib.check(rc, "pp_bn_apply_relu")
+    _run("bn_apply", float(M * Cc * (4 + out.element_size())), "pp_bn_apply_relu", y, y.stride(0), M, Cc, scale, shift,
+         out, out.stride(0), int(relu), dtype_code(out.dtype))
     return out
 
 
 def bn_pool_relu(y, B, h, w, Cc, kh, kw, scale, shift, out, argmax):
-    rc = _timed("bn_pool", float(B * h * w * Cc * 4),
-                lambda: _lib.lib().pp_bn_pool_relu(_p(y), B, h, w, Cc, kh, kw, _p(scale), _p(shift), _p(out),
-                                                   _p(argmax), dtype_code(out.dtype), _lib.stream_ptr()))
-    _lib.check(rc, "pp_bn_pool_relu")
+    _run("bn_pool", float(B * h * w * Cc * 4), "pp_bn_pool_relu", y, B, h, w, Cc, kh, kw, scale, shift, out, argmax,
+         dtype_code(out.dtype))
     return out
 
 
@@ -374,36 +340,24 @@ def bn_train_backward(g, y, M, Cc, mean, rstd, gamma, dx, ws, *, mode=0, scale=N
                       pool=(0, 0, 0, 0, 0), dgamma=None, dbeta=None):
     """mode 0: g is the gradient of the BN output; 1: ReLU follows the BN; 2: MaxPool + ReLU follow it (g is the
     pooled gradient, pool = (B, h, w, kh, kw))."""
-    B, h, w, kh, kw = pool
-    rc = _timed("bn_backward", float(M * Cc * 12),
-                lambda: _lib.lib().pp_bn_train_backward(_p(g), g.stride(0), _p(y), y.stride(0), M, Cc, _p(mean),
-                                                        _p(rstd), _p(scale), _p(shift), _p(gamma), mode, _p(argmax),
-                                                        B, h, w, kh, kw, _p(dgamma), _p(dbeta), _p(dx), dx.stride(0),
-                                                        dtype_code(dx.dtype), _p(ws), _lib.stream_ptr()))
-    _lib.check(rc, "pp_bn_train_backward")
+    _run("bn_backward", float(M * Cc * 12), "pp_bn_train_backward", g, g.stride(0), y, y.stride(0), M, Cc, mean, rstd,
+         scale, shift, gamma, mode, argmax, *pool, dgamma, dbeta, dx, dx.stride(0), dtype_code(dx.dtype), ws)
     return dx
 
 
 def aux_tail_backward(x, w, out, gout, B, Cc, K, dW=None, dB=None, dx=None):
-    rc = _timed("aux_tail_backward", float(4 * B * K * Cc * 4),
-                lambda: _lib.lib().pp_aux_tail_backward(_p(x), _p(w), _p(out), _p(gout), B, Cc, K, _p(dW), _p(dB),
-                                                        _p(dx), dtype_code(w.dtype), _lib.stream_ptr()))
-    _lib.check(rc, "pp_aux_tail_backward")
+    _run("aux_tail_backward", float(4 * B * K * Cc * 4), "pp_aux_tail_backward", x, w, out, gout, B, Cc, K, dW, dB, dx,
+         dtype_code(w.dtype))
 
 
 def heat_clamp(p, out, scale=1.0):
-    rc = _timed("heat_clamp", float(p.numel() * 8),
-                lambda: _lib.lib().pp_heat_clamp(_p(p), _p(out), p.numel(), float(scale), _lib.stream_ptr()))
-    _lib.check(rc, "pp_heat_clamp")
+    _run("heat_clamp", float(p.numel() * 8), "pp_heat_clamp", p, out, p.numel(), float(scale))
     return out
 
 
 def heat_tail_backward(p, g, B, K, HW, scale, sparse, temperature, dz):
-    rc = _timed("heat_tail_backward", float(B * K * HW * 12),
-                lambda: _lib.lib().pp_heat_tail_backward(_p(p), _p(g), B, K, HW, float(scale), int(sparse),
-                                                         float(temperature), _p(dz), dz.stride(0),
-                                                         dtype_code(dz.dtype), _lib.stream_ptr()))
-    _lib.check(rc, "pp_heat_tail_backward")
+    _run("heat_tail_backward", float(B * K * HW * 12), "pp_heat_tail_backward", p, g, B, K, HW, float(scale),
+         int(sparse), float(temperature), dz, dz.stride(0), dtype_code(dz.dtype))
     return dz
 
 
@@ -413,50 +367,40 @@ def layernorm_backward(x, gamma, eps, dy, dres, dres_c, accumulate, dgamma=None,
     dgamma / dbeta [C] f32 (optional)."""
     rows, Cc = x.shape
     if ws is None:
-        ws = torch.empty(int(_lib.lib().pp_layernorm_backward_workspace_bytes(rows, Cc)), dtype=torch.uint8,
+        ws = torch.empty(int(_lib.call("pp_layernorm_backward_workspace_bytes", rows, Cc)), dtype=torch.uint8,
                          device=x.device)
-    rc = _timed("ln_backward", float(rows * Cc * 20),
-                lambda: _lib.lib().pp_layernorm_backward(_p(x), _p(gamma), float(eps), rows, Cc, _p(dy), dy.stride(0),
-                                                         _p(dres), int(accumulate), _p(dres_c),
-                                                         dtype_code(dres_c.dtype), _p(dgamma), _p(dbeta), _p(ws),
-                                                         _lib.stream_ptr()))
-    _lib.check(rc, "pp_layernorm_backward")
+    _run("ln_backward", float(rows * Cc * 20), "pp_layernorm_backward", x, gamma, float(eps), rows, Cc, dy,
+         dy.stride(0), dres, int(accumulate), dres_c, dtype_code(dres_c.dtype), dgamma, dbeta, ws)
     return dres
 
 
 def gelu_forward(x, out):
     """out = GELU(x) (exact erf) in out's dtype; x f32 contiguous."""
-    rc = _timed("gelu", float(x.numel() * (4 + out.element_size())),
-                lambda: _lib.lib().pp_gelu_forward(_p(x), x.numel(), _p(out), dtype_code(out.dtype),
-                                                   _lib.stream_ptr()))
-    _lib.check(rc, "pp_gelu_forward")
+    _run("gelu", float(x.numel() * (4 + out.element_size())), "pp_gelu_forward", x, x.numel(), out,
+         dtype_code(out.dtype))
     return out
 
 
 def gelu_backward(x, g, dx):
     """dx = g * GELU'(x) in dx's dtype; x, g f32 contiguous."""
-    rc = _timed("gelu_backward", float(x.numel() * (8 + dx.element_size())),
-                lambda: _lib.lib().pp_gelu_backward(_p(x), _p(g), x.numel(), _p(dx), dtype_code(dx.dtype),
-                                                    _lib.stream_ptr()))
-    _lib.check(rc, "pp_gelu_backward")
+    _run("gelu_backward", float(x.numel() * (8 + dx.element_size())), "pp_gelu_backward", x, g, x.numel(), dx,
+         dtype_code(dx.dtype))
     return dx
 
 
 def attention_backward(qkv, out, dout, dqkv, B, N, heads, hd, ws=None):
     """dqkv [B*N, 3C] = the gradient of pp_attention (row-layout qkv) given its output and the output's gradient."""
     if ws is None:
-        ws = torch.empty(int(_lib.lib().pp_attention_backward_workspace_bytes(B, N, heads)), dtype=torch.uint8,
+        ws = torch.empty(int(_lib.call("pp_attention_backward_workspace_bytes", B, N, heads)), dtype=torch.uint8,
                          device=qkv.device)
-    rc = _timed("attention_backward", 10.0 * B * heads * N * N * hd,
-                lambda: _lib.lib().pp_attention_backward(_p(qkv), _p(out), _p(dout), _p(dqkv), B, N, heads, hd,
-                                                         dtype_code(qkv.dtype), _p(ws), _lib.stream_ptr()))
-    _lib.check(rc, "pp_attention_backward")
+    _run("attention_backward", 10.0 * B * heads * N * N * hd, "pp_attention_backward", qkv, out, dout, dqkv, B, N,
+         heads, hd, dtype_code(qkv.dtype), ws)
     return dqkv
 
 
 def rows_period_sum(x, B, N, Cc, out):
     """out [N, C] = sum over b of x [B*N, C] (f32, fixed order): the pos_embed gradient."""
-    _lib.check(_lib.lib().pp_rows_period_sum(_p(x), B, N, Cc, _p(out), _lib.stream_ptr()), "pp_rows_period_sum")
+    _lib.launch("pp_rows_period_sum", x, B, N, Cc, out)
     return out
 
 
@@ -464,28 +408,22 @@ def rows_period_sum(x, B, N, Cc, out):
 def crop_rows_gather(src, idx, B, N, Cc, out, scale=1.0):
     """out [kept*N, C] (f32 or bf16) = scale * the crops idx [kept] (int32) of src [B*N, C] f32."""
     kept = idx.numel()
-    rc = _timed("crop_rows_gather", float(kept * N * Cc * (4 + out.element_size())),
-                lambda: _lib.lib().pp_crop_rows_gather(_p(src), _p(idx), B, kept, N, Cc, float(scale), _p(out),
-                                                       dtype_code(out.dtype), _lib.stream_ptr()))
-    _lib.check(rc, "pp_crop_rows_gather")
+    _run("crop_rows_gather", float(kept * N * Cc * (4 + out.element_size())), "pp_crop_rows_gather", src, idx, B, kept,
+         N, Cc, float(scale), out, dtype_code(out.dtype))
     return out
 
 
 def droppath_add(r, branch, slot, B, kept, N, Cc, scale, out):
     """out [B*N, C] = r + scale * branch[slot[b]] for the kept crops (slot [B] int32 >= 0), r's bits for the others;
     r, out f32 [B*N, C], branch f32 [kept*N, C]."""
-    rc = _timed("droppath_add", float((2 * B + kept) * N * Cc * 4),
-                lambda: _lib.lib().pp_droppath_add(_p(r), _p(branch), _p(slot), B, kept, N, Cc, float(scale), _p(out),
-                                                   _lib.stream_ptr()))
-    _lib.check(rc, "pp_droppath_add")
+    _run("droppath_add", float((2 * B + kept) * N * Cc * 4), "pp_droppath_add", r, branch, slot, B, kept, N, Cc,
+         float(scale), out)
     return out
 
 
 def crop_rows_scatter_add(dx, idx, B, N, Cc, dres, dres_c):
     """dres[idx[j]] += dx[j] (crops of N rows, f32) in place; the same rows of dres_c = the new dres in its dtype."""
     kept = idx.numel()
-    rc = _timed("crop_rows_scatter_add", float(kept * N * Cc * (12 + dres_c.element_size())),
-                lambda: _lib.lib().pp_crop_rows_scatter_add(_p(dx), _p(idx), B, kept, N, Cc, _p(dres), _p(dres_c),
-                                                            dtype_code(dres_c.dtype), _lib.stream_ptr()))
-    _lib.check(rc, "pp_crop_rows_scatter_add")
+    _run("crop_rows_scatter_add", float(kept * N * Cc * (12 + dres_c.element_size())), "pp_crop_rows_scatter_add", dx,
+         idx, B, kept, N, Cc, dres, dres_c, dtype_code(dres_c.dtype))
     return dres

@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._buffers import PinnedStaging
 
 _STATE_KEYS = ("step", "exp_avg", "exp_avg_sq")
 _GROUP_KEYS = ("lr", "betas", "eps", "weight_decay")
@@ -108,7 +109,7 @@ class FusedAdamW(torch.optim.Optimizer):
         self._table = None           # the device table, uint8
         self._table_bytes = 0
         self._last_step = None       # event behind the last step's kernels: they read the table the next step rewrites
-        self._staging = []           # [(pinned host buffer, event after its last copy)]
+        self._staging = PinnedStaging()
         self._partials = None
         self._arrive = None
         self._record = None
@@ -169,16 +170,6 @@ class FusedAdamW(torch.optim.Optimizer):
                 st[k] = st[k].contiguous()
         self._layout = None
 
-    def _staging_buffer(self, nbytes: int):
-        """A pinned host buffer that no earlier asynchronous copy can still be reading: one whose event has completed,
-        or a new one.  Never waits."""
-        for slot in self._staging:
-            if slot[0].numel() >= nbytes and slot[1].query():
-                return slot
-        slot = [torch.empty(max(nbytes, 4096), dtype=torch.uint8, pin_memory=True), torch.cuda.Event()]
-        self._staging.append(slot)
-        return slot
-
     # ---- the step ----------------------------------------------------------------------------------------------
     @torch.no_grad()
     def step(self, closure=None):
@@ -232,15 +223,12 @@ class FusedAdamW(torch.optim.Optimizer):
         if not ps:
             return loss
         n = len(ps)
-        L = _lib.lib()
         with torch.cuda.device(self._device):
             counts = np.fromiter((p.numel() for p in ps), dtype=np.int64, count=n)
             layout = counts.tobytes()
             fresh = layout != self._layout
             if fresh:
-                nbytes = int(L.pp_optim_table_bytes(n, counts.ctypes.data, len(groups)))
-                if nbytes < 0:
-                    _lib.check(1, "pp_optim_table_bytes")
+                nbytes = int(_lib.call("pp_optim_table_bytes", n, counts, len(groups)))
                 self._table_bytes = nbytes
                 if self._table is None or self._table.numel() < nbytes:
                     self._table = torch.empty(nbytes, dtype=torch.uint8, device=self._device)
@@ -249,34 +237,28 @@ class FusedAdamW(torch.optim.Optimizer):
             self._ensure_record()
             if self._last_step is not None:     # a step issued on another stream may still be reading the table
                 torch.cuda.current_stream().wait_event(self._last_step)
-            slot = self._staging_buffer(self._table_bytes)
+            slot = self._staging.take(self._table_bytes)
             host = slot[0]
             arrs = [_ptr_array(x) for x in (ps, gs, ms, vs, ts)]
             group_ix = np.asarray(gidx, dtype=np.int32)
             n_chunks, prefix = C.c_int(0), C.c_longlong(0)
-            _lib.check(L.pp_optim_table_build(n, *(a.ctypes.data for a in arrs), counts.ctypes.data,
-                                              group_ix.ctypes.data, len(groups), hyper.ctypes.data,
-                                              self._arrive.data_ptr(), host.data_ptr(), int(fresh), C.byref(n_chunks),
-                                              C.byref(prefix)), "pp_optim_table_build")
+            _lib.call("pp_optim_table_build", n, *arrs, counts, group_ix, len(groups), hyper, self._arrive, host,
+                      int(fresh), C.byref(n_chunks), C.byref(prefix))
             nb = self._table_bytes if fresh else int(prefix.value)
             self._table[:nb].copy_(host[:nb], non_blocking=True)
             slot[1].record()
             self._layout = layout
             nc = int(n_chunks.value)
-            stream = _lib.stream_ptr()
             record = None
             if max_norm is not None or skip:
                 if self._partials is None or self._partials.numel() < nc:
                     self._partials = torch.empty(nc, dtype=torch.float64, device=self._device)
-                _lib.check(L.pp_grad_sqnorm_partials(_lib.ptr(self._table), nc, _lib.ptr(self._partials), stream),
-                           "pp_grad_sqnorm_partials")
-                _lib.check(L.pp_grad_norm_finish(_lib.ptr(self._partials), nc, int(max_norm is not None),
-                                                 float(max_norm or 0.0), int(skip), _lib.ptr(self._record), stream),
-                           "pp_grad_norm_finish")
+                _lib.launch("pp_grad_sqnorm_partials", self._table, nc, self._partials)
+                _lib.launch("pp_grad_norm_finish", self._partials, nc, int(max_norm is not None),
+                            float(max_norm or 0.0), int(skip), self._record)
                 record = self._record
                 self._norm_taken = True
-            _lib.check(L.pp_adamw_step(_lib.ptr(self._table), nc, _lib.ptr(record), int(skip), stream),
-                       "pp_adamw_step")
+            _lib.launch("pp_adamw_step", self._table, nc, record, int(skip))
             if self._last_step is None:
                 self._last_step = torch.cuda.Event()
             self._last_step.record()

@@ -29,20 +29,17 @@ There is no CPU fallback: without a GPU the calls raise ``_lib.HipExtensionError
 """
 from __future__ import annotations
 
+from functools import partial
+
 import numpy as np
 import torch
 
 from . import _lib
-from .cocoeval import _host
+from ._buffers import host_array as _host, room as _room, upload
 
 MODES = {"hard": _lib.PP_POSENMS_HARD, "soft_gaussian": _lib.PP_POSENMS_SOFT_GAUSSIAN,
          "soft_linear": _lib.PP_POSENMS_SOFT_LINEAR}
 MAX_DETS_PER_IMAGE = _lib.PP_POSENMS_MAX_DETS
-
-
-def _room(t: torch.Tensor) -> torch.Tensor:
-    """A tensor the library can take the address of: an empty one gets one element of room."""
-    return t if t.numel() else torch.zeros(1, dtype=t.dtype, device=t.device)
 
 
 def _device_f64(named) -> list:
@@ -85,8 +82,7 @@ def _first_seen(ids: np.ndarray):
 def _rescore(ks: torch.Tensor, bs: torch.Tensor, kpt_thr: float) -> torch.Tensor:
     M, K = ks.shape
     out = torch.empty(M, dtype=torch.float64, device=ks.device)
-    _lib.check(_lib.lib().pp_posenms_rescore(M, K, _lib.ptr(_room(ks)), _lib.ptr(_room(bs)), float(kpt_thr),
-                                             _lib.ptr(_room(out)), _lib.stream_ptr()), "pp_posenms_rescore")
+    _lib.launch("pp_posenms_rescore", M, K, _room(ks), _room(bs), float(kpt_thr), _room(out))
     return out
 
 
@@ -152,11 +148,9 @@ class PoseNMS:
         counts = torch.zeros(n_img, dtype=torch.int32, device=dev)
         hold = [_room(t) for t in (kp_s, ar_s, sc_s, out_s, keep_s, counts)]
         vis_hold = None if vis_s is None else _room(vis_s)
-        _lib.check(_lib.lib().pp_posenms(
-            n_img, self.K, M, off.ctypes.data, _lib.ptr(off_dev), _lib.ptr(hold[0]), _lib.ptr(vis_hold),
-            _lib.ptr(hold[1]), _lib.ptr(hold[2]), _lib.ptr(variances), MODES[self.mode], self.oks_thr,
-            0.0 if self.vis_thr is None else self.vis_thr, self.max_dets, _lib.ptr(hold[3]), _lib.ptr(hold[4]),
-            _lib.ptr(hold[5]), _lib.stream_ptr()), "pp_posenms")
+        _lib.launch("pp_posenms", n_img, self.K, M, off, off_dev, hold[0], vis_hold, hold[1], hold[2], variances,
+                    MODES[self.mode], self.oks_thr, 0.0 if self.vis_thr is None else self.vis_thr, self.max_dets,
+                    *hold[3:])
         return out_s, keep_s, counts
 
     def __call__(self, image_ids, keypoints, box_scores, areas, kpt_scores=None) -> PoseNMSResult:
@@ -212,15 +206,7 @@ class PoseNMS:
             vis = kp3[..., 2] if self.vis_thr is not None else None
 
         staged = []
-
-        def up(a: np.ndarray) -> torch.Tensor:
-            """To the device without a synchronising copy: through a pinned buffer."""
-            if a.size == 0:
-                return torch.zeros(a.shape, dtype=torch.from_numpy(a).dtype, device=dev)
-            t = torch.from_numpy(np.ascontiguousarray(a)).pin_memory()
-            staged.append(t)
-            return t.to(device=dev, non_blocking=True)
-
+        up = partial(upload, device=dev, keep=staged)
         # descending score, then image: two stable sorts leave every image's detections in score order, equal scores
         # in the order they were given
         by_score = torch.sort(sc, descending=True, stable=True).indices

@@ -617,8 +617,8 @@ def test_captured_graph_survives_many_other_batch_sizes(pkg):
         for o, w in zip(out_g, want):
             assert torch.equal(o, w)
     tables = m.head._plan(xs.device)._tables
-    assert sum(1 for v in tables.values() if v["pinned"]) >= 1
-    assert sum(1 for v in tables.values() if not v["pinned"]) <= 8
+    assert sum(1 for k in tables if tables.marked(k)) >= 1
+    assert sum(1 for k in tables if not tables.marked(k)) <= 8
 
 
 def test_vit_b_bs64_fp32_every_crop_against_the_cpu_oracle(pkg):

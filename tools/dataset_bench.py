@@ -92,11 +92,12 @@ def main():
     ap.add_argument("--out")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "dataset_bench needs the GPU: there is nothing to time without it"
+    from probpose_pytorch_amd._buffers import PinnedStaging
     from probpose_pytorch_amd.codec import ArgMaxProbMap, Codec
     from probpose_pytorch_amd.dataset import YOLOPoseDataset
     sigmas = np.full(K, 0.05)
     ds = YOLOPoseDataset.__new__(YOLOPoseDataset)              # no tree on disk: the samples are made in memory
-    ds.codec, ds.annotations, ds._staging = Codec(ArgMaxProbMap(INPUT, HEAT, sigmas)), [], []
+    ds.codec, ds.annotations, ds._staging = Codec(ArgMaxProbMap(INPUT, HEAT, sigmas)), [], PinnedStaging()
     ds.augment, ds.epoch, ds._perm = None, 0, None
     frame, samples, boxes = make_samples()
     src_bytes = sum(s[0].size for s in samples)
