@@ -752,6 +752,43 @@ int pp_posenms(int n_img, int K, long long Dtot, const long long *host_off, cons
                const void *vis, const void *area, const void *scores, const void *vars, int mode, double oks_thr,
                double vis_thr, int max_dets, void *out_scores, void *keep, void *counts, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Visualisation (probpose_pytorch_amd/viz.py): heat overlays and pose drawing on uint8 RGB images, heat
+ * maps as RGBA pictures.  No host sync, no atomics, plain vector stores, the same bytes on every call.
+ *
+ * pp_viz_render: out [B, H, W, 3] uint8 = draw(overlay(image)); one pass, every image byte read and written once.
+ *   image: uint8 [B, H, W, 3] (image_f32chw = 0; out == image is allowed: in place) or float32 [B, 3, H, W]
+ *     (image_f32chw = 1), converted as trunc(min(max(v * 255f + 0.5f, 0), 255)) in float32, NaN -> 0.
+ *   overlay (heat != NULL): heat [B, K, h, w] float32, lut [256, 3] float64 (matplotlib's table of the colormap).  Per
+ *     pixel and map the value is the map's own element when (h, w) == (H, W), else bilinear in float64 with
+ *     u = px (w - 1) / (W - 1) (0 when W == 1), x0 = min(floor(u), w - 1), x1 = min(x0 + 1, w - 1), fx = u - x0, the
+ *     same in y, (a00 (1 - fx) + a01 fx)(1 - fy) + (a10 (1 - fx) + a11 fx) fy, rounded to float32.  Colour: xa = v *
+ *     256f in float32; NaN -> (0, 0, 0); xa < 0 -> row 0; xa >= 256 -> row 255; else row trunc(xa).  v < float32(0.01)
+ *     adds nothing.  The colours are summed in float64 over k ascending from 0.0, times 255.0, saturated at 255,
+ *     truncated, and added to the image byte with saturation at 255.
+ *   draw (kpts != NULL): kpts [N, Kp, 2] and probs [N, Kp] float64; inst [N] int32 = the instances ordered by image
+ *     (stable), img_off [B + 1] int32 = where each image's instances start in inst; style = Kp int32 colours
+ *     (r | g << 8 | b << 16) followed by L limbs (i, j, colour).  A keypoint is drawn unless prob < threshold, when
+ *     its coordinates are finite and below 2^31 in magnitude and its centre (trunc(x), trunc(y)) is inside the image:
+ *     a disc dx^2 + dy^2 <= radius^2 + radius.  A limb is drawn when both its keypoints are and their centres differ:
+ *     the pixels whose squared distance to the segment, times 4, is <= line_width^2, in exact integers.  Per pixel the
+ *     last primitive that covers it wins, in the order: all limbs (instances ascending, then limb order), then all
+ *     discs (instances ascending, then keypoints ascending).
+ *   H, W, h, w, radius and line_width are at most PP_VIZ_MAX_SIDE.
+ * pp_viz_colorize: maps [M, h, w] float32 -> out [M, h, w, 4] uint8: trunc(colour * 255.0) of the colour rule above
+ *   with alpha 255, (0, 0, 0, 0) for NaN; with `normalize` every map is first divided, in float32, by its own maximum
+ *   (NaN when any element is NaN, as numpy's max).  M = 0 launches nothing.
+ * Both refuse on the host, with pp_last_error, before any launch: null pointers, sizes out of range, an out that
+ * overlaps an input.
+ * ---------------------------------------------------------------------- */
+#define PP_VIZ_MAX_SIDE 8192
+int pp_viz_render(const void *image, int image_f32chw, void *out, int B, int H, int W, const float *heat, int K, int h,
+                  int w, const double *lut, const double *kpts, const double *probs, const int *inst,
+                  const int *img_off, int N, int Kp, const int *style, int L, double threshold, int radius,
+                  int line_width, void *stream);
+int pp_viz_colorize(const float *maps, void *out, long long M, int h, int w, const double *lut, int normalize,
+                    void *stream);
+
 #ifdef __cplusplus
 }
 #endif

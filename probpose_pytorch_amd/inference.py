@@ -15,7 +15,13 @@ function, ``run_inference``: ``Codec(ProbMap(input_size, heatmap_size, sigmas))`
   pairs (default for 17 keypoints: COCO's 1-2, 3-4, ..., 15-16);
 * ``--boxes "x,y,w,h[,score];..."`` runs the box path (``run_inference_on_boxes``) on the full-size ``--image``, and
   ``--nms {hard,soft_gaussian,soft_linear}`` / ``--nms-thr`` rescore and suppress the boxes' duplicate poses after
-  decode (``posenms.PoseNMS``); both are off by default.
+  decode (``posenms.PoseNMS``); both are off by default;
+* ``--render`` (with ``--output``) writes the reference's pictures, made on the GPU by ``viz``: ``heatmap_{i}.png``
+  (``viz.colorize`` of the first crop's maps through inferno, honouring ``--normalize``) and ``output_image.png``
+  (``viz.draw_keypoints``: a red disc of radius 5 at every keypoint whose probability is at least
+  ``--render-threshold``, 0.9 as in the reference; no text labels).  With ``--boxes`` the picture is the frame with
+  every pose (with ``--nms``: every kept pose) at its frame coordinates, with the COCO skeleton for 17 keypoints.
+  Without ``--render`` nothing changes: the ``.npy`` dumps stay.
 """
 from __future__ import annotations
 
@@ -157,6 +163,12 @@ def load_frame(path: Path) -> torch.Tensor:
     return torch.from_numpy(np.ascontiguousarray(np.asarray(PIL.Image.open(path).convert("RGB"), dtype=np.uint8)))
 
 
+def save_png(array: np.ndarray, path: Path) -> None:
+    """uint8 [H, W, 3] or [H, W, 4] -> a PNG file (the one host step of --render)."""
+    import PIL.Image
+    PIL.Image.fromarray(array).save(path)
+
+
 def main(argv=None):
     p = argparse.ArgumentParser(description="Inference script for ProbPose (MI355X-native path)")
     p.add_argument("--model", type=Path, default=None, help="state_dict checkpoint (omit: seeded synthetic weights)")
@@ -178,6 +190,10 @@ def main(argv=None):
     p.add_argument("--nms", type=str, default=None, choices=["hard", "soft_gaussian", "soft_linear"],
                    help="with --boxes: rescore the poses and suppress duplicates by OKS after decode (default: off)")
     p.add_argument("--nms-thr", type=float, default=0.9, help="OKS threshold of --nms")
+    p.add_argument("--render", action="store_true",
+                   help="with --output: also write heatmap_{i}.png and output_image.png, drawn on the GPU")
+    p.add_argument("--render-threshold", type=float, default=0.9,
+                   help="--render draws the keypoints whose probability is at least this")
     args = p.parse_args(argv)
     flip_pairs = resolve_flip_pairs(p, args)
     boxes = None
@@ -190,6 +206,10 @@ def main(argv=None):
         p.error("--nms needs --boxes (it applies to the box path)")
     if not 0.0 < args.nms_thr <= 1.0:
         p.error(f"--nms-thr: {args.nms_thr} is outside (0, 1]")
+    if args.render and args.output is None:
+        p.error("--render needs --output (the folder the pictures go to)")
+    if np.isnan(args.render_threshold):
+        p.error("--render-threshold: not a number")
     input_size = tuple(map(int, args.input_size.split(",")))
     model, heatmap_size = build_model(input_size, args.num_keypoints, args.backbone)
     if args.model is not None:
@@ -212,13 +232,24 @@ def main(argv=None):
         from .synthetic import synthetic_crops
         x = synthetic_crops(1, input_size[1], input_size[0], seed=1234)
     print("Input image shape:", tuple(x.shape))
-    output, preds = run_inference(model, codec, x.to("cuda"))
+    x = x.to("cuda")
+    output, preds = run_inference(model, codec, x)
     heatmaps = output[0][0].cpu().numpy()
     print("Output heatmap shape:", heatmaps.shape)
     if args.output is not None:
         args.output.mkdir(parents=True, exist_ok=True)
         for i, hm in enumerate(heatmaps):
             np.save(args.output / f"heatmap_{i}.npy", hm / hm.max() if args.normalize and hm.max() > 0 else hm)
+        if args.render:
+            from . import viz
+            for i, rgba in enumerate(viz.colorize(output[0][0], "inferno", args.normalize).cpu().numpy()):
+                save_png(rgba, args.output / f"heatmap_{i}.png")
+            K = args.num_keypoints
+            kpts = np.ascontiguousarray(np.asarray(preds[0][0], dtype=np.float64)[:1])
+            probs = np.ascontiguousarray(np.asarray(preds[1], dtype=np.float64).reshape(-1, K)[:1])
+            drawn = viz.render(x[:1], None, torch.from_numpy(kpts).to(x.device), torch.from_numpy(probs).to(x.device),
+                               threshold=args.render_threshold)
+            save_png(drawn[0].cpu().numpy(), args.output / "output_image.png")
     print("Predictions:", preds[0])
     print("Probabilities:", preds[1])
     print("Visibilities:", preds[2])
@@ -245,6 +276,16 @@ def _main_boxes(args, model, codec, boxes):
     if nms is not None:
         print("Kept:", out[3].keep.cpu().numpy())
         print("Scores:", out[3].scores.cpu().numpy())
+    if args.render:
+        from . import viz
+        K = args.num_keypoints
+        shown = out[3].keep.cpu().numpy() if nms is not None else np.ones(out[2].shape[0], dtype=bool)
+        kpts, probs = out[2][shown], np.asarray(out[1][1], dtype=np.float64).reshape(-1, K)[shown]
+        drawn = viz.draw_keypoints(frame.numpy(), kpts, probs, threshold=args.render_threshold,
+                                   skeleton=viz.COCO17_SKELETON if K == 17 else None,
+                                   image_index=np.zeros(kpts.shape[0], dtype=np.int64))
+        args.output.mkdir(parents=True, exist_ok=True)
+        save_png(drawn, args.output / "output_image.png")
     return out
 
 

@@ -290,6 +290,30 @@ def flip_merge(heat2, aux2, perm, heat_out, aux_out):
     return heat_out, aux_out
 
 
+# ---- visualisation (pp_viz.hip) -------------------------------------------------------------------------------------
+def viz_render(image, out, heat=None, lut=None, draw=None):
+    """image uint8 [B,H,W,3] or f32 [B,3,H,W] -> out uint8 [B,H,W,3]: the overlay of heat [B,K,h,w] through lut [256,3]
+    f64, then the primitives of ``draw`` = (kpts [N,Kp,2] f64, probs [N,Kp] f64, inst [N] i32, img_off [B+1] i32,
+    style i32, N, Kp, L, threshold, radius, line_width); either half may be None (pp_viz_render in
+    include/probpose_hip.h)."""
+    B, H, W = out.shape[:3]
+    K, h, w = heat.shape[1:] if heat is not None else (0, 0, 0)
+    kpts, probs, inst, img_off, style, N, Kp, L, threshold, radius, line_width = draw or (None,) * 5 + (0, 0, 0, 0.0, 0, 1)
+    _run("viz_render", float(out.numel() * (2 if image.dtype == torch.uint8 else 5) + B * K * H * W * 4),
+         "pp_viz_render", image, int(image.dtype != torch.uint8), out, B, H, W, heat, K, h, w, lut, kpts, probs, inst,
+         img_off, N, Kp, style, L, float(threshold), radius, line_width)
+    return out
+
+
+def viz_colorize(maps, lut, out, normalize=False):
+    """maps f32 [..., h, w] -> out uint8 [..., h, w, 4] through lut [256,3] f64 (pp_viz_colorize)."""
+    h, w = maps.shape[-2:]
+    M = maps.numel() // (h * w)
+    _run("viz_colorize", float(maps.numel() * (12 if normalize else 8)), "pp_viz_colorize", maps, out, M, h, w, lut,
+         int(bool(normalize)))
+    return out
+
+
 # ---- training ProbMapHead (pp_head_grad.hip) ------------------------------------------------------------------
 def wgrad_workspace_floats(M, N, Kd, batch=1) -> int:
     return int(_lib.call("pp_wgrad_workspace_floats", M, N, Kd, batch))
