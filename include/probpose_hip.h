@@ -753,6 +753,54 @@ int pp_posenms(int n_img, int K, long long Dtot, const long long *host_off, cons
                double vis_thr, int max_dets, void *out_scores, void *keep, void *counts, void *stream);
 
 /* ------------------------------------------------------------------------
+ * PoseTracker (probpose_pytorch_amd/tracker.py): greedy OKS association of a frame's poses with the
+ * tracks of its stream, and One-Euro smoothing per keypoint coordinate.  Everything is float64; no host sync, no
+ * atomics, plain vector stores, the same bits on every call.  One update is the three launches below, in this order.
+ *
+ * State of one stream: a block of pp_track_state_bytes(max_tracks, K) bytes, 8-byte aligned, T = max_tracks:
+ *   id int64 [T] (-1 = free) | t_last f64 [T] | area f64 [T] | kp f64 [T, K, 2] | vis f64 [T, K] | xhat f64 [T, K, 2]
+ *   | dxhat f64 [T, K, 2] | next_id int64 | overflow int64 | age int32 [T], padded to 8 bytes | init uint8 [T, K],
+ *   padded to 8 bytes.  A fresh block is all zero except id = -1.
+ * `blocks` is a device array of n_str int64 block addresses, one per stream of the call; `host_off` / `off` are the
+ * n_str + 1 int64 CSR offsets of the detections in HOST memory (checked before any launch: start at 0, monotone,
+ * ending at Dtot, no stream above PP_TRACK_MAX_DETS) and in device memory; `det_stream` [Dtot] int64 is every
+ * detection's stream index.  Stream i owns detections off[i] .. off[i+1], ALREADY in descending score order, equal
+ * scores in the order they were given.  kpts [Dtot, K, 2], vis [Dtot, K] or NULL, area [Dtot], vars [K] = (2 sigma)^2.
+ *
+ * pp_track_oks: oks [Dtot, max_tracks] = pp_posenms's pair OKS of detection d (the pivot) and slot j's stored raw
+ *   keypoints, area and visibilities; a free slot gives 0.  One lane per pair.
+ * pp_track_assign: one wave per stream.  In visiting order each detection takes the slot, live when the call began and
+ *   not yet taken, with the largest OKS (the lowest slot on equal OKS) if that OKS is > match_thr.  Then every live
+ *   slot not taken gets age += 1 and is freed when age > max_age.  Then each unmatched detection, in visiting order,
+ *   takes the lowest free slot with id = next_id++, or none (overflow += 1).  Per detection: ids [Dtot] int64 (-1 =
+ *   none), match_oks [Dtot] f64 (0 unless matched), born [Dtot] uint8, slot_of [Dtot] int32 (-1 = none), te [Dtot] f64
+ *   = t - t_last of a matched slot (0 otherwise).  A taken or born slot gets age = 0, t_last = t, area = the
+ *   detection's.  t - t_prev must be > 0 (t_prev = the previous update's t, -inf for the first).  A stream without
+ *   detections still ages; n_str = 0 launches nothing.
+ * pp_track_filter: one lane per (detection, keypoint) with a slot: out [Dtot, K, 2] and the slot's filter state.
+ *   smooth = 0: out = raw.  Otherwise a keypoint with vis given and vis <= vis_thr: out = raw, init = 0; a born slot or
+ *   init == 0: xhat = x, dxhat = 0, init = 1, out = x; else per coordinate dx = (x - xhat) / te, a_d = alpha(te,
+ *   d_cutoff), dxhat = a_d dx + (1 - a_d) dxhat, a = alpha(te, min_cutoff + beta |dxhat|), xhat = a x + (1 - a) xhat =
+ *   out, with alpha(te, fc) = r / (r + 1), r = ((2 pi) fc) te, unfused.  The slot's kp and vis rows take the raw values
+ *   (vis 1 without visibilities).  A detection without a slot: out = raw.
+ * All refuse on the host, with pp_last_error, before any launch: null pointers, K <= 0, max_tracks outside
+ * 1..PP_TRACK_MAX_TRACKS, match_thr outside [0, 1), max_age < 0, te <= 0, bad offsets, bad filter constants.
+ * ---------------------------------------------------------------------- */
+#define PP_TRACK_MAX_TRACKS 4096
+#define PP_TRACK_MAX_DETS 4096
+long long pp_track_state_bytes(int max_tracks, int K);
+int pp_track_oks(int n_str, int K, int max_tracks, long long Dtot, const long long *host_off, const void *det_stream,
+                 const void *blocks, const void *kpts, const void *vis, const void *area, const void *vars,
+                 double vis_thr, void *oks, void *stream);
+int pp_track_assign(int n_str, int K, int max_tracks, long long Dtot, const long long *host_off, const void *off,
+                    const void *blocks, const void *oks, const void *area, double match_thr, int max_age, double t,
+                    double t_prev, void *ids, void *match_oks, void *born, void *slot_of, void *te, void *stream);
+int pp_track_filter(int K, int max_tracks, long long Dtot, const void *det_stream, const void *blocks,
+                    const void *kpts, const void *vis, double vis_thr, const void *slot_of, const void *born,
+                    const void *te, int smooth, double min_cutoff, double beta, double d_cutoff, void *out,
+                    void *stream);
+
+/* ------------------------------------------------------------------------
  * Visualisation (probpose_pytorch_amd/viz.py): heat overlays and pose drawing on uint8 RGB images, heat
  * maps as RGBA pictures.  No host sync, no atomics, plain vector stores, the same bytes on every call.
  *

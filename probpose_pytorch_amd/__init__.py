@@ -13,7 +13,8 @@ from .codec import ArgMaxProbMap, Codec, ProbMap  # noqa: F401
 from .heatmap import get_heatmap_expected_value  # noqa: F401
 
 __all__ = ["to_numpy", "Codec", "ProbMap", "ArgMaxProbMap", "get_heatmap_expected_value", "FusedAdamW",
-           "Augment", "ModelEma", "ema_update_", "CocoKeypointEval", "PoseNMS", "rescore_instances"]
+           "Augment", "ModelEma", "ema_update_", "CocoKeypointEval", "PoseNMS", "rescore_instances",
+           "PoseTracker", "OneEuro"]
 
 
 def __getattr__(name):  # lazy: the nn.Module side pulls in the engine
@@ -38,6 +39,9 @@ def __getattr__(name):  # lazy: the nn.Module side pulls in the engine
     if name in ("PoseNMS", "rescore_instances"):
         from . import posenms
         return getattr(posenms, name)
+    if name in ("PoseTracker", "OneEuro"):
+        from . import tracker
+        return getattr(tracker, name)
     if name == "Augment":
         from .dataset import Augment
         return Augment

@@ -1,0 +1,364 @@
+// PoseTracker: greedy OKS track association and One-Euro smoothing of decoded poses (probpose_pytorch_amd/tracker.py,
+// DESIGN §4.7d), three launches per update.
+//
+//   track_oks_kernel     one lane per (detection, slot): the pair OKS of §4.7c with the slot's stored raw keypoints, area
+//                        and visibilities as the second detection; a free slot writes 0.  This is the arithmetic (K exp
+//                        per pair) and it is spread over the whole chip.
+//   track_assign_kernel  one wave per stream, four waves to a workgroup.  Lane j % 64 OWNS slot j: its live and taken
+//                        bits are bit j / 64 of two 64-bit registers of that lane (64 lanes x 64 bits =
+//                        PP_TRACK_MAX_TRACKS), and its id, age, t_last and area are written by that lane alone.  The
+//                        stream's detections arrive in visiting order.  A detection's pick is wave_max of the lanes' best
+//                        OKS among their live, untaken slots, then wave_min of the slots that hold it (the lowest on
+//                        equal OKS); whether detection p is still unmatched is bit p / 64 of a register of lane p % 64.
+//                        Ageing and freeing follow, then the births, each through wave_min of the lanes' lowest free
+//                        slot.  What a detection gets (id, OKS, born, slot, te) is written by the lane that owns its
+//                        slot, or by lane 0 when it has none.  No atomics, no LDS, no barrier, plain vector stores: the
+//                        result does not depend on timing.
+//   track_filter_kernel  one lane per (detection, keypoint): reads the slot the assign kernel gave the detection, applies
+//                        the One-Euro step (or initialises, or passes the raw value through) and writes the output, the
+//                        filter state and the slot's raw keypoint and visibility.  A slot belongs to at most one
+//                        detection of a call, so every state element has one writer.  The operations of
+//                        tests/track_reference.py one for one (compiled -ffp-contract=off): the same bits.
+//
+// State of one stream: one block of pp_track_state_bytes(max_tracks, K) bytes, laid out by TrackState below.
+#include <float.h>
+#include <limits.h>
+#include <math.h>
+
+#include "pp_common.h"
+
+namespace pp {
+
+constexpr int kTrackWaves = 4;
+constexpr int kTrackThreads = 256;
+
+// the sections of a stream's block, each a multiple of 8 bytes (T = max_tracks):
+//   id int64 [T] | t_last f64 [T] | area f64 [T] | kp f64 [T, K, 2] | vis f64 [T, K] | xhat f64 [T, K, 2] |
+//   dxhat f64 [T, K, 2] | next_id int64 | overflow int64 | age int32 [T] | init uint8 [T, K]
+struct TrackState {
+  long long *id;
+  double *t_last, *area, *kp, *vis, *xhat, *dxhat;
+  long long *next_id, *overflow;
+  int *age;
+  unsigned char *init;
+};
+
+__host__ __device__ inline long long track_pad8(long long n) { return (n + 7) & ~7ll; }
+
+__host__ __device__ inline long long track_state_bytes(long long T, long long K) {
+  return 8 * (3 * T + 7 * T * K + 2) + track_pad8(4 * T) + track_pad8(T * K);
+}
+
+__device__ __forceinline__ TrackState track_state(long long base, int T, int K) {
+  TrackState s;
+  const long long TK = (long long)T * K;
+  double *w = (double *)base;
+  s.id = (long long *)w;
+  s.t_last = w + T;
+  s.area = w + 2ll * T;
+  s.kp = w + 3ll * T;
+  s.vis = s.kp + 2 * TK;
+  s.xhat = s.vis + TK;
+  s.dxhat = s.xhat + 2 * TK;
+  s.next_id = (long long *)(s.dxhat + 2 * TK);
+  s.overflow = s.next_id + 1;
+  s.age = (int *)(s.overflow + 1);
+  s.init = (unsigned char *)s.age + track_pad8(4ll * T);
+  return s;
+}
+
+__global__ __launch_bounds__(kTrackThreads) void track_oks_kernel(
+    int K, int T, long long Dtot, const long long *__restrict__ det_stream, const long long *__restrict__ blocks,
+    const double *__restrict__ kpts, const double *__restrict__ vis, const double *__restrict__ area,
+    const double *__restrict__ vars, double vis_thr, double *__restrict__ oks) {
+  const long long i = (long long)blockIdx.x * kTrackThreads + threadIdx.x;
+  if (i >= Dtot * T) return;
+  const long long d = i / T;
+  const int j = (int)(i - d * T);
+  const TrackState st = track_state(blocks[det_stream[d]], T, K);
+  if (st.id[j] < 0) {
+    oks[i] = 0.0;
+    return;
+  }
+  const double *ka = kpts + d * K * 2, *kb = st.kp + (long long)j * K * 2;
+  const double *va = vis ? vis + d * K : nullptr, *vb = st.vis + (long long)j * K;
+  // §4.7c's pair OKS, the detection as the pivot: the same operations in the same order
+  const double size = (area[d] + st.area[j]) / 2.0 + DBL_EPSILON;
+  double sum = 0.0;
+  int n = 0;
+  for (int k = 0; k < K; ++k) {
+    if (va && !(va[k] > vis_thr && vb[k] > vis_thr)) continue;
+    const double dx = ka[2 * k] - kb[2 * k], dy = ka[2 * k + 1] - kb[2 * k + 1];
+    const double e = (dx * dx + dy * dy) / vars[k] / size / 2.0;
+    sum += exp(-e);
+    ++n;
+  }
+  oks[i] = n ? sum / (double)n : 0.0;
+}
+
+__global__ __launch_bounds__(64 * kTrackWaves) void track_assign_kernel(
+    int n_str, int K, int T, const long long *__restrict__ off, const long long *__restrict__ blocks,
+    const double *__restrict__ oks, const double *__restrict__ area, double match_thr, int max_age, double t,
+    long long *__restrict__ ids, double *__restrict__ match_oks, unsigned char *__restrict__ born,
+    int *__restrict__ slot_of, double *__restrict__ te) {
+  const long long str = (long long)blockIdx.x * kTrackWaves + (threadIdx.x >> 6);
+  if (str >= n_str) return;
+  const int lane = threadIdx.x & 63;
+  const long long d0 = off[str], span = off[str + 1] - d0;
+  if (span < 0 || span > PP_TRACK_MAX_DETS || T > PP_TRACK_MAX_TRACKS) return;   // refused on the host
+  const int D = (int)span, slots = (T + 63) >> 6;
+  const TrackState st = track_state(blocks[str], T, K);
+
+  // lane-owned: which of the lane's slots exist, are live (at entry) and are taken in this call; which of the
+  // detections p with p % 64 == lane are unmatched
+  unsigned long long valid = 0, live = 0, taken = 0, unmatched = 0;
+  for (int s = 0; s < slots; ++s) {
+    const int j = s * 64 + lane;
+    if (j < T) {
+      valid |= 1ull << s;
+      if (st.id[j] >= 0) live |= 1ull << s;
+    }
+  }
+
+  // association: the detections in visiting order
+  for (int p = 0; p < D; ++p) {
+    const double *row = oks + (d0 + p) * T;
+    double best = -INFINITY;
+    int best_j = INT_MAX;
+    unsigned long long cand = live & ~taken;
+    while (cand) {                                        // ascending slots: the lowest of the lane's on equal OKS
+      const int s = __builtin_ctzll(cand);
+      cand &= cand - 1;
+      const int j = s * 64 + lane;
+      const double v = row[j];
+      if (v > best) {
+        best = v;
+        best_j = j;
+      }
+    }
+    const double top = wave_max(best);
+    const int pick = wave_min(best_j != INT_MAX && best == top ? best_j : INT_MAX);
+    if (pick != INT_MAX && top > match_thr) {             // wave-uniform
+      if (lane == (pick & 63)) {
+        taken |= 1ull << (pick >> 6);
+        const long long d = d0 + p;
+        ids[d] = st.id[pick];
+        match_oks[d] = top;
+        born[d] = 0;
+        slot_of[d] = pick;
+        te[d] = t - st.t_last[pick];
+        st.age[pick] = 0;
+        st.t_last[pick] = t;
+        st.area[pick] = area[d];
+      }
+    } else if (lane == (p & 63)) {
+      unmatched |= 1ull << (p >> 6);
+    }
+  }
+
+  // ageing: every live slot not taken; freed above max_age
+  for (unsigned long long m = live & ~taken; m;) {
+    const int s = __builtin_ctzll(m);
+    m &= m - 1;
+    const int j = s * 64 + lane;
+    const int a = st.age[j] + 1;
+    st.age[j] = a;
+    if (a > max_age) {
+      st.id[j] = -1;
+      live &= ~(1ull << s);
+    }
+  }
+
+  // births: the unmatched detections in visiting order, each into the lowest free slot
+  long long next = *st.next_id, over = 0;                 // wave-uniform
+  bool any = false;
+  for (int p = 0; p < D; ++p) {
+    if (!__shfl((int)((unmatched >> (p >> 6)) & 1ull), p & 63, 64)) continue;   // wave-uniform
+    const unsigned long long free_slots = valid & ~live;
+    const int j = wave_min(free_slots ? __builtin_ctzll(free_slots) * 64 + lane : INT_MAX);
+    const long long d = d0 + p;
+    any = true;
+    if (j != INT_MAX) {
+      if (lane == (j & 63)) {
+        live |= 1ull << (j >> 6);
+        st.id[j] = next;
+        st.age[j] = 0;
+        st.t_last[j] = t;
+        st.area[j] = area[d];
+        ids[d] = next;
+        match_oks[d] = 0.0;
+        born[d] = 1;
+        slot_of[d] = j;
+        te[d] = 0.0;
+      }
+      ++next;
+    } else {
+      if (lane == 0) {
+        ids[d] = -1;
+        match_oks[d] = 0.0;
+        born[d] = 0;
+        slot_of[d] = -1;
+        te[d] = 0.0;
+      }
+      ++over;
+    }
+  }
+  if (any && lane == 0) {
+    *st.next_id = next;
+    *st.overflow += over;
+  }
+}
+
+__device__ __forceinline__ double track_alpha(double te, double fc) {
+  const double r = ((2.0 * M_PI) * fc) * te;
+  return r / (r + 1.0);
+}
+
+__global__ __launch_bounds__(kTrackThreads) void track_filter_kernel(
+    int K, int T, long long Dtot, const long long *__restrict__ det_stream, const long long *__restrict__ blocks,
+    const double *__restrict__ kpts, const double *__restrict__ vis, double vis_thr,
+    const int *__restrict__ slot_of, const unsigned char *__restrict__ born, const double *__restrict__ te_of,
+    int smooth, double min_cutoff, double beta, double d_cutoff, double *__restrict__ out) {
+  const long long i = (long long)blockIdx.x * kTrackThreads + threadIdx.x;
+  if (i >= Dtot * K) return;
+  const long long d = i / K;
+  const int k = (int)(i - d * K);
+  const double x0 = kpts[2 * i], x1 = kpts[2 * i + 1];
+  double o0 = x0, o1 = x1;
+  const int j = slot_of[d];
+  if (j >= 0 && j < T) {
+    const TrackState st = track_state(blocks[det_stream[d]], T, K);
+    const long long e = (long long)j * K + k;
+    const double v = vis ? vis[i] : 1.0;
+    if (smooth) {
+      const bool counted = !vis || v > vis_thr;
+      if (!counted) {
+        st.init[e] = 0;
+      } else if (born[d] || st.init[e] == 0) {
+        st.xhat[2 * e] = x0;
+        st.xhat[2 * e + 1] = x1;
+        st.dxhat[2 * e] = 0.0;
+        st.dxhat[2 * e + 1] = 0.0;
+        st.init[e] = 1;
+      } else {
+        const double te = te_of[d];
+        const double a_d = track_alpha(te, d_cutoff);
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+          const double x = c ? x1 : x0, xh = st.xhat[2 * e + c];
+          const double dx = (x - xh) / te;
+          const double dxh = a_d * dx + (1.0 - a_d) * st.dxhat[2 * e + c];
+          const double a = track_alpha(te, min_cutoff + beta * fabs(dxh));
+          const double nx = a * x + (1.0 - a) * xh;
+          st.dxhat[2 * e + c] = dxh;
+          st.xhat[2 * e + c] = nx;
+          if (c) o1 = nx;
+          else o0 = nx;
+        }
+      }
+    }
+    st.kp[2 * e] = x0;
+    st.kp[2 * e + 1] = x1;
+    st.vis[e] = v;
+  }
+  out[2 * i] = o0;
+  out[2 * i + 1] = o1;
+}
+
+static int track_check_common(const char *who, int n_str, int K, int T, long long Dtot) {
+  PP_REQUIRE(n_str >= 0, "%s: n_str=%d", who, n_str);
+  PP_REQUIRE(K > 0, "%s: K=%d", who, K);
+  PP_REQUIRE(T >= 1 && T <= PP_TRACK_MAX_TRACKS, "%s: max_tracks=%d is outside 1..%d", who, T, PP_TRACK_MAX_TRACKS);
+  PP_REQUIRE(Dtot >= 0, "%s: Dtot=%lld", who, Dtot);
+  return 0;
+}
+
+static int track_check_offsets(const char *who, int n_str, const long long *h, long long Dtot) {
+  PP_REQUIRE(h, "%s: null host offsets", who);
+  PP_REQUIRE(h[0] == 0, "%s: offsets do not start at 0 (%lld)", who, h[0]);
+  for (int i = 0; i < n_str; ++i)
+    PP_REQUIRE(h[i + 1] >= h[i], "%s: detection offsets are not monotone at stream %d (%lld after %lld)", who, i,
+               h[i + 1], h[i]);
+  PP_REQUIRE(h[n_str] == Dtot, "%s: offsets end at %lld, the arrays hold %lld detections", who, h[n_str], Dtot);
+  for (int i = 0; i < n_str; ++i)
+    PP_REQUIRE(h[i + 1] - h[i] <= PP_TRACK_MAX_DETS,
+               "%s: stream %d has %lld detections, more than the %d one call takes", who, i, h[i + 1] - h[i],
+               PP_TRACK_MAX_DETS);
+  return 0;
+}
+
+}  // namespace pp
+
+extern "C" long long pp_track_state_bytes(int max_tracks, int K) {
+  using namespace pp;
+  if (max_tracks < 1 || max_tracks > PP_TRACK_MAX_TRACKS || K <= 0) {
+    fail("pp_track_state_bytes: max_tracks=%d (1..%d), K=%d", max_tracks, PP_TRACK_MAX_TRACKS, K);
+    return -1;
+  }
+  return track_state_bytes(max_tracks, K);
+}
+
+extern "C" int pp_track_oks(int n_str, int K, int max_tracks, long long Dtot, const long long *host_off,
+                            const void *det_stream, const void *blocks, const void *kpts, const void *vis,
+                            const void *area, const void *vars, double vis_thr, void *oks, void *stream) {
+  using namespace pp;
+  if (int rc = track_check_common("pp_track_oks", n_str, K, max_tracks, Dtot)) return rc;
+  PP_REQUIRE(!vis || vis_thr == vis_thr, "pp_track_oks: vis_thr is not a number");
+  PP_REQUIRE(det_stream && blocks && kpts && area && vars && oks, "pp_track_oks: null argument");
+  if (int rc = track_check_offsets("pp_track_oks", n_str, host_off, Dtot)) return rc;
+  if (n_str == 0 || Dtot == 0) return 0;
+  const long long lanes = Dtot * max_tracks, grid = (lanes + kTrackThreads - 1) / kTrackThreads;
+  PP_REQUIRE(grid < (1ll << 31), "pp_track_oks: %lld pairs exceed one grid", lanes);
+  hipLaunchKernelGGL(track_oks_kernel, dim3((unsigned)grid), dim3(kTrackThreads), 0, (hipStream_t)stream, K,
+                     max_tracks, Dtot, (const long long *)det_stream, (const long long *)blocks, (const double *)kpts,
+                     (const double *)vis, (const double *)area, (const double *)vars, vis_thr, (double *)oks);
+  PP_CHECK_LAUNCH("track_oks_kernel");
+  return 0;
+}
+
+extern "C" int pp_track_assign(int n_str, int K, int max_tracks, long long Dtot, const long long *host_off,
+                               const void *off, const void *blocks, const void *oks, const void *area,
+                               double match_thr, int max_age, double t, double t_prev, void *ids, void *match_oks,
+                               void *born, void *slot_of, void *te, void *stream) {
+  using namespace pp;
+  if (int rc = track_check_common("pp_track_assign", n_str, K, max_tracks, Dtot)) return rc;
+  PP_REQUIRE(match_thr >= 0.0 && match_thr < 1.0, "pp_track_assign: match_thr=%g is outside [0, 1)", match_thr);
+  PP_REQUIRE(max_age >= 0, "pp_track_assign: max_age=%d", max_age);
+  PP_REQUIRE(t - t_prev > 0.0 && t < INFINITY,
+             "pp_track_assign: te <= 0 (t=%g after t_prev=%g)", t, t_prev);
+  PP_REQUIRE(off && blocks && oks && area && ids && match_oks && born && slot_of && te,
+             "pp_track_assign: null argument");
+  if (int rc = track_check_offsets("pp_track_assign", n_str, host_off, Dtot)) return rc;
+  if (n_str == 0) return 0;                                // a stream without detections still ages its tracks
+  const unsigned grid = (unsigned)((n_str + kTrackWaves - 1) / kTrackWaves);
+  hipLaunchKernelGGL(track_assign_kernel, dim3(grid), dim3(64 * kTrackWaves), 0, (hipStream_t)stream, n_str, K,
+                     max_tracks, (const long long *)off, (const long long *)blocks, (const double *)oks,
+                     (const double *)area, match_thr, max_age, t, (long long *)ids, (double *)match_oks,
+                     (unsigned char *)born, (int *)slot_of, (double *)te);
+  PP_CHECK_LAUNCH("track_assign_kernel");
+  return 0;
+}
+
+extern "C" int pp_track_filter(int K, int max_tracks, long long Dtot, const void *det_stream, const void *blocks,
+                               const void *kpts, const void *vis, double vis_thr, const void *slot_of,
+                               const void *born, const void *te, int smooth, double min_cutoff, double beta,
+                               double d_cutoff, void *out, void *stream) {
+  using namespace pp;
+  if (int rc = track_check_common("pp_track_filter", 0, K, max_tracks, Dtot)) return rc;
+  PP_REQUIRE(!vis || vis_thr == vis_thr, "pp_track_filter: vis_thr is not a number");
+  if (smooth)
+    PP_REQUIRE(min_cutoff > 0.0 && d_cutoff > 0.0 && beta >= 0.0 && min_cutoff < INFINITY && d_cutoff < INFINITY &&
+                   beta < INFINITY,
+               "pp_track_filter: min_cutoff=%g, d_cutoff=%g (both > 0), beta=%g (>= 0) must be finite", min_cutoff,
+               d_cutoff, beta);
+  PP_REQUIRE(det_stream && blocks && kpts && slot_of && born && te && out, "pp_track_filter: null argument");
+  if (Dtot == 0) return 0;
+  const long long lanes = Dtot * K, grid = (lanes + kTrackThreads - 1) / kTrackThreads;
+  PP_REQUIRE(grid < (1ll << 31), "pp_track_filter: %lld keypoints exceed one grid", lanes);
+  hipLaunchKernelGGL(track_filter_kernel, dim3((unsigned)grid), dim3(kTrackThreads), 0, (hipStream_t)stream, K,
+                     max_tracks, Dtot, (const long long *)det_stream, (const long long *)blocks, (const double *)kpts,
+                     (const double *)vis, vis_thr, (const int *)slot_of, (const unsigned char *)born,
+                     (const double *)te, smooth, min_cutoff, beta, d_cutoff, (double *)out);
+  PP_CHECK_LAUNCH("track_filter_kernel");
+  return 0;
+}

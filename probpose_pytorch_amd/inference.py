@@ -21,11 +21,17 @@ function, ``run_inference``: ``Codec(ProbMap(input_size, heatmap_size, sigmas))`
   (``viz.draw_keypoints``: a red disc of radius 5 at every keypoint whose probability is at least
   ``--render-threshold``, 0.9 as in the reference; no text labels).  With ``--boxes`` the picture is the frame with
   every pose (with ``--nms``: every kept pose) at its frame coordinates, with the COCO skeleton for 17 keypoints.
-  Without ``--render`` nothing changes: the ``.npy`` dumps stay.
+  Without ``--render`` nothing changes: the ``.npy`` dumps stay;
+* ``--frames DIR --boxes-json FILE --track`` runs the box path on every image file of DIR in sorted name order, as the
+  frames of one video stream, with the boxes FILE gives per file name (``{name: [[x, y, w, h, score], ...]}``), and
+  links the poses across the frames (``tracker.PoseTracker``; ``--match-thr``, ``--max-age``, ``--fps``; ``--smooth
+  [min_cutoff,beta,d_cutoff]`` adds the One-Euro filter).  ``--output`` gets ``tracks.json``: per frame and kept
+  detection its track id and (smoothed) keypoints; with ``--render`` also one picture per frame, drawn from those.
 """
 from __future__ import annotations
 
 import argparse
+import json
 from pathlib import Path
 
 import numpy as np
@@ -190,6 +196,17 @@ def main(argv=None):
     p.add_argument("--nms", type=str, default=None, choices=["hard", "soft_gaussian", "soft_linear"],
                    help="with --boxes: rescore the poses and suppress duplicates by OKS after decode (default: off)")
     p.add_argument("--nms-thr", type=float, default=0.9, help="OKS threshold of --nms")
+    p.add_argument("--frames", type=Path, default=None,
+                   help="folder of image files: the frames of one stream, in sorted name order (with --boxes-json)")
+    p.add_argument("--boxes-json", type=Path, default=None,
+                   help="with --frames: JSON {file name: [[x, y, w, h, score], ...]}, the person boxes of every frame")
+    p.add_argument("--track", action="store_true",
+                   help="with --frames: link the poses across the frames by OKS; writes tracks.json to --output")
+    p.add_argument("--smooth", type=str, nargs="?", const="", default=None, metavar="MIN_CUTOFF,BETA,D_CUTOFF",
+                   help="with --track: One-Euro smoothing of the tracked keypoints (no value: the defaults)")
+    p.add_argument("--match-thr", type=float, default=0.3, help="OKS a pose needs to continue a track")
+    p.add_argument("--max-age", type=int, default=30, help="frames a track survives unseen")
+    p.add_argument("--fps", type=float, default=30.0, help="frame rate of --frames: the time base of --smooth")
     p.add_argument("--render", action="store_true",
                    help="with --output: also write heatmap_{i}.png and output_image.png, drawn on the GPU")
     p.add_argument("--render-threshold", type=float, default=0.9,
@@ -202,7 +219,8 @@ def main(argv=None):
             boxes = parse_boxes(args.boxes)
         except ValueError as e:
             p.error(f"--boxes: {e}")
-    if args.nms is not None and boxes is None:
+    track = _track_options(p, args)
+    if args.nms is not None and boxes is None and track is None:
         p.error("--nms needs --boxes (it applies to the box path)")
     if not 0.0 < args.nms_thr <= 1.0:
         p.error(f"--nms-thr: {args.nms_thr} is outside (0, 1]")
@@ -224,6 +242,8 @@ def main(argv=None):
         model.set_compute_dtype(torch.bfloat16)
     model.set_flip_test(flip_pairs)
     codec = Codec(ProbMap(input_size, heatmap_size, np.array([args.sigma] * args.num_keypoints)))
+    if track is not None:
+        return _main_frames(args, model, codec, track)
     if boxes is not None:
         return _main_boxes(args, model, codec, boxes)
     if args.image is not None:
@@ -287,6 +307,96 @@ def _main_boxes(args, model, codec, boxes):
         args.output.mkdir(parents=True, exist_ok=True)
         save_png(drawn, args.output / "output_image.png")
     return out
+
+
+def _track_options(p, args):
+    """The tracking options of the command line, checked: None without --track, else dict(files, boxes, smooth)."""
+    if not args.track:
+        for flag, given in (("--frames", args.frames is not None), ("--boxes-json", args.boxes_json is not None),
+                            ("--smooth", args.smooth is not None)):
+            if given:
+                p.error(f"{flag} needs --track")
+        return None
+    if args.frames is None:
+        p.error("--track needs --frames (a folder of image files)")
+    if args.boxes_json is None:
+        p.error("--track needs --boxes-json (the person boxes of every frame)")
+    if args.image is not None or args.boxes is not None:
+        p.error("--track takes its images from --frames and its boxes from --boxes-json, not --image / --boxes")
+    if args.output is None:
+        p.error("--track needs --output (the folder tracks.json goes to)")
+    if not 0.0 <= args.match_thr < 1.0:
+        p.error(f"--match-thr: {args.match_thr} is outside [0, 1)")
+    if args.max_age < 0:
+        p.error(f"--max-age: {args.max_age} is negative")
+    if not (np.isfinite(args.fps) and args.fps > 0):
+        p.error(f"--fps: {args.fps} is not a positive number")
+    from .tracker import OneEuro
+    smooth = None
+    if args.smooth is not None:
+        try:
+            values = [float(v) for v in args.smooth.split(",") if v.strip()]
+            if len(values) not in (0, 3):
+                raise ValueError(f"{args.smooth!r} is not min_cutoff,beta,d_cutoff")
+            smooth = OneEuro(*values)
+        except (TypeError, ValueError) as e:
+            p.error(f"--smooth: {e}")
+    if not args.frames.is_dir():
+        p.error(f"--frames: {args.frames} is not a folder")
+    files = sorted(f for f in args.frames.iterdir() if f.is_file())
+    if not files:
+        p.error(f"--frames: {args.frames} holds no file")
+    try:
+        table = json.loads(args.boxes_json.read_text())
+        boxes = {}
+        for f in files:
+            rows = np.asarray(table.get(f.name, []), dtype=np.float64).reshape(-1, 5)
+            if rows.size and (rows[:, 2:4] <= 0).any():
+                raise ValueError(f"{f.name}: a box without positive w, h")
+            boxes[f.name] = rows
+    except (OSError, ValueError, AttributeError) as e:
+        p.error(f"--boxes-json: {e}")
+    return dict(files=files, boxes=boxes, smooth=smooth)
+
+
+def _main_frames(args, model, codec, track):
+    """--frames / --track: the box path on every frame, the tracker behind it; tracks.json and, with --render, one
+    picture per frame."""
+    from .tracker import PoseTracker
+    K, dev = args.num_keypoints, "cuda"
+    sigmas = np.array([args.sigma] * K)
+    nms = None
+    if args.nms is not None:
+        from .posenms import PoseNMS
+        nms = PoseNMS(sigmas, mode=args.nms, oks_thr=args.nms_thr)
+    tracker = PoseTracker(sigmas, match_thr=args.match_thr, max_age=args.max_age, smooth=track["smooth"], fps=args.fps)
+    args.output.mkdir(parents=True, exist_ok=True)
+    record = []
+    for path in track["files"]:
+        frame, rows = load_frame(path), track["boxes"][path.name]
+        n = rows.shape[0]
+        kpts, probs = torch.zeros((0, K, 2), dtype=torch.float64, device=dev), np.zeros((0, K))
+        areas = scores = torch.zeros(0, dtype=torch.float64, device=dev)
+        if n:
+            out = run_inference_on_boxes(model, codec, frame.to(dev), rows[:, :4], nms=nms, box_scores=rows[:, 4])
+            kept = out[3].keep.cpu().numpy() if nms is not None else np.ones(n, dtype=bool)
+            kpts = torch.from_numpy(out[2][kept]).to(dev)
+            areas = torch.from_numpy((rows[:, 2] * rows[:, 3])[kept]).to(dev)
+            scores = out[3].scores[out[3].keep] if nms is not None else torch.from_numpy(rows[:, 4]).to(dev)
+            probs = np.asarray(out[1][1], dtype=np.float64).reshape(-1, K)[kept]
+        res = tracker.update(kpts, areas, scores)
+        ids, smoothed = res.ids.cpu().numpy(), res.keypoints.cpu().numpy()
+        record.append(dict(frame=path.name, detections=[dict(id=int(i), keypoints=k.tolist())
+                                                        for i, k in zip(ids, smoothed)]))
+        print(f"{path.name}: ids {ids.tolist()}")
+        if args.render:
+            from . import viz
+            drawn = viz.draw_keypoints(frame.numpy(), smoothed, probs, threshold=args.render_threshold,
+                                       skeleton=viz.COCO17_SKELETON if K == 17 else None,
+                                       image_index=np.zeros(smoothed.shape[0], dtype=np.int64))
+            save_png(drawn, args.output / f"{path.stem}_tracked.png")
+    (args.output / "tracks.json").write_text(json.dumps(record))
+    return record
 
 
 if __name__ == "__main__":

@@ -1,0 +1,321 @@
+"""Identity and temporal smoothing for poses on video: greedy OKS association of a frame's poses with the tracks of
+its stream, and a One-Euro filter per keypoint coordinate, on the GPU.  It reads what ``Codec.decode`` and ``PoseNMS``
+leave on the device and keeps its state there, with the three launches of csrc/pp_track.hip per ``update``:
+
+  pp_track_oks      one lane per (detection, slot): every pair OKS of the call
+  pp_track_assign   one wave per stream; lane j % 64 owns slot j: association, ageing, births, ids
+  pp_track_filter   one lane per (detection, keypoint): the One-Euro step, the output and the slot's new state
+
+Between them run torch device ops that do not synchronise: casts to float64, PoseNMS's two stable sorts (descending
+score, then stream) and gathers.
+
+Rules (restated in tests/track_reference.py, the gauge this module is tested against), float64 throughout.  State per
+stream: ``max_tracks`` slots (id, age, t_last, area, raw keypoints and visibilities, filter state xhat, dxhat, init) and
+the counters next_id and overflow.  For every stream a call names:
+* detections are visited by descending score, equal scores in the order they were given;
+* the OKS of a detection and a live slot (id >= 0 when the call begins) is PoseNMS's pair OKS with the slot's stored raw
+  keypoints, area and visibilities as the second detection;
+* each detection, in visiting order, takes the live slot not yet taken in this call with the largest OKS (the lowest
+  slot on equal OKS) if that OKS is > ``match_thr``;
+* then every live slot not taken ages by one and is freed when its age exceeds ``max_age``;
+* a matched detection gets the slot's id and its keypoints go through the One-Euro step with te = t - t_last; a keypoint
+  that does not count in this frame (visibility <= ``vis_thr``) is passed through raw and its filter is re-initialised
+  when it counts again;
+* then each unmatched detection, in visiting order, takes the lowest free slot (those just freed included) with a new
+  id from the stream's counter; with no slot free it gets id -1 and counts in ``overflow``.
+
+There is no CPU fallback: without a GPU ``update`` raises ``_lib.HipExtensionError``.
+"""
+from __future__ import annotations
+
+from functools import partial
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._buffers import host_array as _host, room as _room, upload
+from .posenms import _first_seen
+
+MAX_TRACKS = _lib.PP_TRACK_MAX_TRACKS
+MAX_DETS_PER_STREAM = _lib.PP_TRACK_MAX_DETS
+STREAMS_PER_CHUNK = 16
+
+
+class OneEuro:
+    """The constants of the One-Euro filter (Casiez et al. 2012): the cutoff at rest, its growth with speed, and the
+    cutoff of the speed estimate, in Hz, 1 / (unit / second) and Hz."""
+    __slots__ = ("min_cutoff", "beta", "d_cutoff")
+
+    def __init__(self, min_cutoff: float = 1.0, beta: float = 0.05, d_cutoff: float = 1.0):
+        for name, v in (("min_cutoff", min_cutoff), ("beta", beta), ("d_cutoff", d_cutoff)):
+            if not np.isfinite(v):
+                raise ValueError(f"{name}: {v} is not finite")
+        if not min_cutoff > 0:
+            raise ValueError(f"min_cutoff: {min_cutoff} is not positive")
+        if not d_cutoff > 0:
+            raise ValueError(f"d_cutoff: {d_cutoff} is not positive")
+        if beta < 0:
+            raise ValueError(f"beta: {beta} is negative")
+        self.min_cutoff, self.beta, self.d_cutoff = float(min_cutoff), float(beta), float(d_cutoff)
+
+    def __repr__(self):
+        return f"OneEuro(min_cutoff={self.min_cutoff}, beta={self.beta}, d_cutoff={self.d_cutoff})"
+
+
+def state_layout(max_tracks: int, K: int) -> dict:
+    """name -> (byte offset, numpy dtype, shape) of a stream's state block (include/probpose_hip.h), and "bytes"."""
+    T, pad8 = int(max_tracks), lambda n: (n + 7) & ~7
+    parts = (("id", np.int64, (T,)), ("t_last", np.float64, (T,)), ("area", np.float64, (T,)),
+             ("keypoints", np.float64, (T, K, 2)), ("vis", np.float64, (T, K)), ("xhat", np.float64, (T, K, 2)),
+             ("dxhat", np.float64, (T, K, 2)), ("next_id", np.int64, (1,)), ("overflow", np.int64, (1,)),
+             ("age", np.int32, (T,)), ("init", np.uint8, (T, K)))
+    layout, at = {}, 0
+    for name, dtype, shape in parts:
+        layout[name] = (at, np.dtype(dtype), shape)
+        at += pad8(int(np.prod(shape)) * np.dtype(dtype).itemsize)
+    layout["bytes"] = at
+    return layout
+
+
+class TrackResult:
+    """What ``PoseTracker.update`` returns, in the order the detections were given, on the device: ``ids`` [M] int64
+    (-1 = not tracked), ``keypoints`` [M, K, 2] float64 (smoothed; raw where not smoothed), ``oks`` [M] float64 (with the
+    matched track, 0 otherwise), ``born`` [M] bool; ``stream_ids``: host list in first-seen order."""
+    __slots__ = ("ids", "keypoints", "oks", "born", "stream_ids", "_staged")
+
+    def __init__(self, ids, keypoints, oks, born, stream_ids, staged):
+        self.ids, self.keypoints, self.oks, self.born = ids, keypoints, oks, born
+        self.stream_ids, self._staged = stream_ids, staged
+
+    def __repr__(self):
+        return f"TrackResult({self.ids.shape[0]} detections of {len(self.stream_ids)} streams)"
+
+
+def _check_inputs(named) -> bool:
+    """Mixed placement and non-float dtypes raise ValueError; returns whether everything is on the device."""
+    names = " / ".join(n for n, _ in named)
+    dev = [isinstance(a, torch.Tensor) and a.is_cuda for _, a in named]
+    if any(dev) and not all(dev):
+        raise ValueError(f"{names}: either all device tensors or all host arrays")
+    for n, a in named:
+        floating = a.dtype.is_floating_point if isinstance(a, torch.Tensor) else np.issubdtype(a.dtype, np.floating)
+        if not floating:
+            raise ValueError(f"{n}: expected a float dtype, got {a.dtype}")
+    return all(dev)
+
+
+class PoseTracker:
+    """Tracks of the poses of independent streams (cameras, videos), one frame of each named stream per ``update``.
+
+    ``sigmas`` [K] are the per-keypoint OKS constants; ``match_thr`` in [0, 1) is the OKS a detection needs to continue
+    a track; a track unseen for more than ``max_age`` frames of its stream is dropped; ``max_tracks`` slots per stream;
+    ``vis_thr`` None lets every keypoint count; ``smooth`` is a ``OneEuro`` or None (raw keypoints out); ``fps`` gives
+    the default time stamps."""
+
+    def __init__(self, sigmas, *, match_thr: float = 0.3, max_age: int = 30, max_tracks: int = 64, vis_thr=None,
+                 smooth: OneEuro | None = None, fps: float = 30.0):
+        self.sigmas = _host(sigmas, "sigmas", np.float64).reshape(-1)
+        if self.sigmas.size == 0 or not np.all(np.isfinite(self.sigmas)) or np.any(self.sigmas <= 0):
+            raise ValueError("sigmas: need K > 0 finite positive values")
+        self.K = int(self.sigmas.size)
+        if not 0.0 <= float(match_thr) < 1.0:
+            raise ValueError(f"match_thr: {match_thr} is outside [0, 1)")
+        if int(max_age) < 0:
+            raise ValueError(f"max_age: {max_age} is negative")
+        if not 1 <= int(max_tracks) <= MAX_TRACKS:
+            raise ValueError(f"max_tracks: {max_tracks} is outside 1..{MAX_TRACKS}")
+        if vis_thr is not None and not np.isfinite(vis_thr):
+            raise ValueError(f"vis_thr: {vis_thr} is not finite")
+        if smooth is not None and not isinstance(smooth, OneEuro):
+            raise ValueError(f"smooth: expected a OneEuro or None, got {type(smooth).__name__}")
+        if not (np.isfinite(fps) and fps > 0):
+            raise ValueError(f"fps: {fps} is not a positive number")
+        self.match_thr, self.max_age, self.max_tracks = float(match_thr), int(max_age), int(max_tracks)
+        self.vis_thr = None if vis_thr is None else float(vis_thr)
+        self.smooth, self.fps = smooth, float(fps)
+        self.layout = state_layout(self.max_tracks, self.K)
+        self._index = {}            # stream id -> its number, in first-seen order
+        self._chunks = []           # uint8 [STREAMS_PER_CHUNK, bytes]: state is never reallocated, only added to
+        self._device = None
+        self._calls = 0
+        self._t_prev = -np.inf
+
+    # ------------------------------------------------------------------------------------------- state
+    def _block(self, n: int) -> torch.Tensor:
+        return self._chunks[n // STREAMS_PER_CHUNK][n % STREAMS_PER_CHUNK]
+
+    def _field(self, block: torch.Tensor, name: str) -> torch.Tensor:
+        at, dtype, shape = self.layout[name]
+        nbytes = int(np.prod(shape)) * dtype.itemsize
+        return block[..., at:at + nbytes].view(getattr(torch, dtype.name))
+
+    def _clear(self, block: torch.Tensor) -> None:
+        block.zero_()
+        self._field(block, "id").fill_(-1)
+
+    def _number(self, stream, device) -> int:
+        n = self._index.get(stream)
+        if n is None:
+            n = self._index[stream] = len(self._index)
+            if n // STREAMS_PER_CHUNK == len(self._chunks):
+                assert _lib.call("pp_track_state_bytes", self.max_tracks, self.K) == self.layout["bytes"]
+                chunk = torch.empty((STREAMS_PER_CHUNK, self.layout["bytes"]), dtype=torch.uint8, device=device)
+                self._clear(chunk)
+                self._chunks.append(chunk)
+        return n
+
+    def reset(self, stream=None) -> None:
+        """Forget one stream's tracks, or every stream's: its slots are free and its ids restart at 0."""
+        if stream is None:
+            for chunk in self._chunks:
+                self._clear(chunk)
+        elif stream in self._index:
+            self._clear(self._block(self._index[stream]))
+
+    def tracks(self, stream) -> dict:
+        """Debugging read-back (synchronises): host arrays over the stream's ``max_tracks`` slots: id (-1 = free), age,
+        t_last, area, keypoints (raw), and the filter state xhat, dxhat, init."""
+        if stream not in self._index:
+            raise KeyError(f"stream: {stream!r} has not been seen")
+        raw = self._block(self._index[stream]).cpu().numpy()
+        out = {}
+        for name in ("id", "age", "t_last", "area", "keypoints", "xhat", "dxhat", "init"):
+            at, dtype, shape = self.layout[name]
+            out[name] = raw[at:at + int(np.prod(shape)) * dtype.itemsize].view(dtype).reshape(shape).copy()
+        return out
+
+    @property
+    def overflow(self) -> torch.Tensor:
+        """Device int64 [number of streams seen so far]: the detections that found no free slot, per stream in
+        first-seen order."""
+        n = len(self._index)
+        if not n:
+            return torch.zeros(0, dtype=torch.int64, device=self._device or "cpu")
+        return torch.cat([self._field(c, "overflow").reshape(-1) for c in self._chunks])[:n]
+
+    # ------------------------------------------------------------------------------------------- update
+    def _launch(self, n_str, off, off_dev, det_stream, blocks, kp_s, vis_s, ar_s, variances, t_now, t_prev):
+        """The three launches on a batch in visiting order: (ids [M] int64, oks [M] float64, born [M] uint8, keypoints
+        [M, K, 2] float64), still in that order."""
+        K, T, M, dev = self.K, self.max_tracks, int(off[-1]), kp_s.device
+        new = partial(torch.empty, device=dev)
+        oks_ws = new(M * T, dtype=torch.float64)
+        ids_s, oks_s = new(M, dtype=torch.int64), new(M, dtype=torch.float64)
+        born_s, slot_s, te_s = new(M, dtype=torch.uint8), new(M, dtype=torch.int32), new(M, dtype=torch.float64)
+        out_s = new((M, K, 2), dtype=torch.float64)
+        vis_thr = 0.0 if self.vis_thr is None else self.vis_thr
+        vis_hold = None if vis_s is None else _room(vis_s)
+        hold = [_room(x) for x in (det_stream, kp_s, ar_s, oks_ws, ids_s, oks_s, born_s, slot_s, te_s, out_s)]
+        det_stream_h, kp_h, ar_h, ws_h, ids_h, oks_h, born_h, slot_h, te_h, out_h = hold
+        _lib.launch("pp_track_oks", n_str, K, T, M, off, det_stream_h, _room(blocks), kp_h, vis_hold, ar_h, variances,
+                    vis_thr, ws_h)
+        _lib.launch("pp_track_assign", n_str, K, T, M, off, off_dev, _room(blocks), ws_h, ar_h, self.match_thr,
+                    self.max_age, t_now, t_prev, ids_h, oks_h, born_h, slot_h, te_h)
+        sm = self.smooth
+        _lib.launch("pp_track_filter", K, T, M, det_stream_h, _room(blocks), kp_h, vis_hold, vis_thr, slot_h, born_h,
+                    te_h, int(sm is not None), *((sm.min_cutoff, sm.beta, sm.d_cutoff) if sm else (1.0, 0.0, 1.0)),
+                    out_h)
+        return ids_s, oks_s, born_s, out_s
+
+    def update(self, keypoints, areas, scores, kpt_scores=None, *, stream_ids=None, t=None, streams=None):
+        """One frame of every named stream: keypoints [M, K, 2|3], areas [M], scores [M], kpt_scores [M, K] or None:
+        device tensors of any float dtype.  ``stream_ids`` [M] says which stream a detection belongs to (host
+        bookkeeping, like PoseNMS's image ids; None: one stream, id 0).  ``streams`` lists the streams this call names
+        when some of them may have no detection (they still age); by default those are the streams of ``stream_ids`` in
+        first-seen order.  A stream the call does not name is untouched.  ``t`` is the frame time in seconds (default:
+        (number of update calls so far + 1) / fps) and must increase strictly from call to call.
+
+        With ``kpt_scores`` they are the visibilities ``vis_thr`` reads, otherwise a third keypoint column is.  Apart
+        from one finiteness boolean per input nothing is read back and nothing waits for the device."""
+        K, T = self.K, self.max_tracks
+        named = [("keypoints", keypoints), ("areas", areas), ("scores", scores)]
+        if kpt_scores is not None:
+            named.append(("kpt_scores", kpt_scores))
+        named = [(n, a if isinstance(a, torch.Tensor) else np.asarray(a)) for n, a in named]
+        shape = tuple(named[0][1].shape)
+        if len(shape) != 3 or shape[1] != K or shape[2] not in (2, 3):
+            raise ValueError(f"keypoints: expected [M, {K}, 2|3] (K = len(sigmas)), got {shape}")
+        M = shape[0]
+        for n, a in named[1:3]:
+            if tuple(a.shape) != (M,):
+                raise ValueError(f"{n}: expected [{M}], got {tuple(a.shape)}")
+        if kpt_scores is not None and tuple(named[3][1].shape) != (M, K):
+            raise ValueError(f"kpt_scores: expected [{M}, {K}], got {tuple(named[3][1].shape)}")
+        if self.vis_thr is not None and kpt_scores is None and shape[2] != 3:
+            raise ValueError("vis_thr: needs visibilities, kpt_scores or a third keypoint column")
+        if stream_ids is None:
+            ids = np.zeros(M, dtype=np.int64)
+        else:
+            ids = (stream_ids.detach().cpu().numpy() if isinstance(stream_ids, torch.Tensor)
+                   else np.asarray(stream_ids))
+            if ids.shape != (M,):
+                raise ValueError(f"stream_ids: expected [{M}], got {ids.shape}")
+        if streams is None:
+            stream_list, pos = _first_seen(ids) if (M or stream_ids is not None) else ([0], np.zeros(0, np.int64))
+        else:
+            stream_list = list(streams)
+            where = {s: i for i, s in enumerate(stream_list)}
+            if len(where) != len(stream_list):
+                raise ValueError("streams: a stream is named twice")
+            missing = [s for s in ids.tolist() if s not in where]
+            if missing:
+                raise ValueError(f"stream_ids: stream {missing[0]!r} is not in streams")
+            pos = np.fromiter((where[s] for s in ids.tolist()), dtype=np.int64, count=M)
+        n_str = len(stream_list)
+        d_cnt = np.bincount(pos, minlength=n_str).astype(np.int64) if n_str else np.zeros(0, dtype=np.int64)
+        if n_str and int(d_cnt.max()) > MAX_DETS_PER_STREAM:
+            worst = int(d_cnt.argmax())
+            raise ValueError(f"stream_ids: stream {stream_list[worst]!r} has {int(d_cnt[worst])} detections, more "
+                             f"than the {MAX_DETS_PER_STREAM} that PoseTracker takes per stream and call")
+        t_now = (self._calls + 1) / self.fps if t is None else float(t)
+        if not (np.isfinite(t_now) and t_now > self._t_prev):
+            raise ValueError(f"t: {t_now} is not greater than the previous call's {self._t_prev}")
+        on_device = _check_inputs(named)
+        if not on_device:
+            _lib.require_device()
+            raise _lib.HipExtensionError("keypoints / areas / scores: expected tensors on the GPU (cuda/HIP device); "
+                                         "there is no CPU fallback")
+        tensors = [a.detach().to(torch.float64).contiguous() for _, a in named]
+        finite = torch.stack([torch.isfinite(x).all() for x in tensors]).cpu().numpy()      # the one read-back
+        for (n, _), ok in zip(named, finite):
+            if not bool(ok):
+                raise ValueError(f"{n}: non-finite values")
+        kp3, ar, sc = tensors[:3]
+        dev = kp3.device
+        if self._device is None:
+            self._device = dev
+        elif dev != self._device:
+            raise ValueError(f"keypoints: on {dev}, the tracker's state is on {self._device}")
+        if self.vis_thr is None:
+            vis = None
+        else:
+            vis = tensors[3] if kpt_scores is not None else kp3[..., 2]
+
+        off = np.zeros(n_str + 1, dtype=np.int64)
+        off[1:] = np.cumsum(d_cnt)
+        numbers = [self._number(s, dev) for s in stream_list]
+        addresses = np.array([self._block(n).data_ptr() for n in numbers], dtype=np.int64)
+
+        staged = []
+        up = partial(upload, device=dev, keep=staged)
+        # descending score, then stream: PoseNMS's two stable sorts
+        by_score = torch.sort(sc, descending=True, stable=True).indices
+        pos_dev = up(pos)
+        by_stream = torch.sort(pos_dev[by_score], stable=True).indices
+        perm = by_score[by_stream]
+        kp_s = kp3[..., :2][perm].contiguous()
+        vis_s = None if vis is None else vis[perm].contiguous()
+        ar_s, det_stream = ar[perm].contiguous(), pos_dev[perm].contiguous()
+        variances, off_dev, blocks = up((self.sigmas * 2) ** 2), up(off), up(addresses)
+
+        ids_s, oks_s, born_s, out_s = self._launch(n_str, off, off_dev, det_stream, blocks, kp_s, vis_s, ar_s, variances,
+                                                   t_now, self._t_prev)
+        self._calls += 1
+        self._t_prev = t_now
+
+        new = partial(torch.empty, device=dev)
+        ids_out, oks_out = torch.empty_like(ids_s), torch.empty_like(oks_s)
+        born_out, kp_out = new(M, dtype=torch.bool), torch.empty_like(out_s)
+        ids_out[perm], oks_out[perm], born_out[perm], kp_out[perm] = ids_s, oks_s, born_s.to(torch.bool), out_s
+        return TrackResult(ids_out, kp_out, oks_out, born_out, stream_list, staged)
