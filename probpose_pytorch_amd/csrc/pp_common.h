@@ -116,6 +116,53 @@ __device__ __forceinline__ int wave_min(int v) {
   return v;
 }
 
+// ---- np.argmax order -------------------------------------------------------
+// The running result of a flat arg-max with numpy's semantics: the first maximum in row-major order wins; a NaN is the
+// maximum, and the first NaN wins.
+struct ArgmaxBest {
+  float v;
+  int i;
+  // "nothing seen yet": every real (v, i) -- NaN included -- is ahead of it, so it never wins a reduction
+  static __device__ __forceinline__ ArgmaxBest none() { return ArgmaxBest{-__builtin_inff(), 0x7fffffff}; }
+};
+
+// is (av, ai) strictly ahead of (bv, bi) in np.argmax's order?
+__device__ __forceinline__ bool argmax_ahead(float av, int ai, float bv, int bi) {
+  bool an = av != av, bn = bv != bv;
+  if (an || bn) {
+    if (an && bn) return ai < bi;
+    return an;
+  }
+  return av > bv || (av == bv && ai < bi);
+}
+
+__device__ __forceinline__ void argmax_take(ArgmaxBest &b, float v, int i) {
+  if (argmax_ahead(v, i, b.v, b.i)) {
+    b.v = v;
+    b.i = i;
+  }
+}
+
+// every thread of the workgroup (whole waves) returns the workgroup's best
+__device__ __forceinline__ ArgmaxBest block_argmax(ArgmaxBest mine, ArgmaxBest *red /* [waves] in LDS */) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    float ov = __shfl_down(mine.v, o, 64);
+    int oi = __shfl_down(mine.i, o, 64);
+    if (argmax_ahead(ov, oi, mine.v, mine.i)) {
+      mine.v = ov;
+      mine.i = oi;
+    }
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  if (lane == 0) red[wave] = mine;
+  __syncthreads();
+  ArgmaxBest r = red[0];
+  for (int w = 1; w < nw; ++w)
+    if (argmax_ahead(red[w].v, red[w].i, r.v, r.i)) r = red[w];
+  return r;
+}
+
 inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
 // Raise a kernel's dynamic-LDS limit to `bytes` on the calling thread's current device, once per (kernel, device): the

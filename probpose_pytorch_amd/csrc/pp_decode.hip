@@ -33,42 +33,8 @@ __device__ __forceinline__ int reflect_idx(int i, int n) {
 }
 
 // single reflection, valid while -n <= i < 2n (always true for |offset| <= radius <= n): no division
-__device__ __forceinline__ int reflect_once(int i, int n) {
+constexpr __host__ __device__ __forceinline__ int reflect_once(int i, int n) {
   return i < 0 ? -i - 1 : (i >= n ? 2 * n - 1 - i : i);
-}
-
-struct Best {
-  float v;
-  int i;
-};
-
-// a strictly better than b under np.argmax semantics
-__device__ __forceinline__ bool better(float av, int ai, float bv, int bi) {
-  bool an = av != av, bn = bv != bv;
-  if (an || bn) {
-    if (an && bn) return ai < bi;
-    return an;
-  }
-  return av > bv || (av == bv && ai < bi);
-}
-
-__device__ __forceinline__ Best block_argmax(Best mine, Best *red /* [waves] in LDS */) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    float ov = __shfl_down(mine.v, o, 64);
-    int oi = __shfl_down(mine.i, o, 64);
-    if (better(ov, oi, mine.v, mine.i)) {
-      mine.v = ov;
-      mine.i = oi;
-    }
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  if (lane == 0) red[wave] = mine;
-  __syncthreads();
-  Best r = red[0];
-  for (int w = 1; w < nw; ++w)
-    if (better(red[w].v, red[w].i, r.v, r.i)) r = red[w];
-  return r;
 }
 
 struct DecodeOut {
@@ -80,13 +46,32 @@ struct DecodeOut {
   double *packed;   // [B*K][7] f64: x, y (input space), score, prob, vis, oks, err: the record the all-gather ships
 };
 
-// Everything after the argmax; one thread.  c(y,x) reads the float32 convolved map.
+// What every decode form is given.  finalize() and the per-map device functions take it by reference.  A kernel takes
+// its fields as separate parameters (PP_DECODE_PARAMS; pp_decode_f32's own parameters carry the same names, so a launch
+// passes PP_DECODE_VALUES) and puts the record together where it hands it on.  Not the record by value: the compiler
+// fetches a by-value aggregate where the kernel starts and cannot move those loads over a barrier to where finalize()
+// reads them, and the pointers in it cannot be __restrict__ (measurements: profiles/decode_refactor_resources.txt).
+struct DecodeArgs {
+  const float *heatmaps;                // [B*K][H][W]
+  const float *prob, *vis, *oks, *err;  // [B*K] each, any of them may be null
+  int B, K, H, W;
+  const double *taps;                   // [K][PP_MAX_TAPS] normalised 1-D Gaussians
+  const int *radius;                    // [K]
+  double den_x, den_y, in_w, in_h;      // kpts = locs / den * in (codec.py:237)
+  DecodeOut o;
+};
+#define PP_DECODE_PARAMS                                                                                        \
+  const float *__restrict__ heatmaps, const float *prob, const float *vis, const float *oks, const float *err,  \
+      int B, int K, int H, int W, const double *__restrict__ taps, const int *__restrict__ radius, double den_x, \
+      double den_y, double in_w, double in_h, DecodeOut o
+#define PP_DECODE_VALUES heatmaps, prob, vis, oks, err, B, K, H, W, taps, radius, den_x, den_y, in_w, in_h, o
+
+// Everything after the argmax; one thread.  c(y,x) reads the float32 convolved map.  H and W come beside the record so
+// that the wave kernel's compile-time shape stays compile-time here.
 template <typename ConvAt>
-__device__ __forceinline__ void finalize(int map, int B, int K, int H, int W, int best_idx,
-                                         ConvAt c, const float *__restrict__ raw_map,
-                                         const float *prob, const float *vis, const float *oks,
-                                         const float *err, double den_x, double den_y,
-                                         double in_w, double in_h, DecodeOut o) {
+__device__ __forceinline__ void finalize(const DecodeArgs &a, int map, int H, int W, int best_idx, ConvAt c,
+                                         const float *__restrict__ raw_map) {
+  const DecodeOut &o = a.o;
   const int x = best_idx % W, y = best_idx / W;
   float fx = (float)x, fy = (float)y;
   if (x > 0 && x < W - 1 && y > 0 && y < H - 1) {  // heatmap.py:120-125
@@ -106,29 +91,44 @@ __device__ __forceinline__ void finalize(int map, int B, int K, int H, int W, in
     o.locs[2 * map + 1] = fy;
   }
   if (o.kpts) {
-    o.kpts[2 * map + 0] = (double)fx / den_x * in_w;  // codec.py:237
-    o.kpts[2 * map + 1] = (double)fy / den_y * in_h;
+    o.kpts[2 * map + 0] = (double)fx / a.den_x * a.in_w;  // codec.py:237
+    o.kpts[2 * map + 1] = (double)fy / a.den_y * a.in_h;
   }
   if (o.scores) o.scores[map] = raw_map[y * W + x];  // heatmap.py:375-379
-  const int BK = B * K;
+  const int BK = a.B * a.K;
   if (o.aux) {
-    if (prob) o.aux[map] = prob[map];
-    if (vis) o.aux[BK + map] = vis[map];
-    if (oks) o.aux[2 * BK + map] = oks[map];
+    if (a.prob) o.aux[map] = a.prob[map];
+    if (a.vis) o.aux[BK + map] = a.vis[map];
+    if (a.oks) o.aux[2 * BK + map] = a.oks[map];
   }
-  if (o.err && err)  // codec.py:260-261: float32 / np.float64 scalar -> float64
-    o.err[map] = (double)err[map] / sqrt((double)(H * H + W * W));
+  if (o.err && a.err)  // codec.py:260-261: float32 / np.float64 scalar -> float64
+    o.err[map] = (double)a.err[map] / sqrt((double)(H * H + W * W));
   if (o.packed) {   // every field exactly as above, widened to f64 (lossless for the f32 ones)
     double *r = o.packed + (size_t)map * 7;
-    r[0] = (double)fx / den_x * in_w;
-    r[1] = (double)fy / den_y * in_h;
+    r[0] = (double)fx / a.den_x * a.in_w;
+    r[1] = (double)fy / a.den_y * a.in_h;
     r[2] = (double)raw_map[y * W + x];
-    r[3] = prob ? (double)prob[map] : 0.0;
-    r[4] = vis ? (double)vis[map] : 0.0;
-    r[5] = oks ? (double)oks[map] : 0.0;
-    r[6] = err ? (double)err[map] / sqrt((double)(H * H + W * W)) : 0.0;
+    r[3] = a.prob ? (double)a.prob[map] : 0.0;
+    r[4] = a.vis ? (double)a.vis[map] : 0.0;
+    r[5] = a.oks ? (double)a.oks[map] : 0.0;
+    r[6] = a.err ? (double)a.err[map] / sqrt((double)(H * H + W * W)) : 0.0;
   }
 }
+
+// The float32 and float64 passes are compiled per radius (2 .. 9, i.e. up to PP_MAX_TAPS = 19 taps); a map's radius is
+// block-uniform.  PP_FOR_RADIUS(r, statement) runs the statement with `R` a compile-time constant.  A macro on purpose:
+// it expands to the plain switch, so the code is what the spelled-out switch gave.
+#define PP_FOR_RADIUS(r, ...)                             \
+  switch (r) { /* block-uniform */                        \
+    case 2: { constexpr int R = 2; __VA_ARGS__; } break;  \
+    case 3: { constexpr int R = 3; __VA_ARGS__; } break;  \
+    case 4: { constexpr int R = 4; __VA_ARGS__; } break;  \
+    case 5: { constexpr int R = 5; __VA_ARGS__; } break;  \
+    case 6: { constexpr int R = 6; __VA_ARGS__; } break;  \
+    case 7: { constexpr int R = 7; __VA_ARGS__; } break;  \
+    case 8: { constexpr int R = 8; __VA_ARGS__; } break;  \
+    default: { constexpr int R = 9; __VA_ARGS__; } break; \
+  }
 
 // ---------------------------------------------------------------------------
 // LDS-resident path: 8 B (f64 row-pass intermediate) + 4 B (f32 map with a reflected 12-column halo,
@@ -137,15 +137,15 @@ __device__ __forceinline__ void finalize(int map, int B, int K, int H, int W, in
 // threads per map, measured: 256 -> 512: 64x48 maps +5 %, 96x72 maps +29 %; 1024: slower on 64x48
 constexpr int DEC_THREADS = 512;
 
-// Row pass + column pass for a compile-time radius R.  Each thread produces 4 adjacent outputs per
-// item from one shared window of 4 + 2R inputs (3.5x fewer LDS reads than one output per thread at
-// R = 9) with 4 independent float64 FMA chains; per output the taps are still accumulated in
-// ascending order, so the result does not depend on the blocking.
 constexpr int DEC_HALO = 12;  // reflected halo columns on each side of a row in LDS: 4 * ceil(9 / 4)
+// padded row of the LDS image of a raw map, in floats: [halo | W (+pad to 4) | halo]
+constexpr __host__ __device__ int padded_row(int W) { return 4 * ((W + 3) >> 2) + 2 * DEC_HALO; }
+__device__ __forceinline__ bool nonfinite(float v) { return !(fabsf(v) <= 3.0e38f); }
 
 // Row pass + column pass for a compile-time radius R.  Each thread produces 4 adjacent outputs per
-// item from one shared window of 4 + 2R inputs with 4 independent float64 FMA chains; per output the
-// taps are accumulated in ascending order, so the result does not depend on the blocking.
+// item from one shared window of 4 + 2R inputs (3.5x fewer LDS reads than one output per thread at
+// R = 9) with 4 independent float64 FMA chains; per output the taps are accumulated in ascending
+// order, so the result does not depend on the blocking.
 // The raw map sits in LDS with a reflected halo (rawp, row stride WP), so every row window is read
 // with 16-B aligned, lane-consecutive ds_read_b128: the stride-4 scalar reads this replaces were an
 // 8-way LDS bank conflict and made the row pass LDS-bound.
@@ -239,8 +239,8 @@ __device__ __forceinline__ void conv_passes(const float *__restrict__ rawp, int 
           buf[p] = cv;  // the raw copy is dead after the row pass
           if (out_conv_map) out_conv_map[p] = cv;
           // rows ascend, so within a thread a later pixel always has the larger flat index: a strict
-          // '>' keeps the first maximum; NaN handling stays in better()
-          if (!have || better(cv, p, best_v, best_i)) {
+          // '>' keeps the first maximum; NaN handling stays in argmax_ahead()
+          if (!have || argmax_ahead(cv, p, best_v, best_i)) {
             best_v = cv;
             best_i = p;
             have = true;
@@ -258,23 +258,21 @@ __device__ __forceinline__ void conv_passes(const float *__restrict__ rawp, int 
 }
 
 template <int NT>
-__device__ __forceinline__ void decode_lds_map(
-    const int map, char *smem, Best *red, const float *__restrict__ heatmaps, const float *prob, const float *vis,
-    const float *oks, const float *err, int B, int K, int H, int W, const double *__restrict__ taps,
-    const int *__restrict__ radius, double den_x, double den_y, double in_w, double in_h,
-    DecodeOut o, float *__restrict__ out_conv) {
-  const int HW = H * W;
-  const int WP = 4 * ((W + 3) >> 2) + 2 * DEC_HALO;              // padded row: [halo | W (+pad to 4) | halo]
+__device__ __forceinline__ void decode_lds_map(const DecodeArgs &a, const int map, char *smem, ArgmaxBest *red,
+                                               float *__restrict__ out_conv) {
+  const int H = a.H, W = a.W, HW = H * W;
+  const int WP = padded_row(W);
   double *tmp = reinterpret_cast<double *>(smem);               // [HW] f64 row-pass result
   float *rawp = reinterpret_cast<float *>(smem + (size_t)HW * 8);  // [H][WP] f32 raw map + reflected halo
   float *buf = rawp;                                             // [HW] f32 convolved map (raw is dead by then)
 
-  const int k = map % K;
-  const float *__restrict__ src = heatmaps + (size_t)map * HW;
+  const int k = map % a.K;
+  const float *__restrict__ src = a.heatmaps + (size_t)map * HW;
+  const double *__restrict__ taps = a.taps;
   const int tid = threadIdx.x;
 
   // taps and radius are block-uniform: scalar loads issued now, their latency hides under the map load
-  const int r = __builtin_amdgcn_readfirstlane(radius[k]);
+  const int r = __builtin_amdgcn_readfirstlane(a.radius[k]);
   double wk[PP_MAX_TAPS];
 #pragma unroll
   for (int j = 0; j < PP_MAX_TAPS; ++j) wk[j] = taps[k * PP_MAX_TAPS + j];
@@ -312,42 +310,24 @@ __device__ __forceinline__ void decode_lds_map(
   __syncthreads();
 
   // 2+3. separable float64 convolution -> float32 map in LDS + per-thread running argmax
-  Best mine;
-  mine.v = -__builtin_inff();
-  mine.i = 0x7fffffff;
+  ArgmaxBest mine = ArgmaxBest::none();
   bool have = false;
   float *ocm = out_conv ? out_conv + (size_t)map * HW : nullptr;
-  switch (r) {  // block-uniform
-    case 2: conv_passes<2, NT>(rawp, WP, buf, tmp, H, W, wk, ocm, mine.v, mine.i, have); break;
-    case 3: conv_passes<3, NT>(rawp, WP, buf, tmp, H, W, wk, ocm, mine.v, mine.i, have); break;
-    case 4: conv_passes<4, NT>(rawp, WP, buf, tmp, H, W, wk, ocm, mine.v, mine.i, have); break;
-    case 5: conv_passes<5, NT>(rawp, WP, buf, tmp, H, W, wk, ocm, mine.v, mine.i, have); break;
-    case 6: conv_passes<6, NT>(rawp, WP, buf, tmp, H, W, wk, ocm, mine.v, mine.i, have); break;
-    case 7: conv_passes<7, NT>(rawp, WP, buf, tmp, H, W, wk, ocm, mine.v, mine.i, have); break;
-    case 8: conv_passes<8, NT>(rawp, WP, buf, tmp, H, W, wk, ocm, mine.v, mine.i, have); break;
-    default: conv_passes<9, NT>(rawp, WP, buf, tmp, H, W, wk, ocm, mine.v, mine.i, have); break;
-  }
-  if (!have) {  // more threads than pixels: never wins
-    mine.v = -__builtin_inff();
-    mine.i = 0x7fffffff;
-  }
+  PP_FOR_RADIUS(r, conv_passes<R, NT>(rawp, WP, buf, tmp, H, W, wk, ocm, mine.v, mine.i, have));
+  if (!have) mine = ArgmaxBest::none();  // more threads than pixels: never wins
   __syncthreads();
-  const Best b = block_argmax(mine, red);
+  const ArgmaxBest b = block_argmax(mine, red);
   if (tid == 0) {
     auto at = [&](int yy, int xx) { return buf[yy * W + xx]; };
-    finalize(map, B, K, H, W, b.i, at, src, prob, vis, oks, err, den_x, den_y, in_w, in_h, o);
+    finalize(a, map, H, W, b.i, at, src);
   }
 }
 
-__global__ __launch_bounds__(DEC_THREADS) void decode_lds_kernel(
-    const float *__restrict__ heatmaps, const float *prob, const float *vis, const float *oks,
-    const float *err, int B, int K, int H, int W, const double *__restrict__ taps,
-    const int *__restrict__ radius, double den_x, double den_y, double in_w, double in_h,
-    DecodeOut o, float *__restrict__ out_conv) {
+__global__ __launch_bounds__(DEC_THREADS) void decode_lds_kernel(PP_DECODE_PARAMS, float *__restrict__ out_conv) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  __shared__ Best red[DEC_THREADS / 64];
-  decode_lds_map<DEC_THREADS>(blockIdx.x, smem, red, heatmaps, prob, vis, oks, err, B, K, H, W, taps, radius, den_x,
-                              den_y, in_w, in_h, o, out_conv);
+  __shared__ ArgmaxBest red[DEC_THREADS / 64];
+  const DecodeArgs a{PP_DECODE_VALUES};
+  decode_lds_map<DEC_THREADS>(a, blockIdx.x, smem, red, out_conv);
 }
 
 // ---------------------------------------------------------------------------
@@ -371,6 +351,9 @@ __global__ __launch_bounds__(DEC_THREADS) void decode_lds_kernel(
 // ---------------------------------------------------------------------------
 constexpr int DF_THREADS = 256;
 constexpr int DF_MAXCAND = 512;
+
+// step 3's candidate threshold: 128 u A below the float32 maximum (u = 2^-24), see the error budget above
+__device__ __forceinline__ float screen_threshold(float m32, float A) { return m32 - 128.0f * 5.9604645e-08f * A; }
 
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -462,21 +445,18 @@ __device__ __forceinline__ float exact_conv_at(const float *__restrict__ rawp, i
 // DF_KEEP: column-pass items a thread keeps in registers (4 outputs each): 3 covers 64x48 maps (92 VGPRs: five
 // workgroups per CU, one round for the 1 088 maps of a bs-64 K=17 batch), 7 covers 96x72.
 template <int DF_KEEP>
-__global__ __launch_bounds__(DF_THREADS, DF_KEEP <= 3 ? 5 : 4) void decode_screen_kernel(
-    const float *__restrict__ heatmaps, const float *prob, const float *vis, const float *oks, const float *err, int B,
-    int K, int H, int W, const double *__restrict__ taps, const int *__restrict__ radius, double den_x, double den_y,
-    double in_w, double in_h, DecodeOut o) {
+__global__ __launch_bounds__(DF_THREADS, DF_KEEP <= 3 ? 5 : 4) void decode_screen_kernel(PP_DECODE_PARAMS) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int NW = DF_THREADS / 64;
   const int HW = H * W;
-  const int WP = 4 * ((W + 3) >> 2) + 2 * DEC_HALO;
+  const int WP = padded_row(W);
   float *rawp = reinterpret_cast<float *>(smem);                              // [H][WP]
   float *tmp32 = rawp + (size_t)H * WP;                                       // [HW]
   int *cand = reinterpret_cast<int *>(tmp32 + HW);                            // [DF_MAXCAND]
   __shared__ double wk[PP_MAX_TAPS];
   __shared__ double scratch[NW][PP_MAX_TAPS + 1];
   __shared__ float redf[NW], redmin[NW], redmax[NW];
-  __shared__ Best red[NW];
+  __shared__ ArgmaxBest red[NW];
   __shared__ int ncand_s;
   __shared__ float nbr[5];
 
@@ -498,7 +478,7 @@ __global__ __launch_bounds__(DF_THREADS, DF_KEEP <= 3 ? 5 : 4) void decode_scree
       amax = fmaxf(fmaxf(amax, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
       vmin = fminf(fminf(vmin, fminf(v.x, v.y)), fminf(v.z, v.w));
       vmax = fmaxf(fmaxf(vmax, fmaxf(v.x, v.y)), fmaxf(v.z, v.w));
-      bad |= !(fabsf(v.x) <= 3.0e38f) | !(fabsf(v.y) <= 3.0e38f) | !(fabsf(v.z) <= 3.0e38f) | !(fabsf(v.w) <= 3.0e38f);
+      bad |= nonfinite(v.x) | nonfinite(v.y) | nonfinite(v.z) | nonfinite(v.w);
     }
   } else {
     for (int p = tid; p < HW; p += DF_THREADS) {
@@ -508,7 +488,7 @@ __global__ __launch_bounds__(DF_THREADS, DF_KEEP <= 3 ? 5 : 4) void decode_scree
       amax = fmaxf(amax, fabsf(v));
       vmin = fminf(vmin, v);
       vmax = fmaxf(vmax, v);
-      bad |= !(fabsf(v) <= 3.0e38f);
+      bad |= nonfinite(v);
     }
   }
   {
@@ -543,7 +523,7 @@ __global__ __launch_bounds__(DF_THREADS, DF_KEEP <= 3 ? 5 : 4) void decode_scree
     // every convolved value is the same number and np.argmax returns index 0 -- a border pixel, no sub-pixel step
     if (tid == 0) {
       auto at = [&](int, int) { return 0.f; };
-      finalize(map, B, K, H, W, 0, at, src, prob, vis, oks, err, den_x, den_y, in_w, in_h, o);
+      finalize(DecodeArgs{PP_DECODE_VALUES}, map, H, W, 0, at, src);
     }
     return;
   }
@@ -559,18 +539,7 @@ __global__ __launch_bounds__(DF_THREADS, DF_KEEP <= 3 ? 5 : 4) void decode_scree
     for (int j = 0; j < PP_MAX_TAPS; ++j) w32[j] = (float)taps[k * PP_MAX_TAPS + j];
     float best = -__builtin_inff();
     float keep[DF_KEEP][4];
-#define PP_SCREEN(R_) screen_passes<R_, DF_KEEP>(rawp, WP, tmp32, H, W, w32, keep, best)
-    switch (r) {
-      case 2: PP_SCREEN(2); break;
-      case 3: PP_SCREEN(3); break;
-      case 4: PP_SCREEN(4); break;
-      case 5: PP_SCREEN(5); break;
-      case 6: PP_SCREEN(6); break;
-      case 7: PP_SCREEN(7); break;
-      case 8: PP_SCREEN(8); break;
-      default: PP_SCREEN(9); break;
-    }
-#undef PP_SCREEN
+    PP_FOR_RADIUS(r, screen_passes<R, DF_KEEP>(rawp, WP, tmp32, H, W, w32, keep, best));
     best = wave_max(best);
     __syncthreads();                     // redf readers above are done
     if (lane == 0) redf[wave] = best;
@@ -578,7 +547,7 @@ __global__ __launch_bounds__(DF_THREADS, DF_KEEP <= 3 ? 5 : 4) void decode_scree
     float m32 = redf[0];
 #pragma unroll
     for (int w_ = 1; w_ < NW; ++w_) m32 = fmaxf(m32, redf[w_]);
-    thr = m32 - 128.0f * 5.9604645e-08f * A;
+    thr = screen_threshold(m32, A);
     if (keepable) {
       listed = true;
 #pragma unroll
@@ -598,13 +567,11 @@ __global__ __launch_bounds__(DF_THREADS, DF_KEEP <= 3 ? 5 : 4) void decode_scree
   const int nc = (finite && listed) ? ncand_s : DF_MAXCAND + 1;
 
   // 4. exact values of the candidates, first-index arg-max (np.argmax semantics incl. NaN)
-  Best mine;
-  mine.v = -__builtin_inff();
-  mine.i = 0x7fffffff;
+  ArgmaxBest mine = ArgmaxBest::none();
   bool have = false;
   auto consider = [&](int p) {
     const float cv = exact_conv_at(rawp, WP, H, W, r, wk, p / W, p % W, scratch[wave]);
-    if (!have || better(cv, p, mine.v, mine.i)) {
+    if (!have || argmax_ahead(cv, p, mine.v, mine.i)) {
       mine.v = cv;
       mine.i = p;
       have = true;
@@ -624,16 +591,11 @@ __global__ __launch_bounds__(DF_THREADS, DF_KEEP <= 3 ? 5 : 4) void decode_scree
   } else {
     for (int p = wave; p < HW; p += NW) consider(p);
   }
-  if (!have || lane != 0) {
-    // every lane of a wave holds the same (mine); keep one copy per wave for the reduction
-    if (lane != 0 || !have) {
-      mine.v = -__builtin_inff();
-      mine.i = 0x7fffffff;
-    }
-  }
+  // every lane of a wave holds the same (mine); keep one copy per wave for the reduction
+  if (lane != 0 || !have) mine = ArgmaxBest::none();
   __syncthreads();
-  // block_argmax's better() treats a NaN value as winning; the "no candidate" sentinel (-inf, INT_MAX) never wins
-  const Best b = block_argmax(mine, red);
+  // block_argmax's argmax_ahead() treats a NaN value as winning; the "no candidate" sentinel (-inf, INT_MAX) never wins
+  const ArgmaxBest b = block_argmax(mine, red);
   // exact neighbours of the winner (interior only), one wave each
   const int bx = b.i % W, by = b.i / W;
   const bool interior = bx > 0 && bx < W - 1 && by > 0 && by < H - 1;
@@ -649,7 +611,7 @@ __global__ __launch_bounds__(DF_THREADS, DF_KEEP <= 3 ? 5 : 4) void decode_scree
     auto at = [&](int yy, int xx) {
       return yy == by ? (xx == bx ? nbr[0] : (xx == bx + 1 ? nbr[1] : nbr[2])) : (yy == by + 1 ? nbr[3] : nbr[4]);
     };
-    finalize(map, B, K, H, W, b.i, at, src, prob, vis, oks, err, den_x, den_y, in_w, in_h, o);
+    finalize(DecodeArgs{PP_DECODE_VALUES}, map, H, W, b.i, at, src);
   }
 }
 
@@ -673,22 +635,9 @@ __global__ __launch_bounds__(DF_THREADS, DF_KEEP <= 3 ? 5 : 4) void decode_scree
 // Non-finite maps and flat maps (clamped plateaus: more than DWV_MAXCAND candidates) are not settled by a wave: it
 // appends the map to a list in the workspace and the all-pixel float64 kernel (decode_lds_list_kernel, 512 threads per
 // map) that follows on the stream decodes exactly those maps; the list resets itself there (no reset launch).
-// Round 3 first tried to keep that work INSIDE the wave kernel's launch (helper workgroups polling an in-launch work list,
-// the last screening workgroup draining it).  It was correct and it lost: (1) `sc1` loads of the list counters went
-// stale across XCDs (helpers that had polled the empty list never saw pushes), so every read had to become an atomic
-// read-modify-write; (2) 64 - 256 pollers on three counter words (a word serves ~88 atomics per us chip-wide) plus one
-// arrival atomic per screening workgroup cost the launch 5 - 10 % at B = 1024; (3) helpers are the last block ids, so they
-// start when the screening is nearly over, and a 256-thread workgroup decodes a flat map in 12 us where the 512-thread
-// list kernel needs 8: on the bench model's heatmaps (5 % flat maps) 588 us per 256 crops against 69 for the all-pixel
-// kernel alone.  An EARLY flat-map test on the raw map ("n pixels at the maximum", n = 12 or (2r + 1)^2) handed a third of
-// those maps to the slow path (a saturated blob rarely holds a whole all-maximum kernel window).  All of it was removed.
-// (A wave-local exact path for flat maps -- row chains shared through an LDS ring -- was built in round 2 and measured
-// at 150 us per 64-crop batch of random-weight heatmaps: one wave's float64 chains are latency-bound.)
 // ---------------------------------------------------------------------------
 constexpr int DWV_MAXCAND = 2;           // more candidates than this: the map goes to the all-pixel kernel's list
                                          // (a candidate costs a wave ~1.5 us of serial float64 chains; 94 % of maps have 1)
-
-constexpr __host__ __device__ int reflect_c(int i, int n) { return i < 0 ? -i - 1 : (i >= n ? 2 * n - 1 - i : i); }
 
 template <int H_, int W_> struct WaveGeom {
   static constexpr int H = H_, W = W_, HW = H * W;
@@ -850,18 +799,25 @@ __device__ __forceinline__ void wl_push(int *ws, int map, int maps) {
   if ((unsigned)i < (unsigned)maps) ws[2 + i] = map;
 }
 
+// The row and column chains are compiled for three bounds on the taps (see dwv_row_chain).  PP_FOR_TAP_BOUND(T,
+// statement) runs the statement with `NT` the compile-time bound for T taps; a macro for the same reason as PP_FOR_RADIUS.
+#define PP_FOR_TAP_BOUND(T, ...)                                     \
+  {                                                                  \
+    if ((T) <= 7) { constexpr int NT = 7; __VA_ARGS__; }             \
+    else if ((T) <= 13) { constexpr int NT = 13; __VA_ARGS__; }      \
+    else { constexpr int NT = PP_MAX_TAPS; __VA_ARGS__; }            \
+  }
+
 template <int H, int W>
-__device__ __forceinline__ void wave_decode_map(
-    const int map, float *__restrict__ buf, const float *__restrict__ heatmaps, const float *prob, const float *vis,
-    const float *oks, const float *err, int B, int K, const double *__restrict__ taps, const int *__restrict__ radius,
-    double den_x, double den_y, double in_w, double in_h, DecodeOut o, int *__restrict__ ws) {
+__device__ __forceinline__ void wave_decode_map(const DecodeArgs &a, const int map, float *__restrict__ buf,
+                                                int *__restrict__ ws) {
   using G = WaveGeom<H, W>;
   constexpr int HW = G::HW;
   const int lane = threadIdx.x & 63;
-  const int k = map % K;
-  const float *__restrict__ src = heatmaps + (size_t)map * HW;
-  const int r = __builtin_amdgcn_readfirstlane(radius[k]);
-  const double *__restrict__ wk = taps + (size_t)k * PP_MAX_TAPS;
+  const int k = map % a.K;
+  const float *__restrict__ src = a.heatmaps + (size_t)map * HW;
+  const int r = __builtin_amdgcn_readfirstlane(a.radius[k]);
+  const double *__restrict__ wk = a.taps + (size_t)k * PP_MAX_TAPS;
 
   // 1. HBM -> LDS (row stride RS), A = max |x| (NaN / inf make the map "not finite")
   float amax = 0.f, vmin = __builtin_inff(), vmax = -__builtin_inff();
@@ -883,8 +839,8 @@ __device__ __forceinline__ void wave_decode_map(
         amax = fmaxf(fmaxf(amax, fmaxf(fabsf(v[i].x), fabsf(v[i].y))), fmaxf(fabsf(v[i].z), fabsf(v[i].w)));
         vmin = fminf(fminf(vmin, fminf(v[i].x, v[i].y)), fminf(v[i].z, v[i].w));
         vmax = fmaxf(fmaxf(vmax, fmaxf(v[i].x, v[i].y)), fmaxf(v[i].z, v[i].w));
-        bad |= !(fabsf(v[i].x) <= 3.0e38f) | !(fabsf(v[i].y) <= 3.0e38f) | !(fabsf(v[i].z) <= 3.0e38f) |
-               !(fabsf(v[i].w) <= 3.0e38f);
+        bad |= nonfinite(v[i].x) | nonfinite(v[i].y) | nonfinite(v[i].z) |
+               nonfinite(v[i].w);
       }
     }
   }
@@ -894,7 +850,7 @@ __device__ __forceinline__ void wave_decode_map(
     // constant map: every convolved value is the same number, np.argmax returns index 0 (a border pixel)
     if (lane == 0) {
       auto at = [&](int, int) { return 0.f; };
-      finalize(map, B, K, H, W, 0, at, src, prob, vis, oks, err, den_x, den_y, in_w, in_h, o);
+      finalize(a, map, H, W, 0, at, src);
     }
     return;
   }
@@ -904,18 +860,9 @@ __device__ __forceinline__ void wave_decode_map(
   int ncand = DWV_MAXCAND + 1;                               // "every pixel" unless the screen says less
   if (finite) {
     float lm;
-    switch (r) {
-      case 2: lm = wave_passes<G, 2>(buf, wk); break;
-      case 3: lm = wave_passes<G, 3>(buf, wk); break;
-      case 4: lm = wave_passes<G, 4>(buf, wk); break;
-      case 5: lm = wave_passes<G, 5>(buf, wk); break;
-      case 6: lm = wave_passes<G, 6>(buf, wk); break;
-      case 7: lm = wave_passes<G, 7>(buf, wk); break;
-      case 8: lm = wave_passes<G, 8>(buf, wk); break;
-      default: lm = wave_passes<G, 9>(buf, wk); break;
-    }
+    PP_FOR_RADIUS(r, lm = wave_passes<G, R>(buf, wk));
     const float m32 = wave_max(lm);
-    const float thr = m32 - 128.0f * 5.9604645e-08f * A;     // see the error budget of the screened path above
+    const float thr = screen_threshold(m32, A);
     // columns whose maximum reaches the threshold (usually one) are scanned by the whole wave, one row per lane.
     // A lane holds the maximum over its NCI columns, so every column of a flagged lane is scanned.
     ncand = 0;
@@ -954,7 +901,7 @@ __device__ __forceinline__ void wave_decode_map(
   if (ncand > DWV_MAXCAND) {
     // Flat map (a clamped plateau: hundreds of exact ties and near-ties) or non-finite map (every pixel counts): not
     // worth a wave's serial chains.  It goes on the work list of the all-pixel float64 decode (whole workgroups).
-    if (lane == 0) wl_push(ws, map, B * K);
+    if (lane == 0) wl_push(ws, map, a.B * a.K);
     return;
   }
   // 5. exact values, first-index arg-max (np.argmax semantics incl. NaN).  Row chains on lanes 0..T-1, handed to the
@@ -965,24 +912,16 @@ __device__ __forceinline__ void wave_decode_map(
   for (int j = 0; j < PP_MAX_TAPS; ++j) wkr[j] = wk[j];
   auto exact_at = [&](int y, int x) __attribute__((always_inline)) {
     double t = 0.0, c;
-    if (T <= 7) {
-      if (lane < T) t = dwv_row_chain<7>(src, H, W, r, T, wkr, y - r + lane, x);
-      c = dwv_col_chain<7>(t, 0, T, wkr);
-    } else if (T <= 13) {
-      if (lane < T) t = dwv_row_chain<13>(src, H, W, r, T, wkr, y - r + lane, x);
-      c = dwv_col_chain<13>(t, 0, T, wkr);
-    } else {
-      if (lane < T) t = dwv_row_chain<PP_MAX_TAPS>(src, H, W, r, T, wkr, y - r + lane, x);
-      c = dwv_col_chain<PP_MAX_TAPS>(t, 0, T, wkr);
-    }
+    PP_FOR_TAP_BOUND(T, {
+      if (lane < T) t = dwv_row_chain<NT>(src, H, W, r, T, wkr, y - r + lane, x);
+      c = dwv_col_chain<NT>(t, 0, T, wkr);
+    });
     return (float)c;                       // the same number on every lane
   };
-  Best best;
-  best.v = -__builtin_inff();
-  best.i = 0x7fffffff;
+  ArgmaxBest best = ArgmaxBest::none();
   bool have = false;
   auto consider = [&](int p, float cv) __attribute__((always_inline)) {
-    if (!have || better(cv, p, best.v, best.i)) {
+    if (!have || argmax_ahead(cv, p, best.v, best.i)) {
       best.v = cv;
       best.i = p;
       have = true;
@@ -1012,14 +951,12 @@ __device__ __forceinline__ void wave_decode_map(
       const int idx = lane - grp * T;
       const int xx = grp == 0 ? bx + 1 : (grp == 1 ? bx - 1 : bx);
       const int yy = grp == 2 ? by - 1 - r + idx : by - r + idx;
-      if (T <= 7) t = dwv_row_chain<7>(src, H, W, r, T, wkr, yy, xx);
-      else if (T <= 13) t = dwv_row_chain<13>(src, H, W, r, T, wkr, yy, xx);
-      else t = dwv_row_chain<PP_MAX_TAPS>(src, H, W, r, T, wkr, yy, xx);
+      PP_FOR_TAP_BOUND(T, t = dwv_row_chain<NT>(src, H, W, r, T, wkr, yy, xx));
     }
     // lane 4: the centre itself (rows y - r .. y + r of the third group)
     const int base = lane == 0 ? 0 : (lane == 1 ? T : (lane == 2 ? 2 * T + 2 : (lane == 3 ? 2 * T : 2 * T + 1)));
-    const double c = T <= 7 ? dwv_col_chain<7>(t, base, T, wkr)          // lanes >= 5: unused values
-                            : (T <= 13 ? dwv_col_chain<13>(t, base, T, wkr) : dwv_col_chain<PP_MAX_TAPS>(t, base, T, wkr));
+    double c;                              // lanes >= 5: unused values
+    PP_FOR_TAP_BOUND(T, c = dwv_col_chain<NT>(t, base, T, wkr));
     nb = (float)c;
     if (single) best.v = __shfl(nb, 4, 64);
   } else if (single) {
@@ -1030,54 +967,47 @@ __device__ __forceinline__ void wave_decode_map(
     auto at = [&](int yy, int xx) {
       return yy == by ? (xx == bx ? best.v : (xx == bx + 1 ? n_xp : n_xm)) : (yy == by + 1 ? n_yp : n_ym);
     };
-    finalize(map, B, K, H, W, best.i, at, src, prob, vis, oks, err, den_x, den_y, in_w, in_h, o);
+    finalize(a, map, H, W, best.i, at, src);
   }
 }
 
 // NWV waves (= maps) per workgroup; MINW = waves per SIMD the register budget is cut for.
-template <int H, int W, int NWV, int MINW>
-__global__ __launch_bounds__(NWV * 64, MINW) void decode_wave_kernel(
-    const float *__restrict__ heatmaps, const float *prob, const float *vis, const float *oks, const float *err, int B,
-    int K, const double *__restrict__ taps, const int *__restrict__ radius, double den_x, double den_y, double in_w,
-    double in_h, DecodeOut o, int *__restrict__ ws) {
-  using G = WaveGeom<H, W>;
+template <int MH, int MW, int NWV, int MINW>   // the map's shape is compile-time here; the H and W parameters repeat it
+__global__ __launch_bounds__(NWV * 64, MINW) void decode_wave_kernel(PP_DECODE_PARAMS, int *__restrict__ ws) {
+  using G = WaveGeom<MH, MW>;
   __shared__ __attribute__((aligned(16))) float lds[NWV][G::BUF];
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int map = blockIdx.x * NWV + wave;
   if (map >= B * K) return;                          // whole waves leave; nothing synchronises across waves
-  wave_decode_map<H, W>(map, lds[wave], heatmaps, prob, vis, oks, err, B, K, taps, radius, den_x, den_y, in_w, in_h, o, ws);
+  const DecodeArgs a{PP_DECODE_VALUES};
+  wave_decode_map<MH, MW>(a, map, lds[wave], ws);
 }
 
 // The all-pixel float64 decode over the LIST the wave kernel left (the launch before this one on the stream).  The grid
 // is fixed (graph-capturable); workgroups stride over the list and leave at once when it is empty.  The list resets
 // itself: every workgroup reads the count, then arrives on a second counter; the last to arrive -- every workgroup has
-// read the count by then -- zeroes both.  The caller zeroes the workspace once when it allocates it; no memset node, no
-// reset kernel (round 2 spent 5 us per batch on one).
-__global__ __launch_bounds__(DEC_THREADS) void decode_lds_list_kernel(
-    int *__restrict__ list, const float *__restrict__ heatmaps, const float *prob, const float *vis,
-    const float *oks, const float *err, int B, int K, int H, int W, const double *__restrict__ taps,
-    const int *__restrict__ radius, double den_x, double den_y, double in_w, double in_h, DecodeOut o) {
+// read the count by then -- zeroes both.  The arrival is an acquire-release read-modify-write: a workgroup's read of the
+// count is ordered before its own arrival, the arrivals form one release sequence, and the last arriver's stores come
+// after all of them, so no workgroup can read the count after it was zeroed.  The caller zeroes the workspace once when
+// it allocates it; no memset node, no reset kernel (round 2 spent 5 us per batch on one).
+__global__ __launch_bounds__(DEC_THREADS) void decode_lds_list_kernel(int *__restrict__ list, PP_DECODE_PARAMS) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  __shared__ Best red[DEC_THREADS / 64];
+  __shared__ ArgmaxBest red[DEC_THREADS / 64];
   __shared__ int s_n;
   if (threadIdx.x == 0) {
     s_n = __hip_atomic_load(list, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (atomicAdd(list + 1, 1) == (int)gridDim.x - 1) {      // everybody has read the count
+    if (__hip_atomic_fetch_add(list + 1, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == (int)gridDim.x - 1) {
       __hip_atomic_store(list, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       __hip_atomic_store(list + 1, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
   __syncthreads();
+  const DecodeArgs a{PP_DECODE_VALUES};
   const int n = min(max(s_n, 0), B * K);              // (bounded whatever the workspace held: see wl_push)
   for (int b = blockIdx.x; b < n; b += gridDim.x) {
-    decode_lds_map<DEC_THREADS>(min(max(list[2 + b], 0), B * K - 1), smem, red, heatmaps, prob, vis, oks, err, B, K, H, W, taps, radius, den_x,
-                                den_y, in_w, in_h, o, nullptr);
+    decode_lds_map<DEC_THREADS>(a, min(max(list[2 + b], 0), B * K - 1), smem, red, nullptr);
     __syncthreads();                     // the next map reuses the LDS image and the reduction slots
   }
-}
-
-static size_t screen_lds_bytes(int H, int W) {
-  return ((size_t)H * (4 * ((W + 3) / 4) + 2 * DEC_HALO) + (size_t)H * W + DF_MAXCAND) * 4;
 }
 
 // ---------------------------------------------------------------------------
@@ -1119,36 +1049,65 @@ __global__ __launch_bounds__(DEC_THREADS) void decode_argmax_kernel(
     const float *__restrict__ heatmaps, const float *__restrict__ conv, const float *prob,
     const float *vis, const float *oks, const float *err, int B, int K, int H, int W,
     double den_x, double den_y, double in_w, double in_h, DecodeOut o) {
-  __shared__ Best red[DEC_THREADS / 64];
+  __shared__ ArgmaxBest red[DEC_THREADS / 64];
   const int map = blockIdx.x, HW = H * W, tid = threadIdx.x;
   const float *c = conv + (size_t)map * HW;
-  Best mine;
-  mine.v = -__builtin_inff();
-  mine.i = 0x7fffffff;
+  ArgmaxBest mine = ArgmaxBest::none();
   bool have = false;
   for (int p = tid; p < HW; p += DEC_THREADS) {
     const float cv = c[p];
-    if (!have || better(cv, p, mine.v, mine.i)) {
+    if (!have || argmax_ahead(cv, p, mine.v, mine.i)) {
       mine.v = cv;
       mine.i = p;
       have = true;
     }
   }
-  const Best b = block_argmax(mine, red);
+  const ArgmaxBest b = block_argmax(mine, red);
   if (tid == 0) {
     auto at = [&](int yy, int xx) { return c[yy * W + xx]; };
-    finalize(map, B, K, H, W, b.i, at, heatmaps + (size_t)map * HW, prob, vis, oks, err, den_x,
-             den_y, in_w, in_h, o);
+    const DecodeArgs a{heatmaps, prob, vis, oks, err, B, K, H, W, nullptr, nullptr, den_x, den_y, in_w, in_h, o};
+    finalize(a, map, H, W, b.i, at, heatmaps + (size_t)map * HW);
   }
 }
 
 constexpr size_t LDS_LIMIT = 160 * 1024 - 256;
+constexpr size_t SCREEN_DYN_LIMIT = 156 * 1024;    // the screened kernel also holds ~1.5 KB of static LDS
 
-static size_t lds_bytes(int H, int W) {
-  return (size_t)H * W * 8 + (size_t)H * (4 * ((W + 3) / 4) + 2 * DEC_HALO) * 4;
-}
+static size_t lds_bytes(int H, int W) { return (size_t)H * W * 8 + (size_t)H * padded_row(W) * 4; }
+static size_t screen_lds_bytes(int H, int W) { return ((size_t)H * padded_row(W) + (size_t)H * W + DF_MAXCAND) * 4; }
 static bool fits_lds(int H, int W) { return lds_bytes(H, W) <= LDS_LIMIT; }
 static bool wave_geometry(int H, int W) { return (H == 64 && W == 48) || (H == 96 && W == 72); }
+
+enum class DecodeForm { Wave, Screen, AllPixel, Global };
+
+// Which form decodes this call.  All forms return the same numbers; only the all-pixel and the global-memory form can
+// write the convolved maps.
+static DecodeForm choose_form(const void *heatmaps, int H, int W, int maps, int flags, bool out_conv,
+                              const void *workspace) {
+  const bool may_screen = !out_conv && !(flags & PP_DECODE_ALL_PIXEL);
+  // wave-per-map kernel: 64x48 maps (256x192 models) and 96x72 maps (384x288), when the caller passed the (zeroed)
+  // workspace pp_decode_workspace_bytes asks for (without one: the workgroup-per-map kernels below).
+  // Batches of at most two rounds of the all-pixel kernel's resident workgroups (3 per CU at 64x48, 1 at 96x72) take that
+  // kernel: ONE launch, 22 - 24 us at bs 64 x 17 whatever the maps hold, where the wave kernel + its list kernel need
+  // 20 - 25 us on peaked maps and ~27 on the bench model's plateau-ridden ones.  Above that the wave kernel wins by up to
+  // 2.4x (B = 1024: 94 - 99 vs 232 us) and the second launch is noise.  PP_DECODE_WAVE forces the wave path at any size.
+  int ncu = 0;
+  if (cu_count(&ncu) != 0) ncu = 256;        // a wrong count only moves the cross-over
+  const long long small_batch = 2ll * ncu * (H == 64 ? 3 : 1);
+  const bool wave_wanted = (flags & PP_DECODE_WAVE) || maps > small_batch;
+  if (may_screen && !(flags & PP_DECODE_NO_WAVE) && wave_wanted && workspace && ((uintptr_t)heatmaps & 15) == 0 &&
+      ((uintptr_t)workspace & 3) == 0 && wave_geometry(H, W))
+    return DecodeForm::Wave;
+  // Workgroup-per-map screened form against the all-pixel form, measured (tools/decode_ab.py, one process,
+  // interleaved): 96x72 maps 699 vs 884 us per 128 x 133 maps (-21 %); 64x48 maps 24.3 vs 22.9 us at B = 64 and 236 vs
+  // 234 us at B = 1024 (a tie: both forms are bound by the latency of their short barrier-separated phases, not by HBM,
+  // LDS or the FMA rate).  The screened form is the default where it wins (maps larger than 4096 pixels); flag
+  // PP_DECODE_SCREEN forces it everywhere, PP_DECODE_ALL_PIXEL never.
+  const bool want_screen = (flags & PP_DECODE_SCREEN) || (long long)H * W > 4096;
+  if (may_screen && want_screen && screen_lds_bytes(H, W) <= SCREEN_DYN_LIMIT) return DecodeForm::Screen;
+  if (fits_lds(H, W)) return DecodeForm::AllPixel;
+  return DecodeForm::Global;   // three passes through the workspace
+}
 }  // namespace pp
 
 extern "C" size_t pp_decode_workspace_bytes(int B, int K, int H, int W) {
@@ -1169,83 +1128,62 @@ extern "C" int pp_decode_f32(const float *heatmaps, const float *prob, const flo
   if (B == 0) return 0;  // empty batch: nothing to launch (buffers may be null)
   PP_REQUIRE(heatmaps && taps && radius, "pp_decode_f32: null input");
   PP_REQUIRE((long long)H * W < (1ll << 30), "pp_decode_f32: map too large");
-  hipStream_t s = (hipStream_t)stream;
-  DecodeOut o{out_kpts, out_scores, out_locs, out_aux, out_err, out_packed};
-  const int maps = B * K;
-  constexpr size_t SCREEN_DYN_LIMIT = 156 * 1024;    // the kernel also holds ~1.5 KB of static LDS
-  // Measured (tools/decode_ab.py, one process, interleaved): 96x72 maps 699 vs 884 us per 128 x 133 maps (-21 %); 64x48
-  // maps 24.3 vs 22.9 us at B = 64 and 236 vs 234 us at B = 1024 (a tie: both forms are bound by the latency of their
-  // short barrier-separated phases, not by HBM, LDS or the FMA rate).  The screened form is the default where it
-  // wins (maps larger than 4096 pixels); flag PP_DECODE_SCREEN forces it everywhere, PP_DECODE_ALL_PIXEL never.
-  // wave-per-map kernel: 64x48 maps (256x192 models) and 96x72 maps (384x288), when the caller passed the (zeroed)
-  // workspace pp_decode_workspace_bytes asks for (without one: the workgroup-per-map kernels below)
   PP_REQUIRE((flags & ~(PP_DECODE_NO_WAVE | PP_DECODE_SCREEN | PP_DECODE_ALL_PIXEL | PP_DECODE_WAVE)) == 0,
              "pp_decode_f32: bad flags %d", flags);
-  const bool exact_all = (flags & PP_DECODE_ALL_PIXEL) != 0;
-  // Batches of at most two rounds of the all-pixel kernel's resident workgroups (3 per CU at 64x48, 1 at 96x72) take that
-  // kernel: ONE launch, 22 - 24 us at bs 64 x 17 whatever the maps hold, where the wave kernel + its list kernel need
-  // 20 - 25 us on peaked maps and ~27 on the bench model's plateau-ridden ones.  Above that the wave kernel wins by up to
-  // 2.4x (B = 1024: 94 - 99 vs 232 us) and the second launch is noise.  PP_DECODE_WAVE forces the wave path at any size.
-  int ncu = 0;
-  if (cu_count(&ncu) != 0) ncu = 256;        // a wrong count only moves the cross-over
-  const long long small_batch = 2ll * ncu * (H == 64 ? 3 : 1);
-  const bool wave_wanted = (flags & PP_DECODE_WAVE) || maps > small_batch;
-  if (!out_conv && !(flags & PP_DECODE_NO_WAVE) && wave_wanted && !exact_all && workspace && ((uintptr_t)heatmaps & 15) == 0 &&
-      ((uintptr_t)workspace & 3) == 0 && wave_geometry(H, W)) {
-    int *ws = reinterpret_cast<int *>(workspace);       // [0] count, [1] arrivals of the list kernel, [2 ..] maps
-    if (H == 64)
-      hipLaunchKernelGGL((decode_wave_kernel<64, 48, 4, 3>), dim3((unsigned)cdiv(maps, 4)), dim3(256), 0, s, heatmaps, prob,
-                         vis, oks, err, B, K, taps, radius, den_x, den_y, in_w, in_h, o, ws);
-    else
-      hipLaunchKernelGGL((decode_wave_kernel<96, 72, 1, 2>), dim3((unsigned)maps), dim3(64), 0, s, heatmaps, prob, vis, oks,
-                         err, B, K, taps, radius, den_x, den_y, in_w, in_h, o, ws);
-    PP_CHECK_LAUNCH("decode_wave_kernel");
-    const size_t lds = lds_bytes(H, W);
-    if (lds > 64 * 1024)
-      if (int rc = ensure_dynamic_lds(decode_lds_list_kernel, LDS_LIMIT)) return rc;
-    hipLaunchKernelGGL(decode_lds_list_kernel, dim3((unsigned)(maps < 256 ? maps : 256)), dim3(DEC_THREADS), lds, s, ws,
-                       heatmaps, prob, vis, oks, err, B, K, H, W, taps, radius, den_x, den_y, in_w, in_h, o);
-    PP_CHECK_LAUNCH("decode_lds_list_kernel");
-    return 0;
-  }
-  const bool want_screen = (flags & PP_DECODE_SCREEN) || (long long)H * W > 4096;
-  if (!out_conv && want_screen && !exact_all && screen_lds_bytes(H, W) <= SCREEN_DYN_LIMIT) {
-    const size_t lds = screen_lds_bytes(H, W);
-    const int items = ((H + 3) / 4) * W;
-    if (items <= 3 * DF_THREADS) {
-      hipLaunchKernelGGL(decode_screen_kernel<3>, dim3(maps), dim3(DF_THREADS), lds, s, heatmaps, prob, vis, oks, err, B,
-                         K, H, W, taps, radius, den_x, den_y, in_w, in_h, o);
-    } else {
-      if (lds > 48 * 1024)
-        if (int rc = ensure_dynamic_lds(decode_screen_kernel<7>, SCREEN_DYN_LIMIT)) return rc;
-      hipLaunchKernelGGL(decode_screen_kernel<7>, dim3(maps), dim3(DF_THREADS), lds, s, heatmaps, prob, vis, oks, err, B,
-                         K, H, W, taps, radius, den_x, den_y, in_w, in_h, o);
+  hipStream_t s = (hipStream_t)stream;
+  const DecodeOut o{out_kpts, out_scores, out_locs, out_aux, out_err, out_packed};
+  const int maps = B * K;
+  switch (choose_form(heatmaps, H, W, maps, flags, out_conv != nullptr, workspace)) {
+    case DecodeForm::Wave: {
+      int *ws = reinterpret_cast<int *>(workspace);       // [0] count, [1] arrivals of the list kernel, [2 ..] maps
+      if (H == 64)
+        hipLaunchKernelGGL((decode_wave_kernel<64, 48, 4, 3>), dim3((unsigned)cdiv(maps, 4)), dim3(256), 0, s, PP_DECODE_VALUES, ws);
+      else
+        hipLaunchKernelGGL((decode_wave_kernel<96, 72, 1, 2>), dim3((unsigned)maps), dim3(64), 0, s, PP_DECODE_VALUES, ws);
+      PP_CHECK_LAUNCH("decode_wave_kernel");
+      const size_t lds = lds_bytes(H, W);
+      if (lds > 64 * 1024)
+        if (int rc = ensure_dynamic_lds(decode_lds_list_kernel, LDS_LIMIT)) return rc;
+      hipLaunchKernelGGL(decode_lds_list_kernel, dim3((unsigned)(maps < 256 ? maps : 256)), dim3(DEC_THREADS), lds, s, ws,
+                         PP_DECODE_VALUES);
+      PP_CHECK_LAUNCH("decode_lds_list_kernel");
+      return 0;
     }
-    PP_CHECK_LAUNCH("decode_screen_kernel");
-    return 0;
-  }
-  if (fits_lds(H, W)) {
-    const size_t lds = lds_bytes(H, W);
-    if (lds > 64 * 1024)
-      if (int rc = ensure_dynamic_lds(decode_lds_kernel, LDS_LIMIT)) return rc;
-    hipLaunchKernelGGL(decode_lds_kernel, dim3(maps), dim3(DEC_THREADS), lds, s, heatmaps, prob, vis,
-                       oks, err, B, K, H, W, taps, radius, den_x, den_y, in_w, in_h, o, out_conv);
-    PP_CHECK_LAUNCH("decode_lds_kernel");
-    return 0;
+    case DecodeForm::Screen: {
+      const size_t lds = screen_lds_bytes(H, W);
+      const int items = ((H + 3) / 4) * W;
+      if (items <= 3 * DF_THREADS) {
+        hipLaunchKernelGGL(decode_screen_kernel<3>, dim3(maps), dim3(DF_THREADS), lds, s, PP_DECODE_VALUES);
+      } else {
+        if (lds > 48 * 1024)
+          if (int rc = ensure_dynamic_lds(decode_screen_kernel<7>, SCREEN_DYN_LIMIT)) return rc;
+        hipLaunchKernelGGL(decode_screen_kernel<7>, dim3(maps), dim3(DF_THREADS), lds, s, PP_DECODE_VALUES);
+      }
+      PP_CHECK_LAUNCH("decode_screen_kernel");
+      return 0;
+    }
+    case DecodeForm::AllPixel: {
+      const size_t lds = lds_bytes(H, W);
+      if (lds > 64 * 1024)
+        if (int rc = ensure_dynamic_lds(decode_lds_kernel, LDS_LIMIT)) return rc;
+      hipLaunchKernelGGL(decode_lds_kernel, dim3(maps), dim3(DEC_THREADS), lds, s, PP_DECODE_VALUES, out_conv);
+      PP_CHECK_LAUNCH("decode_lds_kernel");
+      return 0;
+    }
+    case DecodeForm::Global:
+      break;
   }
   PP_REQUIRE(workspace, "pp_decode_f32: map %dx%d needs a workspace (pp_decode_workspace_bytes)", H,
              W);
   double *tmp = reinterpret_cast<double *>(workspace);
   float *conv = out_conv ? out_conv : reinterpret_cast<float *>(tmp + (size_t)maps * H * W);
   const int bx = cdiv((long long)H * W, 256 * 4) > 65535 ? 65535 : cdiv((long long)H * W, 256 * 4);
-  hipLaunchKernelGGL(decode_rowpass_kernel, dim3(maps, bx), dim3(256), 0, s, heatmaps, tmp, K, H, W,
-                     taps, radius);
+  hipLaunchKernelGGL(decode_rowpass_kernel, dim3(maps, bx), dim3(256), 0, s, heatmaps, tmp, K, H, W, taps, radius);
   PP_CHECK_LAUNCH("decode_rowpass_kernel");
-  hipLaunchKernelGGL(decode_colpass_kernel, dim3(maps, bx), dim3(256), 0, s, tmp, conv, K, H, W, taps,
-                     radius);
+  hipLaunchKernelGGL(decode_colpass_kernel, dim3(maps, bx), dim3(256), 0, s, tmp, conv, K, H, W, taps, radius);
   PP_CHECK_LAUNCH("decode_colpass_kernel");
-  hipLaunchKernelGGL(decode_argmax_kernel, dim3(maps), dim3(DEC_THREADS), 0, s, heatmaps, conv, prob,
-                     vis, oks, err, B, K, H, W, den_x, den_y, in_w, in_h, o);
+  hipLaunchKernelGGL(decode_argmax_kernel, dim3(maps), dim3(DEC_THREADS), 0, s, heatmaps, conv, prob, vis, oks, err, B, K,
+                     H, W, den_x, den_y, in_w, in_h, o);
   PP_CHECK_LAUNCH("decode_argmax_kernel");
   return 0;
 }

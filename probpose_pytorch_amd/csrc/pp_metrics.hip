@@ -52,44 +52,23 @@ __global__ __launch_bounds__(256) void pck_counts_kernel(const T *__restrict__ p
 // ---- get_heatmap_maximum (heatmap.py:13-52) for maps of ANY size: flat arg-max with numpy's semantics (the first
 // maximum in row-major order wins; a NaN is the maximum, and the first NaN wins), vals = the maximum itself, the
 // location (-1, -1) where it is <= 0.  One workgroup per map, 16-byte loads when the map allows, the map read once.
-struct ArgBest {
-  float v;
-  int i;
-};
-__device__ __forceinline__ bool arg_better(float v, int i, const ArgBest &b) {   // is (v, i) ahead of b in np.argmax's order?
-  const bool vn = v != v, bn = b.v != b.v;
-  if (vn != bn) return vn;
-  if (!vn && v != b.v) return v > b.v;
-  return i < b.i;
-}
 __global__ __launch_bounds__(256) void heatmap_argmax_kernel(const float *__restrict__ hm, int HW, int W,
                                                              float *__restrict__ locs, float *__restrict__ vals) {
   const float *m = hm + (size_t)blockIdx.x * HW;
-  ArgBest best{-__builtin_inff(), 0x7fffffff};
+  ArgmaxBest best = ArgmaxBest::none();
   if ((HW & 3) == 0 && (((uintptr_t)m) & 15) == 0) {
     for (int q = threadIdx.x; q < HW / 4; q += 256) {
       const float4 t = reinterpret_cast<const float4 *>(m)[q];
       const float e[4] = {t.x, t.y, t.z, t.w};
 #pragma unroll
-      for (int j = 0; j < 4; ++j)
-        if (arg_better(e[j], 4 * q + j, best)) best = ArgBest{e[j], 4 * q + j};
+      for (int j = 0; j < 4; ++j) argmax_take(best, e[j], 4 * q + j);
     }
   } else {
-    for (int i = threadIdx.x; i < HW; i += 256)
-      if (arg_better(m[i], i, best)) best = ArgBest{m[i], i};
+    for (int i = threadIdx.x; i < HW; i += 256) argmax_take(best, m[i], i);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(best.v, o, 64);
-    const int oi = __shfl_xor(best.i, o, 64);
-    if (arg_better(ov, oi, best)) best = ArgBest{ov, oi};
-  }
-  __shared__ ArgBest wb[4];
-  if ((threadIdx.x & 63) == 0) wb[threadIdx.x >> 6] = best;
-  __syncthreads();
+  __shared__ ArgmaxBest wb[4];
+  best = block_argmax(best, wb);
   if (threadIdx.x == 0) {
-    for (int w = 1; w < 4; ++w)
-      if (arg_better(wb[w].v, wb[w].i, best)) best = wb[w];
     const bool dead = best.v <= 0.0f;                      // NaN: not dead (like `nan <= 0`)
     locs[2 * blockIdx.x + 0] = dead ? -1.0f : (float)(best.i % W);
     locs[2 * blockIdx.x + 1] = dead ? -1.0f : (float)(best.i / W);

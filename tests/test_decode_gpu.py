@@ -91,11 +91,12 @@ def test_large_map_fallback_reference_test_shape(pp):
 
 
 @pytest.mark.parametrize("shape", [(3, 5, 7, 9), (1, 4, 4, 3), (2, 3, 33, 31), (1, 2, 128, 96),
-                                   (1, 1, 1, 1), (2, 17, 64, 48)])
+                                   (1, 1, 1, 1), (2, 17, 64, 48), (1, 3, 6, 8)])
 @pytest.mark.parametrize("kind", ["uniform", "peaked"])
 def test_ragged_shapes_against_oracle(pp, shape, kind):
     """Odd sizes (no float4 path), maps smaller than the kernel radius (multiple
-    reflections), the largest map that still fits LDS (128x96)."""
+    reflections), the largest map that still fits LDS (128x96), a float4-path map
+    (W % 4 == 0) narrower than the 12-column halo and smaller than the radius (6x8)."""
     B, K, H, W = shape
     hm = orc.synthetic_heatmaps(B, K, H, W, seed=H * 1000 + W, kind=kind)
     sig = np.random.default_rng(K).uniform(0.02, 0.2, K)
@@ -332,6 +333,7 @@ def test_screened_decode_equals_all_pixel_float64_decode(pp, monkeypatch):
     cases.append(hard(96, 72))
     cases.append(rng.random((2, 5, 7, 5), dtype=np.float32))            # smaller than the kernel radius
     cases.append(rng.random((1, 3, 33, 27), dtype=np.float32))          # W % 4 != 0
+    cases.append(rng.random((1, 3, 6, 8), dtype=np.float32))            # W % 4 == 0, narrower than the halo and the radius
     for hm in cases:
         B, K, H, W = hm.shape
         sig = (orc.COCO17_SIGMAS if K == 17 else np.random.default_rng(K).uniform(0.02, 0.11, K))
