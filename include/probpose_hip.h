@@ -689,6 +689,21 @@ int pp_ema_update(const void *table, int n_chunks, double weight, void *stream);
  *   vars [K] = (2 sigma_k)^2, gt_flags [Gtot] bytes (below).  Over the keypoints with v > 0:
  *   e = (dx^2 + dy^2) / vars / (area + DBL_EPSILON) / 2, OKS = mean(exp(-e)); a ground truth flagged NO_VISIBLE is
  *   scored over all K keypoints by the distance to its box grown by its own size on every side.
+ * pp_cocoeval_exoks: the same matrices with Ex-OKS, the presence-aware OKS of ProbPose, in place of OKS; the other two
+ *   entries run on its output unchanged.  Adds det_presence [Dtot, K] (the detection's probability that keypoint k is
+ *   inside what the model saw), gt_window [Gtot, 4] xyxy (x0, y0, x1, y1: the region the model saw of that ground
+ *   truth) and presence_thr in [0, 1] (anything else, NaN included, is refused; so is a null det_presence or
+ *   gt_window).  Per keypoint with v > 0, gin = x0 <= xg < x1 and y0 <= yg < y1, pin = det_presence >= presence_thr
+ *   (equal counts as present), and the term is
+ *     gin and pin          exp(-e), e as in pp_cocoeval_oks, the same operations in the same order
+ *     gin and not pin      0 (missed)
+ *     not gin and not pin  1 (correctly reported absent)
+ *     not gin and pin      exp(-e) with e = b b / vars / (area + DBL_EPSILON) / 2 and
+ *                          b = max(0, min(xd - x0, x1 - xd, yd - y0, y1 - yd)): a false positive is charged by how far
+ *                          inside the window it was placed, one on or outside the border costs nothing
+ *   ExOKS = (sum of the terms, added in keypoint order) / (number of keypoints with v > 0).  A ground truth flagged
+ *   NO_VISIBLE takes the grown-box branch of pp_cocoeval_oks.  With every annotated keypoint inside its window and
+ *   every presence >= presence_thr the result is pp_cocoeval_oks's bit for bit.
  * pp_cocoeval_match: the greedy matching of all (image, area range, threshold) triples in one launch.
  *   area_ranges [A, 2] (lo, hi), thr [T], det_area [Dtot].  A ground truth is ignored in a range when it is CROWD or
  *   NO_VISIBLE or its area is outside [lo, hi].  Per detection, in order: the best still-free ground truth with
@@ -707,6 +722,10 @@ int pp_ema_update(const void *table, int n_chunks, double weight, void *stream);
 int pp_cocoeval_oks(int n_img, int K, long long Dtot, long long Gtot, long long oks_total, const long long *host_offs,
                     const void *offs, const void *det_kpts, const void *gt_kpts, const void *gt_bbox,
                     const void *gt_area, const void *gt_flags, const void *vars, void *oks, void *stream);
+int pp_cocoeval_exoks(int n_img, int K, long long Dtot, long long Gtot, long long oks_total, const long long *host_offs,
+                      const void *offs, const void *det_kpts, const void *gt_kpts, const void *gt_bbox,
+                      const void *gt_area, const void *gt_flags, const void *vars, const void *det_presence,
+                      const void *gt_window, double presence_thr, void *oks, void *stream);
 int pp_cocoeval_match(int n_img, int A, int T, long long Dtot, long long Gtot, long long oks_total,
                       const long long *host_offs, const void *offs, const void *oks, const void *gt_flags,
                       const void *gt_area, const void *det_area, const void *area_ranges, const void *thr,

@@ -140,6 +140,7 @@ _SIGNATURES = {
     "pp_ema_table_build": (C.c_int, [_i] + [_vp] * 5 + [C.POINTER(C.c_int)]),
     "pp_ema_update": (C.c_int, [_vp, _i, _d, _vp]),
     "pp_cocoeval_oks": (C.c_int, [_i, _i] + [C.c_longlong] * 3 + [_vp] * 10),
+    "pp_cocoeval_exoks": (C.c_int, [_i, _i] + [C.c_longlong] * 3 + [_vp] * 10 + [_d, _vp, _vp]),
     "pp_cocoeval_match": (C.c_int, [_i, _i, _i] + [C.c_longlong] * 3 + [_vp] * 13),
     "pp_cocoeval_accumulate": (C.c_int, [C.c_longlong, _i, _i, _i] + [_vp] * 10),
     "pp_posenms_rescore": (C.c_int, [C.c_longlong, _i, _vp, _vp, _d, _vp, _vp]),

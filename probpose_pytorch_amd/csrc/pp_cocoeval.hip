@@ -13,8 +13,15 @@
 //                               tests/cocoeval_reference.py's compute_oks one for one (compiled -ffp-contract=off), so
 //                               the exponent e is the gauge's bit for bit and the only differences are exp() and the
 //                               roundings of a K-term sum of terms that differ by exp()'s error
-//                               (tests/test_cocoeval_gpu.py counts them).
-//   cocoeval_match_kernel       one wave per (image, area range, threshold), four waves to a workgroup.
+//                               (tests/test_cocoeval_gpu.py counts them).  Its second form, <true>, is Ex-OKS
+//                               (pp_cocoeval_exoks): per annotated keypoint the ground truth is inside its activation
+//                               window or not and the detection's presence probability reaches the threshold or not;
+//                               both: the plain term, same operations; inside but reported absent: 0; outside and
+//                               reported absent: 1; outside but reported present: exp(-e) of the depth b of the
+//                               prediction inside the window.  The 0 and 1 terms are exact, so the plain bound holds
+//                               (tests/test_exoks_gpu.py).  The four cases diverge per keypoint within a wave; the
+//                               kernel is 2 % of an evaluation, so they are left to.
+//   cocoeval_match_kernel      one wave per (image, area range, threshold), four waves to a workgroup.
 //                               Detections are visited one after the other; for one detection the 64 lanes stride
 //                               over the ground truths, each lane keeping its best candidate of the non-ignored
 //                               and of the ignored ground truths with a >=
@@ -40,10 +47,15 @@ namespace pp {
 constexpr int kCocoAccThreads = 1024;
 constexpr int kCocoMatchWaves = 4;
 
+// EX = false: plain OKS (det_presence and gt_window are not read).  EX = true: Ex-OKS, the same loop with the four
+// presence cases of the header per annotated keypoint; the both-present case is the plain term, operation for operation.
+template <bool EX>
 __global__ __launch_bounds__(64) void cocoeval_oks_kernel(
     int n_img, int K, const long long *__restrict__ offs, const double *__restrict__ det_kpts,
     const double *__restrict__ gt_kpts, const double *__restrict__ gt_bbox, const double *__restrict__ gt_area,
-    const unsigned char *__restrict__ gt_flags, const double *__restrict__ vars, double *__restrict__ oks) {
+    const unsigned char *__restrict__ gt_flags, const double *__restrict__ vars,
+    const double *__restrict__ det_presence, const double *__restrict__ gt_window, double presence_thr,
+    double *__restrict__ oks) {
   const int img = blockIdx.x;
   if (img >= n_img) return;
   const long long d0 = offs[img], D = offs[img + 1] - d0;
@@ -58,11 +70,33 @@ __global__ __launch_bounds__(64) void cocoeval_oks_kernel(
     double sum = 0.0;
     int cnt = 0;
     if (!(gt_flags[g0 + g] & PP_COCO_GT_NO_VISIBLE)) {
+      double wx0 = 0.0, wy0 = 0.0, wx1 = 0.0, wy1 = 0.0;
+      const double *pr = nullptr;
+      if constexpr (EX) {
+        const double *w = gt_window + (g0 + g) * 4;
+        wx0 = w[0], wy0 = w[1], wx1 = w[2], wy1 = w[3];
+        pr = det_presence + (d0 + d) * (long long)K;
+      }
       for (int k = 0; k < K; ++k) {
         if (gk[3 * k + 2] > 0.0) {
-          const double dx = dk[2 * k] - gk[3 * k], dy = dk[2 * k + 1] - gk[3 * k + 1];
-          const double e = (dx * dx + dy * dy) / vars[k] / size / 2.0;
-          sum += exp(-e);
+          bool gin = true, pin = true;
+          if constexpr (EX) {
+            const double xg = gk[3 * k], yg = gk[3 * k + 1];
+            gin = wx0 <= xg && xg < wx1 && wy0 <= yg && yg < wy1;
+            pin = pr[k] >= presence_thr;
+          }
+          if (gin && pin) {
+            const double dx = dk[2 * k] - gk[3 * k], dy = dk[2 * k + 1] - gk[3 * k + 1];
+            const double e = (dx * dx + dy * dy) / vars[k] / size / 2.0;
+            sum += exp(-e);
+          } else if (!gin && !pin) {        // correctly reported absent
+            sum += 1.0;
+          } else if (!gin) {                // a false positive: charged by its depth inside the window
+            const double xd = dk[2 * k], yd = dk[2 * k + 1];
+            const double b = fmax(0.0, fmin(fmin(xd - wx0, wx1 - xd), fmin(yd - wy0, wy1 - yd)));
+            const double e = b * b / vars[k] / size / 2.0;
+            sum += exp(-e);
+          }                                 // gin && !pin: missed, the term is 0
           ++cnt;
         }
       }
@@ -290,24 +324,48 @@ static int coco_check_offsets(const char *who, int n_img, const long long *h, lo
   return 0;
 }
 
+// both OKS entries: the checks they share, then the launch of one form of the kernel
+template <bool EX>
+static int coco_oks_launch(const char *who, int n_img, int K, long long Dtot, long long Gtot, long long oks_total,
+                           const long long *host_offs, const void *offs, const void *det_kpts, const void *gt_kpts,
+                           const void *gt_bbox, const void *gt_area, const void *gt_flags, const void *vars,
+                           const void *det_presence, const void *gt_window, double presence_thr, void *oks,
+                           void *stream) {
+  PP_REQUIRE(K > 0, "%s: K=%d", who, K);
+  PP_REQUIRE(offs && det_kpts && gt_kpts && gt_bbox && gt_area && gt_flags && vars && oks &&
+                 (!EX || (det_presence && gt_window)),
+             "%s: null argument", who);
+  if constexpr (EX)       // written so that a NaN fails it
+    PP_REQUIRE(presence_thr >= 0.0 && presence_thr <= 1.0, "%s: presence_thr=%g is not in [0, 1]", who, presence_thr);
+  if (int rc = coco_check_offsets(who, n_img, host_offs, Dtot, Gtot, oks_total)) return rc;
+  if (n_img == 0 || oks_total == 0) return 0;
+  hipLaunchKernelGGL(cocoeval_oks_kernel<EX>, dim3(n_img), dim3(64), 0, (hipStream_t)stream, n_img, K,
+                     (const long long *)offs, (const double *)det_kpts, (const double *)gt_kpts,
+                     (const double *)gt_bbox, (const double *)gt_area, (const unsigned char *)gt_flags,
+                     (const double *)vars, (const double *)det_presence, (const double *)gt_window, presence_thr,
+                     (double *)oks);
+  PP_CHECK_LAUNCH(EX ? "cocoeval_oks_kernel<ex>" : "cocoeval_oks_kernel");
+  return 0;
+}
+
 }  // namespace pp
 
 extern "C" int pp_cocoeval_oks(int n_img, int K, long long Dtot, long long Gtot, long long oks_total,
                                const long long *host_offs, const void *offs, const void *det_kpts,
                                const void *gt_kpts, const void *gt_bbox, const void *gt_area, const void *gt_flags,
                                const void *vars, void *oks, void *stream) {
-  using namespace pp;
-  PP_REQUIRE(K > 0, "pp_cocoeval_oks: K=%d", K);
-  PP_REQUIRE(offs && det_kpts && gt_kpts && gt_bbox && gt_area && gt_flags && vars && oks,
-             "pp_cocoeval_oks: null argument");
-  if (int rc = coco_check_offsets("pp_cocoeval_oks", n_img, host_offs, Dtot, Gtot, oks_total)) return rc;
-  if (n_img == 0 || oks_total == 0) return 0;
-  hipLaunchKernelGGL(cocoeval_oks_kernel, dim3(n_img), dim3(64), 0, (hipStream_t)stream, n_img, K,
-                     (const long long *)offs, (const double *)det_kpts, (const double *)gt_kpts,
-                     (const double *)gt_bbox, (const double *)gt_area, (const unsigned char *)gt_flags,
-                     (const double *)vars, (double *)oks);
-  PP_CHECK_LAUNCH("cocoeval_oks_kernel");
-  return 0;
+  return pp::coco_oks_launch<false>("pp_cocoeval_oks", n_img, K, Dtot, Gtot, oks_total, host_offs, offs, det_kpts,
+                                    gt_kpts, gt_bbox, gt_area, gt_flags, vars, nullptr, nullptr, 0.0, oks, stream);
+}
+
+extern "C" int pp_cocoeval_exoks(int n_img, int K, long long Dtot, long long Gtot, long long oks_total,
+                                 const long long *host_offs, const void *offs, const void *det_kpts,
+                                 const void *gt_kpts, const void *gt_bbox, const void *gt_area, const void *gt_flags,
+                                 const void *vars, const void *det_presence, const void *gt_window,
+                                 double presence_thr, void *oks, void *stream) {
+  return pp::coco_oks_launch<true>("pp_cocoeval_exoks", n_img, K, Dtot, Gtot, oks_total, host_offs, offs, det_kpts,
+                                   gt_kpts, gt_bbox, gt_area, gt_flags, vars, det_presence, gt_window, presence_thr,
+                                   oks, stream);
 }
 
 extern "C" int pp_cocoeval_match(int n_img, int A, int T, long long Dtot, long long Gtot, long long oks_total,
