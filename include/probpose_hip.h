@@ -820,6 +820,56 @@ int pp_track_filter(int K, int max_tracks, long long Dtot, const void *det_strea
                     void *stream);
 
 /* ------------------------------------------------------------------------
+ * Track-driven person boxes (PoseTracker.propose_boxes): the tracker's state read back out as the box
+ * each track's person is expected in at time t, one launch, one lane per (stream, slot) with a serial loop over the
+ * slot's K keypoints.  It writes no state; no atomics, no LDS, no barrier, plain vector stores: the same bits on every
+ * call.  `blocks` [n_str] int64 as above.  frame_wh: device f64 [n_str, 2] (w, h) or NULL; a row (0, 0) does not clamp
+ * that stream.  host_sup_off / sup_off: n_str + 1 int64 CSR offsets into sup_boxes, in HOST memory (checked) and in
+ * device memory, both or neither; sup_boxes: device f64 [n_sup, 4] xywh, the boxes a proposal must not duplicate.
+ * Outputs, [n_str * max_tracks], row s * max_tracks + j: boxes f64 x 4 (xywh), ids int64 (the slot's id, -1 when
+ * free), scores f64, status uint8 (PP_TRACK_BOX_*).
+ *
+ * Rule for slot j of stream s; float64, every step one IEEE basic operation, in this order, unfused:
+ *    1. id[j] < 0 -> FREE.
+ *    2. age[j] > max_age -> OLD.
+ *    3. dt = t - t_last[j]; if dt > max_dt then dt = max_dt (max_dt = +inf is allowed).
+ *    4. for k ascending, a keypoint counts if !use_vis or vis[j, k] > vis_thr.  Its point is xhat + dxhat * dt (the
+ *       product, then the sum, per coordinate) when smooth && init[j, k] && extrapolate, xhat when smooth && init[j, k]
+ *       without extrapolate, else the raw kp.  The first counted point starts x0, x1, y0, y1; later points update them
+ *       by < / > comparisons.  sum += vis[j, k] (from 0.0); n += 1.
+ *    5. n < min_keypoints -> FEW.
+ *    6. cx = (x0 + x1) * 0.5, cy likewise; w = (x1 - x0) * pad, h = (y1 - y0) * pad; if !(w >= min_side) then
+ *       w = min_side, the same for h.
+ *    7. with aspect > 0 (w / h): if w < h * aspect then w = h * aspect, else h = w / aspect.
+ *    8. bx = cx - w * 0.5, by = cy - h * 0.5, ex = bx + w, ey = by + h.
+ *    9. with a frame (fw > 0): bx < 0 -> 0, by < 0 -> 0, ex > fw -> fw, ey > fh -> fh.
+ *   10. always: w = ex - bx, h = ey - by.
+ *   11. any of bx, by, w, h not finite, or !(w >= min_side && h >= min_side) -> OUTSIDE.
+ *   12. for each given box (gx, gy, gw, gh) of stream s, in the order given, with gw > 0 && gh > 0:
+ *       ix = min(ex, gx + gw) - max(bx, gx), iy likewise (min / max by one < / > comparison, the first operand when it
+ *       holds); inter = (ix > 0 && iy > 0) ? ix * iy : 0; uni = (w * h + gw * gh) - inter; iou = uni > 0 ? inter /
+ *       uni : 0; any iou > iou_thr -> SUPPRESSED.
+ *   13. else PROPOSED.  PROPOSED and SUPPRESSED rows carry the box (bx, by, w, h) and score = sum / n; all other rows
+ *       carry zeros.
+ * Refused on the host, with pp_last_error naming the argument, before any launch: n_str < 0, K <= 0, max_tracks
+ * outside 1..PP_TRACK_MAX_TRACKS, t not finite, vis_thr NaN with use_vis, max_dt negative or NaN, max_age < 0,
+ * min_keypoints < 1, pad or min_side not finite or <= 0, aspect negative or not finite, iou_thr outside [0, 1],
+ * sup_off not ascending from 0 or given on one side only, boxes expected but sup_boxes NULL, and, when n_str > 0, NULL
+ * blocks or outputs.  n_str = 0 launches nothing.
+ * ---------------------------------------------------------------------- */
+#define PP_TRACK_BOX_FREE 0
+#define PP_TRACK_BOX_PROPOSED 1
+#define PP_TRACK_BOX_OLD 2
+#define PP_TRACK_BOX_FEW 3
+#define PP_TRACK_BOX_OUTSIDE 4
+#define PP_TRACK_BOX_SUPPRESSED 5
+int pp_track_boxes(int n_str, int K, int max_tracks, const void *blocks, double t, int use_vis, double vis_thr,
+                   int smooth, int extrapolate, double max_dt, int max_age, int min_keypoints, double pad,
+                   double min_side, double aspect, const void *frame_wh, const long long *host_sup_off,
+                   const void *sup_off, const void *sup_boxes, double iou_thr, void *boxes, void *ids, void *scores,
+                   void *status, void *stream);
+
+/* ------------------------------------------------------------------------
  * Visualisation (probpose_pytorch_amd/viz.py): heat overlays and pose drawing on uint8 RGB images, heat
  * maps as RGBA pictures.  No host sync, no atomics, plain vector stores, the same bytes on every call.
  *

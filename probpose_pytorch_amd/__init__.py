@@ -14,7 +14,7 @@ from .heatmap import get_heatmap_expected_value  # noqa: F401
 
 __all__ = ["to_numpy", "Codec", "ProbMap", "ArgMaxProbMap", "get_heatmap_expected_value", "FusedAdamW",
            "Augment", "ModelEma", "ema_update_", "CocoKeypointEval", "PoseNMS", "rescore_instances",
-           "PoseTracker", "OneEuro"]
+           "PoseTracker", "OneEuro", "PoseFollower"]
 
 
 def __getattr__(name):  # lazy: the nn.Module side pulls in the engine
@@ -42,6 +42,9 @@ def __getattr__(name):  # lazy: the nn.Module side pulls in the engine
     if name in ("PoseTracker", "OneEuro"):
         from . import tracker
         return getattr(tracker, name)
+    if name == "PoseFollower":
+        from .follow import PoseFollower
+        return PoseFollower
     if name == "Augment":
         from .dataset import Augment
         return Augment

@@ -362,3 +362,162 @@ extern "C" int pp_track_filter(int K, int max_tracks, long long Dtot, const void
   PP_CHECK_LAUNCH("track_filter_kernel");
   return 0;
 }
+
+// ---- pp_track_boxes: the tracks read back out as person boxes ---------------------------------------
+// One lane per (stream, slot) with a serial loop over the slot's K keypoints, as track_oks_kernel walks a pair.  Reads
+// the state, writes only its four outputs: no atomics, no LDS, no barrier, plain vector stores.  Every step is one
+// IEEE basic operation in the order of include/probpose_hip.h (compiled -ffp-contract=off): the bits of
+// tests/trackbox_reference.py.
+namespace pp {
+
+__global__ __launch_bounds__(kTrackThreads) void track_boxes_kernel(
+    int n_str, int K, int T, const long long *__restrict__ blocks, double t, int use_vis, double vis_thr, int smooth,
+    int extrapolate, double max_dt, int max_age, int min_keypoints, double pad, double min_side, double aspect,
+    const double *__restrict__ frame_wh, const long long *__restrict__ sup_off, const double *__restrict__ sup_boxes,
+    double iou_thr, double *__restrict__ boxes, long long *__restrict__ ids, double *__restrict__ scores,
+    unsigned char *__restrict__ status) {
+  const long long i = (long long)blockIdx.x * kTrackThreads + threadIdx.x;
+  if (i >= (long long)n_str * T) return;
+  const long long s = i / T;
+  const int j = (int)(i - s * T);
+  const TrackState st = track_state(blocks[s], T, K);
+  const long long id = st.id[j];
+  double o0 = 0.0, o1 = 0.0, o2 = 0.0, o3 = 0.0, score = 0.0;
+  int code = PP_TRACK_BOX_FREE;
+  do {
+    if (id < 0) break;
+    code = PP_TRACK_BOX_OLD;
+    if (st.age[j] > max_age) break;
+    double dt = t - st.t_last[j];
+    if (dt > max_dt) dt = max_dt;
+    const long long e0 = (long long)j * K;
+    double x0 = 0.0, x1 = 0.0, y0 = 0.0, y1 = 0.0, sum = 0.0;
+    int n = 0;
+    for (int k = 0; k < K; ++k) {
+      const double v = st.vis[e0 + k];
+      if (use_vis && !(v > vis_thr)) continue;
+      const long long e = 2 * (e0 + k);
+      double px, py;
+      if (smooth && st.init[e0 + k]) {
+        px = st.xhat[e];
+        py = st.xhat[e + 1];
+        if (extrapolate) {
+          px = px + st.dxhat[e] * dt;
+          py = py + st.dxhat[e + 1] * dt;
+        }
+      } else {
+        px = st.kp[e];
+        py = st.kp[e + 1];
+      }
+      if (n == 0) {
+        x0 = x1 = px;
+        y0 = y1 = py;
+      } else {
+        if (px < x0) x0 = px;
+        if (px > x1) x1 = px;
+        if (py < y0) y0 = py;
+        if (py > y1) y1 = py;
+      }
+      sum += v;
+      ++n;
+    }
+    code = PP_TRACK_BOX_FEW;
+    if (n < min_keypoints) break;
+    const double cx = (x0 + x1) * 0.5, cy = (y0 + y1) * 0.5;
+    double w = (x1 - x0) * pad, h = (y1 - y0) * pad;
+    if (!(w >= min_side)) w = min_side;
+    if (!(h >= min_side)) h = min_side;
+    if (aspect > 0.0) {
+      const double wa = h * aspect;
+      if (w < wa) w = wa;
+      else h = w / aspect;
+    }
+    double bx = cx - w * 0.5, by = cy - h * 0.5;
+    double ex = bx + w, ey = by + h;
+    if (frame_wh) {
+      const double fw = frame_wh[2 * s], fh = frame_wh[2 * s + 1];
+      if (fw > 0.0) {
+        if (bx < 0.0) bx = 0.0;
+        if (by < 0.0) by = 0.0;
+        if (ex > fw) ex = fw;
+        if (ey > fh) ey = fh;
+      }
+    }
+    w = ex - bx;
+    h = ey - by;
+    code = PP_TRACK_BOX_OUTSIDE;
+    if (!(isfinite(bx) && isfinite(by) && isfinite(w) && isfinite(h)) || !(w >= min_side && h >= min_side)) break;
+    code = PP_TRACK_BOX_PROPOSED;
+    if (sup_off && sup_boxes) {
+      const double mine = w * h;
+      for (long long g = sup_off[s], g1 = sup_off[s + 1]; g < g1; ++g) {
+        const double gx = sup_boxes[4 * g], gy = sup_boxes[4 * g + 1], gw = sup_boxes[4 * g + 2],
+                     gh = sup_boxes[4 * g + 3];
+        if (!(gw > 0.0 && gh > 0.0)) continue;
+        const double gex = gx + gw, gey = gy + gh;
+        const double ix = (ex < gex ? ex : gex) - (bx > gx ? bx : gx);
+        const double iy = (ey < gey ? ey : gey) - (by > gy ? by : gy);
+        const double inter = (ix > 0.0 && iy > 0.0) ? ix * iy : 0.0;
+        const double uni = (mine + gw * gh) - inter;
+        const double iou = uni > 0.0 ? inter / uni : 0.0;
+        if (iou > iou_thr) {
+          code = PP_TRACK_BOX_SUPPRESSED;
+          break;
+        }
+      }
+    }
+    o0 = bx;
+    o1 = by;
+    o2 = w;
+    o3 = h;
+    score = sum / (double)n;
+  } while (false);
+  boxes[4 * i] = o0;
+  boxes[4 * i + 1] = o1;
+  boxes[4 * i + 2] = o2;
+  boxes[4 * i + 3] = o3;
+  ids[i] = id < 0 ? -1 : id;
+  scores[i] = score;
+  status[i] = (unsigned char)code;
+}
+
+}  // namespace pp
+
+extern "C" int pp_track_boxes(int n_str, int K, int max_tracks, const void *blocks, double t, int use_vis,
+                              double vis_thr, int smooth, int extrapolate, double max_dt, int max_age,
+                              int min_keypoints, double pad, double min_side, double aspect, const void *frame_wh,
+                              const long long *host_sup_off, const void *sup_off, const void *sup_boxes, double iou_thr,
+                              void *boxes, void *ids, void *scores, void *status, void *stream) {
+  using namespace pp;
+  if (int rc = track_check_common("pp_track_boxes", n_str, K, max_tracks, 0)) return rc;
+  PP_REQUIRE(isfinite(t), "pp_track_boxes: t=%g is not finite", t);
+  PP_REQUIRE(!use_vis || vis_thr == vis_thr, "pp_track_boxes: vis_thr is not a number");
+  PP_REQUIRE(max_dt >= 0.0, "pp_track_boxes: max_dt=%g is negative or not a number", max_dt);
+  PP_REQUIRE(max_age >= 0, "pp_track_boxes: max_age=%d", max_age);
+  PP_REQUIRE(min_keypoints >= 1, "pp_track_boxes: min_keypoints=%d", min_keypoints);
+  PP_REQUIRE(isfinite(pad) && pad > 0.0, "pp_track_boxes: pad=%g must be finite and > 0", pad);
+  PP_REQUIRE(isfinite(min_side) && min_side > 0.0, "pp_track_boxes: min_side=%g must be finite and > 0", min_side);
+  PP_REQUIRE(isfinite(aspect) && aspect >= 0.0, "pp_track_boxes: aspect=%g must be finite and >= 0", aspect);
+  PP_REQUIRE(iou_thr >= 0.0 && iou_thr <= 1.0, "pp_track_boxes: iou_thr=%g is outside [0, 1]", iou_thr);
+  PP_REQUIRE(!host_sup_off == !sup_off, "pp_track_boxes: sup_off needs its host copy and its device copy, or neither");
+  if (host_sup_off) {
+    PP_REQUIRE(host_sup_off[0] == 0, "pp_track_boxes: sup_off does not start at 0 (%lld)", host_sup_off[0]);
+    for (int i = 0; i < n_str; ++i)
+      PP_REQUIRE(host_sup_off[i + 1] >= host_sup_off[i],
+                 "pp_track_boxes: sup_off is not ascending at stream %d (%lld after %lld)", i, host_sup_off[i + 1],
+                 host_sup_off[i]);
+    PP_REQUIRE(host_sup_off[n_str] == 0 || sup_boxes, "pp_track_boxes: sup_off names %lld boxes, sup_boxes is null",
+               host_sup_off[n_str]);
+  }
+  if (n_str == 0) return 0;
+  PP_REQUIRE(blocks && boxes && ids && scores && status, "pp_track_boxes: null argument (blocks or an output)");
+  const long long lanes = (long long)n_str * max_tracks, grid = (lanes + kTrackThreads - 1) / kTrackThreads;
+  PP_REQUIRE(grid < (1ll << 31), "pp_track_boxes: %lld slots exceed one grid", lanes);
+  hipLaunchKernelGGL(track_boxes_kernel, dim3((unsigned)grid), dim3(kTrackThreads), 0, (hipStream_t)stream, n_str, K,
+                     max_tracks, (const long long *)blocks, t, use_vis, vis_thr, smooth, extrapolate, max_dt, max_age,
+                     min_keypoints, pad, min_side, aspect, (const double *)frame_wh, (const long long *)sup_off,
+                     (const double *)sup_boxes, iou_thr, (double *)boxes, (long long *)ids, (double *)scores,
+                     (unsigned char *)status);
+  PP_CHECK_LAUNCH("track_boxes_kernel");
+  return 0;
+}

@@ -26,7 +26,12 @@ function, ``run_inference``: ``Codec(ProbMap(input_size, heatmap_size, sigmas))`
   frames of one video stream, with the boxes FILE gives per file name (``{name: [[x, y, w, h, score], ...]}``), and
   links the poses across the frames (``tracker.PoseTracker``; ``--match-thr``, ``--max-age``, ``--fps``; ``--smooth
   [min_cutoff,beta,d_cutoff]`` adds the One-Euro filter).  ``--output`` gets ``tracks.json``: per frame and kept
-  detection its track id and (smoothed) keypoints; with ``--render`` also one picture per frame, drawn from those.
+  detection its track id and (smoothed) keypoints; with ``--render`` also one picture per frame, drawn from those;
+* ``--propagate [VIS_THR,PAD,IOU]`` (with ``--track``) follows the people from frame to frame (``follow.PoseFollower``):
+  every track proposes its person's next box from its own last pose, so FILE needs boxes for a key frame only.  A frame
+  FILE names uses its boxes and the proposals that do not duplicate them (IoU <= IOU), a frame it does not name uses
+  the proposals alone; each detection of ``tracks.json`` then also holds its ``"box"`` and its ``"source"``
+  (``"boxes"`` or ``"track"``).  The defaults 0.3, 1.25, 0.3 are common top-down practice, not tuned on data.
 """
 from __future__ import annotations
 
@@ -204,6 +209,9 @@ def main(argv=None):
                    help="with --frames: link the poses across the frames by OKS; writes tracks.json to --output")
     p.add_argument("--smooth", type=str, nargs="?", const="", default=None, metavar="MIN_CUTOFF,BETA,D_CUTOFF",
                    help="with --track: One-Euro smoothing of the tracked keypoints (no value: the defaults)")
+    p.add_argument("--propagate", type=str, nargs="?", const="", default=None, metavar="VIS_THR,PAD,IOU",
+                   help="with --track: crop each track's next box from its own last pose; --boxes-json then needs "
+                        "boxes for key frames only (no value: 0.3,1.25,0.3)")
     p.add_argument("--match-thr", type=float, default=0.3, help="OKS a pose needs to continue a track")
     p.add_argument("--max-age", type=int, default=30, help="frames a track survives unseen")
     p.add_argument("--fps", type=float, default=30.0, help="frame rate of --frames: the time base of --smooth")
@@ -310,10 +318,11 @@ def _main_boxes(args, model, codec, boxes):
 
 
 def _track_options(p, args):
-    """The tracking options of the command line, checked: None without --track, else dict(files, boxes, smooth)."""
+    """The tracking options of the command line, checked: None without --track, else dict(files, boxes, smooth,
+    propagate)."""
     if not args.track:
         for flag, given in (("--frames", args.frames is not None), ("--boxes-json", args.boxes_json is not None),
-                            ("--smooth", args.smooth is not None)):
+                            ("--smooth", args.smooth is not None), ("--propagate", args.propagate is not None)):
             if given:
                 p.error(f"{flag} needs --track")
         return None
@@ -341,6 +350,22 @@ def _track_options(p, args):
             smooth = OneEuro(*values)
         except (TypeError, ValueError) as e:
             p.error(f"--smooth: {e}")
+    propagate = None
+    if args.propagate is not None:
+        try:
+            values = [float(v) for v in args.propagate.split(",") if v.strip()]
+            if len(values) not in (0, 3):
+                raise ValueError(f"{args.propagate!r} is not vis_thr,pad,iou")
+            vis_thr, pad, iou = values or (0.3, 1.25, 0.3)
+            if not np.isfinite(vis_thr):
+                raise ValueError(f"vis_thr: {vis_thr} is not finite")
+            if not (np.isfinite(pad) and pad > 0):
+                raise ValueError(f"pad: {pad} is not a positive number")
+            if not 0.0 <= iou <= 1.0:
+                raise ValueError(f"iou: {iou} is outside [0, 1]")
+            propagate = (vis_thr, pad, iou)
+        except ValueError as e:
+            p.error(f"--propagate: {e}")
     if not args.frames.is_dir():
         p.error(f"--frames: {args.frames} is not a folder")
     files = sorted(f for f in args.frames.iterdir() if f.is_file())
@@ -356,7 +381,7 @@ def _track_options(p, args):
             boxes[f.name] = rows
     except (OSError, ValueError, AttributeError) as e:
         p.error(f"--boxes-json: {e}")
-    return dict(files=files, boxes=boxes, smooth=smooth)
+    return dict(files=files, boxes=boxes, smooth=smooth, propagate=propagate)
 
 
 def _main_frames(args, model, codec, track):
@@ -369,6 +394,8 @@ def _main_frames(args, model, codec, track):
     if args.nms is not None:
         from .posenms import PoseNMS
         nms = PoseNMS(sigmas, mode=args.nms, oks_thr=args.nms_thr)
+    if track["propagate"] is not None:
+        return _main_follow(args, model, codec, track, nms)
     tracker = PoseTracker(sigmas, match_thr=args.match_thr, max_age=args.max_age, smooth=track["smooth"], fps=args.fps)
     args.output.mkdir(parents=True, exist_ok=True)
     record = []
@@ -392,6 +419,47 @@ def _main_frames(args, model, codec, track):
         if args.render:
             from . import viz
             drawn = viz.draw_keypoints(frame.numpy(), smoothed, probs, threshold=args.render_threshold,
+                                       skeleton=viz.COCO17_SKELETON if K == 17 else None,
+                                       image_index=np.zeros(smoothed.shape[0], dtype=np.int64))
+            save_png(drawn, args.output / f"{path.stem}_tracked.png")
+    (args.output / "tracks.json").write_text(json.dumps(record))
+    return record
+
+
+def box_estimator(model, codec):
+    """The ``estimate`` of a ``follow.PoseFollower``: ``run_inference_on_boxes`` on a (H, W, 3) uint8 device frame,
+    giving the keypoints in frame pixels and their scores as device tensors."""
+    def estimate(frame, boxes):
+        _, preds, frame_kpts = run_inference_on_boxes(model, codec, frame, boxes)
+        scores = np.ascontiguousarray(preds[0][1], dtype=np.float64)
+        return torch.from_numpy(frame_kpts).to(frame.device), torch.from_numpy(scores).to(frame.device)
+    return estimate
+
+
+def _main_follow(args, model, codec, track, nms):
+    """--propagate: the frames through a PoseFollower; the record also says which box every detection was cropped by
+    and where that box came from."""
+    from .follow import PoseFollower
+    from .tracker import PoseTracker
+    K, dev = args.num_keypoints, "cuda"
+    vis_thr, pad, iou = track["propagate"]
+    tracker = PoseTracker(np.array([args.sigma] * K), match_thr=args.match_thr, max_age=args.max_age, vis_thr=vis_thr,
+                          smooth=track["smooth"], fps=args.fps)
+    follower = PoseFollower(tracker, box_estimator(model, codec), nms=nms, pad=pad, iou_thr=iou)
+    args.output.mkdir(parents=True, exist_ok=True)
+    record = []
+    for path in track["files"]:
+        frame, rows = load_frame(path), track["boxes"][path.name]
+        step = follower.step(frame.to(dev), rows[:, :4], rows[:, 4], frame_size=(frame.shape[1], frame.shape[0]))
+        ids, smoothed = step.tracks.ids.cpu().numpy(), step.tracks.keypoints.cpu().numpy()
+        record.append(dict(frame=path.name, detections=[
+            dict(id=int(i), keypoints=k.tolist(), box=b.tolist(), source="track" if s else "boxes")
+            for i, k, b, s in zip(ids, smoothed, step.boxes, step.source)]))
+        print(f"{path.name}: ids {ids.tolist()} from {['track' if s else 'boxes' for s in step.source]}")
+        if args.render:
+            from . import viz
+            drawn = viz.draw_keypoints(frame.numpy(), smoothed, step.kpt_scores.cpu().numpy(),
+                                       threshold=args.render_threshold,
                                        skeleton=viz.COCO17_SKELETON if K == 17 else None,
                                        image_index=np.zeros(smoothed.shape[0], dtype=np.int64))
             save_png(drawn, args.output / f"{path.stem}_tracked.png")

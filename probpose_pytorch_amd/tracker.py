@@ -24,7 +24,10 @@ the counters next_id and overflow.  For every stream a call names:
 * then each unmatched detection, in visiting order, takes the lowest free slot (those just freed included) with a new
   id from the stream's counter; with no slot free it gets id -1 and counts in ``overflow``.
 
-There is no CPU fallback: without a GPU ``update`` raises ``_lib.HipExtensionError``.
+``propose_boxes`` reads the state back out as the person box every track expects its person in next (one more launch,
+pp_track_boxes; restated in tests/trackbox_reference.py); follow.py builds the frame loop on it.
+
+There is no CPU fallback: without a GPU ``update`` and ``propose_boxes`` raise ``_lib.HipExtensionError``.
 """
 from __future__ import annotations
 
@@ -90,6 +93,36 @@ class TrackResult:
 
     def __repr__(self):
         return f"TrackResult({self.ids.shape[0]} detections of {len(self.stream_ids)} streams)"
+
+
+class BoxProposals:
+    """What ``PoseTracker.propose_boxes`` returns, on the device, over the S named streams and their T = ``max_tracks``
+    slots: ``boxes`` [S, T, 4] float64 xywh, ``ids`` [S, T] int64 (-1 = free slot), ``scores`` [S, T] float64 (the mean
+    visibility of the counted keypoints), ``status`` [S, T] uint8 (``_lib.PP_TRACK_BOX_*``); ``stream_ids``: host list.
+    Rows that are neither PROPOSED nor SUPPRESSED hold zeros."""
+    __slots__ = ("boxes", "ids", "scores", "status", "stream_ids", "_staged")
+
+    def __init__(self, boxes, ids, scores, status, stream_ids, staged):
+        self.boxes, self.ids, self.scores, self.status = boxes, ids, scores, status
+        self.stream_ids, self._staged = stream_ids, staged
+
+    def __repr__(self):
+        return f"BoxProposals({self.status.shape[1]} slots of {len(self.stream_ids)} streams)"
+
+    def compact(self):
+        """The PROPOSED rows as host arrays, streams in order and slots ascending: (boxes [P, 4] float64, ids [P]
+        int64, scores [P] float64, stream_index [P] int64 into ``stream_ids``).  The one call that waits for the device:
+        the four tensors cross in one copy."""
+        S, T = self.status.shape
+        n = S * T
+        if n == 0:
+            return np.zeros((0, 4)), np.zeros(0, dtype=np.int64), np.zeros(0), np.zeros(0, dtype=np.int64)
+        raw = torch.cat([x.reshape(-1).view(torch.uint8) for x in (self.boxes, self.ids, self.scores, self.status)])
+        raw = raw.cpu().numpy()
+        boxes = raw[:32 * n].view(np.float64).reshape(n, 4)
+        ids, scores = raw[32 * n:40 * n].view(np.int64), raw[40 * n:48 * n].view(np.float64)
+        rows = np.flatnonzero(raw[48 * n:] == _lib.PP_TRACK_BOX_PROPOSED)
+        return boxes[rows].copy(), ids[rows].copy(), scores[rows].copy(), (rows // T).astype(np.int64)
 
 
 def _check_inputs(named) -> bool:
@@ -193,6 +226,125 @@ class PoseTracker:
         if not n:
             return torch.zeros(0, dtype=torch.int64, device=self._device or "cpu")
         return torch.cat([self._field(c, "overflow").reshape(-1) for c in self._chunks])[:n]
+
+    # ------------------------------------------------------------------------------------------- boxes
+    def _launch_boxes(self, n_str, blocks, t, frame_wh, sup_off, sup_off_dev, sup_boxes, opts, device):
+        """The one launch of ``propose_boxes``: (boxes [S, T, 4], ids, scores, status) on ``device``."""
+        K, T = self.K, self.max_tracks
+        new = partial(torch.empty, device=device)
+        boxes, ids = new((n_str, T, 4), dtype=torch.float64), new((n_str, T), dtype=torch.int64)
+        scores, status = new((n_str, T), dtype=torch.float64), new((n_str, T), dtype=torch.uint8)
+        pad, aspect, min_side, min_keypoints, max_age, extrapolate, max_dt, iou_thr = opts
+        _lib.launch("pp_track_boxes", n_str, K, T, blocks, t, int(self.vis_thr is not None),
+                    0.0 if self.vis_thr is None else self.vis_thr, int(self.smooth is not None), int(extrapolate),
+                    max_dt, max_age, min_keypoints, pad, min_side, aspect, frame_wh, sup_off, sup_off_dev,
+                    None if sup_boxes is None else _room(sup_boxes), iou_thr, boxes, ids, scores, status)
+        return boxes, ids, scores, status
+
+    def propose_boxes(self, t=None, *, streams=None, frame_size=None, pad: float = 1.25, aspect=None,
+                      min_side: float = 2.0, min_keypoints: int = 3, max_age: int = 0, extrapolate: bool = True,
+                      max_dt=None, suppress=None, iou_thr: float = 0.3) -> BoxProposals:
+        """The person box every track is expected in at time ``t``, from the tracks' own last poses: what a top-down
+        estimator crops next when no detector runs on the frame.  One launch (pp_track_boxes, whose rule
+        include/probpose_hip.h states); it is no update: neither the state nor the call count nor the time change, and
+        nothing is read back (``BoxProposals.compact`` does that).
+
+        ``t`` defaults to the time the next default ``update`` would use and must be greater than the previous
+        update's.  ``streams`` defaults to every stream seen so far, in first-seen order; an unseen one raises
+        ``KeyError``.  A box is the extent of the track's counted keypoints (visibility > ``vis_thr``), taken from the
+        One-Euro position, moved by the One-Euro speed times ``min(t - t_last, max_dt)`` with ``extrapolate``, or from
+        the raw keypoints where no filter runs; grown by ``pad`` about its centre, at least ``min_side`` wide and high,
+        widened or heightened to ``aspect`` (w / h, None: as it is) and clamped to ``frame_size``: (w, h), or
+        {stream: (w, h)}, a stream it does not name is not clamped.  Tracks unseen for more than ``max_age`` of their
+        stream's frames or with fewer than ``min_keypoints`` counted keypoints propose nothing.  ``suppress`` = (boxes
+        [n, 4] xywh, stream_ids [n] or None for the only stream): a proposal whose IoU with one of its stream's boxes
+        exceeds ``iou_thr`` is marked SUPPRESSED.  The defaults are common top-down practice, not tuned on data."""
+        t_now = (self._calls + 1) / self.fps if t is None else float(t)
+        if not (np.isfinite(t_now) and t_now > self._t_prev):
+            raise ValueError(f"t: {t_now} is not greater than the previous update's {self._t_prev}")
+        for name, v in (("pad", pad), ("min_side", min_side)):
+            if not (np.isfinite(v) and v > 0):
+                raise ValueError(f"{name}: {v} is not a positive number")
+        if aspect is not None and not (np.isfinite(aspect) and aspect > 0):
+            raise ValueError(f"aspect: {aspect} is not a positive number (None: none)")
+        aspect = 0.0 if aspect is None else float(aspect)
+        if int(min_keypoints) < 1:
+            raise ValueError(f"min_keypoints: {min_keypoints} is below 1")
+        if int(max_age) < 0:
+            raise ValueError(f"max_age: {max_age} is negative")
+        max_dt = np.inf if max_dt is None else float(max_dt)
+        if not max_dt >= 0:
+            raise ValueError(f"max_dt: {max_dt} is negative or not a number")
+        if not 0.0 <= float(iou_thr) <= 1.0:
+            raise ValueError(f"iou_thr: {iou_thr} is outside [0, 1]")
+        stream_list = list(self._index) if streams is None else list(streams)
+        where = {s: i for i, s in enumerate(stream_list)}
+        if len(where) != len(stream_list):
+            raise ValueError("streams: a stream is named twice")
+        for s in stream_list:
+            if s not in self._index:
+                raise KeyError(f"stream: {s!r} has not been seen")
+        n_str = len(stream_list)
+
+        frame_wh = None
+        if frame_size is not None:
+            sizes = frame_size if isinstance(frame_size, dict) else dict.fromkeys(stream_list or [None], frame_size)
+            frame_wh = np.zeros((n_str, 2), dtype=np.float64)
+            for s, wh in sizes.items():
+                wh = np.asarray(wh, dtype=np.float64).reshape(-1)
+                if wh.shape != (2,) or not np.all(np.isfinite(wh)) or not np.all(wh > 0):
+                    raise ValueError(f"frame_size: expected positive (w, h), got {wh.tolist()} for stream {s!r}")
+                if s in where:
+                    frame_wh[where[s]] = wh
+
+        sup_off = sup_boxes = sup_perm = None
+        if suppress is not None:
+            sup_boxes, sup_streams = suppress
+            if not isinstance(sup_boxes, torch.Tensor):
+                sup_boxes = _host(sup_boxes, "suppress", np.float64)
+            if sup_boxes.ndim != 2 or sup_boxes.shape[1] != 4:
+                raise ValueError(f"suppress: expected boxes [n, 4], got {tuple(sup_boxes.shape)}")
+            n_sup = int(sup_boxes.shape[0])
+            if sup_streams is None:
+                if n_sup and n_str != 1:
+                    raise ValueError(f"suppress: stream_ids are needed with {n_str} streams")
+                pos = np.zeros(n_sup, dtype=np.int64)
+            else:
+                names = (sup_streams.detach().cpu().numpy() if isinstance(sup_streams, torch.Tensor)
+                         else np.asarray(sup_streams)).tolist()
+                if len(names) != n_sup:
+                    raise ValueError(f"suppress: expected stream_ids [{n_sup}], got {len(names)}")
+                missing = [s for s in names if s not in where]
+                if missing:
+                    raise ValueError(f"suppress: stream {missing[0]!r} is not in streams")
+                pos = np.fromiter((where[s] for s in names), dtype=np.int64, count=n_sup)
+            sup_perm = np.argsort(pos, kind="stable")                   # by stream, the given order within it
+            sup_off = np.zeros(n_str + 1, dtype=np.int64)
+            sup_off[1:] = np.cumsum(np.bincount(pos, minlength=n_str)[:n_str])
+
+        _lib.require_device()
+        dev = self._device if self._device is not None else torch.device("cuda")
+        opts = (float(pad), aspect, float(min_side), int(min_keypoints), int(max_age), bool(extrapolate), max_dt,
+                float(iou_thr))
+        if n_str == 0:
+            empty = partial(torch.zeros, device=dev)
+            return BoxProposals(empty((0, self.max_tracks, 4), dtype=torch.float64),
+                                empty((0, self.max_tracks), dtype=torch.int64),
+                                empty((0, self.max_tracks), dtype=torch.float64),
+                                empty((0, self.max_tracks), dtype=torch.uint8), stream_list, [])
+        staged = []
+        up = partial(upload, device=dev, keep=staged)
+        blocks = up(np.array([self._block(self._index[s]).data_ptr() for s in stream_list], dtype=np.int64))
+        frame_dev = None if frame_wh is None else up(frame_wh)
+        sup_off_dev = sup_dev = None
+        if sup_off is not None:
+            sup_off_dev = up(sup_off)
+            if isinstance(sup_boxes, torch.Tensor) and sup_boxes.is_cuda:
+                sup_dev = sup_boxes.detach().to(torch.float64)[up(sup_perm)].contiguous()
+            else:
+                sup_dev = up(np.ascontiguousarray(np.asarray(sup_boxes, dtype=np.float64)[sup_perm]))
+        out = self._launch_boxes(n_str, blocks, t_now, frame_dev, sup_off, sup_off_dev, sup_dev, opts, dev)
+        return BoxProposals(*out, stream_list, staged)
 
     # ------------------------------------------------------------------------------------------- update
     def _launch(self, n_str, off, off_dev, det_stream, blocks, kp_s, vis_s, ar_s, variances, t_now, t_prev):

@@ -9,6 +9,10 @@ tensors, as a decoder leaves them.  The frames are walked forwards and backwards
                finiteness readback, two stable sorts, gathers, the three launches, scatters
   launches     pp_track_oks, pp_track_assign and pp_track_filter of one such call alone, on its sorted batch (with their
                workspace and output allocations), replayed with advancing time
+  propose      one PoseTracker.propose_boxes over the 64 streams of the tracker the update variant drives (pad 1.25,
+               extrapolation on, no frame, no suppression): the block addresses through a pinned upload, four output
+               allocations, the one launch; nothing is read back
+  propose_launch  pp_track_boxes of one such call alone (with its output allocations), replayed
   host_numpy   the same rules on the host: the D2H copy of keypoints, areas and scores, then per stream a vectorised
                OKS matrix, the greedy walk over the detections, vectorised ageing, births and One-Euro steps
 
@@ -140,6 +144,22 @@ def launch_arguments(tracker, *inputs):
     return seen[0]
 
 
+def box_launch_arguments(tracker):
+    """One propose_boxes of ``tracker``: what it hands to its launch."""
+    launch, seen = tracker._launch_boxes, []
+
+    def spy(*args):
+        seen.append(args)
+        return launch(*args)
+
+    tracker._launch_boxes = spy
+    try:
+        tracker.propose_boxes()
+    finally:
+        del tracker._launch_boxes
+    return seen[0]
+
+
 def window(fn, steps):
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     a.record()
@@ -206,6 +226,9 @@ def main():
             clock["t"] = a[-2]
             return alone._launch(*a)
         variants[f"{P}/launches"] = launches
+        variants[f"{P}/propose"] = dev.propose_boxes
+        box_args = box_launch_arguments(alone)
+        variants[f"{P}/propose_launch"] = lambda alone=alone, a=box_args: alone._launch_boxes(*a)
 
     steps = {}
     for name, fn in variants.items():
