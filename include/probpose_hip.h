@@ -820,6 +820,36 @@ int pp_track_filter(int K, int max_tracks, long long Dtot, const void *det_strea
                     void *stream);
 
 /* ------------------------------------------------------------------------
+ * Optimal track association (PoseTracker(assign="optimal")): pp_track_assign with its association
+ * replaced by the matching of largest total weight; the launch shape, every other phase, the outputs and the state
+ * layout are pp_track_assign's.  total: int64 [n_str] or NULL, per stream the sum of q over its matched pairs.
+ *
+ * Per stream: rows are its D detections in visiting order, columns 0 .. T-1 its slots (T = max_tracks), m = max(D, T);
+ * columns T .. m-1 are virtual ("unmatched").  Weights q[i][j], int64:
+ *   q = 0 if j >= T, or slot j is not live when the call begins, or !(oks[i][j] > match_thr) (a NaN is inadmissible);
+ *   otherwise q = 1 + floor(min(oks[i][j] - match_thr, 1.0) * 2^40), each step one IEEE float64 operation.
+ * Costs a = -q.  Shortest augmenting paths with potentials, all int64, INF = 2^62:
+ *   1. u[i] = 0, v[j] = 0, no column holds a row.
+ *   2. for rows i = 0 .. D-1 in order: minv[j] = INF, used[j] = false, way[j] = root for every j; root is an extra
+ *      start column that holds row i; cur = root.  Repeat: mark cur used (the root counts); i0 = the row cur holds; for
+ *      every unused column j: c = a[i0][j] - u[i0] - v[j]; if c < minv[j] then minv[j] = c, way[j] = cur.  delta = the
+ *      minimum of minv over the unused columns, j1 = the LOWEST column that attains it.  For every used column (root
+ *      included): u[row it holds] += delta, v[col] -= delta; for every unused column: minv[j] -= delta.  cur = j1; stop
+ *      when cur holds no row.  Then walk back: while cur != root: prev = way[cur], cur takes the row prev held,
+ *      cur = prev.  Every step marks one more column used: a row ends after at most m + 1 steps on any input.
+ *   3. detection i is matched to slot j iff column j holds row i, j < T and q[i][j] > 0.
+ * This maximises the sum of q over the matchings of admissible pairs; every admissible pair has q >= 1.  A matched pair
+ * is written as pp_track_assign writes one (match_oks = oks[i][j]); ageing and births follow unchanged.
+ * Refused on the host like pp_track_assign, and also, naming the limit: max_tracks > PP_TRACK_OPT_MAX, a stream with
+ * more than PP_TRACK_OPT_MAX detections.
+ * ---------------------------------------------------------------------- */
+#define PP_TRACK_OPT_MAX 256
+int pp_track_assign_optimal(int n_str, int K, int max_tracks, long long Dtot, const long long *host_off,
+                            const void *off, const void *blocks, const void *oks, const void *area, double match_thr,
+                            int max_age, double t, double t_prev, void *ids, void *match_oks, void *born,
+                            void *slot_of, void *te, void *total, void *stream);
+
+/* ------------------------------------------------------------------------
  * Track-driven person boxes (PoseTracker.propose_boxes): the tracker's state read back out as the box
  * each track's person is expected in at time t, one launch, one lane per (stream, slot) with a serial loop over the
  * slot's K keypoints.  It writes no state; no atomics, no LDS, no barrier, plain vector stores: the same bits on every

@@ -148,6 +148,7 @@ _SIGNATURES = {
     "pp_track_state_bytes": (C.c_longlong, [_i, _i]),
     "pp_track_oks": (C.c_int, [_i, _i, _i, C.c_longlong] + [_vp] * 7 + [_d, _vp, _vp]),
     "pp_track_assign": (C.c_int, [_i, _i, _i, C.c_longlong] + [_vp] * 5 + [_d, _i, _d, _d] + [_vp] * 6),
+    "pp_track_assign_optimal": (C.c_int, [_i, _i, _i, C.c_longlong] + [_vp] * 5 + [_d, _i, _d, _d] + [_vp] * 7),
     "pp_track_filter": (C.c_int, [_i, _i, C.c_longlong] + [_vp] * 4 + [_d] + [_vp] * 3 + [_i, _d, _d, _d, _vp, _vp]),
     "pp_track_boxes": (C.c_int, [_i, _i, _i, _vp, _d, _i, _d, _i, _i, _d, _i, _i, _d, _d, _d] + [_vp] * 4 + [_d]
                        + [_vp] * 5),
@@ -161,6 +162,7 @@ PP_COCO_GT_CROWD, PP_COCO_GT_NO_VISIBLE = 1, 2
 PP_POSENMS_HARD, PP_POSENMS_SOFT_GAUSSIAN, PP_POSENMS_SOFT_LINEAR = 0, 1, 2
 PP_POSENMS_MAX_DETS = 4096
 PP_TRACK_MAX_TRACKS, PP_TRACK_MAX_DETS = 4096, 4096
+PP_TRACK_OPT_MAX = 256
 (PP_TRACK_BOX_FREE, PP_TRACK_BOX_PROPOSED, PP_TRACK_BOX_OLD, PP_TRACK_BOX_FEW, PP_TRACK_BOX_OUTSIDE,
  PP_TRACK_BOX_SUPPRESSED) = range(6)
 EXPORTS = tuple(_SIGNATURES)

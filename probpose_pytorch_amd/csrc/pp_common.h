@@ -115,6 +115,23 @@ __device__ __forceinline__ int wave_min(int v) {
   for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
   return v;
 }
+__device__ __forceinline__ long long wave_sum_i64(long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+// every lane gets the wave's smallest v and the smallest i among the lanes that hold it: one butterfly over the pair
+__device__ __forceinline__ void wave_argmin_i64(long long &v, int &i) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const long long ov = __shfl_xor(v, o, 64);
+    const int oi = __shfl_xor(i, o, 64);
+    if (ov < v || (ov == v && oi < i)) {
+      v = ov;
+      i = oi;
+    }
+  }
+}
 
 // ---- np.argmax order -------------------------------------------------------
 // The running result of a flat arg-max with numpy's semantics: the first maximum in row-major order wins; a NaN is the

@@ -14,6 +14,13 @@
 //                        slot.  What a detection gets (id, OKS, born, slot, te) is written by the lane that owns its
 //                        slot, or by lane 0 when it has none.  No atomics, no LDS, no barrier, plain vector stores: the
 //                        result does not depend on timing.
+//   track_assign_optimal_kernel  the same launch shape, phases and outputs with the association replaced by the
+//                        assignment of largest total weight: shortest augmenting paths with potentials
+//                        in int64, at most PP_TRACK_OPT_MAX rows and columns.  Lane j % 64 owns column j (at most four):
+//                        its v, minv, way, used bit, the row it holds and that row's u are registers of that lane; a
+//                        step is one coalesced load of the scanned row's OKS (a row's first step: loaded a row ahead)
+//                        and one wave_argmin_i64.  Ageing, births
+//                        and the matched pair's stores are the greedy kernel's own functions.
 //   track_filter_kernel  one lane per (detection, keypoint): reads the slot the assign kernel gave the detection, applies
 //                        the One-Euro step (or initialises, or passes the raw value through) and writes the output, the
 //                        filter state and the slot's raw keypoint and visibility.  A slot belongs to at most one
@@ -96,66 +103,37 @@ __global__ __launch_bounds__(kTrackThreads) void track_oks_kernel(
   oks[i] = n ? sum / (double)n : 0.0;
 }
 
-__global__ __launch_bounds__(64 * kTrackWaves) void track_assign_kernel(
-    int n_str, int K, int T, const long long *__restrict__ off, const long long *__restrict__ blocks,
-    const double *__restrict__ oks, const double *__restrict__ area, double match_thr, int max_age, double t,
-    long long *__restrict__ ids, double *__restrict__ match_oks, unsigned char *__restrict__ born,
-    int *__restrict__ slot_of, double *__restrict__ te) {
-  const long long str = (long long)blockIdx.x * kTrackWaves + (threadIdx.x >> 6);
-  if (str >= n_str) return;
-  const int lane = threadIdx.x & 63;
-  const long long d0 = off[str], span = off[str + 1] - d0;
-  if (span < 0 || span > PP_TRACK_MAX_DETS || T > PP_TRACK_MAX_TRACKS) return;   // refused on the host
-  const int D = (int)span, slots = (T + 63) >> 6;
-  const TrackState st = track_state(blocks[str], T, K);
+// What the lanes of a stream's wave share between the association modes.  The per-detection outputs of the assign
+// launch, and the call's constants they are written with:
+struct TrackOut {
+  const double *area;
+  double t;
+  long long *ids;
+  double *match_oks;
+  unsigned char *born;
+  int *slot_of;
+  double *te;
+};
 
-  // lane-owned: which of the lane's slots exist, are live (at entry) and are taken in this call; which of the
-  // detections p with p % 64 == lane are unmatched
-  unsigned long long valid = 0, live = 0, taken = 0, unmatched = 0;
-  for (int s = 0; s < slots; ++s) {
-    const int j = s * 64 + lane;
-    if (j < T) {
-      valid |= 1ull << s;
-      if (st.id[j] >= 0) live |= 1ull << s;
-    }
-  }
+// detection d continues slot j with pair OKS v: called by the lane that owns j
+__device__ __forceinline__ void track_take(const TrackState &st, const TrackOut &o, long long d, int j, double v) {
+  o.ids[d] = st.id[j];
+  o.match_oks[d] = v;
+  o.born[d] = 0;
+  o.slot_of[d] = j;
+  o.te[d] = o.t - st.t_last[j];
+  st.age[j] = 0;
+  st.t_last[j] = o.t;
+  st.area[j] = o.area[d];
+}
 
-  // association: the detections in visiting order
-  for (int p = 0; p < D; ++p) {
-    const double *row = oks + (d0 + p) * T;
-    double best = -INFINITY;
-    int best_j = INT_MAX;
-    unsigned long long cand = live & ~taken;
-    while (cand) {                                        // ascending slots: the lowest of the lane's on equal OKS
-      const int s = __builtin_ctzll(cand);
-      cand &= cand - 1;
-      const int j = s * 64 + lane;
-      const double v = row[j];
-      if (v > best) {
-        best = v;
-        best_j = j;
-      }
-    }
-    const double top = wave_max(best);
-    const int pick = wave_min(best_j != INT_MAX && best == top ? best_j : INT_MAX);
-    if (pick != INT_MAX && top > match_thr) {             // wave-uniform
-      if (lane == (pick & 63)) {
-        taken |= 1ull << (pick >> 6);
-        const long long d = d0 + p;
-        ids[d] = st.id[pick];
-        match_oks[d] = top;
-        born[d] = 0;
-        slot_of[d] = pick;
-        te[d] = t - st.t_last[pick];
-        st.age[pick] = 0;
-        st.t_last[pick] = t;
-        st.area[pick] = area[d];
-      }
-    } else if (lane == (p & 63)) {
-      unmatched |= 1ull << (p >> 6);
-    }
-  }
-
+// After the association: ageing of every live slot not taken (freed above max_age), then the births of the unmatched
+// detections in visiting order, each through wave_min of the lanes' lowest free slot.  valid / live / taken: bit s of
+// a lane is its slot s * 64 + lane; unmatched: bit p / 64 of lane p % 64 is detection p.
+__device__ __forceinline__ void track_age_and_bear(const TrackState &st, const TrackOut &o, int lane, long long d0,
+                                                   int D, int max_age, unsigned long long valid,
+                                                   unsigned long long live, unsigned long long taken,
+                                                   unsigned long long unmatched) {
   // ageing: every live slot not taken; freed above max_age
   for (unsigned long long m = live & ~taken; m;) {
     const int s = __builtin_ctzll(m);
@@ -183,22 +161,22 @@ __global__ __launch_bounds__(64 * kTrackWaves) void track_assign_kernel(
         live |= 1ull << (j >> 6);
         st.id[j] = next;
         st.age[j] = 0;
-        st.t_last[j] = t;
-        st.area[j] = area[d];
-        ids[d] = next;
-        match_oks[d] = 0.0;
-        born[d] = 1;
-        slot_of[d] = j;
-        te[d] = 0.0;
+        st.t_last[j] = o.t;
+        st.area[j] = o.area[d];
+        o.ids[d] = next;
+        o.match_oks[d] = 0.0;
+        o.born[d] = 1;
+        o.slot_of[d] = j;
+        o.te[d] = 0.0;
       }
       ++next;
     } else {
       if (lane == 0) {
-        ids[d] = -1;
-        match_oks[d] = 0.0;
-        born[d] = 0;
-        slot_of[d] = -1;
-        te[d] = 0.0;
+        o.ids[d] = -1;
+        o.match_oks[d] = 0.0;
+        o.born[d] = 0;
+        o.slot_of[d] = -1;
+        o.te[d] = 0.0;
       }
       ++over;
     }
@@ -207,6 +185,235 @@ __global__ __launch_bounds__(64 * kTrackWaves) void track_assign_kernel(
     *st.next_id = next;
     *st.overflow += over;
   }
+}
+
+// which of the lane's slots exist and which are live when the call begins
+__device__ __forceinline__ void track_slot_masks(const TrackState &st, int lane, int T, unsigned long long &valid,
+                                                 unsigned long long &live) {
+  valid = live = 0;
+  for (int s = 0, slots = (T + 63) >> 6; s < slots; ++s) {
+    const int j = s * 64 + lane;
+    if (j < T) {
+      valid |= 1ull << s;
+      if (st.id[j] >= 0) live |= 1ull << s;
+    }
+  }
+}
+
+__global__ __launch_bounds__(64 * kTrackWaves) void track_assign_kernel(
+    int n_str, int K, int T, const long long *__restrict__ off, const long long *__restrict__ blocks,
+    const double *__restrict__ oks, const double *__restrict__ area, double match_thr, int max_age, double t,
+    long long *__restrict__ ids, double *__restrict__ match_oks, unsigned char *__restrict__ born,
+    int *__restrict__ slot_of, double *__restrict__ te) {
+  const long long str = (long long)blockIdx.x * kTrackWaves + (threadIdx.x >> 6);
+  if (str >= n_str) return;
+  const int lane = threadIdx.x & 63;
+  const long long d0 = off[str], span = off[str + 1] - d0;
+  if (span < 0 || span > PP_TRACK_MAX_DETS || T > PP_TRACK_MAX_TRACKS) return;   // refused on the host
+  const int D = (int)span;
+  const TrackState st = track_state(blocks[str], T, K);
+  const TrackOut out{area, t, ids, match_oks, born, slot_of, te};
+
+  // lane-owned: which of the lane's slots exist, are live (at entry) and are taken in this call; which of the
+  // detections p with p % 64 == lane are unmatched
+  unsigned long long valid, live, taken = 0, unmatched = 0;
+  track_slot_masks(st, lane, T, valid, live);
+
+  // association: the detections in visiting order
+  for (int p = 0; p < D; ++p) {
+    const double *row = oks + (d0 + p) * T;
+    double best = -INFINITY;
+    int best_j = INT_MAX;
+    unsigned long long cand = live & ~taken;
+    while (cand) {                                        // ascending slots: the lowest of the lane's on equal OKS
+      const int s = __builtin_ctzll(cand);
+      cand &= cand - 1;
+      const int j = s * 64 + lane;
+      const double v = row[j];
+      if (v > best) {
+        best = v;
+        best_j = j;
+      }
+    }
+    const double top = wave_max(best);
+    const int pick = wave_min(best_j != INT_MAX && best == top ? best_j : INT_MAX);
+    if (pick != INT_MAX && top > match_thr) {             // wave-uniform
+      if (lane == (pick & 63)) {
+        taken |= 1ull << (pick >> 6);
+        track_take(st, out, d0 + p, pick, top);
+      }
+    } else if (lane == (p & 63)) {
+      unmatched |= 1ull << (p >> 6);
+    }
+  }
+  track_age_and_bear(st, out, lane, d0, D, max_age, valid, live, taken, unmatched);
+}
+
+// ---- the optimal association (the rule: include/probpose_hip.h, tests/trackopt_reference.py) ---------
+constexpr int kOptCols = PP_TRACK_OPT_MAX / 64;           // columns a lane owns at most
+constexpr long long kOptInf = 1ll << 62;
+constexpr int kOptRoot = -1;                              // the extra start column
+
+// q of a pair whose slot is real and live at entry
+__device__ __forceinline__ long long track_weight(double oks, double match_thr) {
+  if (!(oks > match_thr)) return 0;                       // a NaN is inadmissible
+  return 1 + (long long)floor(fmin(oks - match_thr, 1.0) * 1099511627776.0 /* 2^40 */);
+}
+
+// x[s] of a register array with a wave-uniform s, as lane `src` holds it
+template <typename V>
+__device__ __forceinline__ V opt_fetch(const V (&x)[kOptCols], int col) {
+  const int s = col >> 6;
+  V mine = x[0];
+#pragma unroll
+  for (int c = 1; c < kOptCols; ++c)
+    if (s == c) mine = x[c];
+  return __shfl(mine, col & 63, 64);
+}
+
+// row[j] at the lane's columns that are slots live at entry (bit s of live: slot s * 64 + lane < T), 0 elsewhere
+__device__ __forceinline__ void opt_load_row(const double *row, int lane, unsigned long long live,
+                                             double (&x)[kOptCols]) {
+#pragma unroll
+  for (int s = 0; s < kOptCols; ++s) x[s] = ((live >> s) & 1ull) ? row[s * 64 + lane] : 0.0;
+}
+
+__global__ __launch_bounds__(64 * kTrackWaves) void track_assign_optimal_kernel(
+    int n_str, int K, int T, const long long *__restrict__ off, const long long *__restrict__ blocks,
+    const double *__restrict__ oks, const double *__restrict__ area, double match_thr, int max_age, double t,
+    long long *__restrict__ ids, double *__restrict__ match_oks, unsigned char *__restrict__ born,
+    int *__restrict__ slot_of, double *__restrict__ te, long long *__restrict__ total) {
+  const long long str = (long long)blockIdx.x * kTrackWaves + (threadIdx.x >> 6);
+  if (str >= n_str) return;
+  const int lane = threadIdx.x & 63;
+  const long long d0 = off[str], span = off[str + 1] - d0;
+  if (span < 0 || span > PP_TRACK_OPT_MAX || T < 1 || T > PP_TRACK_OPT_MAX) return;   // refused on the host
+  const int D = (int)span, m = D > T ? D : T, cols = (m + 63) >> 6;
+  const TrackState st = track_state(blocks[str], T, K);
+  const TrackOut out{area, t, ids, match_oks, born, slot_of, te};
+
+  unsigned long long valid, live, taken = 0, unmatched = 0;
+  track_slot_masks(st, lane, T, valid, live);
+
+  // lane-owned, column s * 64 + lane in element s: the potential v, the row the column holds (-1: none) and that
+  // row's potential u (a row's u travels with the column that holds it; a row not yet added has u = 0)
+  long long v[kOptCols], u_held[kOptCols];
+  int held[kOptCols];
+#pragma unroll
+  for (int s = 0; s < kOptCols; ++s) {
+    v[s] = u_held[s] = 0;
+    held[s] = -1;
+  }
+
+  // the OKS of the scanned row at the lane's columns.  A row's first step always scans that row itself, so its OKS are
+  // loaded one row ahead, behind the previous row's path; only the later steps wait for a load their row index needs
+  double x[kOptCols], ahead[kOptCols];
+  if (D > 0) opt_load_row(oks + d0 * T, lane, live, ahead);
+  for (int i = 0; i < D; ++i) {                           // the rows in visiting order, one augmenting path each
+#pragma unroll
+    for (int s = 0; s < kOptCols; ++s) x[s] = ahead[s];
+    if (i + 1 < D) opt_load_row(oks + (d0 + i + 1) * T, lane, live, ahead);
+    long long minv[kOptCols];
+    int way[kOptCols];
+    unsigned used = 0;                                    // bit s: the lane's column s is on the tree
+#pragma unroll
+    for (int s = 0; s < kOptCols; ++s) {
+      minv[s] = kOptInf;
+      way[s] = kOptRoot;
+    }
+    int cur = kOptRoot, i0 = i;                           // wave-uniform: the column being scanned, its row,
+    long long u0 = 0, u_root = 0;                         // that row's u, and the u of row i (the root's)
+    bool open = false;
+    for (int step = 0; step <= m; ++step) {               // every step marks one more column: at most m + 1
+      if (cur != kOptRoot && lane == (cur & 63)) used |= 1u << (cur >> 6);
+      if (step > 0) opt_load_row(oks + (d0 + i0) * T, lane, live, x);
+      long long delta = LLONG_MAX;
+      int j1 = INT_MAX;
+#pragma unroll
+      for (int s = 0; s < kOptCols; ++s) {                // ascending columns: the lowest of the lane's on equal minv
+        const int j = s * 64 + lane;
+        if (s < cols && j < m && !((used >> s) & 1u)) {
+          const long long q = ((live >> s) & 1ull) ? track_weight(x[s], match_thr) : 0;
+          const long long c = -q - u0 - v[s];
+          if (c < minv[s]) {
+            minv[s] = c;
+            way[s] = cur;
+          }
+          if (minv[s] < delta) {
+            delta = minv[s];
+            j1 = j;
+          }
+        }
+      }
+      wave_argmin_i64(delta, j1);
+      if (j1 == INT_MAX) break;                           // no unused column: cannot happen, rows on the tree < m
+#pragma unroll
+      for (int s = 0; s < kOptCols; ++s) {
+        if ((used >> s) & 1u) {
+          u_held[s] += delta;
+          v[s] -= delta;
+        } else {
+          minv[s] -= delta;
+        }
+      }
+      u_root += delta;
+      cur = j1;
+      i0 = opt_fetch(held, cur);
+      u0 = opt_fetch(u_held, cur);
+      if (i0 < 0) {
+        open = true;
+        break;
+      }
+    }
+    // walk back: every column of the path takes the row of the column before it
+    for (int hop = 0; open && cur != kOptRoot && hop <= m; ++hop) {
+      const int prev = opt_fetch(way, cur);
+      int row_prev = i;
+      long long u_prev = u_root;
+      if (prev != kOptRoot) {                             // wave-uniform
+        row_prev = opt_fetch(held, prev);
+        u_prev = opt_fetch(u_held, prev);
+      }
+      if (lane == (cur & 63)) {
+#pragma unroll
+        for (int s = 0; s < kOptCols; ++s)
+          if (s == (cur >> 6)) {
+            held[s] = row_prev;
+            u_held[s] = u_prev;
+          }
+      }
+      cur = prev;
+    }
+  }
+
+  // a held row is matched if its column is a slot and the pair is admissible; written by the slot's lane
+  long long sum = 0;
+#pragma unroll
+  for (int s = 0; s < kOptCols; ++s) {
+    const int j = s * 64 + lane;
+    if (j < T && ((live >> s) & 1ull) && held[s] >= 0) {
+      const double x = oks[(d0 + held[s]) * T + j];
+      const long long q = track_weight(x, match_thr);
+      if (q > 0) {
+        sum += q;
+        taken |= 1ull << s;
+        track_take(st, out, d0 + held[s], j, x);
+      } else {
+        held[s] = -1;
+      }
+    } else {
+      held[s] = -1;
+    }
+  }
+  sum = wave_sum_i64(sum);
+  if (total && lane == 0) total[str] = sum;
+  for (int p = 0; p < D; ++p) {
+    bool mine = false;
+#pragma unroll
+    for (int s = 0; s < kOptCols; ++s) mine |= held[s] == p;
+    if (!__any(mine) && lane == (p & 63)) unmatched |= 1ull << (p >> 6);
+  }
+  track_age_and_bear(st, out, lane, d0, D, max_age, valid, live, taken, unmatched);
 }
 
 __device__ __forceinline__ double track_alpha(double te, double fc) {
@@ -287,6 +494,17 @@ static int track_check_offsets(const char *who, int n_str, const long long *h, l
   return 0;
 }
 
+// what both assign entries check, in this order
+static int track_check_assign(const char *who, int n_str, int K, int T, long long Dtot, const long long *host_off,
+                              double match_thr, int max_age, double t, double t_prev, bool pointers) {
+  if (int rc = track_check_common(who, n_str, K, T, Dtot)) return rc;
+  PP_REQUIRE(match_thr >= 0.0 && match_thr < 1.0, "%s: match_thr=%g is outside [0, 1)", who, match_thr);
+  PP_REQUIRE(max_age >= 0, "%s: max_age=%d", who, max_age);
+  PP_REQUIRE(t - t_prev > 0.0 && t < INFINITY, "%s: te <= 0 (t=%g after t_prev=%g)", who, t, t_prev);
+  PP_REQUIRE(pointers, "%s: null argument", who);
+  return track_check_offsets(who, n_str, host_off, Dtot);
+}
+
 }  // namespace pp
 
 extern "C" long long pp_track_state_bytes(int max_tracks, int K) {
@@ -321,14 +539,9 @@ extern "C" int pp_track_assign(int n_str, int K, int max_tracks, long long Dtot,
                                double match_thr, int max_age, double t, double t_prev, void *ids, void *match_oks,
                                void *born, void *slot_of, void *te, void *stream) {
   using namespace pp;
-  if (int rc = track_check_common("pp_track_assign", n_str, K, max_tracks, Dtot)) return rc;
-  PP_REQUIRE(match_thr >= 0.0 && match_thr < 1.0, "pp_track_assign: match_thr=%g is outside [0, 1)", match_thr);
-  PP_REQUIRE(max_age >= 0, "pp_track_assign: max_age=%d", max_age);
-  PP_REQUIRE(t - t_prev > 0.0 && t < INFINITY,
-             "pp_track_assign: te <= 0 (t=%g after t_prev=%g)", t, t_prev);
-  PP_REQUIRE(off && blocks && oks && area && ids && match_oks && born && slot_of && te,
-             "pp_track_assign: null argument");
-  if (int rc = track_check_offsets("pp_track_assign", n_str, host_off, Dtot)) return rc;
+  if (int rc = track_check_assign("pp_track_assign", n_str, K, max_tracks, Dtot, host_off, match_thr, max_age, t,
+                                  t_prev, off && blocks && oks && area && ids && match_oks && born && slot_of && te))
+    return rc;
   if (n_str == 0) return 0;                                // a stream without detections still ages its tracks
   const unsigned grid = (unsigned)((n_str + kTrackWaves - 1) / kTrackWaves);
   hipLaunchKernelGGL(track_assign_kernel, dim3(grid), dim3(64 * kTrackWaves), 0, (hipStream_t)stream, n_str, K,
@@ -336,6 +549,32 @@ extern "C" int pp_track_assign(int n_str, int K, int max_tracks, long long Dtot,
                      (const double *)area, match_thr, max_age, t, (long long *)ids, (double *)match_oks,
                      (unsigned char *)born, (int *)slot_of, (double *)te);
   PP_CHECK_LAUNCH("track_assign_kernel");
+  return 0;
+}
+
+extern "C" int pp_track_assign_optimal(int n_str, int K, int max_tracks, long long Dtot, const long long *host_off,
+                                       const void *off, const void *blocks, const void *oks, const void *area,
+                                       double match_thr, int max_age, double t, double t_prev, void *ids,
+                                       void *match_oks, void *born, void *slot_of, void *te, void *total,
+                                       void *stream) {
+  using namespace pp;
+  const char *who = "pp_track_assign_optimal";
+  if (int rc = track_check_assign(who, n_str, K, max_tracks, Dtot, host_off, match_thr, max_age, t, t_prev,
+                                  off && blocks && oks && area && ids && match_oks && born && slot_of && te))
+    return rc;
+  PP_REQUIRE(max_tracks <= PP_TRACK_OPT_MAX, "%s: max_tracks=%d is above PP_TRACK_OPT_MAX = %d", who, max_tracks,
+             PP_TRACK_OPT_MAX);
+  for (int i = 0; i < n_str; ++i)
+    PP_REQUIRE(host_off[i + 1] - host_off[i] <= PP_TRACK_OPT_MAX,
+               "%s: stream %d has %lld detections, more than PP_TRACK_OPT_MAX = %d", who, i,
+               host_off[i + 1] - host_off[i], PP_TRACK_OPT_MAX);
+  if (n_str == 0) return 0;
+  const unsigned grid = (unsigned)((n_str + kTrackWaves - 1) / kTrackWaves);
+  hipLaunchKernelGGL(track_assign_optimal_kernel, dim3(grid), dim3(64 * kTrackWaves), 0, (hipStream_t)stream, n_str,
+                     K, max_tracks, (const long long *)off, (const long long *)blocks, (const double *)oks,
+                     (const double *)area, match_thr, max_age, t, (long long *)ids, (double *)match_oks,
+                     (unsigned char *)born, (int *)slot_of, (double *)te, (long long *)total);
+  PP_CHECK_LAUNCH("track_assign_optimal_kernel");
   return 0;
 }
 

@@ -25,7 +25,8 @@ function, ``run_inference``: ``Codec(ProbMap(input_size, heatmap_size, sigmas))`
 * ``--frames DIR --boxes-json FILE --track`` runs the box path on every image file of DIR in sorted name order, as the
   frames of one video stream, with the boxes FILE gives per file name (``{name: [[x, y, w, h, score], ...]}``), and
   links the poses across the frames (``tracker.PoseTracker``; ``--match-thr``, ``--max-age``, ``--fps``; ``--smooth
-  [min_cutoff,beta,d_cutoff]`` adds the One-Euro filter).  ``--output`` gets ``tracks.json``: per frame and kept
+  [min_cutoff,beta,d_cutoff]`` adds the One-Euro filter; ``--assign optimal`` replaces the greedy association by the
+  matching of largest total weight, for at most 256 people per frame).  ``--output`` gets ``tracks.json``: per frame and kept
   detection its track id and (smoothed) keypoints; with ``--render`` also one picture per frame, drawn from those;
 * ``--propagate [VIS_THR,PAD,IOU]`` (with ``--track``) follows the people from frame to frame (``follow.PoseFollower``):
   every track proposes its person's next box from its own last pose, so FILE needs boxes for a key frame only.  A frame
@@ -214,6 +215,9 @@ def main(argv=None):
                         "boxes for key frames only (no value: 0.3,1.25,0.3)")
     p.add_argument("--match-thr", type=float, default=0.3, help="OKS a pose needs to continue a track")
     p.add_argument("--max-age", type=int, default=30, help="frames a track survives unseen")
+    p.add_argument("--assign", type=str, default="greedy", choices=["greedy", "optimal"],
+                   help="with --track: how poses take tracks: each in turn its best free one, or the best matching "
+                        "overall (Hungarian)")
     p.add_argument("--fps", type=float, default=30.0, help="frame rate of --frames: the time base of --smooth")
     p.add_argument("--render", action="store_true",
                    help="with --output: also write heatmap_{i}.png and output_image.png, drawn on the GPU")
@@ -322,7 +326,8 @@ def _track_options(p, args):
     propagate)."""
     if not args.track:
         for flag, given in (("--frames", args.frames is not None), ("--boxes-json", args.boxes_json is not None),
-                            ("--smooth", args.smooth is not None), ("--propagate", args.propagate is not None)):
+                            ("--smooth", args.smooth is not None), ("--propagate", args.propagate is not None),
+                            ("--assign", args.assign != "greedy")):
             if given:
                 p.error(f"{flag} needs --track")
         return None
@@ -396,7 +401,8 @@ def _main_frames(args, model, codec, track):
         nms = PoseNMS(sigmas, mode=args.nms, oks_thr=args.nms_thr)
     if track["propagate"] is not None:
         return _main_follow(args, model, codec, track, nms)
-    tracker = PoseTracker(sigmas, match_thr=args.match_thr, max_age=args.max_age, smooth=track["smooth"], fps=args.fps)
+    tracker = PoseTracker(sigmas, match_thr=args.match_thr, max_age=args.max_age, smooth=track["smooth"], fps=args.fps,
+                          assign=args.assign)
     args.output.mkdir(parents=True, exist_ok=True)
     record = []
     for path in track["files"]:
@@ -444,7 +450,7 @@ def _main_follow(args, model, codec, track, nms):
     K, dev = args.num_keypoints, "cuda"
     vis_thr, pad, iou = track["propagate"]
     tracker = PoseTracker(np.array([args.sigma] * K), match_thr=args.match_thr, max_age=args.max_age, vis_thr=vis_thr,
-                          smooth=track["smooth"], fps=args.fps)
+                          smooth=track["smooth"], fps=args.fps, assign=args.assign)
     follower = PoseFollower(tracker, box_estimator(model, codec), nms=nms, pad=pad, iou_thr=iou)
     args.output.mkdir(parents=True, exist_ok=True)
     record = []

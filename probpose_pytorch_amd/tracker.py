@@ -24,6 +24,13 @@ the counters next_id and overflow.  For every stream a call names:
 * then each unmatched detection, in visiting order, takes the lowest free slot (those just freed included) with a new
   id from the stream's counter; with no slot free it gets id -1 and counts in ``overflow``.
 
+``PoseTracker(assign="optimal")`` replaces the third rule (restated in tests/trackopt_reference.py): the
+detections of a stream take the live slots by the matching of largest total weight, where a pair with OKS >
+``match_thr`` weighs 1 + floor(min(OKS - match_thr, 1) * 2^40) and every other pair nothing (Hungarian assignment by
+shortest augmenting paths in int64, pp_track_assign_optimal in place of pp_track_assign: still three launches).  Two
+people close together then keep their ids where the greedy walk gives the first detection the other's track.  The mode
+takes at most ``OPT_MAX`` = 256 slots and 256 detections per stream and call; every other rule is unchanged.
+
 ``propose_boxes`` reads the state back out as the person box every track expects its person in next (one more launch,
 pp_track_boxes; restated in tests/trackbox_reference.py); follow.py builds the frame loop on it.
 
@@ -42,6 +49,7 @@ from .posenms import _first_seen
 
 MAX_TRACKS = _lib.PP_TRACK_MAX_TRACKS
 MAX_DETS_PER_STREAM = _lib.PP_TRACK_MAX_DETS
+OPT_MAX = _lib.PP_TRACK_OPT_MAX         # slots, and detections per stream and call, of assign="optimal"
 STREAMS_PER_CHUNK = 16
 
 
@@ -144,10 +152,14 @@ class PoseTracker:
     ``sigmas`` [K] are the per-keypoint OKS constants; ``match_thr`` in [0, 1) is the OKS a detection needs to continue
     a track; a track unseen for more than ``max_age`` frames of its stream is dropped; ``max_tracks`` slots per stream;
     ``vis_thr`` None lets every keypoint count; ``smooth`` is a ``OneEuro`` or None (raw keypoints out); ``fps`` gives
-    the default time stamps."""
+    the default time stamps; ``assign`` is "greedy" (each detection in turn takes its best free track) or "optimal"
+    (the matching of largest total weight; at most ``OPT_MAX`` slots and detections per stream and call)."""
 
     def __init__(self, sigmas, *, match_thr: float = 0.3, max_age: int = 30, max_tracks: int = 64, vis_thr=None,
-                 smooth: OneEuro | None = None, fps: float = 30.0):
+                 smooth: OneEuro | None = None, fps: float = 30.0, assign: str = "greedy"):
+        if assign not in ("greedy", "optimal"):
+            raise ValueError(f'assign: expected "greedy" or "optimal", got {assign!r}')
+        self.assign = assign
         self.sigmas = _host(sigmas, "sigmas", np.float64).reshape(-1)
         if self.sigmas.size == 0 or not np.all(np.isfinite(self.sigmas)) or np.any(self.sigmas <= 0):
             raise ValueError("sigmas: need K > 0 finite positive values")
@@ -158,6 +170,8 @@ class PoseTracker:
             raise ValueError(f"max_age: {max_age} is negative")
         if not 1 <= int(max_tracks) <= MAX_TRACKS:
             raise ValueError(f"max_tracks: {max_tracks} is outside 1..{MAX_TRACKS}")
+        if assign == "optimal" and int(max_tracks) > OPT_MAX:
+            raise ValueError(f'max_tracks: {max_tracks} is above the {OPT_MAX} that assign="optimal" takes')
         if vis_thr is not None and not np.isfinite(vis_thr):
             raise ValueError(f"vis_thr: {vis_thr} is not finite")
         if smooth is not None and not isinstance(smooth, OneEuro):
@@ -362,8 +376,12 @@ class PoseTracker:
         det_stream_h, kp_h, ar_h, ws_h, ids_h, oks_h, born_h, slot_h, te_h, out_h = hold
         _lib.launch("pp_track_oks", n_str, K, T, M, off, det_stream_h, _room(blocks), kp_h, vis_hold, ar_h, variances,
                     vis_thr, ws_h)
-        _lib.launch("pp_track_assign", n_str, K, T, M, off, off_dev, _room(blocks), ws_h, ar_h, self.match_thr,
-                    self.max_age, t_now, t_prev, ids_h, oks_h, born_h, slot_h, te_h)
+        assign_args = (n_str, K, T, M, off, off_dev, _room(blocks), ws_h, ar_h, self.match_thr, self.max_age, t_now,
+                       t_prev, ids_h, oks_h, born_h, slot_h, te_h)
+        if self.assign == "optimal":
+            _lib.launch("pp_track_assign_optimal", *assign_args, None)
+        else:
+            _lib.launch("pp_track_assign", *assign_args)
         sm = self.smooth
         _lib.launch("pp_track_filter", K, T, M, det_stream_h, _room(blocks), kp_h, vis_hold, vis_thr, slot_h, born_h,
                     te_h, int(sm is not None), *((sm.min_cutoff, sm.beta, sm.d_cutoff) if sm else (1.0, 0.0, 1.0)),
@@ -420,6 +438,10 @@ class PoseTracker:
             worst = int(d_cnt.argmax())
             raise ValueError(f"stream_ids: stream {stream_list[worst]!r} has {int(d_cnt[worst])} detections, more "
                              f"than the {MAX_DETS_PER_STREAM} that PoseTracker takes per stream and call")
+        if self.assign == "optimal" and n_str and int(d_cnt.max()) > OPT_MAX:
+            worst = int(d_cnt.argmax())
+            raise ValueError(f"stream_ids: stream {stream_list[worst]!r} has {int(d_cnt[worst])} detections, more "
+                             f'than the {OPT_MAX} that assign="optimal" takes per stream and call')
         t_now = (self._calls + 1) / self.fps if t is None else float(t)
         if not (np.isfinite(t_now) and t_now > self._t_prev):
             raise ValueError(f"t: {t_now} is not greater than the previous call's {self._t_prev}")

@@ -13,6 +13,10 @@ tensors, as a decoder leaves them.  The frames are walked forwards and backwards
                extrapolation on, no frame, no suppression): the block addresses through a pinned upload, four output
                allocations, the one launch; nothing is read back
   propose_launch  pp_track_boxes of one such call alone (with its output allocations), replayed
+  assign_greedy, assign_optimal, update_optimal   with `--assign optimal`: pp_track_assign and pp_track_assign_optimal
+               alone (with their output allocations) on one OKS workspace and one state, those of the second frame of a
+               tracker that has seen the first, so every detection has its track; and `update` of a tracker built with
+               assign="optimal".  `optimal_over_greedy` holds the ratios of the medians
   host_numpy   the same rules on the host: the D2H copy of keypoints, areas and scores, then per stream a vectorised
                OKS matrix, the greedy walk over the detections, vectorised ageing, births and One-Euro steps
 
@@ -160,6 +164,36 @@ def box_launch_arguments(tracker):
     return seen[0]
 
 
+def assign_launchers(tracker, frame):
+    """One update of ``tracker`` on ``frame``; before its launches touch the state, pp_track_oks fills a workspace of
+    this call's own.  Returns (greedy, optimal): pp_track_assign and pp_track_assign_optimal alone on that workspace
+    and on the tracker's state (with their output allocations).  Everybody is matched, so a replay leaves the state's
+    ids, and with them what the next replay does, as they are."""
+    from probpose_pytorch_amd import _lib
+    launch, made = tracker._launch, {}
+
+    def spy(n_str, off, off_dev, det_stream, blocks, kp_s, vis_s, ar_s, variances, t_now, t_prev):
+        T, M = tracker.max_tracks, int(off[-1])
+        ws = torch.empty(M * T, dtype=torch.float64, device=kp_s.device)
+        _lib.launch("pp_track_oks", n_str, K, T, M, off, det_stream, blocks, kp_s, None, ar_s, variances, 0.0, ws)
+
+        def run(entry, *tail):
+            new = lambda dtype: torch.empty(M, dtype=dtype, device=ws.device)
+            _lib.launch(entry, n_str, K, T, M, off, off_dev, blocks, ws, ar_s, MATCH_THR, MAX_AGE, t_now, t_prev,
+                        new(torch.int64), new(torch.float64), new(torch.uint8), new(torch.int32), new(torch.float64),
+                        *tail)
+        made["greedy"] = lambda: run("pp_track_assign")
+        made["optimal"] = lambda: run("pp_track_assign_optimal", None)
+        return launch(n_str, off, off_dev, det_stream, blocks, kp_s, vis_s, ar_s, variances, t_now, t_prev)
+
+    tracker._launch = spy
+    try:
+        tracker.update(*frame[1:], stream_ids=frame[0])
+    finally:
+        del tracker._launch
+    return made["greedy"], made["optimal"]
+
+
 def window(fn, steps):
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     a.record()
@@ -184,6 +218,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--assign", choices=["greedy", "optimal"], default="greedy",
+                    help="optimal: also time pp_track_assign_optimal beside pp_track_assign and the update in both modes")
     ap.add_argument("--out")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "track_bench needs the GPU: there is nothing to time without it"
@@ -200,15 +236,16 @@ def main():
             return frames[n if n < F else 2 * F - 2 - n]
         return nxt
 
-    new = lambda: PoseTracker(SIGMAS, match_thr=MATCH_THR, max_age=MAX_AGE, max_tracks=MAX_TRACKS, smooth=OneEuro(),
-                              fps=FPS)
+    new = lambda assign="greedy": PoseTracker(SIGMAS, match_thr=MATCH_THR, max_age=MAX_AGE, max_tracks=MAX_TRACKS,
+                                              smooth=OneEuro(), fps=FPS, assign=assign)
     variants, sizes = {}, {}
     for P in args.people:
         frames = make_video(args.streams, P, args.frames, args.seed + P)
         dev, host = new(), HostTracker(args.streams)
-        agree, matched = True, 0
+        agree, matched, dev_ids = True, 0, []
         for f in frames[:5]:                            # the host variant against the device, before anything is timed
             res = dev.update(*f[1:], stream_ids=f[0])
+            dev_ids.append(res.ids)
             got = host.update(*f)[0]
             agree = agree and bool(np.array_equal(res.ids.cpu().numpy(), got))
             matched = int((~res.born).sum())
@@ -229,6 +266,18 @@ def main():
         variants[f"{P}/propose"] = dev.propose_boxes
         box_args = box_launch_arguments(alone)
         variants[f"{P}/propose_launch"] = lambda alone=alone, a=box_args: alone._launch_boxes(*a)
+        if args.assign == "optimal":
+            opt, same = new("optimal"), True
+            for f in frames[:5]:
+                same = same and bool(torch.equal(opt.update(*f[1:], stream_ids=f[0]).ids,
+                                                 dev_ids.pop(0)))
+            sizes[str(P)]["optimal_ids_are_greedy_ids"] = same
+            step_opt = walker(frames[5:])
+            variants[f"{P}/update_optimal"] = lambda opt=opt, nxt=step_opt: (
+                lambda f: opt.update(*f[1:], stream_ids=f[0]))(nxt())
+            pair = new()
+            pair.update(*frames[0][1:], stream_ids=frames[0][0])
+            variants[f"{P}/assign_greedy"], variants[f"{P}/assign_optimal"] = assign_launchers(pair, frames[1])
 
     steps = {}
     for name, fn in variants.items():
@@ -244,6 +293,11 @@ def main():
                repeats=args.repeats, warmup=args.warmup, sizes=sizes, steps=steps)
     for name, ts in times.items():
         out[name] = spread(ts)
+    if args.assign == "optimal":                        # optimal / greedy, of the medians
+        ratio = lambda a, b: round(out[a]["ms_median"] / max(out[b]["ms_median"], 1e-6), 2)
+        out["optimal_over_greedy"] = {str(P): dict(assign=ratio(f"{P}/assign_optimal", f"{P}/assign_greedy"),
+                                                   update=ratio(f"{P}/update_optimal", f"{P}/update"))
+                                      for P in args.people}
     line = json.dumps(out)
     print(line)
     if args.out:
