@@ -900,6 +900,69 @@ int pp_track_boxes(int n_str, int K, int max_tracks, const void *blocks, double 
                    void *status, void *stream);
 
 /* ------------------------------------------------------------------------
+ * PoseTrackEval (probpose_pytorch_amd/trackeval.py): CLEAR-MOT and identity (IDF1) metrics of tracked
+ * poses against annotated ones.  The frames of all sequences are the "images" of pp_cocoeval_oks, which is launched
+ * first and unchanged; the three entries below read its matrices.  No host sync, no float atomics, no LDS; the same
+ * result on every call.
+ *
+ * Tables, each given in HOST memory (checked before any launch) and in device memory (what the kernels read):
+ *   host_offs / offs  [3, n_frames + 1] int64: pp_cocoeval_oks's own table with the predictions as its detections:
+ *     pred_off | gt_off | oks_off.  Frame f's matrix is D_f x G_f row-major: s[g][d] = oks[oks_off[f] + d * G_f + g].
+ *   host_seq / seq    [4, n_seq + 1] int64: frame_off (sequence q owns frames frame_off[q] .. frame_off[q+1], in time
+ *     order) | gid_off (running sum of NG_q, its ground-truth identities) | pid_off (running sum of NP_q, its predicted
+ *     identities) | c_off (running sum of NG_q * NP_q).
+ *   host_thr / thr    [n_thr] float64, each in (0, 1].
+ * gt_idx [Gtot] and pred_idx [Dtot], int32, device: every instance's identity as a dense index within its sequence,
+ * 0 <= gt_idx < NG_q, 0 <= pred_idx < NP_q, distinct within one frame (an index out of range is passed over).
+ *
+ * The rule.  s[g][d] is pp_cocoeval_oks of the frame, exactly.
+ * CLEAR, per sequence and threshold thr, frames in order.  State per ground-truth identity: last = the predicted
+ * identity it was matched to most recently, or none; prev = the one it was matched to in the frame immediately before
+ * this one, none if it was absent or unmatched there.  A frame with G ground truths (rows, in the order given) and D
+ * predictions (columns) has the int64 weights
+ *   q[i][j] = 0 unless s[i][j] >= thr (a NaN is inadmissible); otherwise
+ *   q[i][j] = 1 + floor(min(s[i][j] - thr, 1.0) * 2^32) + (2^42 if prev[gt i] == pred j else 0),
+ * each step one IEEE float64 operation.  256 * (2^32 + 1) < 2^42: an admissible continued pair outweighs any set of
+ * new pairs; every total stays below 2^53.  The assignment is that of pp_track_assign_optimal's steps 1 - 3 on q
+ * (rows in order, int64 potentials, the lowest column on equal minv, m = max(G, D) with virtual columns, a pair
+ * matched iff its column is real and q > 0).  Then TP += matches, FN += G - matches, FP += D - matches; for each
+ * matched (g, p): IDSW += 1 if last[g] exists and is not p; s[g][p] is added to a float64 sum (MOTP = sum / TP);
+ * last[g] = prev[g] = p for the matched, prev = none for every other identity.  Per identity, matched = the number of
+ * frames it is matched in and runs = the number of maximal runs of consecutive frames OF THE SEQUENCE in which it is
+ * matched; with present = the number of frames it appears in: MT iff 5 matched > 4 present, ML iff 5 matched < present,
+ * PT otherwise; Frag += max(0, runs - 1); MOTA = 1 - (FN + FP + IDSW) / (TP + FN).
+ * Identity, per sequence and threshold: c[a][b] = the number of frames in which ground-truth identity a and predicted
+ * identity b are both present with s >= thr; IDTP = the largest total of c over one-to-one assignments (the same
+ * solver; the total is unique); IDFN = ground-truth instances - IDTP, IDFP = predicted instances - IDTP; IDF1 =
+ * 2 IDTP / (2 IDTP + IDFP + IDFN), IDP = IDTP / (IDTP + IDFP), IDR = IDTP / (IDTP + IDFN).
+ *
+ * pp_trackeval_clear: one wave per (sequence, threshold).  Workspace, [n_thr, n_gid] each (n_gid = gid_off[n_seq]),
+ *   needing no initialisation: last int32, prev int64.  Outputs: matched, runs int32 [n_thr, n_gid]; rec int64
+ *   [n_seq, n_thr, 4] = TP, FN, FP, IDSW; oks_sum float64 [n_seq, n_thr] (per-lane sums added in a fixed order).
+ * pp_trackeval_overlap: one lane per (OKS entry, threshold): c [n_thr, c_total] int32 (c_total = c_off[n_seq]; sequence
+ *   q's matrix is NG_q x NP_q row-major at c_off[q]) gets += 1 by an integer atomic.  c must be ZERO on entry.
+ * pp_trackeval_identity: one wave per (sequence, threshold): idtp int64 [n_seq, n_thr].  A lane owns 4 columns when
+ *   both identity counts are at most PP_TRACKEVAL_MAX_FRAME, 16 otherwise.
+ * All refuse on the host, with pp_last_error naming the entry, before any launch: null pointers, n_seq < 0, n_thr < 1,
+ * a threshold outside (0, 1], tables that do not start at 0, are not monotone or do not end at the totals given, a
+ * frame with more than PP_TRACKEVAL_MAX_FRAME ground truths or predictions, a sequence with more than
+ * PP_TRACKEVAL_MAX_IDS ground-truth or predicted identities.  n_seq = 0 (overlap: also oks_total = 0) launches nothing.
+ * ---------------------------------------------------------------------- */
+#define PP_TRACKEVAL_MAX_FRAME 256
+#define PP_TRACKEVAL_MAX_IDS 1024
+int pp_trackeval_clear(int n_seq, int n_thr, int n_frames, long long Dtot, long long Gtot, long long oks_total,
+                       long long n_gid, const long long *host_offs, const long long *host_seq, const double *host_thr,
+                       const void *offs, const void *seq, const void *thr, const void *oks, const void *gt_idx,
+                       const void *pred_idx, void *last, void *prev, void *matched, void *runs, void *rec,
+                       void *oks_sum, void *stream);
+int pp_trackeval_overlap(int n_seq, int n_thr, int n_frames, long long Dtot, long long Gtot, long long oks_total,
+                         long long c_total, const long long *host_offs, const long long *host_seq,
+                         const double *host_thr, const void *offs, const void *seq, const void *thr, const void *oks,
+                         const void *gt_idx, const void *pred_idx, void *c, void *stream);
+int pp_trackeval_identity(int n_seq, int n_thr, long long c_total, const long long *host_seq, const void *seq,
+                          const void *c, void *idtp, void *stream);
+
+/* ------------------------------------------------------------------------
  * Visualisation (probpose_pytorch_amd/viz.py): heat overlays and pose drawing on uint8 RGB images, heat
  * maps as RGBA pictures.  No host sync, no atomics, plain vector stores, the same bytes on every call.
  *

@@ -14,7 +14,7 @@ from .heatmap import get_heatmap_expected_value  # noqa: F401
 
 __all__ = ["to_numpy", "Codec", "ProbMap", "ArgMaxProbMap", "get_heatmap_expected_value", "FusedAdamW",
            "Augment", "ModelEma", "ema_update_", "CocoKeypointEval", "PoseNMS", "rescore_instances",
-           "PoseTracker", "OneEuro", "PoseFollower"]
+           "PoseTracker", "OneEuro", "PoseFollower", "PoseTrackEval"]
 
 
 def __getattr__(name):  # lazy: the nn.Module side pulls in the engine
@@ -45,6 +45,9 @@ def __getattr__(name):  # lazy: the nn.Module side pulls in the engine
     if name == "PoseFollower":
         from .follow import PoseFollower
         return PoseFollower
+    if name == "PoseTrackEval":
+        from .trackeval import PoseTrackEval
+        return PoseTrackEval
     if name == "Augment":
         from .dataset import Augment
         return Augment

@@ -152,6 +152,9 @@ _SIGNATURES = {
     "pp_track_filter": (C.c_int, [_i, _i, C.c_longlong] + [_vp] * 4 + [_d] + [_vp] * 3 + [_i, _d, _d, _d, _vp, _vp]),
     "pp_track_boxes": (C.c_int, [_i, _i, _i, _vp, _d, _i, _d, _i, _i, _d, _i, _i, _d, _d, _d] + [_vp] * 4 + [_d]
                        + [_vp] * 5),
+    "pp_trackeval_clear": (C.c_int, [_i] * 3 + [C.c_longlong] * 4 + [_vp] * 16),
+    "pp_trackeval_overlap": (C.c_int, [_i] * 3 + [C.c_longlong] * 4 + [_vp] * 11),
+    "pp_trackeval_identity": (C.c_int, [_i, _i, C.c_longlong] + [_vp] * 5),
     "pp_viz_render": (C.c_int, [_vp, _i, _vp, _i, _i, _i, _vp, _i, _i, _i] + [_vp] * 5 + [_i, _i, _vp, _i, _d, _i, _i,
                                                                                           _vp]),
     "pp_viz_colorize": (C.c_int, [_vp, _vp, C.c_longlong, _i, _i, _vp, _i, _vp]),
@@ -165,6 +168,7 @@ PP_TRACK_MAX_TRACKS, PP_TRACK_MAX_DETS = 4096, 4096
 PP_TRACK_OPT_MAX = 256
 (PP_TRACK_BOX_FREE, PP_TRACK_BOX_PROPOSED, PP_TRACK_BOX_OLD, PP_TRACK_BOX_FEW, PP_TRACK_BOX_OUTSIDE,
  PP_TRACK_BOX_SUPPRESSED) = range(6)
+PP_TRACKEVAL_MAX_FRAME, PP_TRACKEVAL_MAX_IDS = 256, 1024
 EXPORTS = tuple(_SIGNATURES)
 
 

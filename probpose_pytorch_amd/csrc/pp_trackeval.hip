@@ -1,0 +1,469 @@
+// PoseTrackEval: CLEAR-MOT and identity (IDF1) metrics of tracked poses on the device (probpose_pytorch_amd/
+// trackeval.py; the rule: include/probpose_hip.h, tests/trackeval_reference.py).  The similarity is
+// pp_cocoeval_oks with the frames of all sequences as its images; the three launches here read its matrices.
+//
+// A batch is described by two offset tables, each given twice (a HOST copy that is checked before any launch and the
+// DEVICE copy the kernels read):
+//   offs  [3, n_frames + 1] int64   pp_cocoeval_oks's own table: prediction, ground-truth and OKS offsets per frame;
+//                                   frame f's matrix is D_f x G_f row-major, s[g][d] = oks[oks_off[f] + d * G_f + g]
+//   seq   [4, n_seq + 1]    int64   frame_off (sequence s owns frames frame_off[s] .. frame_off[s+1], in time order) |
+//                                   gid_off (running sum of its ground-truth identities NG_s) | pid_off (of its
+//                                   predicted identities NP_s) | c_off (running sum of NG_s * NP_s)
+// gt_idx [Gtot] / pred_idx [Dtot] int32 are the dense identity indices within the sequence.
+//
+//   sap_solve                   the shortest-augmenting-path solver of §4.7f, written once: a device template over the
+//                               number of columns NC a lane owns (lane j % 64 owns column j) and over how the weights
+//                               of a row are fetched.  v, minv, way, the used bits, the held row and its u are
+//                               registers of the owning lane; a step is one fetch and one wave_argmin_i64.
+//   trackeval_clear_kernel      one wave per (sequence, threshold), four waves to a workgroup; the frames in order,
+//                               sap_solve<4> per frame with the weights formed on the fly from the OKS column and the
+//                               row's `prev`.  last / prev / matched / runs per ground-truth identity live in a global
+//                               workspace this wave alone owns; the rows of a frame are distinct identities, so every
+//                               element has one writer.  prev carries the frame it was set in: nothing is reset.  A
+//                               frame's stores are fenced before the next frame reads them from other lanes.
+//   trackeval_overlap_kernel    one lane per (OKS entry, threshold): atomicAdd of 1 into the int32 c[a][b] of its
+//                               sequence where s >= thr.  Integer atomics: exact in any order.
+//   trackeval_identity_kernel   one wave per (sequence, threshold): sap_solve on c; 4 columns per lane when both
+//                               identity counts are at most 256, 16 otherwise.
+// No float atomics, no LDS, no barrier; every result is the same on every call.
+#include <limits.h>
+#include <math.h>
+
+#include "pp_common.h"
+
+namespace pp {
+
+constexpr int kTevWaves = 4;
+constexpr int kTevThreads = 64 * kTevWaves;
+constexpr long long kSapInf = 1ll << 62;
+constexpr int kSapRoot = -1;                              // the extra start column
+constexpr long long kTevBonus = 1ll << 42;                // what a continued pair's weight gains
+
+// x[col / 64] of a lane-owned register array as lane col % 64 holds it; col is wave-uniform
+template <int NC, typename V>
+__device__ __forceinline__ V sap_fetch(const V (&x)[NC], int col) {
+  const int s = col >> 6;
+  V mine = x[0];
+#pragma unroll
+  for (int c = 1; c < NC; ++c)
+    if (s == c) mine = x[c];
+  return __shfl(mine, col & 63, 64);
+}
+
+// The assignment of largest total weight by the rule of §4.7f: rows 0 .. R-1 in order, columns 0 .. m-1 (m >= R; the
+// columns the fetch gives 0 for are virtual).  fetch(i0, q) fills q[s] with the int64 weight of row i0 and the lane's
+// column s * 64 + lane.  On return held[s] is the row that column holds, or -1.  Every loop bound is wave-uniform.
+template <int NC, typename Fetch>
+__device__ __forceinline__ void sap_solve(int lane, int R, int m, const Fetch &fetch, int (&held)[NC]) {
+  long long v[NC], u_held[NC];                            // a row's u travels with the column that holds it
+#pragma unroll
+  for (int s = 0; s < NC; ++s) {
+    v[s] = u_held[s] = 0;
+    held[s] = -1;
+  }
+  for (int i = 0; i < R; ++i) {                           // one augmenting path per row
+    long long minv[NC];
+    int way[NC];
+    unsigned used = 0;                                    // bit s: the lane's column s is on the tree
+#pragma unroll
+    for (int s = 0; s < NC; ++s) {
+      minv[s] = kSapInf;
+      way[s] = kSapRoot;
+    }
+    int cur = kSapRoot, i0 = i;                           // wave-uniform: the column being scanned, its row,
+    long long u0 = 0, u_root = 0;                         // that row's u, and the u of row i (the root's)
+    bool open = false;
+    for (int step = 0; step <= m; ++step) {               // every step marks one more column: at most m + 1
+      if (cur != kSapRoot && lane == (cur & 63)) used |= 1u << (cur >> 6);
+      long long q[NC];
+      fetch(i0, q);
+      long long delta = LLONG_MAX;
+      int j1 = INT_MAX;
+#pragma unroll
+      for (int s = 0; s < NC; ++s) {                      // ascending columns: the lowest of the lane's on equal minv
+        const int j = s * 64 + lane;
+        if (j < m && !((used >> s) & 1u)) {
+          const long long c = -q[s] - u0 - v[s];
+          if (c < minv[s]) {
+            minv[s] = c;
+            way[s] = cur;
+          }
+          if (minv[s] < delta) {
+            delta = minv[s];
+            j1 = j;
+          }
+        }
+      }
+      wave_argmin_i64(delta, j1);
+      if (j1 == INT_MAX) break;                           // no unused column: cannot happen, rows on the tree < m
+#pragma unroll
+      for (int s = 0; s < NC; ++s) {
+        if ((used >> s) & 1u) {
+          u_held[s] += delta;
+          v[s] -= delta;
+        } else {
+          minv[s] -= delta;
+        }
+      }
+      u_root += delta;
+      cur = j1;
+      i0 = sap_fetch<NC>(held, cur);
+      u0 = sap_fetch<NC>(u_held, cur);
+      if (i0 < 0) {
+        open = true;
+        break;
+      }
+    }
+    // walk back: every column of the path takes the row of the column before it
+    for (int hop = 0; open && cur != kSapRoot && hop <= m; ++hop) {
+      const int prev = sap_fetch<NC>(way, cur);
+      int row_prev = i;
+      long long u_prev = u_root;
+      if (prev != kSapRoot) {                             // wave-uniform
+        row_prev = sap_fetch<NC>(held, prev);
+        u_prev = sap_fetch<NC>(u_held, prev);
+      }
+      if (lane == (cur & 63)) {
+#pragma unroll
+        for (int s = 0; s < NC; ++s)
+          if (s == (cur >> 6)) {
+            held[s] = row_prev;
+            u_held[s] = u_prev;
+          }
+      }
+      cur = prev;
+    }
+  }
+}
+
+// q of a pair without the continuation bonus: 0 = inadmissible (a NaN is)
+__device__ __forceinline__ long long tev_weight(double s, double thr) {
+  if (!(s >= thr)) return 0;
+  return 1 + (long long)floor(fmin(s - thr, 1.0) * 4294967296.0 /* 2^32 */);
+}
+
+// the rows of the sequence table
+struct TevSeq {
+  long long f0, f1, a0, NG, NP, c0;
+};
+__device__ __forceinline__ TevSeq tev_seq(const long long *seq, int n_seq, long long s) {
+  const long long *fo = seq, *go = seq + (n_seq + 1), *po = seq + 2ll * (n_seq + 1), *co = seq + 3ll * (n_seq + 1);
+  return TevSeq{fo[s], fo[s + 1], go[s], go[s + 1] - go[s], po[s + 1] - po[s], co[s]};
+}
+
+constexpr int kClearCols = PP_TRACKEVAL_MAX_FRAME / 64;   // columns a lane owns in a frame
+
+__global__ __launch_bounds__(kTevThreads) void trackeval_clear_kernel(
+    int n_seq, int n_thr, int n_frames, long long n_gid, const long long *__restrict__ offs,
+    const long long *__restrict__ seq, const double *__restrict__ thr, const double *__restrict__ oks,
+    const int *__restrict__ gt_idx, const int *__restrict__ pred_idx, int *last, long long *prev, int *matched,
+    int *runs, long long *__restrict__ rec, double *__restrict__ oks_sum) {
+  const long long w = (long long)blockIdx.x * kTevWaves + (threadIdx.x >> 6);
+  if (w >= (long long)n_seq * n_thr) return;
+  const int lane = threadIdx.x & 63;
+  const long long s = w / n_thr;
+  const int t = (int)(w - s * n_thr);
+  const TevSeq q = tev_seq(seq, n_seq, s);
+  if (q.f0 < 0 || q.f1 < q.f0 || q.f1 > n_frames || q.NG < 0 || q.NG > PP_TRACKEVAL_MAX_IDS || q.a0 < 0 ||
+      q.a0 + q.NG > n_gid)
+    return;                                               // refused on the host
+  const int NG = (int)q.NG;
+  const double th = thr[t];
+  const long long base = (long long)t * n_gid + q.a0;     // this wave's slice of the per-identity workspace
+  // last: the predicted identity + 1 (0 = none); prev: (frame tag << 32) | predicted identity, tag 0 = never
+  for (int a = lane; a < NG; a += 64) {
+    last[base + a] = 0;
+    prev[base + a] = 0;
+    matched[base + a] = 0;
+    runs[base + a] = 0;
+  }
+  __threadfence();
+  long long tp = 0, idsw = 0, n_gt = 0, n_pr = 0;
+  double sum = 0.0;
+  for (long long f = q.f0; f < q.f1; ++f) {
+    const long long d0 = offs[f], Dl = offs[f + 1] - d0;
+    const long long g0 = offs[n_frames + 1 + f], Gl = offs[n_frames + 2 + f] - g0;
+    const long long o0 = offs[2ll * n_frames + 2 + f];
+    if (Dl < 0 || Gl < 0 || Dl > PP_TRACKEVAL_MAX_FRAME || Gl > PP_TRACKEVAL_MAX_FRAME) return;   // refused on the host
+    const int D = (int)Dl, G = (int)Gl;
+    n_gt += G;
+    n_pr += D;
+    if (G == 0 || D == 0) continue;                       // nothing can match
+    const long long tag = f - q.f0 + 2;                   // tag - 1 >= 1: the frame before, never the "never" tag
+
+    // lane-owned: the prev of row r * 64 + lane (-1: none) and the predicted identity of column s * 64 + lane
+    int prow[kClearCols], pcol[kClearCols];
+#pragma unroll
+    for (int r = 0; r < kClearCols; ++r) {
+      const int i = r * 64 + lane;
+      prow[r] = pcol[r] = -1;
+      if (i < G) {
+        const int a = gt_idx[g0 + i];
+        if (a >= 0 && a < NG) {
+          const long long pk = prev[base + a];
+          if ((pk >> 32) == tag - 1) prow[r] = (int)(pk & 0xffffffffll);
+        }
+      }
+      if (i < D) pcol[r] = pred_idx[d0 + i];
+    }
+    const double *mat = oks + o0;
+    const auto fetch = [&](int i0, long long (&wq)[kClearCols]) {
+      const int pv = sap_fetch<kClearCols>(prow, i0);
+#pragma unroll
+      for (int c = 0; c < kClearCols; ++c) {
+        const int j = c * 64 + lane;
+        long long x = 0;
+        if (j < D) {
+          x = tev_weight(mat[(long long)j * G + i0], th);
+          if (x > 0 && pv >= 0 && pcol[c] == pv) x += kTevBonus;
+        }
+        wq[c] = x;
+      }
+    };
+    int held[kClearCols];
+    sap_solve<kClearCols>(lane, G, G > D ? G : D, fetch, held);
+
+    // a held row is matched if its column is real and the pair admissible; written by the column's lane
+#pragma unroll
+    for (int c = 0; c < kClearCols; ++c) {
+      const int j = c * 64 + lane;
+      if (j < D && held[c] >= 0 && held[c] < G) {
+        const double x = mat[(long long)j * G + held[c]];
+        if (tev_weight(x, th) > 0) {
+          ++tp;
+          sum += x;
+          const int a = gt_idx[g0 + held[c]], p = pcol[c];
+          if (a >= 0 && a < NG) {
+            const int was = last[base + a];
+            if (was != 0 && was != p + 1) ++idsw;
+            last[base + a] = p + 1;
+            if ((prev[base + a] >> 32) != tag - 1) runs[base + a] += 1;
+            matched[base + a] += 1;
+            prev[base + a] = (tag << 32) | (long long)(unsigned)p;
+          }
+        }
+      }
+    }
+    __threadfence();                                      // the next frame reads these from other lanes
+  }
+  tp = wave_sum_i64(tp);
+  idsw = wave_sum_i64(idsw);
+  sum = wave_sum(sum);
+  if (lane == 0) {
+    rec[4 * w] = tp;
+    rec[4 * w + 1] = n_gt - tp;
+    rec[4 * w + 2] = n_pr - tp;
+    rec[4 * w + 3] = idsw;
+    oks_sum[w] = sum;
+  }
+}
+
+// the last index i of a[0 .. n] (ascending, a[0] <= x < a[n]) with a[i] <= x
+__device__ __forceinline__ long long tev_owner(const long long *a, long long n, long long x) {
+  long long lo = 0, hi = n;
+  while (hi - lo > 1) {
+    const long long mid = lo + (hi - lo) / 2;
+    if (a[mid] <= x) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+
+__global__ __launch_bounds__(kTevThreads) void trackeval_overlap_kernel(
+    int n_seq, int n_thr, int n_frames, long long oks_total, long long c_total, const long long *__restrict__ offs,
+    const long long *__restrict__ seq, const double *__restrict__ thr, const double *__restrict__ oks,
+    const int *__restrict__ gt_idx, const int *__restrict__ pred_idx, int *c) {
+  const long long i = (long long)blockIdx.x * kTevThreads + threadIdx.x;
+  if (i >= oks_total * n_thr) return;
+  const long long e = i / n_thr;
+  const int t = (int)(i - e * n_thr);
+  if (!(oks[e] >= thr[t])) return;
+  const long long f = tev_owner(offs + 2ll * (n_frames + 1), n_frames, e);
+  const long long d0 = offs[f], D = offs[f + 1] - d0;
+  const long long g0 = offs[n_frames + 1 + f], G = offs[n_frames + 2 + f] - g0;
+  const long long r = e - offs[2ll * n_frames + 2 + f];
+  if (G <= 0 || r < 0 || r >= D * G) return;              // refused on the host
+  const long long d = r / G, g = r - d * G;
+  const TevSeq q = tev_seq(seq, n_seq, tev_owner(seq, n_seq, f));
+  const long long a = gt_idx[g0 + g], b = pred_idx[d0 + d];
+  if (a < 0 || a >= q.NG || b < 0 || b >= q.NP) return;
+  const long long at = q.c0 + a * q.NP + b;
+  if (at < 0 || at >= c_total) return;
+  atomicAdd(&c[(long long)t * c_total + at], 1);
+}
+
+template <int NC>
+__device__ __forceinline__ long long tev_identity(int lane, int NG, int NP, const int *__restrict__ c) {
+  const auto fetch = [&](int i0, long long (&wq)[NC]) {
+#pragma unroll
+    for (int s = 0; s < NC; ++s) {
+      const int j = s * 64 + lane;
+      wq[s] = j < NP ? (long long)c[(long long)i0 * NP + j] : 0;
+    }
+  };
+  int held[NC];
+  sap_solve<NC>(lane, NG, NG > NP ? NG : NP, fetch, held);
+  long long sum = 0;
+#pragma unroll
+  for (int s = 0; s < NC; ++s) {
+    const int j = s * 64 + lane;
+    if (j < NP && held[s] >= 0 && held[s] < NG) sum += c[(long long)held[s] * NP + j];
+  }
+  return wave_sum_i64(sum);
+}
+
+constexpr int kIdentityCols = PP_TRACKEVAL_MAX_IDS / 64;  // columns a lane owns in the wide form
+
+__global__ __launch_bounds__(kTevThreads) void trackeval_identity_kernel(
+    int n_seq, int n_thr, long long c_total, const long long *__restrict__ seq, const int *__restrict__ c,
+    long long *__restrict__ idtp) {
+  const long long w = (long long)blockIdx.x * kTevWaves + (threadIdx.x >> 6);
+  if (w >= (long long)n_seq * n_thr) return;
+  const int lane = threadIdx.x & 63;
+  const long long s = w / n_thr, t = w - s * n_thr;
+  const TevSeq q = tev_seq(seq, n_seq, s);
+  if (q.NG < 0 || q.NP < 0 || q.NG > PP_TRACKEVAL_MAX_IDS || q.NP > PP_TRACKEVAL_MAX_IDS || q.c0 < 0 ||
+      q.c0 + q.NG * q.NP > c_total)
+    return;                                               // refused on the host
+  const int NG = (int)q.NG, NP = (int)q.NP;
+  const int *mine = c + t * c_total + q.c0;
+  long long total = 0;
+  if (NG > 0 && NP > 0) {                                 // wave-uniform
+    if (NG <= PP_TRACKEVAL_MAX_FRAME && NP <= PP_TRACKEVAL_MAX_FRAME) total = tev_identity<kClearCols>(lane, NG, NP, mine);
+    else total = tev_identity<kIdentityCols>(lane, NG, NP, mine);
+  }
+  if (lane == 0) idtp[w] = total;
+}
+
+// ---- host checks: everything an entry refuses, before any launch ---------------------------------------------------
+static int tev_check_counts(const char *who, int n_seq, int n_thr) {
+  PP_REQUIRE(n_seq >= 0, "%s: n_seq=%d", who, n_seq);
+  PP_REQUIRE(n_thr >= 1, "%s: n_thr=%d", who, n_thr);
+  return 0;
+}
+
+static int tev_check_thr(const char *who, int n_thr, const double *h) {
+  PP_REQUIRE(h, "%s: null host thresholds", who);
+  for (int i = 0; i < n_thr; ++i)                         // written so that a NaN fails it
+    PP_REQUIRE(h[i] > 0.0 && h[i] <= 1.0, "%s: threshold %d = %g is outside (0, 1]", who, i, h[i]);
+  return 0;
+}
+
+// the host copy of the sequence table; n_frames < 0: the caller has no frames to hold it against
+static int tev_check_seq(const char *who, int n_seq, const long long *h, long long n_frames, long long n_gid,
+                         long long c_total) {
+  PP_REQUIRE(h, "%s: null host sequence table", who);
+  const long long *fo = h, *go = h + (n_seq + 1), *po = h + 2ll * (n_seq + 1), *co = h + 3ll * (n_seq + 1);
+  PP_REQUIRE(fo[0] == 0 && go[0] == 0 && po[0] == 0 && co[0] == 0,
+             "%s: sequence offsets do not start at 0 (frames %lld, gt ids %lld, pred ids %lld, c %lld)", who, fo[0],
+             go[0], po[0], co[0]);
+  for (int i = 0; i < n_seq; ++i) {
+    PP_REQUIRE(fo[i + 1] >= fo[i], "%s: frame offsets are not monotone at sequence %d (%lld after %lld)", who, i,
+               fo[i + 1], fo[i]);
+    const long long ng = go[i + 1] - go[i], np = po[i + 1] - po[i];
+    PP_REQUIRE(ng >= 0 && np >= 0, "%s: identity offsets are not monotone at sequence %d", who, i);
+    PP_REQUIRE(ng <= PP_TRACKEVAL_MAX_IDS && np <= PP_TRACKEVAL_MAX_IDS,
+               "%s: sequence %d has %lld ground-truth and %lld predicted identities, more than "
+               "PP_TRACKEVAL_MAX_IDS = %d", who, i, ng, np, PP_TRACKEVAL_MAX_IDS);
+    PP_REQUIRE(co[i + 1] - co[i] == ng * np, "%s: c offsets of sequence %d span %lld entries, expected %lld x %lld",
+               who, i, co[i + 1] - co[i], ng, np);
+  }
+  PP_REQUIRE(n_frames < 0 || fo[n_seq] == n_frames, "%s: frame offsets end at %lld, there are %lld frames", who,
+             fo[n_seq], n_frames);
+  PP_REQUIRE(n_gid < 0 || go[n_seq] == n_gid, "%s: ground-truth identity offsets end at %lld, the workspace holds %lld",
+             who, go[n_seq], n_gid);
+  PP_REQUIRE(co[n_seq] == c_total, "%s: c offsets end at %lld, c holds %lld per threshold", who, co[n_seq], c_total);
+  return 0;
+}
+
+// the host copy of pp_cocoeval_oks's table, and the frame limit
+static int tev_check_frames(const char *who, int n_frames, const long long *h, long long Dtot, long long Gtot,
+                            long long oks_total) {
+  PP_REQUIRE(n_frames >= 0, "%s: n_frames=%d", who, n_frames);
+  PP_REQUIRE(h, "%s: null host offsets", who);
+  const long long *d = h, *g = h + n_frames + 1, *o = h + 2ll * (n_frames + 1);
+  PP_REQUIRE(d[0] == 0 && g[0] == 0 && o[0] == 0, "%s: offsets do not start at 0 (pred %lld, gt %lld, oks %lld)", who,
+             d[0], g[0], o[0]);
+  for (int i = 0; i < n_frames; ++i) {
+    const long long D = d[i + 1] - d[i], G = g[i + 1] - g[i];
+    PP_REQUIRE(D >= 0 && G >= 0, "%s: offsets are not monotone at frame %d", who, i);
+    PP_REQUIRE(D <= PP_TRACKEVAL_MAX_FRAME && G <= PP_TRACKEVAL_MAX_FRAME,
+               "%s: frame %d has %lld ground truths and %lld predictions, more than PP_TRACKEVAL_MAX_FRAME = %d", who,
+               i, G, D, PP_TRACKEVAL_MAX_FRAME);
+    PP_REQUIRE(o[i + 1] - o[i] == D * G, "%s: OKS offsets of frame %d span %lld entries, expected D x G = %lld x %lld",
+               who, i, o[i + 1] - o[i], D, G);
+  }
+  PP_REQUIRE(d[n_frames] == Dtot && g[n_frames] == Gtot && o[n_frames] == oks_total,
+             "%s: offsets end at (pred %lld, gt %lld, oks %lld), the arrays hold (%lld, %lld, %lld)", who, d[n_frames],
+             g[n_frames], o[n_frames], Dtot, Gtot, oks_total);
+  return 0;
+}
+
+}  // namespace pp
+
+extern "C" int pp_trackeval_clear(int n_seq, int n_thr, int n_frames, long long Dtot, long long Gtot,
+                                  long long oks_total, long long n_gid, const long long *host_offs,
+                                  const long long *host_seq, const double *host_thr, const void *offs, const void *seq,
+                                  const void *thr, const void *oks, const void *gt_idx, const void *pred_idx,
+                                  void *last, void *prev, void *matched, void *runs, void *rec, void *oks_sum,
+                                  void *stream) {
+  using namespace pp;
+  const char *who = "pp_trackeval_clear";
+  if (int rc = tev_check_counts(who, n_seq, n_thr)) return rc;
+  PP_REQUIRE(n_gid >= 0, "%s: n_gid=%lld", who, n_gid);
+  PP_REQUIRE(offs && seq && thr && oks && gt_idx && pred_idx && last && prev && matched && runs && rec && oks_sum,
+             "%s: null argument", who);
+  if (int rc = tev_check_thr(who, n_thr, host_thr)) return rc;
+  if (int rc = tev_check_frames(who, n_frames, host_offs, Dtot, Gtot, oks_total)) return rc;
+  PP_REQUIRE(host_seq, "%s: null host sequence table", who);
+  if (int rc = tev_check_seq(who, n_seq, host_seq, n_frames, n_gid, host_seq[4ll * (n_seq + 1) - 1])) return rc;
+  if (n_seq == 0) return 0;
+  const long long grid = ((long long)n_seq * n_thr + kTevWaves - 1) / kTevWaves;
+  PP_REQUIRE(grid < (1ll << 31), "%s: %lld (sequence, threshold) pairs exceed one grid", who, (long long)n_seq * n_thr);
+  hipLaunchKernelGGL(trackeval_clear_kernel, dim3((unsigned)grid), dim3(kTevThreads), 0, (hipStream_t)stream, n_seq,
+                     n_thr, n_frames, n_gid, (const long long *)offs, (const long long *)seq, (const double *)thr,
+                     (const double *)oks, (const int *)gt_idx, (const int *)pred_idx, (int *)last, (long long *)prev,
+                     (int *)matched, (int *)runs, (long long *)rec, (double *)oks_sum);
+  PP_CHECK_LAUNCH("trackeval_clear_kernel");
+  return 0;
+}
+
+extern "C" int pp_trackeval_overlap(int n_seq, int n_thr, int n_frames, long long Dtot, long long Gtot,
+                                    long long oks_total, long long c_total, const long long *host_offs,
+                                    const long long *host_seq, const double *host_thr, const void *offs,
+                                    const void *seq, const void *thr, const void *oks, const void *gt_idx,
+                                    const void *pred_idx, void *c, void *stream) {
+  using namespace pp;
+  const char *who = "pp_trackeval_overlap";
+  if (int rc = tev_check_counts(who, n_seq, n_thr)) return rc;
+  PP_REQUIRE(c_total >= 0, "%s: c_total=%lld", who, c_total);
+  PP_REQUIRE(offs && seq && thr && oks && gt_idx && pred_idx && c, "%s: null argument", who);
+  if (int rc = tev_check_thr(who, n_thr, host_thr)) return rc;
+  if (int rc = tev_check_frames(who, n_frames, host_offs, Dtot, Gtot, oks_total)) return rc;
+  if (int rc = tev_check_seq(who, n_seq, host_seq, n_frames, -1, c_total)) return rc;
+  if (n_seq == 0 || oks_total == 0) return 0;
+  const long long lanes = oks_total * n_thr, grid = (lanes + kTevThreads - 1) / kTevThreads;
+  PP_REQUIRE(grid < (1ll << 31), "%s: %lld (OKS entry, threshold) pairs exceed one grid", who, lanes);
+  hipLaunchKernelGGL(trackeval_overlap_kernel, dim3((unsigned)grid), dim3(kTevThreads), 0, (hipStream_t)stream, n_seq,
+                     n_thr, n_frames, oks_total, c_total, (const long long *)offs, (const long long *)seq,
+                     (const double *)thr, (const double *)oks, (const int *)gt_idx, (const int *)pred_idx, (int *)c);
+  PP_CHECK_LAUNCH("trackeval_overlap_kernel");
+  return 0;
+}
+
+extern "C" int pp_trackeval_identity(int n_seq, int n_thr, long long c_total, const long long *host_seq,
+                                     const void *seq, const void *c, void *idtp, void *stream) {
+  using namespace pp;
+  const char *who = "pp_trackeval_identity";
+  if (int rc = tev_check_counts(who, n_seq, n_thr)) return rc;
+  PP_REQUIRE(c_total >= 0, "%s: c_total=%lld", who, c_total);
+  PP_REQUIRE(seq && c && idtp, "%s: null argument", who);
+  if (int rc = tev_check_seq(who, n_seq, host_seq, -1, -1, c_total)) return rc;
+  if (n_seq == 0) return 0;
+  const long long grid = ((long long)n_seq * n_thr + kTevWaves - 1) / kTevWaves;
+  PP_REQUIRE(grid < (1ll << 31), "%s: %lld (sequence, threshold) pairs exceed one grid", who, (long long)n_seq * n_thr);
+  hipLaunchKernelGGL(trackeval_identity_kernel, dim3((unsigned)grid), dim3(kTevThreads), 0, (hipStream_t)stream, n_seq,
+                     n_thr, c_total, (const long long *)seq, (const int *)c, (long long *)idtp);
+  PP_CHECK_LAUNCH("trackeval_identity_kernel");
+  return 0;
+}
