@@ -963,6 +963,79 @@ int pp_trackeval_identity(int n_seq, int n_thr, long long c_total, const long lo
                           const void *c, void *idtp, void *stream);
 
 /* ------------------------------------------------------------------------
+ * HOTA for PoseTrackEval (PoseTrackEval(hota=True)): higher order tracking accuracy (Luiten et al., IJCV
+ * 2021) with OKS as the similarity, per sequence and alpha: the counts and sums from which DetA, AssA, LocA and HOTA
+ * are finished on the host.  Four entries after pp_cocoeval_oks, on the tables of the entries above; the same
+ * principles: no host sync, no float atomics, no LDS, the same result on every call.
+ *
+ * The rule.  s[g][d] is pp_cocoeval_oks's entry of the frame (in [0, 1] or NaN); an s that is not > 0 (a NaN is not)
+ * counts as 0 everywhere below.  a and b are the dense identities of g and d in their sequence; every float step is
+ * one IEEE float64 operation.
+ *  1. Potential matches, per frame: R_g = sum over d of s[g][d] and C_d = sum over g of s[g][d], each a sequential sum
+ *     from 0.0 in ascending index.  For every pair with s > 0: x = s / ((R_g + C_d) - s), w = floor(x * 2^32) as int64
+ *     (x <= 1, since both sums hold s), pmc[a][b] += w (an int64 atomic: exact in any order).  ng[a] and np[b] are the
+ *     numbers of frames an identity appears in, counted on the host.
+ *  2. Alignment: A[a][b] = double(pmc) / double(2^32 (ng[a] + np[b]) - pmc), the denominator formed in int64 (it is
+ *     at least 2^32 max(ng, np) where both identities appear; A = 0 if it is not > 0).  Both operands stay below 2^53
+ *     while a sequence has at most PP_TRACKEVAL_HOTA_MAX_FRAMES = 2^20 frames.
+ *  3. Matching, one per frame for all alphas: q[g][d] = 0 unless s > 0, else 1 + floor((A[a][b] * s) * 2^32); the
+ *     assignment is pp_track_assign_optimal's steps 1 - 3 on q exactly as for CLEAR above: rows (ground truths) in
+ *     order, int64 potentials, the lowest column on equal minv, m = max(G, D) with virtual columns, a pair matched iff
+ *     its column is real and q > 0.  A matching's total / 2^32 differs from its sum of A s by less than 2^-23 (at
+ *     most 256 pairs, each q / 2^32 within 2^-32 above A s, and the roundings of A s).
+ *  4. Counts, per alpha_i: a matched pair counts iff s >= alpha_i.  TP_i = the counted pairs of all frames, FN_i =
+ *     ground-truth instances - TP_i, FP_i = predicted instances - TP_i, loc_i = the sum of s over the counted pairs,
+ *     mc_i[a][b] += 1 (an int32 atomic).  TP and loc take no atomics: every frame writes its own record (the lane of
+ *     column d % 64 adds its columns in ascending order, then one butterfly over the lanes), launch 4 adds the frames.
+ *  5. Association, per sequence and alpha, with m = mc_i[a][b] over the NG x NP entries: assA = sum of m m / (ng[a] +
+ *     np[b] - m), assRe = sum of m m / ng[a], assPr = sum of m m / np[b]; m m is formed in int64.
+ *  6. On the host, with everything summed over the sequences: DetA = TP / (TP + FN + FP), DetRe = TP / (TP + FN), DetPr
+ *     = TP / (TP + FP), AssA = assA / TP, AssRe = assRe / TP, AssPr = assPr / TP, LocA = loc / TP, HOTA = sqrt(DetA
+ *     AssA); a ratio whose denominator is 0 is 0, LocA is then 1.
+ * A float sum of launch 4 is: lane l adds the elements l, l + 64, .. in ascending order, then one butterfly.
+ *
+ * gt_present [n_gid] / pred_present [n_pid] int64, device: ng and np of every identity, at gid_off / pid_off of its
+ *   sequence (n_pid = pid_off[n_seq]).  host_alpha / alpha [n_alpha] float64, each in (0, 1], n_alpha <=
+ *   PP_TRACKEVAL_HOTA_MAX_ALPHAS.
+ * pp_trackeval_hota_align (step 1): one wave per frame, four to a workgroup.  pmc int64 [c_total], laid out like one
+ *   threshold's c above; it must be ZERO on entry.
+ * pp_trackeval_hota_weights (steps 2, 3): one lane per OKS entry: q int64 [oks_total]; frame f's weights are G_f x D_f
+ *   row-major (the transpose of its OKS matrix): q[g][d] = q[oks_off[f] + g * D_f + d], so that the solver loads a row
+ *   coalesced and no division is left in it.  Every entry is written.
+ * pp_trackeval_hota_match (steps 3, 4): one wave per frame, four to a workgroup, four columns per lane.  mc int32
+ *   [n_alpha, c_total] must be ZERO on entry.  Outputs: held_row int32 [Dtot] = the row (ground truth of the frame)
+ *   every prediction is matched to, or -1; frame_tp int64 and frame_loc float64 [n_frames, n_alpha].
+ * pp_trackeval_hota_assoc (steps 4, 5): one wave per (sequence, alpha): tp int64 [n_seq, n_alpha]; sums float64
+ *   [n_seq, n_alpha, 4] = loc, assA, assRe, assPr.
+ * Workspace: pmc and mc take (8 + 4 n_alpha) NG NP bytes per sequence: about 84 MB for one 1024 x 1024 sequence with 19
+ * alphas; q takes 8 bytes per OKS entry.
+ * All refuse on the host, with pp_last_error naming the entry, before any launch: what the entries above refuse of the
+ * tables they are given, n_alpha outside [1, PP_TRACKEVAL_HOTA_MAX_ALPHAS], an alpha outside (0, 1], predicted identity
+ * offsets that do not end at n_pid, a sequence of more than PP_TRACKEVAL_HOTA_MAX_FRAMES frames.  n_seq = 0 launches
+ * nothing (align, weights: also oks_total = 0; match: also n_frames = 0).
+ * ---------------------------------------------------------------------- */
+#define PP_TRACKEVAL_HOTA_MAX_ALPHAS 32
+#define PP_TRACKEVAL_HOTA_MAX_FRAMES 1048576
+int pp_trackeval_hota_align(int n_seq, int n_frames, long long Dtot, long long Gtot, long long oks_total,
+                            long long c_total, const long long *host_offs, const long long *host_seq, const void *offs,
+                            const void *seq, const void *oks, const void *gt_idx, const void *pred_idx, void *pmc,
+                            void *stream);
+int pp_trackeval_hota_weights(int n_seq, int n_frames, long long Dtot, long long Gtot, long long oks_total,
+                              long long c_total, long long n_gid, long long n_pid, const long long *host_offs,
+                              const long long *host_seq, const void *offs, const void *seq, const void *oks,
+                              const void *gt_idx, const void *pred_idx, const void *pmc, const void *gt_present,
+                              const void *pred_present, void *q, void *stream);
+int pp_trackeval_hota_match(int n_seq, int n_alpha, int n_frames, long long Dtot, long long Gtot, long long oks_total,
+                            long long c_total, const long long *host_offs, const long long *host_seq,
+                            const double *host_alpha, const void *offs, const void *seq, const void *alpha,
+                            const void *oks, const void *q, const void *gt_idx, const void *pred_idx, void *mc,
+                            void *held_row, void *frame_tp, void *frame_loc, void *stream);
+int pp_trackeval_hota_assoc(int n_seq, int n_alpha, int n_frames, long long c_total, long long n_gid, long long n_pid,
+                            const long long *host_seq, const void *seq, const void *mc, const void *gt_present,
+                            const void *pred_present, const void *frame_tp, const void *frame_loc, void *tp, void *sums,
+                            void *stream);
+
+/* ------------------------------------------------------------------------
  * Visualisation (probpose_pytorch_amd/viz.py): heat overlays and pose drawing on uint8 RGB images, heat
  * maps as RGBA pictures.  No host sync, no atomics, plain vector stores, the same bytes on every call.
  *

@@ -155,6 +155,10 @@ _SIGNATURES = {
     "pp_trackeval_clear": (C.c_int, [_i] * 3 + [C.c_longlong] * 4 + [_vp] * 16),
     "pp_trackeval_overlap": (C.c_int, [_i] * 3 + [C.c_longlong] * 4 + [_vp] * 11),
     "pp_trackeval_identity": (C.c_int, [_i, _i, C.c_longlong] + [_vp] * 5),
+    "pp_trackeval_hota_align": (C.c_int, [_i, _i] + [C.c_longlong] * 4 + [_vp] * 9),
+    "pp_trackeval_hota_weights": (C.c_int, [_i, _i] + [C.c_longlong] * 6 + [_vp] * 12),
+    "pp_trackeval_hota_match": (C.c_int, [_i] * 3 + [C.c_longlong] * 4 + [_vp] * 15),
+    "pp_trackeval_hota_assoc": (C.c_int, [_i] * 3 + [C.c_longlong] * 3 + [_vp] * 10),
     "pp_viz_render": (C.c_int, [_vp, _i, _vp, _i, _i, _i, _vp, _i, _i, _i] + [_vp] * 5 + [_i, _i, _vp, _i, _d, _i, _i,
                                                                                           _vp]),
     "pp_viz_colorize": (C.c_int, [_vp, _vp, C.c_longlong, _i, _i, _vp, _i, _vp]),
@@ -169,6 +173,7 @@ PP_TRACK_OPT_MAX = 256
 (PP_TRACK_BOX_FREE, PP_TRACK_BOX_PROPOSED, PP_TRACK_BOX_OLD, PP_TRACK_BOX_FEW, PP_TRACK_BOX_OUTSIDE,
  PP_TRACK_BOX_SUPPRESSED) = range(6)
 PP_TRACKEVAL_MAX_FRAME, PP_TRACKEVAL_MAX_IDS = 256, 1024
+PP_TRACKEVAL_HOTA_MAX_ALPHAS, PP_TRACKEVAL_HOTA_MAX_FRAMES = 32, 1 << 20
 EXPORTS = tuple(_SIGNATURES)
 
 

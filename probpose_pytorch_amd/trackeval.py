@@ -16,16 +16,27 @@ Ids are arbitrary non-negative int64; they become dense indices per sequence in 
 host, as cocoeval.py turns image ids into positions.  MT / PT / ML / Frag and the ratios are finished on the host from
 the integers that come back.  No parity with any evaluation package is claimed.
 
+``PoseTrackEval(..., hota=True)`` adds HOTA (Luiten et al., IJCV 2021; DESIGN 4.7h, the gauge: tests/
+hota_reference.py) with OKS as the similarity: four more launches on the same stream, the same one synchronisation:
+
+  pp_trackeval_hota_align    per frame the soft-Jaccard potential matches, added into the sequence's int64 pmc[a][b]
+  pp_trackeval_hota_weights  per OKS entry the integer weight 1 + floor(A s 2^32), A the alignment of the two identities
+  pp_trackeval_hota_match    per frame ONE matching of largest total weight for all alphas; per alpha the counted pairs:
+                             the frame's TP and OKS sum, and mc[a][b] += 1
+  pp_trackeval_hota_assoc    per (sequence, alpha) the frames added up and the association sums over mc
+
 There is no CPU fallback: without a GPU ``evaluate()`` raises ``_lib.HipExtensionError``.
 
 ``python -m probpose_pytorch_amd.trackeval GT.json TRACKS.json [--thr 0.5[,0.75..]] [--sigmas coco17|v,v,..]
-[--seq NAME]`` scores the ``tracks.json`` of ``inference.py --track`` against ``[{frame, persons: [{id, keypoints
-[K][3], bbox [4], area}]}]`` and prints one JSON line per threshold.
+[--seq NAME] [--hota]`` scores the ``tracks.json`` of ``inference.py --track`` against ``[{frame, persons: [{id,
+keypoints [K][3], bbox [4], area}]}]`` and prints one JSON line per threshold; with ``--hota`` one more line with the
+eight HOTA means and the HOTA curve.
 """
 from __future__ import annotations
 
 import argparse
 import json
+import math
 import sys
 from functools import partial
 
@@ -39,6 +50,9 @@ from .cocoeval import COCO17_SIGMAS
 INT_KEYS = ("TP", "FN", "FP", "IDSW", "MT", "PT", "ML", "Frag", "IDTP", "IDFN", "IDFP")
 RATIO_KEYS = ("MOTA", "MOTP", "IDF1", "IDP", "IDR")
 MAX_FRAME, MAX_IDS = _lib.PP_TRACKEVAL_MAX_FRAME, _lib.PP_TRACKEVAL_MAX_IDS
+HOTA_KEYS = ("HOTA", "DetA", "AssA", "DetRe", "DetPr", "AssRe", "AssPr", "LocA")
+HOTA_SUM_KEYS = ("loc_sum", "assa_sum", "assre_sum", "asspr_sum")
+HOTA_MAX_ALPHAS, HOTA_MAX_FRAMES = _lib.PP_TRACKEVAL_HOTA_MAX_ALPHAS, _lib.PP_TRACKEVAL_HOTA_MAX_FRAMES
 
 
 def _ratio(num, den) -> float:
@@ -78,6 +92,28 @@ def _float_dtype(a, name: str) -> None:
         raise ValueError(f"{name}: expected a float dtype for coordinates, got {a.dtype}")
 
 
+def _hota_ratio(num, den, empty=0.0) -> float:
+    return float(np.float64(num) / np.float64(den)) if den else empty
+
+
+def hota_curves(tot: dict, alphas) -> dict:
+    """``res["hota"]`` from TP FN FP (ints) and loc_sum assa_sum assre_sum asspr_sum (floats), each a list per alpha.  A
+    ratio whose denominator is 0 is 0 and LocA is then 1, as HOTA's reference practice has it."""
+    curves = {k: [] for k in HOTA_KEYS}
+    for i in range(len(alphas)):
+        tp, fn, fp = tot["TP"][i], tot["FN"][i], tot["FP"][i]
+        det_a, ass_a = _hota_ratio(tp, tp + fn + fp), _hota_ratio(tot["assa_sum"][i], tp)
+        for k, v in (("HOTA", math.sqrt(det_a * ass_a)), ("DetA", det_a), ("AssA", ass_a),
+                     ("DetRe", _hota_ratio(tp, tp + fn)), ("DetPr", _hota_ratio(tp, tp + fp)),
+                     ("AssRe", _hota_ratio(tot["assre_sum"][i], tp)), ("AssPr", _hota_ratio(tot["asspr_sum"][i], tp)),
+                     ("LocA", _hota_ratio(tot["loc_sum"][i], tp, empty=1.0))):
+            curves[k].append(v)
+    out = dict(alphas=[float(a) for a in alphas], TP=list(tot["TP"]), FN=list(tot["FN"]), FP=list(tot["FP"]),
+               curves=curves)
+    out.update({k: float(np.mean(np.asarray(curves[k], dtype=np.float64))) for k in HOTA_KEYS})
+    return out
+
+
 class _Sequence:
     def __init__(self):
         self.gt_index, self.pred_index = {}, {}     # id -> dense index, in order of first appearance
@@ -91,9 +127,16 @@ class PoseTrackEval:
     (0, 1].  ``evaluate()`` returns ``{"thresholds": [...], "metrics": [one dict per threshold], "per_sequence": {name:
     [one dict per threshold]}}``: a metrics dict holds TP FN FP IDSW MT PT ML Frag IDTP IDFN IDFP (Python ints, summed
     over the sequences) and MOTA MOTP IDF1 IDP IDR (floats; NaN where the denominator is 0); a per-sequence dict the
-    integers and ``oks_sum``."""
+    integers and ``oks_sum``.
 
-    def __init__(self, sigmas, thresholds=(0.5,)):
+    ``hota=True`` adds ``"hota"``: ``{"alphas", "TP" / "FN" / "FP": ints per alpha, "curves": {HOTA DetA AssA DetRe
+    DetPr AssRe AssPr LocA: floats per alpha}, and under the same eight names the means over the alphas}``, and
+    ``"per_sequence_hota"``: ``{name: {TP FN FP loc_sum assa_sum assre_sum asspr_sum: lists per alpha}}``.
+    ``hota_alphas`` (default 0.05, 0.10 .. 0.95) are the localisation thresholds, each in (0, 1], 32 at the most.
+    Unlike the CLEAR keys, a HOTA ratio whose denominator is 0 is 0, and LocA is then 1: HOTA's reference practice.  A
+    sequence may then have at most 2^20 frames."""
+
+    def __init__(self, sigmas, thresholds=(0.5,), *, hota=False, hota_alphas=None):
         self.sigmas = _host(sigmas, "sigmas", np.float64).reshape(-1)
         if self.sigmas.size == 0 or not np.all(np.isfinite(self.sigmas)) or np.any(self.sigmas <= 0):
             raise ValueError("sigmas: need K > 0 finite positive values")
@@ -103,6 +146,13 @@ class PoseTrackEval:
             raise ValueError("thresholds: need at least one value")
         if not np.all((self.thresholds > 0) & (self.thresholds <= 1)):        # false for a NaN as well
             raise ValueError(f"thresholds: {self.thresholds.tolist()} are not all in (0, 1]")
+        self.hota = bool(hota)
+        self.hota_alphas = _host([i / 20.0 for i in range(1, 20)] if hota_alphas is None else hota_alphas,
+                                 "hota_alphas", np.float64).reshape(-1)
+        if self.hota_alphas.size == 0 or self.hota_alphas.size > HOTA_MAX_ALPHAS:
+            raise ValueError(f"hota_alphas: need between 1 and {HOTA_MAX_ALPHAS} values, got {self.hota_alphas.size}")
+        if not np.all((self.hota_alphas > 0) & (self.hota_alphas <= 1)):
+            raise ValueError(f"hota_alphas: {self.hota_alphas.tolist()} are not all in (0, 1]")
         self.reset()
 
     def reset(self) -> None:
@@ -161,6 +211,9 @@ class PoseTrackEval:
                 if n > MAX_IDS:
                     raise ValueError(f"sequence {name!r} has {n} {what} identities, more than PP_TRACKEVAL_MAX_IDS = "
                                      f"{MAX_IDS}")
+            if self.hota and len(sq.frames) > HOTA_MAX_FRAMES:
+                raise ValueError(f"sequence {name!r} has {len(sq.frames)} frames, more than "
+                                 f"PP_TRACKEVAL_HOTA_MAX_FRAMES = {HOTA_MAX_FRAMES}")
         frames = [f for _, sq in seqs for f in sq.frames]
         S, F = len(seqs), len(frames)
         g_cnt = np.array([f[0].size for f in frames], dtype=np.int64)
@@ -184,14 +237,17 @@ class PoseTrackEval:
         seq_of_frame = np.repeat(np.arange(S), n_f)
         present = np.bincount(np.repeat(table[1, seq_of_frame], g_cnt) + cat(0, (0,), np.int64),
                               minlength=int(table[1, -1])).astype(np.int64)
+        pred_present = np.bincount(np.repeat(table[2, seq_of_frame], d_cnt) + cat(4, (0,), np.int64),
+                                   minlength=int(table[2, -1])).astype(np.int64)
         return dict(names=[n for n, _ in seqs], S=S, F=F, offs=offs, table=table, frames=frames, gt_kp=gt_kp,
                     gt_bb=gt_bb, gt_ar=gt_ar, flags=flags, gt_idx=cat(0, (0,), np.int32),
-                    pred_idx=cat(4, (0,), np.int32), present=present,
+                    pred_idx=cat(4, (0,), np.int32), present=present, pred_present=pred_present,
                     n_gt=np.bincount(seq_of_frame, weights=g_cnt, minlength=S).astype(np.int64),
                     n_pred=np.bincount(seq_of_frame, weights=d_cnt, minlength=S).astype(np.int64))
 
     def evaluate(self) -> dict:
-        """Score everything added so far (module docstring): four launches, one synchronisation."""
+        """Score everything added so far (module docstring): four launches, with ``hota=True`` eight, and one
+        synchronisation."""
         b = self._tables()
         _lib.require_device()
         out, sizes, keep = self._enqueue(b)
@@ -226,7 +282,10 @@ class PoseTrackEval:
         # everything that comes back, in one buffer of 8-byte words: rec [S, T, 4] | idtp [S, T] | oks_sum [S, T] f64 |
         # matched, runs [T, n_gid] int32 (two to a word)
         n_rec, n_st, n_id = 4 * S * T, S * T, (T * n_gid + 1) // 2
-        out = torch.empty(max(n_rec + 2 * n_st + 2 * n_id, 1), dtype=torch.int64, device=dev)
+        # with hota, after those: tp [S, A] | sums [S, A, 4] f64 = loc, assA, assRe, assPr
+        A = int(self.hota_alphas.size) if self.hota else 0
+        n_base = n_rec + 2 * n_st + 2 * n_id
+        out = torch.empty(max(n_base + 5 * S * A, 1), dtype=torch.int64, device=dev)
         rec, idtp = out[:n_rec], out[n_rec:n_rec + n_st]
         oks_sum = out[n_rec + n_st:n_rec + 2 * n_st].view(torch.float64)
         matched = out[n_rec + 2 * n_st:n_rec + 2 * n_st + n_id].view(torch.int32)
@@ -241,7 +300,29 @@ class PoseTrackEval:
             _lib.launch("pp_trackeval_overlap", S, T, F, Dtot, Gtot, oks_total, c_total, offs, table, self.thresholds,
                         d_offs, d_table, d_thr, oks, gt_idx, pred_idx, c)
             _lib.launch("pp_trackeval_identity", S, T, c_total, table, d_table, c, idtp)
-        keep = (staged, pred_kp, d_offs, d_table, d_thr, args, variances, gt_idx, pred_idx, oks, last, prev, c)
+        keep = [staged, pred_kp, d_offs, d_table, d_thr, args, variances, gt_idx, pred_idx, oks, last, prev, c]
+        if self.hota and S:
+            n_pid = int(table[2, -1])
+            d_alpha = up(self.hota_alphas)
+            gt_present, pred_present = room(up(b["present"])), room(up(b["pred_present"]))
+            pmc = torch.zeros(max(c_total, 1), dtype=torch.int64, device=dev)
+            mc = torch.zeros(max(A * c_total, 1), dtype=torch.int32, device=dev)
+            q = torch.empty(max(oks_total, 1), dtype=torch.int64, device=dev)
+            held_row = torch.empty(max(Dtot, 1), dtype=torch.int32, device=dev)
+            frame_tp = torch.empty(max(F * A, 1), dtype=torch.int64, device=dev)
+            frame_loc = torch.empty(max(F * A, 1), dtype=torch.float64, device=dev)
+            h_tp = out[n_base:n_base + S * A]
+            h_sums = out[n_base + S * A:n_base + 5 * S * A].view(torch.float64)
+            _lib.launch("pp_trackeval_hota_align", S, F, Dtot, Gtot, oks_total, c_total, offs, table, d_offs, d_table,
+                        oks, gt_idx, pred_idx, pmc)
+            _lib.launch("pp_trackeval_hota_weights", S, F, Dtot, Gtot, oks_total, c_total, n_gid, n_pid, offs, table,
+                        d_offs, d_table, oks, gt_idx, pred_idx, pmc, gt_present, pred_present, q)
+            _lib.launch("pp_trackeval_hota_match", S, A, F, Dtot, Gtot, oks_total, c_total, offs, table,
+                        self.hota_alphas, d_offs, d_table, d_alpha, oks, q, gt_idx, pred_idx, mc, held_row, frame_tp,
+                        frame_loc)
+            _lib.launch("pp_trackeval_hota_assoc", S, A, F, c_total, n_gid, n_pid, table, d_table, mc, gt_present,
+                        pred_present, frame_tp, frame_loc, h_tp, h_sums)
+            keep += [d_alpha, gt_present, pred_present, pmc, mc, q, held_row, frame_tp, frame_loc]
         return out, (n_rec, n_st, n_id), keep
 
     def _finish(self, b, host, n_rec, n_st, n_id) -> dict:
@@ -272,7 +353,23 @@ class PoseTrackEval:
             tot["oks_sum"] = float(sum(np.float64(per_sequence[n][t]["oks_sum"]) for n in per_sequence))
             tot.update(ratios(tot))
             metrics.append(tot)
-        return dict(thresholds=[float(t) for t in self.thresholds], metrics=metrics, per_sequence=per_sequence)
+        res = dict(thresholds=[float(t) for t in self.thresholds], metrics=metrics, per_sequence=per_sequence)
+        if self.hota:
+            A, n_base = int(self.hota_alphas.size), n_rec + 2 * n_st + 2 * n_id
+            h_tp = host[n_base:n_base + S * A].reshape(S, A)
+            h_sums = host[n_base + S * A:n_base + 5 * S * A].view(np.float64).reshape(S, A, 4)
+            per_seq = {}
+            for s, name in enumerate(b["names"]):
+                tp = [int(v) for v in h_tp[s]]
+                per_seq[name] = dict(TP=tp, FN=[int(b["n_gt"][s]) - v for v in tp],
+                                     FP=[int(b["n_pred"][s]) - v for v in tp],
+                                     **{k: [float(v) for v in h_sums[s, :, j]] for j, k in enumerate(HOTA_SUM_KEYS)})
+            tot = {k: [sum(r[k][i] for r in per_seq.values()) for i in range(A)] for k in ("TP", "FN", "FP")}
+            for k in HOTA_SUM_KEYS:
+                tot[k] = [float(sum(np.float64(r[k][i]) for r in per_seq.values())) for i in range(A)]
+            res["hota"] = hota_curves(tot, self.hota_alphas)
+            res["per_sequence_hota"] = per_seq
+        return res
 
 
 # ------------------------------------------------------------------------------------------------ command line
@@ -346,14 +443,18 @@ def _cli_sigmas(spec: str, K: int) -> np.ndarray:
 
 def _parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="python -m probpose_pytorch_amd.trackeval",
-                                 description="CLEAR-MOT and IDF1 of a tracks.json against annotated tracks, computed "
-                                             "on the GPU; prints one JSON line per OKS threshold.")
+                                 description="CLEAR-MOT and IDF1 (with --hota also HOTA) of a tracks.json against "
+                                             "annotated tracks, computed on the GPU; prints one JSON line per OKS "
+                                             "threshold.")
     ap.add_argument("ground_truth", metavar="GT.json",
                     help="[{frame, persons: [{id, keypoints [K][3], bbox [4], area}]}]")
     ap.add_argument("tracks", metavar="TRACKS.json", help="what inference.py --track writes")
     ap.add_argument("--thr", default="0.5", help="OKS thresholds in (0, 1], separated by commas")
     ap.add_argument("--sigmas", default="coco17", help="'coco17', one number for every keypoint, or K numbers")
     ap.add_argument("--seq", default="sequence", help="the name the sequence is reported under")
+    ap.add_argument("--hota", action="store_true",
+                    help="one more JSON line: HOTA DetA AssA DetRe DetPr AssRe AssPr LocA (means over the alphas "
+                         "0.05 .. 0.95), the alphas and the HOTA curve")
     return ap
 
 
@@ -364,13 +465,16 @@ def main(argv=None) -> int:
     except ValueError:
         raise ValueError(f"--thr: expected numbers separated by commas, got {args.thr!r}") from None
     frames, K, slotless = load_json_frames(args.ground_truth, args.tracks)
-    ev = PoseTrackEval(_cli_sigmas(args.sigmas, K), thresholds=thr)
+    ev = PoseTrackEval(_cli_sigmas(args.sigmas, K), thresholds=thr, hota=args.hota)
     for fr in frames:
         ev.add_frame(args.seq, *fr)
     res = ev.evaluate()
     print(f"{args.seq}: {len(frames)} frames; {slotless} detections without a slot scored as one-frame tracks")
     for t, m in zip(res["thresholds"], res["metrics"]):
         print(json.dumps(dict(thr=t, **{k: m[k] for k in INT_KEYS + RATIO_KEYS})))
+    if args.hota:
+        h = res["hota"]
+        print(json.dumps(dict(**{k: h[k] for k in HOTA_KEYS}, alphas=h["alphas"], curve=h["curves"]["HOTA"])))
     return 0
 
 
