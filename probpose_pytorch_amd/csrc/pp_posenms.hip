@@ -16,12 +16,12 @@
 //                           memory traffic, no atomic, no LDS, no barrier, and the result does not depend on timing.
 //                           Each lane evaluates the pair OKS of the pivot and of its own live detections with the
 //                           gauge's operations in the gauge's order; what differs is exp() (tests/test_posenms_gpu.py
-//                           counts the roundings).
-#include <float.h>
+//                           counts the roundings).  That pair OKS is pp_assoc.h's pair_oks, the function
+//                           pp_track.hip's track_oks_kernel calls.
 #include <limits.h>
 #include <math.h>
 
-#include "pp_common.h"
+#include "pp_assoc.h"
 
 namespace pp {
 
@@ -45,24 +45,6 @@ __global__ __launch_bounds__(kNmsRescoreThreads) void posenms_rescore_kernel(
   }
   const double mean = n ? sum / (double)n : 0.0;
   out[i] = box_scores[i] * mean;
-}
-
-// OKS of detections a (the pivot) and b of one image; vis_a == nullptr: every keypoint counts
-__device__ __forceinline__ double nms_pair_oks(int K, const double *__restrict__ ka, const double *__restrict__ kb,
-                                               const double *__restrict__ vis_a, const double *__restrict__ vis_b,
-                                               double vis_thr, double area_a, double area_b,
-                                               const double *__restrict__ vars) {
-  const double size = (area_a + area_b) / 2.0 + DBL_EPSILON;
-  double sum = 0.0;
-  int n = 0;
-  for (int k = 0; k < K; ++k) {
-    if (vis_a && !(vis_a[k] > vis_thr && vis_b[k] > vis_thr)) continue;
-    const double dx = ka[2 * k] - kb[2 * k], dy = ka[2 * k + 1] - kb[2 * k + 1];
-    const double e = (dx * dx + dy * dy) / vars[k] / size / 2.0;
-    sum += exp(-e);
-    ++n;
-  }
-  return n ? sum / (double)n : 0.0;
 }
 
 __global__ __launch_bounds__(64 * kNmsWaves) void posenms_kernel(
@@ -113,8 +95,8 @@ __global__ __launch_bounds__(64 * kNmsWaves) void posenms_kernel(
       for (int s = p >> 6; s < slots; ++s) {
         const int j = s * 64 + lane;
         if (j > p && ((live >> s) & 1ull)) {
-          const double oks = nms_pair_oks(K, kpp, kp + (long long)j * K * 2, vsp, vs ? vs + (long long)j * K : nullptr,
-                                          vis_thr, area_p, ar[j], vars);
+          const double oks = pair_oks(K, kpp, kp + (long long)j * K * 2, vsp, vs ? vs + (long long)j * K : nullptr,
+                                      vis_thr, area_p, ar[j], vars);
           if (oks > oks_thr) live &= ~(1ull << s);
         }
       }
@@ -137,8 +119,8 @@ __global__ __launch_bounds__(64 * kNmsWaves) void posenms_kernel(
       for (int s = 0; s < slots; ++s) {
         if (!((live >> s) & 1ull)) continue;
         const int j = s * 64 + lane;
-        const double oks = nms_pair_oks(K, kpp, kp + (long long)j * K * 2, vsp, vs ? vs + (long long)j * K : nullptr,
-                                        vis_thr, area_p, ar[j], vars);
+        const double oks = pair_oks(K, kpp, kp + (long long)j * K * 2, vsp, vs ? vs + (long long)j * K : nullptr,
+                                    vis_thr, area_p, ar[j], vars);
         double v = sc[j];
         if (mode == PP_POSENMS_SOFT_GAUSSIAN) {
           v = v * exp(-(oks * oks) / oks_thr);

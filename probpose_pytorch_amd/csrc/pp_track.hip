@@ -1,9 +1,10 @@
 // PoseTracker: greedy OKS track association and One-Euro smoothing of decoded poses (probpose_pytorch_amd/tracker.py,
 // DESIGN §4.7d), three launches per update.
 //
-//   track_oks_kernel     one lane per (detection, slot): the pair OKS of §4.7c with the slot's stored raw keypoints, area
-//                        and visibilities as the second detection; a free slot writes 0.  This is the arithmetic (K exp
-//                        per pair) and it is spread over the whole chip.
+//   track_oks_kernel     one lane per (detection, slot): the pair OKS of §4.7c (pp_assoc.h's pair_oks, the function
+//                        posenms_kernel calls) with the slot's stored raw keypoints, area and visibilities as the
+//                        second detection; a free slot writes 0.  This is the arithmetic (K exp per pair) and it is
+//                        spread over the whole chip.
 //   track_assign_kernel  one wave per stream, four waves to a workgroup.  Lane j % 64 OWNS slot j: its live and taken
 //                        bits are bit j / 64 of two 64-bit registers of that lane (64 lanes x 64 bits =
 //                        PP_TRACK_MAX_TRACKS), and its id, age, t_last and area are written by that lane alone.  The
@@ -19,8 +20,10 @@
 //                        in int64, at most PP_TRACK_OPT_MAX rows and columns.  Lane j % 64 owns column j (at most four):
 //                        its v, minv, way, used bit, the row it holds and that row's u are registers of that lane; a
 //                        step is one coalesced load of the scanned row's OKS (a row's first step: loaded a row ahead)
-//                        and one wave_argmin_i64.  Ageing, births
-//                        and the matched pair's stores are the greedy kernel's own functions.
+//                        and one wave_argmin_i64.  The loop is pp_assoc.h's sap_solve statement for statement, kept
+//                        written out here for the row-ahead load (the header says what calling sap_solve cost); the
+//                        shuffle sap_fetch and the constants are the header's.  Ageing, births and the matched pair's
+//                        stores are the greedy kernel's own functions.
 //   track_filter_kernel  one lane per (detection, keypoint): reads the slot the assign kernel gave the detection, applies
 //                        the One-Euro step (or initialises, or passes the raw value through) and writes the output, the
 //                        filter state and the slot's raw keypoint and visibility.  A slot belongs to at most one
@@ -28,11 +31,10 @@
 //                        tests/track_reference.py one for one (compiled -ffp-contract=off): the same bits.
 //
 // State of one stream: one block of pp_track_state_bytes(max_tracks, K) bytes, laid out by TrackState below.
-#include <float.h>
 #include <limits.h>
 #include <math.h>
 
-#include "pp_common.h"
+#include "pp_assoc.h"
 
 namespace pp {
 
@@ -89,18 +91,7 @@ __global__ __launch_bounds__(kTrackThreads) void track_oks_kernel(
   }
   const double *ka = kpts + d * K * 2, *kb = st.kp + (long long)j * K * 2;
   const double *va = vis ? vis + d * K : nullptr, *vb = st.vis + (long long)j * K;
-  // §4.7c's pair OKS, the detection as the pivot: the same operations in the same order
-  const double size = (area[d] + st.area[j]) / 2.0 + DBL_EPSILON;
-  double sum = 0.0;
-  int n = 0;
-  for (int k = 0; k < K; ++k) {
-    if (va && !(va[k] > vis_thr && vb[k] > vis_thr)) continue;
-    const double dx = ka[2 * k] - kb[2 * k], dy = ka[2 * k + 1] - kb[2 * k + 1];
-    const double e = (dx * dx + dy * dy) / vars[k] / size / 2.0;
-    sum += exp(-e);
-    ++n;
-  }
-  oks[i] = n ? sum / (double)n : 0.0;
+  oks[i] = pair_oks(K, ka, kb, va, vb, vis_thr, area[d], st.area[j], vars);   // the detection as the pivot
 }
 
 // What the lanes of a stream's wave share between the association modes.  The per-detection outputs of the assign
@@ -251,24 +242,11 @@ __global__ __launch_bounds__(64 * kTrackWaves) void track_assign_kernel(
 
 // ---- the optimal association (the rule: include/probpose_hip.h, tests/trackopt_reference.py) ---------
 constexpr int kOptCols = PP_TRACK_OPT_MAX / 64;           // columns a lane owns at most
-constexpr long long kOptInf = 1ll << 62;
-constexpr int kOptRoot = -1;                              // the extra start column
 
 // q of a pair whose slot is real and live at entry
 __device__ __forceinline__ long long track_weight(double oks, double match_thr) {
   if (!(oks > match_thr)) return 0;                       // a NaN is inadmissible
   return 1 + (long long)floor(fmin(oks - match_thr, 1.0) * 1099511627776.0 /* 2^40 */);
-}
-
-// x[s] of a register array with a wave-uniform s, as lane `src` holds it
-template <typename V>
-__device__ __forceinline__ V opt_fetch(const V (&x)[kOptCols], int col) {
-  const int s = col >> 6;
-  V mine = x[0];
-#pragma unroll
-  for (int c = 1; c < kOptCols; ++c)
-    if (s == c) mine = x[c];
-  return __shfl(mine, col & 63, 64);
 }
 
 // row[j] at the lane's columns that are slots live at entry (bit s of live: slot s * 64 + lane < T), 0 elsewhere
@@ -318,14 +296,14 @@ __global__ __launch_bounds__(64 * kTrackWaves) void track_assign_optimal_kernel(
     unsigned used = 0;                                    // bit s: the lane's column s is on the tree
 #pragma unroll
     for (int s = 0; s < kOptCols; ++s) {
-      minv[s] = kOptInf;
-      way[s] = kOptRoot;
+      minv[s] = kSapInf;
+      way[s] = kSapRoot;
     }
-    int cur = kOptRoot, i0 = i;                           // wave-uniform: the column being scanned, its row,
+    int cur = kSapRoot, i0 = i;                           // wave-uniform: the column being scanned, its row,
     long long u0 = 0, u_root = 0;                         // that row's u, and the u of row i (the root's)
     bool open = false;
     for (int step = 0; step <= m; ++step) {               // every step marks one more column: at most m + 1
-      if (cur != kOptRoot && lane == (cur & 63)) used |= 1u << (cur >> 6);
+      if (cur != kSapRoot && lane == (cur & 63)) used |= 1u << (cur >> 6);
       if (step > 0) opt_load_row(oks + (d0 + i0) * T, lane, live, x);
       long long delta = LLONG_MAX;
       int j1 = INT_MAX;
@@ -358,21 +336,21 @@ __global__ __launch_bounds__(64 * kTrackWaves) void track_assign_optimal_kernel(
       }
       u_root += delta;
       cur = j1;
-      i0 = opt_fetch(held, cur);
-      u0 = opt_fetch(u_held, cur);
+      i0 = sap_fetch<kOptCols>(held, cur);
+      u0 = sap_fetch<kOptCols>(u_held, cur);
       if (i0 < 0) {
         open = true;
         break;
       }
     }
     // walk back: every column of the path takes the row of the column before it
-    for (int hop = 0; open && cur != kOptRoot && hop <= m; ++hop) {
-      const int prev = opt_fetch(way, cur);
+    for (int hop = 0; open && cur != kSapRoot && hop <= m; ++hop) {
+      const int prev = sap_fetch<kOptCols>(way, cur);
       int row_prev = i;
       long long u_prev = u_root;
-      if (prev != kOptRoot) {                             // wave-uniform
-        row_prev = opt_fetch(held, prev);
-        u_prev = opt_fetch(u_held, prev);
+      if (prev != kSapRoot) {                             // wave-uniform
+        row_prev = sap_fetch<kOptCols>(held, prev);
+        u_prev = sap_fetch<kOptCols>(u_held, prev);
       }
       if (lane == (cur & 63)) {
 #pragma unroll

@@ -11,10 +11,10 @@
 //                                   predicted identities NP_s) | c_off (running sum of NG_s * NP_s)
 // gt_idx [Gtot] / pred_idx [Dtot] int32 are the dense identity indices within the sequence.
 //
-//   sap_solve                   the shortest-augmenting-path solver of §4.7f, written once: a device template over the
-//                               number of columns NC a lane owns (lane j % 64 owns column j) and over how the weights
-//                               of a row are fetched.  v, minv, way, the used bits, the held row and its u are
-//                               registers of the owning lane; a step is one fetch and one wave_argmin_i64.
+//   sap_solve                   the shortest-augmenting-path solver of §4.7f lives in pp_assoc.h: a device template over
+//                               the number of columns NC a lane owns (lane j % 64 owns column j) and over how the
+//                               weights of a row are fetched.  The three solver kernels here differ in their fetch
+//                               alone.  (pp_track.hip's kernel keeps the loop written out: see the header.)
 //   trackeval_clear_kernel      one wave per (sequence, threshold), four waves to a workgroup; the frames in order,
 //                               sap_solve<4> per frame with the weights formed on the fly from the OKS column and the
 //                               row's `prev`.  last / prev / matched / runs per ground-truth identity live in a global
@@ -37,117 +37,19 @@
 #include <limits.h>
 #include <math.h>
 
-#include "pp_common.h"
+#include "pp_assoc.h"
 
 namespace pp {
 
 constexpr int kTevWaves = 4;
 constexpr int kTevThreads = 64 * kTevWaves;
-constexpr long long kSapInf = 1ll << 62;
-constexpr int kSapRoot = -1;                              // the extra start column
 constexpr long long kTevBonus = 1ll << 42;                // what a continued pair's weight gains
-
-// x[col / 64] of a lane-owned register array as lane col % 64 holds it; col is wave-uniform
-template <int NC, typename V>
-__device__ __forceinline__ V sap_fetch(const V (&x)[NC], int col) {
-  const int s = col >> 6;
-  V mine = x[0];
-#pragma unroll
-  for (int c = 1; c < NC; ++c)
-    if (s == c) mine = x[c];
-  return __shfl(mine, col & 63, 64);
-}
-
-// The assignment of largest total weight by the rule of §4.7f: rows 0 .. R-1 in order, columns 0 .. m-1 (m >= R; the
-// columns the fetch gives 0 for are virtual).  fetch(i0, q) fills q[s] with the int64 weight of row i0 and the lane's
-// column s * 64 + lane.  On return held[s] is the row that column holds, or -1.  Every loop bound is wave-uniform.
-template <int NC, typename Fetch>
-__device__ __forceinline__ void sap_solve(int lane, int R, int m, const Fetch &fetch, int (&held)[NC]) {
-  long long v[NC], u_held[NC];                            // a row's u travels with the column that holds it
-#pragma unroll
-  for (int s = 0; s < NC; ++s) {
-    v[s] = u_held[s] = 0;
-    held[s] = -1;
-  }
-  for (int i = 0; i < R; ++i) {                           // one augmenting path per row
-    long long minv[NC];
-    int way[NC];
-    unsigned used = 0;                                    // bit s: the lane's column s is on the tree
-#pragma unroll
-    for (int s = 0; s < NC; ++s) {
-      minv[s] = kSapInf;
-      way[s] = kSapRoot;
-    }
-    int cur = kSapRoot, i0 = i;                           // wave-uniform: the column being scanned, its row,
-    long long u0 = 0, u_root = 0;                         // that row's u, and the u of row i (the root's)
-    bool open = false;
-    for (int step = 0; step <= m; ++step) {               // every step marks one more column: at most m + 1
-      if (cur != kSapRoot && lane == (cur & 63)) used |= 1u << (cur >> 6);
-      long long q[NC];
-      fetch(i0, q);
-      long long delta = LLONG_MAX;
-      int j1 = INT_MAX;
-#pragma unroll
-      for (int s = 0; s < NC; ++s) {                      // ascending columns: the lowest of the lane's on equal minv
-        const int j = s * 64 + lane;
-        if (j < m && !((used >> s) & 1u)) {
-          const long long c = -q[s] - u0 - v[s];
-          if (c < minv[s]) {
-            minv[s] = c;
-            way[s] = cur;
-          }
-          if (minv[s] < delta) {
-            delta = minv[s];
-            j1 = j;
-          }
-        }
-      }
-      wave_argmin_i64(delta, j1);
-      if (j1 == INT_MAX) break;                           // no unused column: cannot happen, rows on the tree < m
-#pragma unroll
-      for (int s = 0; s < NC; ++s) {
-        if ((used >> s) & 1u) {
-          u_held[s] += delta;
-          v[s] -= delta;
-        } else {
-          minv[s] -= delta;
-        }
-      }
-      u_root += delta;
-      cur = j1;
-      i0 = sap_fetch<NC>(held, cur);
-      u0 = sap_fetch<NC>(u_held, cur);
-      if (i0 < 0) {
-        open = true;
-        break;
-      }
-    }
-    // walk back: every column of the path takes the row of the column before it
-    for (int hop = 0; open && cur != kSapRoot && hop <= m; ++hop) {
-      const int prev = sap_fetch<NC>(way, cur);
-      int row_prev = i;
-      long long u_prev = u_root;
-      if (prev != kSapRoot) {                             // wave-uniform
-        row_prev = sap_fetch<NC>(held, prev);
-        u_prev = sap_fetch<NC>(u_held, prev);
-      }
-      if (lane == (cur & 63)) {
-#pragma unroll
-        for (int s = 0; s < NC; ++s)
-          if (s == (cur >> 6)) {
-            held[s] = row_prev;
-            u_held[s] = u_prev;
-          }
-      }
-      cur = prev;
-    }
-  }
-}
+constexpr double kTwo32 = 4294967296.0;
 
 // q of a pair without the continuation bonus: 0 = inadmissible (a NaN is)
 __device__ __forceinline__ long long tev_weight(double s, double thr) {
   if (!(s >= thr)) return 0;
-  return 1 + (long long)floor(fmin(s - thr, 1.0) * 4294967296.0 /* 2^32 */);
+  return 1 + (long long)floor(fmin(s - thr, 1.0) * kTwo32);
 }
 
 // the rows of the sequence table
@@ -157,6 +59,19 @@ struct TevSeq {
 __device__ __forceinline__ TevSeq tev_seq(const long long *seq, int n_seq, long long s) {
   const long long *fo = seq, *go = seq + (n_seq + 1), *po = seq + 2ll * (n_seq + 1), *co = seq + 3ll * (n_seq + 1);
   return TevSeq{fo[s], fo[s + 1], go[s], go[s + 1] - go[s], po[s + 1] - po[s], co[s]};
+}
+
+// a frame's extents in pp_cocoeval_oks's table; ok = false: refused on the host
+struct TevFrame {
+  long long d0, g0, o0;
+  int D, G;
+  bool ok;
+};
+__device__ __forceinline__ TevFrame tev_frame(const long long *offs, int n_frames, long long f) {
+  const long long d0 = offs[f], Dl = offs[f + 1] - d0;
+  const long long g0 = offs[n_frames + 1 + f], Gl = offs[n_frames + 2 + f] - g0;
+  const bool ok = Dl >= 0 && Gl >= 0 && Dl <= PP_TRACKEVAL_MAX_FRAME && Gl <= PP_TRACKEVAL_MAX_FRAME;
+  return TevFrame{d0, g0, offs[2ll * n_frames + 2 + f], (int)Dl, (int)Gl, ok};
 }
 
 constexpr int kClearCols = PP_TRACKEVAL_MAX_FRAME / 64;   // columns a lane owns in a frame
@@ -189,11 +104,10 @@ __global__ __launch_bounds__(kTevThreads) void trackeval_clear_kernel(
   long long tp = 0, idsw = 0, n_gt = 0, n_pr = 0;
   double sum = 0.0;
   for (long long f = q.f0; f < q.f1; ++f) {
-    const long long d0 = offs[f], Dl = offs[f + 1] - d0;
-    const long long g0 = offs[n_frames + 1 + f], Gl = offs[n_frames + 2 + f] - g0;
-    const long long o0 = offs[2ll * n_frames + 2 + f];
-    if (Dl < 0 || Gl < 0 || Dl > PP_TRACKEVAL_MAX_FRAME || Gl > PP_TRACKEVAL_MAX_FRAME) return;   // refused on the host
-    const int D = (int)Dl, G = (int)Gl;
+    const TevFrame fr = tev_frame(offs, n_frames, f);
+    if (!fr.ok) return;                                   // refused on the host
+    const long long d0 = fr.d0, g0 = fr.g0;
+    const int D = fr.D, G = fr.G;
     n_gt += G;
     n_pr += D;
     if (G == 0 || D == 0) continue;                       // nothing can match
@@ -214,7 +128,7 @@ __global__ __launch_bounds__(kTevThreads) void trackeval_clear_kernel(
       }
       if (i < D) pcol[r] = pred_idx[d0 + i];
     }
-    const double *mat = oks + o0;
+    const double *mat = oks + fr.o0;
     const auto fetch = [&](int i0, long long (&wq)[kClearCols]) {
       const int pv = sap_fetch<kClearCols>(prow, i0);
 #pragma unroll
@@ -344,23 +258,8 @@ __global__ __launch_bounds__(kTevThreads) void trackeval_identity_kernel(
 }
 
 // ---- HOTA (the rule: include/probpose_hip.h, tests/hota_reference.py) ---------------------------------
-constexpr double kTwo32 = 4294967296.0;
-
 // an OKS as the HOTA rule reads it: what is not > 0 (a NaN is not) counts as 0
 __device__ __forceinline__ double hota_s(double s) { return s > 0.0 ? s : 0.0; }
-
-// a frame's extents; ok = false: refused on the host
-struct HotaFrame {
-  long long d0, g0, o0;
-  int D, G;
-  bool ok;
-};
-__device__ __forceinline__ HotaFrame hota_frame(const long long *offs, int n_frames, long long f) {
-  const long long d0 = offs[f], Dl = offs[f + 1] - d0;
-  const long long g0 = offs[n_frames + 1 + f], Gl = offs[n_frames + 2 + f] - g0;
-  const bool ok = Dl >= 0 && Gl >= 0 && Dl <= PP_TRACKEVAL_MAX_FRAME && Gl <= PP_TRACKEVAL_MAX_FRAME;
-  return HotaFrame{d0, g0, offs[2ll * n_frames + 2 + f], (int)Dl, (int)Gl, ok};
-}
 
 // where the identities (a, b) of sequence q sit in a [c_total] array, or -1: an index out of range is passed over
 __device__ __forceinline__ long long hota_at(const TevSeq &q, long long c_total, long long a, long long b) {
@@ -378,7 +277,7 @@ __global__ __launch_bounds__(kTevThreads) void trackeval_hota_align_kernel(
   const long long f = (long long)blockIdx.x * kTevWaves + (threadIdx.x >> 6);
   if (f >= n_frames) return;
   const int lane = threadIdx.x & 63;
-  const HotaFrame fr = hota_frame(offs, n_frames, f);
+  const TevFrame fr = tev_frame(offs, n_frames, f);
   if (!fr.ok || fr.G == 0 || fr.D == 0) return;
   const TevSeq q = tev_seq(seq, n_seq, tev_owner(seq, n_seq, f));
   const int D = fr.D, G = fr.G;
@@ -424,7 +323,7 @@ __global__ __launch_bounds__(kTevThreads) void trackeval_hota_weights_kernel(
   const long long e = (long long)blockIdx.x * kTevThreads + threadIdx.x;
   if (e >= oks_total) return;
   const long long f = tev_owner(offs + 2ll * (n_frames + 1), n_frames, e);
-  const HotaFrame fr = hota_frame(offs, n_frames, f);
+  const TevFrame fr = tev_frame(offs, n_frames, f);
   const long long r = e - fr.o0;
   if (!fr.ok || fr.G == 0 || r < 0 || r >= (long long)fr.D * fr.G) return;      // refused on the host
   const long long d = r / fr.G, g = r - d * fr.G;
@@ -456,7 +355,7 @@ __global__ __launch_bounds__(kTevThreads) void trackeval_hota_match_kernel(
   const long long f = (long long)blockIdx.x * kTevWaves + (threadIdx.x >> 6);
   if (f >= n_frames) return;
   const int lane = threadIdx.x & 63;
-  const HotaFrame fr = hota_frame(offs, n_frames, f);
+  const TevFrame fr = tev_frame(offs, n_frames, f);
   if (!fr.ok) return;                                     // refused on the host
   const int D = fr.D, G = fr.G;
   double sp[kClearCols];                                  // the OKS of the lane's matched pairs, 0 = none
