@@ -221,18 +221,24 @@ int pp_maxpool_relu(const void *x, void *out, int B, int h, int w, int C, int kh
 /* Final 1x1 conv + /temperature + clamp(0,1), channels-last rows -> NCHW float32 (head.py:525-532),
  * as a streaming (HBM-bound) kernel for small K:  x [B*HW, Cin], w [K, Cin], bias [K] ->
  * heat [B, K, HW] f32 = clamp((x w^T + bias) / temperature, 0, 1).  (K*Cin*sizeof + 64 rows must fit
- * LDS; larger final layers / k > 1 kernels go through pp_gemm with PP_EPI_HEATMAP.) */
+ * LDS; larger final layers / k > 1 kernels go through pp_gemm with PP_EPI_HEATMAP.)
+ * A NaN pre-activation gives 0 (the clamp is fminf(fmaxf(v, 0), 1), which returns the non-NaN operand), exactly as the
+ * PP_EPI_HEATMAP epilogue of pp_gemm does, so the two routes of one layer agree; torch.clamp would keep the NaN.
+ * +Inf gives 1, -Inf gives 0. */
 int pp_final_heatmap(const void *x, const void *w, const float *bias, float *out, int B, int HW,
                      int Cin, int K, float temperature, int dtype, void *stream);
 
 /* Same contraction without the clamp: logits = (x w^T + bias) / temperature, the input of the Sparsemax
- * normalisation (head.py:526-528 with normalize != None). */
+ * normalisation (head.py:526-528 with normalize != None).  Nothing is clamped: a NaN or Inf pre-activation is
+ * written as it is. */
 int pp_final_logits(const void *x, const void *w, const float *bias, float *out, int B, int HW,
                     int Cin, int K, float temperature, int dtype, void *stream);
 
 /* Sparsemax over the last axis of x [rows, n] f32 (in place), then * scale and clamp(0, 1): head.py:237-245
  * (normalize_layer = Sparsemax(dim=-1), third-party sparsemax==0.1.9: restated from the published algorithm,
- * Martins & Astudillo 2016 -- parity unpinned) + head.py:529-531 (x * normalize, clamp).  One workgroup per row. */
+ * Martins & Astudillo 2016 -- parity unpinned) + head.py:529-531 (x * normalize, clamp).  One workgroup per row.
+ * A row that holds a NaN or +Inf comes back NaN in every element, as the library's max(0, input - taus) with a NaN
+ * tau and torch.clamp give; every other row is unaffected by it. */
 int pp_sparsemax_rows(float *x, long long rows, int n, float scale, void *stream);
 
 /* ArgMaxProbMap.decode (codec.py:515-543): raw arg-max of every heatmap (heatmap.py:13-52 get_heatmap_maximum)
@@ -245,7 +251,9 @@ int pp_dark_decode_f32(const float *heatmaps, int B, int K, int H, int W, const 
                        double in_w, double in_h, double *out_kpts, float *out_scores, float *out_locs, void *stream);
 
 /* Aux tail: 1x1 conv C->K on pooled 1x1 features + Sigmoid/ReLU (head.py:277-286,:391-400).
- * x [4 branches][B, C] -> out [4][B,K] f32 (branches 0..2 sigmoid, 3 relu). */
+ * x [B, 4*C] (one row per crop, the four branches' C columns side by side: branch br at columns br*C ..), w [4][K][C],
+ * bias [4][K] -> out [4][B,K] f32 (branches 0..2 sigmoid, 3 relu).  The ReLU is fmaxf(s, 0): a NaN pre-activation
+ * of branch 3 gives 0 (torch.relu would keep it); the sigmoid branches keep a NaN. */
 int pp_aux_tail(const void *x, const void *w, const float *bias, float *out, int B, int C,
                 int K, int dtype, void *stream);
 

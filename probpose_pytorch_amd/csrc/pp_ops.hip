@@ -740,11 +740,12 @@ static int final_heatmap_launch(const void *x, const void *w, const float *bias,
   if (dtype == PP_BF16 && HW % 16 == 0 && Cin % 32 == 0 && Cin <= 32 * FHM_MAXKS && K <= 144 &&
       ((uintptr_t)x & 15) == 0 && ((uintptr_t)w & 15) == 0 && ((uintptr_t)out & 15) == 0) {
     const int nt = cdiv(K, 16), tiles = (int)(M / 16);
-    const size_t lds_w = (size_t)nt * 16 * (Cin * 2 + 16);
     const int grid = (int)std::min<long long>(cdiv(tiles, 4), 256 * 2);
     hipStream_t sm = (hipStream_t)stream;
+    // the kernel stages and reads NT * 16 rows of W^T (zeros from row K on), so the LDS is sized by NT, not by K
 #define PP_FHM(NT_)                                                                                       \
   do {                                                                                                    \
+    const size_t lds_w = (size_t)NT_ * 16 * (Cin * 2 + 16);                                               \
     if (lds_w > 64 * 1024)                                                                                \
       if (int rc = ensure_dynamic_lds(final_heatmap_mfma_kernel<NT_, CLAMP>, lds_w)) return rc;           \
     hipLaunchKernelGGL((final_heatmap_mfma_kernel<NT_, CLAMP>), dim3(grid), dim3(256), lds_w, sm, (const bf16_t *)x, \

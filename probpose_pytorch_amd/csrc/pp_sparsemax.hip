@@ -87,6 +87,20 @@ __global__ __launch_bounds__(SM_THREADS) void sparsemax_rows_kernel(float *__res
   }
   SumCount sc = block_sum_count(s, 0, red_s, red_c);
   double tau = (sc.s - 1.0) / (double)n;
+  if (tau != tau) {
+    // The shifted row holds a NaN: a NaN input, or +Inf (Inf - Inf).  fmaxf dropped it from m, and neither the
+    // iteration nor fmaxf(z - tau, 0) below would carry it, so the row is written here: NaN in every element, as the
+    // library's max(0, input - taus) gives with a NaN tau (torch.max and torch.clamp keep a NaN).  The sum of a row
+    // without a NaN is finite or -Inf, so no other row comes here.  sc is the same in every thread.
+    const float qnan = __builtin_nanf("");
+    if ((n & 3) == 0) {
+      for (int i = tid * 4; i < n; i += SM_THREADS * 4)
+        *reinterpret_cast<float4 *>(g + i) = make_float4(qnan, qnan, qnan, qnan);
+    } else {
+      for (int i = tid; i < n; i += SM_THREADS) g[i] = qnan;
+    }
+    return;
+  }
   int count = n;
   bool done = false;
   for (int it = 0; it < SM_MAX_ITERS; ++it) {
@@ -100,7 +114,7 @@ __global__ __launch_bounds__(SM_THREADS) void sparsemax_rows_kernel(float *__res
       }
     }
     sc = block_sum_count(ps, pc, red_s, red_c);
-    if (sc.c == 0) break;                // NaN rows: leave tau as it is (the output is NaN like the library's)
+    if (sc.c == 0) break;                // unreachable for a NaN-free row (the maximum, z = 0, is above tau); kept as a stop
     tau = (sc.s - 1.0) / (double)sc.c;
     if (sc.c == count) {
       done = true;

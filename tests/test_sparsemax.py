@@ -114,6 +114,41 @@ def test_sparsemax_kernel_edge_rows(built_lib):
     assert ops.sparsemax_rows(torch.empty((0, 16), device="cuda"), 1.0).shape == (0, 16)
 
 
+def _non_finite_rows(n):
+    """A finite row, a row with one NaN, an all-NaN row, a row with one +Inf, a finite row.  (No -Inf row: the
+    restatement turns it into NaN through 0 * -Inf in the support sum, not into the projection of the rest.)"""
+    z = _rows(n, 5, 7 + n, 1.0)
+    z[1, n // 3] = float("nan")
+    z[2] = float("nan")
+    z[3, n - 2] = float("inf")
+    return z
+
+
+@pytest.mark.parametrize("n", [3072, 1001])
+def test_oracle_sparsemax_non_finite_rows_are_nan(n):
+    """torch's own rules (x.max keeps a NaN, Inf - Inf, torch.max(0, z - tau)) make the whole row NaN."""
+    z = _non_finite_rows(n)
+    p = orc.sparsemax_lastdim(z)
+    assert bool(torch.isnan(p[1:4]).all()) and not bool(torch.isnan(p[[0, 4]]).any())
+    assert torch.equal(p[[0, 4]], orc.sparsemax_lastdim(z[[0, 4]]))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [3072, 1001, 50000])
+@pytest.mark.parametrize("scale", [1.0, 40.0])
+def test_sparsemax_kernel_non_finite_rows_are_nan(built_lib, n, scale):
+    """A row holding a NaN or +Inf comes back NaN in every element (the library's max(0, input - taus) with a NaN tau,
+    then torch.clamp), in the float4 path (n = 3072), the scalar path (n = 1001) and the form that keeps the row in
+    global memory (n = 50000); the finite rows beside them are unaffected."""
+    from probpose_pytorch_amd import ops
+    z = _non_finite_rows(n)
+    want = torch.clamp(orc.sparsemax_lastdim(z) * scale, 0, 1)
+    got = ops.sparsemax_rows(z.cuda().contiguous(), scale).cpu()
+    assert bool(torch.isnan(got[1:4]).all()), [int(torch.isnan(got[r]).sum()) for r in range(5)]
+    torch.testing.assert_close(got[[0, 4]], want[[0, 4]], rtol=0, atol=1e-6 * scale)
+    assert torch.equal(got[[0, 4]], ops.sparsemax_rows(z[[0, 4]].cuda().contiguous(), scale).cpu())
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 def test_head_with_normalize_matches_oracle(built_lib, dtype):
