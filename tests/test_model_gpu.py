@@ -349,8 +349,9 @@ def test_full_size_forward_properties_vit_h_wholebody_bs128_bf16(pkg):
 
 
 def test_full_size_forward_properties_vit_l_bs256_fp8(pkg):
-    """BASELINE.json configs[4]: ViT-L fp8 weights / activations, batch 256.  No fp8 reference exists: properties
-    + the deviation from the bf16 path of the same model on the same batch is bounded loosely and recorded."""
+    """BASELINE.json configs[4]: ViT-L fp8 weights / activations, batch 256.  Properties + the deviation from the bf16
+    path of the same model on the same batch, bounded loosely and recorded.  What fp8 mode computes is held to its float64
+    restatement stage by stage in tests/test_fp8_walk_gpu.py (tests/fp8_walk_reference.py); this test is the full size."""
     import bench
     cfg, sd, x, full8 = _full_size_properties(pkg, "vit_l", torch.float8_e4m3fn, 256)
     model, codec, _ = bench.build(cfg, torch.bfloat16, torch.device("cuda", 0))
@@ -387,8 +388,10 @@ def test_run_inference_on_boxes_matches_crop_then_forward(pkg):
 @pytest.mark.parametrize("fp8_proj", [False, True])
 def test_fp8_forward_tracks_bf16(pkg, fp8_proj, monkeypatch):
     """BASELINE config 5 (fp8 weights / activations on the fp8 MFMA): same model, bf16 vs fp8 ViT GEMMs.
-    No reference exists for fp8 (the reference is fp32-only): the deviation from the bf16 path is bounded loosely and
-    the decode of the fp8 heatmaps must stay well-formed; determinism and graph capture after calibration are checked."""
+    The scales, the launch sequence and every stage's value are held to the float64 restatement of fp8 mode in
+    tests/test_fp8_walk_gpu.py (tests/fp8_walk_reference.py); here the end-to-end deviation from the bf16 path is bounded
+    loosely and the decode of the fp8 heatmaps must stay well-formed; determinism and graph capture after calibration are
+    checked."""
     from probpose_pytorch_amd import engine
     monkeypatch.setattr(engine, "FP8_PROJ", fp8_proj)
     model, _ = _build(pkg, (256, 192), 384, 4, 12, 17, [(4, 3), (2, 2), (2, 2)])
@@ -466,7 +469,8 @@ def test_fp8_explicit_calibration_covers_a_brighter_batch(pkg):
     """static fp8 activation scales came from the first batch with margin 1.0 and later batches with
     larger activations saturated silently.  calibrate_fp8() fixes the scales from given batches with head-room
     (margin 1.25); a model calibrated on both batches must track bf16 on the high-contrast batch at least as well as
-    one calibrated on the flat batch only."""
+    one calibrated on the flat batch only.  (The running maximum, its reset and the margin are held to exact values in
+    tests/test_fp8_walk_gpu.py::test_recalibration_running_maximum_reset_and_margin.)"""
     model, _ = _build(pkg, (256, 192), 384, 4, 12, 17, [(4, 3), (2, 2), (2, 2)])
     flat = (pkg["syn"].synthetic_crops(4, 256, 192, seed=3) * 0.2 + 0.4).cuda()
     g = torch.Generator().manual_seed(9)
