@@ -202,6 +202,16 @@ int pp_attention_headmajor(const void *qkv, void *out, int B, int N, int heads, 
 int pp_attention_fp8out(const void *qkv, unsigned char *out, int B, int N, int heads, int hd,
                         float inv_scale, void *stream);
 
+/* attn.qkv and the attention of one ViT block in ONE launch (timm Attention.forward: qkv = self.qkv(x), then
+ * softmax(q k^T * hd^-1/2) v), for N = 192 tokens per crop (256x192 input) and head_dim 64, bf16: q, k and v stay in
+ * LDS and never go to memory.  h [B*192, C] bf16 (the LayerNorm output); w_hm [heads*192, C] bf16 and b_hm
+ * [heads*192] f32 = qkv.weight / qkv.bias with the rows permuted HEAD-MAJOR: row 192 h + 64 t + d is row
+ * t C + 64 h + d of the original (t = 0, 1, 2 for q, k, v), so one head's q, k and v rows are one 192-row panel;
+ * out [B*192, C] bf16, bit-identical to pp_gemm (tile 14, PP_EPI_BIAS) followed by pp_attention.
+ * Refused: C != 64 heads, C % 64 != 0, C < 128, operands not 16-byte aligned, B * heads beyond one launch's grid. */
+int pp_qkv_attention_bf16(const void *h, const void *w_hm, const float *b_hm, void *out, int B, int heads, int C,
+                          void *stream);
+
 /* Patch im2col + cast: x [B,3,H,W] f32 NCHW -> A [B*gh*gw, 3*p*p] (k = c*p*p + py*p + px),
  * the A operand of patch_embed.proj as a GEMM (timm PatchEmbed, stride = patch). */
 int pp_patchify(const float *x, void *out, int B, int H, int W, int patch, int dtype,

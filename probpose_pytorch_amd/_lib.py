@@ -76,6 +76,7 @@ _SIGNATURES = {
     "pp_attention": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "pp_attention_headmajor": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "pp_attention_fp8out": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _f, _vp]),
+    "pp_qkv_attention_bf16": (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "pp_patchify": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "pp_maxpool_relu": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "pp_maxpool_relu_sum": (C.c_int, [_vp, _i, C.c_longlong, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),

@@ -19,8 +19,14 @@
 // attention_stream_kernel is the same computation for any N and head_dim 32 / 64 / 80 (ViT-H: N = 432
 // at 384x288, hd = 80): one workgroup per (crop, head, block of 128 queries), the keys stream
 // through LDS in blocks of 96 with the online-softmax rescale between blocks.
+// qkv_attention_kernel (N = 192, head_dim 64) computes q, k and v itself, as one tile of the Duo GEMM form, and runs the
+// one-shot kernel's block body on them without leaving the workgroup: q, k and v are never written to memory.
 // Everything else (fp32 parity mode, other head dims) runs the exact fp32 VALU kernel in pp_ops.hip.
+#include <algorithm>
+
 #include "pp_common.h"
+#include "pp_gemm_duo.h"
+#include "pp_gemm_forms.h"
 
 namespace pp {
 
@@ -74,6 +80,167 @@ __device__ __forceinline__ void att_store_fp8(unsigned char *orow8, const f32x4 
 template <int PENDING>
 __device__ __forceinline__ void att_wait_barrier() {
   asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(PENDING) : "memory");
+}
+
+// ---- the block body as device functions, statement for statement that of attention_mfma_kernel and
+// attention_stream_kernel below; qkv_attention_kernel is built from them.  The two older kernels keep their in-line
+// copies: calling these helpers from them changes their code (profiles/device_helpers_refactor_variants.txt: operands
+// commuted, another schedule, and at the 168-register limit of three workgroups per CU a growing private segment), which
+// needs an A/B of every attention form before it may go in.  One block of KBT key tiles against a wave's QT query
+// tiles.  Ks / Vs: the K / V images in LDS ([rows][HD] bf16, chunks swizzled by
+// AttGeom<HD>::swz), the block's first key at LDS row `row0`; lane = (lrow, g).
+//
+// S^T block = K_block Q^T : sacc[kt][t] rows = keys 16 kt + 4g + r of the block, col = query.  MASK: keys >= N (global
+// key of the block's first row: key0) start at -inf.  after_tile(kt) runs behind key tile kt's MFMAs (the one-shot
+// kernel requests the rest of K / V from there).
+template <int HD, int QT, int KBT, bool MASK, typename F>
+__device__ __forceinline__ void att_scores(const char *Ks, int row0, int key0, int N,
+                                           const uint4 (&qf)[QT][AttGeom<HD>::KS], f32x4 (&sacc)[KBT][QT], int lrow,
+                                           int g, F after_tile) {
+  using G = AttGeom<HD>;
+#pragma unroll
+  for (int kt = 0; kt < KBT; ++kt) {
+    const f32x4 init = MASK ? att_mask_init(key0 + kt * 16 + g * 4, N) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int t = 0; t < QT; ++t) sacc[kt][t] = init;
+    const int r = row0 + kt * 16 + lrow;
+#pragma unroll
+    for (int s = 0; s < G::KS; ++s) {
+      uint4 kf = make_uint4(0, 0, 0, 0);
+      if (s < G::KS - 1 || g < G::KLIVE)
+        kf = *reinterpret_cast<const uint4 *>(Ks + r * G::KROW + (G::swz(r, 4 * s + g) << 4));
+#pragma unroll
+      for (int t = 0; t < QT; ++t)
+        sacc[kt][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8 *>(&kf),
+                                                              *reinterpret_cast<const bf16x8 *>(&qf[t][s]),
+                                                              sacc[kt][t], 0, 0, 0);
+    }
+    after_tile(kt);
+  }
+}
+
+// online softmax over the block's keys, per query column: sacc becomes the probabilities, the running max m, the
+// per-lane partial sum l and the output accumulator are rescaled by alpha = exp2(m_old - m_new).  VALU diet (this
+// phase, not the MFMAs, bounds the kernels): padded keys are masked through the accumulator init, scores are pre-scaled
+// by c = log2(e)/sqrt(hd) so each probability is one FMA + one raw v_exp_f32.
+template <int DT, int QT, int KBT>
+__device__ __forceinline__ void att_softmax(f32x4 (&sacc)[KBT][QT], float (&m_run)[QT], float (&l_run)[QT],
+                                            f32x4 (&oacc)[DT][QT], float scale_log2e) {
+#pragma unroll
+  for (int t = 0; t < QT; ++t) {
+    float mb = sacc[0][t][0];
+#pragma unroll
+    for (int kt = 0; kt < KBT; ++kt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) mb = fmaxf(mb, sacc[kt][t][r]);
+    mb = fmaxf(mb, __shfl_xor(mb, 16, 64));
+    mb = fmaxf(mb, __shfl_xor(mb, 32, 64));
+    const float m_new = fmaxf(m_run[t], mb * scale_log2e);   // running max of the SCALED scores; finite
+    const float alpha = __builtin_amdgcn_exp2f(m_run[t] - m_new);  // block 0: exp2(-inf) = 0
+    // two scores per instruction: v_pk_fma_f32 for the exponent, v_pk_add_f32 for the partial sums
+    att_f32x2 l2 = {0.f, 0.f};
+    const att_f32x2 c2 = {scale_log2e, scale_log2e}, nm2 = {-m_new, -m_new};
+#pragma unroll
+    for (int kt = 0; kt < KBT; ++kt)
+#pragma unroll
+      for (int r = 0; r < 4; r += 2) {
+        const att_f32x2 e = __builtin_elementwise_fma((att_f32x2){sacc[kt][t][r], sacc[kt][t][r + 1]}, c2, nm2);
+        const att_f32x2 pv = {__builtin_amdgcn_exp2f(e.x), __builtin_amdgcn_exp2f(e.y)};
+        sacc[kt][t][r] = pv.x;
+        sacc[kt][t][r + 1] = pv.y;
+        l2 += pv;
+      }
+    const float l = l2.x + l2.y;
+    l_run[t] = l_run[t] * alpha + l;
+    m_run[t] = m_new;
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt) {
+      oacc[dt][t][0] *= alpha; oacc[dt][t][1] *= alpha; oacc[dt][t][2] *= alpha; oacc[dt][t][3] *= alpha;
+    }
+  }
+}
+
+// O^T += V_block^T P_block^T : rows = dims 16*dt + 4g + r, col = query; P^T comes straight from the score registers
+template <int HD, int QT, int KBT>
+__device__ __forceinline__ void att_pv(const char *Vs, int row0, const f32x4 (&sacc)[KBT][QT],
+                                       f32x4 (&oacc)[AttGeom<HD>::DT][QT], int lrow, int g) {
+  using G = AttGeom<HD>;
+#pragma unroll
+  for (int u = 0; u < KBT / 2; ++u) {  // 32 keys per step
+    uint4 pf[QT];
+#pragma unroll
+    for (int t = 0; t < QT; ++t) {
+      pf[t].x = pack_bf16x2(sacc[2 * u][t][0], sacc[2 * u][t][1]);
+      pf[t].y = pack_bf16x2(sacc[2 * u][t][2], sacc[2 * u][t][3]);
+      pf[t].z = pack_bf16x2(sacc[2 * u + 1][t][0], sacc[2 * u + 1][t][1]);
+      pf[t].w = pack_bf16x2(sacc[2 * u + 1][t][2], sacc[2 * u + 1][t][3]);
+    }
+#pragma unroll
+    for (int dt = 0; dt < G::DT; ++dt) {
+      // A operand = V^T fragment: lane (dim = lrow, g) needs keys {4g..4g+3} and {16+4g..16+4g+3}
+      // of this 32-key step for its dim.  Each 16-lane group g issues one transposing read per key
+      // quartet: lane 4q+p of the group addresses row (key) q, dims 4p..4p+3 of the 16-dim block;
+      // lane i receives dim i of the 4 keys.  (EXEC is all ones here; addresses are 8-B aligned.)
+      const int tq = lrow >> 2, tp = lrow & 3;
+      const int key0 = row0 + 32 * u + 4 * g + tq;
+      const int ch = 2 * dt + (tp >> 1);
+      const int a0 = key0 * G::KROW + (G::swz(key0, ch) << 4) + (tp & 1) * 8;
+      const int key1 = key0 + 16;
+      const int a1 = key1 * G::KROW + (G::swz(key1, ch) << 4) + (tp & 1) * 8;
+      const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+          (__attribute__((address_space(3))) s16x4 *)(Vs + a0));
+      const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+          (__attribute__((address_space(3))) s16x4 *)(Vs + a1));
+      uint4 vf;
+      vf.x = (unsigned)(unsigned short)lo[0] | ((unsigned)(unsigned short)lo[1] << 16);
+      vf.y = (unsigned)(unsigned short)lo[2] | ((unsigned)(unsigned short)lo[3] << 16);
+      vf.z = (unsigned)(unsigned short)hi[0] | ((unsigned)(unsigned short)hi[1] << 16);
+      vf.w = (unsigned)(unsigned short)hi[2] | ((unsigned)(unsigned short)hi[3] << 16);
+#pragma unroll
+      for (int t = 0; t < QT; ++t)
+        oacc[dt][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8 *>(&vf),
+                                                              *reinterpret_cast<const bf16x8 *>(&pf[t]),
+                                                              oacc[dt][t], 0, 0, 0);
+    }
+  }
+}
+
+// head_dim 64 and no row guards: query tile t of a wave leaves as whole 128-byte lines.  A head's output row is ONE
+// aligned 128-byte line.  What a store costs is the lines it touches (tools/ubench/store_bw.hip), and 8 bytes per lane
+// is 16 rows x 32 B = 16 lines per 512 B.  As in gemm_quad_stream_kernel: two v_permlane16_swap_b32 per pair of dim
+// tiles give a lane 8 consecutive dims, rows lrow / lrow ^ 1 then trade halves by DPP so that one 16-byte store holds
+// the whole line of 8 rows: 2 stores of 8 lines per query tile instead of 4 stores of 16.  head_q: the head's 64
+// columns of output row q (the lane's own query; every lane takes part).
+template <int QT>
+__device__ __forceinline__ void att_store_lines64(bf16_t *head_rows, int q, int C, const f32x4 (&oacc)[4][QT], int t,
+                                                  float inv_l, int lrow, int g) {
+  unsigned w[8];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) {
+    w[2 * dt] = pack_bf16x2(oacc[dt][t][0] * inv_l, oacc[dt][t][1] * inv_l);
+    w[2 * dt + 1] = pack_bf16x2(oacc[dt][t][2] * inv_l, oacc[dt][t][3] * inv_l);
+  }
+  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+  u32x4 PQ[2];
+#pragma unroll
+  for (int jp = 0; jp < 2; ++jp) {       // dim tiles 2 jp, 2 jp + 1: even g -> dims 4 g .. + 7 of tile 2 jp, odd g -> of tile 2 jp + 1
+    const auto r0 = __builtin_amdgcn_permlane16_swap(w[4 * jp], w[4 * jp + 2], false, false);
+    const auto r1 = __builtin_amdgcn_permlane16_swap(w[4 * jp + 1], w[4 * jp + 3], false, false);
+    PQ[jp] = u32x4{r0[0], r1[0], r0[1], r1[1]};
+  }
+  const bool odd = (lrow & 1) != 0;
+  u32x4 X, Y;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const unsigned give = odd ? PQ[0][e] : PQ[1][e];                                   // what lane lrow ^ 1 needs
+    const unsigned got = (unsigned)__builtin_amdgcn_mov_dpp((int)give, 0xB1, 0xF, 0xF, true);   // quad_perm [1, 0, 3, 2]
+    X[e] = odd ? got : PQ[0][e];       // the even row: dims 0 .. 31 from the even lane, 32 .. 63 from the odd lane
+    Y[e] = odd ? PQ[1][e] : got;       // the odd row
+  }
+  const int lane_dim = ((g & 1) ? 16 + (g - 1) * 4 : g * 4) + (odd ? 32 : 0);
+  bf16_t *even_row = head_rows + (size_t)(q & ~1) * C + lane_dim;
+  *reinterpret_cast<u32x4 *>(even_row) = X;
+  *reinterpret_cast<u32x4 *>(even_row + C) = Y;
 }
 
 // The staging is issued as Q, then groups of 12 one-KiB pieces (3 per wave) in the order the products consume them
@@ -593,6 +760,121 @@ static int launch_stream(const void *qkv, void *out, int B, int N, int heads, fl
   return launch_stream_cfg<HD, 4, 2, 64>(qkv, out, B, N, heads, fp8_inv_scale, s, headmajor);
 }
 
+// ---- qkv projection + attention of one (crop, head) in one workgroup: N = 192, head_dim 64, bf16.
+// The q, k and v rows of head h are rows [192 h, 192 h + 192) of the head-major weight w_hm (64 q rows, 64 k rows,
+// 64 v rows), so q_h | k_h | v_h of crop b is ONE 192x192 GEMM tile over K = C: the tile of gemm_duo_kernel.
+//   phase 1   the Duo K-loop (pp_gemm_duo.h): 4 waves, 96x96 each, 3 x 24 KB ring = 72 KB of LDS;
+//   hand-over the ring is dead after the last K-tile (barrier); every wave adds the bias, rounds to bf16 exactly as the
+//             GEMM epilogue does and writes its part INTO THE RING'S MEMORY as the three [192][64] images K | V | Q
+//             (24 KB each = the same 72 KB), all in the swizzled layout the block body reads K in; barrier;
+//   phase 2   the block body of attention_mfma_kernel<64, true>, with nothing to request and nothing to wait for.
+// q, k and v never go to global memory (56.6 MB written and read back per ViT-B block at batch 64).  Two workgroups
+// share a CU (__launch_bounds__(256, 2): 256 registers, 2 x 72 KB) and drift out of phase, so one's softmax (VALU) and
+// fill run under the other's K-loop (MFMA, LDS-DMA).  Lane (frow, fq) of wave (wm, wn) holds tile rows
+// wm 96 + 16 i + frow (tokens) and columns wn 96 + 16 j + 4 fq .. + 3: column c is dim c % 64 of q / k / v = c / 64.
+__global__ __launch_bounds__(256, 2) void qkv_attention_kernel(const char *__restrict__ hA, const char *__restrict__ W,
+                                                               const float *__restrict__ bias, bf16_t *__restrict__ out,
+                                                               int B, int heads, int rn, float scale_log2e) {
+  using D = DuoLoop;
+  using G = AttGeom<64>;
+  constexpr int IMG = AT_NMAX * G::KROW;       // one [192][64] bf16 image: 24 KB
+  static_assert(3 * IMG == D::LDS_BYTES && D::BM == AT_NMAX && D::BN == 3 * 64, "Q, K, V alias the ring exactly");
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char *Ks = smem, *Vs = smem + IMG, *Qs = smem + 2 * IMG;
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave >> 1, wn = wave & 1;
+  const int frow = lane & 15, fq = lane >> 4;
+  int b, h;
+  if (!duo_blocked_tile(blockIdx.x, rn, B, heads, b, h)) return;
+  const int C = heads * 64;
+
+  // ---- phase 1: acc = h[192 b .., :] w_hm[192 h .., :]^T
+  D duo;
+  duo.init(smem, lane, wave);
+#pragma unroll
+  for (int j = 0; j < D::PA; ++j) duo.a_src[j] = hA + ((size_t)b * AT_NMAX + duo.piece_row(j)) * C * 2 + duo.lchunk_off;
+#pragma unroll
+  for (int j = 0; j < D::PB; ++j) {
+    duo.w_ok[j] = true;
+    duo.w_src[j] = W + ((size_t)h * AT_NMAX + duo.piece_row(j)) * C * 2 + duo.lchunk_off;
+  }
+  duo.init_ring(lane, wm, wn);
+  const int nkt = C / D::BK;
+  f32x4 acc[D::TM][D::TN];
+  duo.fill(nkt);
+#pragma unroll
+  for (int i = 0; i < D::TM; ++i)
+#pragma unroll
+    for (int j = 0; j < D::TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  duo.run(nkt, acc);
+
+  // ---- hand-over.  This wave's DMA has all landed (the loop's last wait is vmcnt(0)); the bias is fetched now so
+  // that no ordinary load is in flight under the loop's counted waits.  The barrier: every wave is done reading the ring.
+  float4 b4[D::TN];
+#pragma unroll
+  for (int j = 0; j < D::TN; ++j)
+    b4[j] = *reinterpret_cast<const float4 *>(bias + (size_t)h * AT_NMAX + wn * 96 + j * 16 + fq * 4);
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < D::TN; ++j) {
+    const int cj = wn * 6 + j;                          // 16-column tile of the 192: 0-3 q, 4-7 k, 8-11 v
+    const int mat = cj >> 2;
+    char *img = mat == 0 ? Qs : (mat == 1 ? Ks : Vs);
+    const int chunk = (cj & 3) * 2 + (fq >> 1);         // 16-byte chunk (8 dims) of the 128-byte row
+#pragma unroll
+    for (int i = 0; i < D::TM; ++i) {
+      const int m = wm * 96 + i * 16 + frow;
+      uint2 pk;
+      pk.x = pack_bf16x2(acc[i][j][0] + b4[j].x, acc[i][j][1] + b4[j].y);
+      pk.y = pack_bf16x2(acc[i][j][2] + b4[j].z, acc[i][j][3] + b4[j].w);
+      *reinterpret_cast<uint2 *>(img + m * G::KROW + (G::swz(m, chunk) << 4) + (fq & 1) * 8) = pk;
+    }
+  }
+  __syncthreads();
+
+  // ---- phase 2: attention of the 48 query rows of this wave against the resident K and V
+  const int lrow = frow, g = fq;
+  const int q0 = wave * (AT_QT * 16);
+  uint4 qf[AT_QT][G::KS];
+#pragma unroll
+  for (int t = 0; t < AT_QT; ++t) {
+    const int q = q0 + t * 16 + lrow;
+#pragma unroll
+    for (int s = 0; s < G::KS; ++s)
+      qf[t][s] = *reinterpret_cast<const uint4 *>(Qs + q * G::KROW + (G::swz(q, 4 * s + g) << 4));
+  }
+  constexpr int KB_TILES = AT_NT / 2;
+  float m_run[AT_QT], l_run[AT_QT];
+  f32x4 oacc[G::DT][AT_QT];
+#pragma unroll
+  for (int t = 0; t < AT_QT; ++t) {
+    m_run[t] = -__builtin_inff();
+    l_run[t] = 0.f;
+#pragma unroll
+    for (int dt = 0; dt < G::DT; ++dt) oacc[dt][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+#pragma unroll
+  for (int kb = 0; kb < 2; ++kb) {
+    f32x4 sacc[KB_TILES][AT_QT];
+    // the scheduling fences stand where attention_mfma_kernel has its counted waits: without them the K and V
+    // fragment reads of both blocks are hoisted to the front until the register file is full (68 bytes of scratch)
+    att_scores<64, AT_QT, KB_TILES, false>(Ks, kb * (KB_TILES * 16), kb * (KB_TILES * 16), AT_NMAX, qf, sacc, lrow, g,
+                                           [](int) {});
+    __builtin_amdgcn_sched_barrier(0);
+    att_softmax<G::DT, AT_QT, KB_TILES>(sacc, m_run, l_run, oacc, scale_log2e);
+    __builtin_amdgcn_sched_barrier(0);
+    att_pv<64, AT_QT, KB_TILES>(Vs, kb * (KB_TILES * 16), sacc, oacc, lrow, g);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+#pragma unroll
+  for (int t = 0; t < AT_QT; ++t) {
+    float l = l_run[t];
+    l += __shfl_xor(l, 16, 64);
+    l += __shfl_xor(l, 32, 64);
+    att_store_lines64<AT_QT>(out + (size_t)b * AT_NMAX * C + h * 64, q0 + t * 16 + lrow, C, oacc, t, 1.0f / l, lrow, g);
+  }
+}
+
 }  // namespace pp
 
 static int attention_dispatch(const void *qkv, void *out, int B, int N, int heads, int hd, int dtype,
@@ -647,6 +929,32 @@ extern "C" int pp_attention_fp8out(const void *qkv, unsigned char *out, int B, i
                                    float inv_scale, void *stream) {
   if (!(inv_scale > 0.f)) return pp::fail("pp_attention_fp8out: inv_scale must be positive");
   return attention_dispatch(qkv, out, B, N, heads, hd, PP_BF16, inv_scale, stream);
+}
+
+/* The qkv projection and the attention of a ViT block in one launch: see include/probpose_hip.h. */
+extern "C" int pp_qkv_attention_bf16(const void *h, const void *w_hm, const float *b_hm, void *out, int B, int heads,
+                                     int C, void *stream) {
+  using namespace pp;
+  PP_REQUIRE(B >= 0 && heads > 0 && C > 0, "pp_qkv_attention_bf16: bad shape B=%d heads=%d C=%d", B, heads, C);
+  PP_REQUIRE(C % 64 == 0 && C >= 128 && (long long)heads * 64 == C,
+             "pp_qkv_attention_bf16: needs head_dim 64 (C = 64 heads), C a multiple of 64 and C >= 128 (got C=%d, heads=%d)",
+             C, heads);
+  if (B == 0) return 0;
+  PP_REQUIRE(h && w_hm && b_hm && out, "pp_qkv_attention_bf16: null pointer");
+  PP_REQUIRE(((uintptr_t)h & 15) == 0 && ((uintptr_t)w_hm & 15) == 0 && ((uintptr_t)b_hm & 15) == 0 &&
+                 ((uintptr_t)out & 15) == 0,
+             "pp_qkv_attention_bf16: h, w_hm, b_hm and out must be 16-byte aligned");
+  // the XCD-blocked order of gemm_duo_kernel over (crops, heads): blocks of 8 crops x rn heads, whole groups of 8 blocks
+  const int rn = std::min(gemm_form(14).xcd_rn, heads);
+  const long long nblk = (long long)cdiv(B, DUO_XCD_RM) * cdiv(heads, rn);
+  const long long grid = (nblk + 7) / 8 * 8 * DUO_XCD_RM * rn;
+  PP_REQUIRE(grid < (1ll << 31), "pp_qkv_attention_bf16: B * heads = %lld is too large for one launch", (long long)B * heads);
+  if (int rc = ensure_dynamic_lds(qkv_attention_kernel, DuoLoop::LDS_BYTES)) return rc;
+  const float scale_log2e = 1.4426950408889634f / sqrtf(64.0f);
+  hipLaunchKernelGGL(qkv_attention_kernel, dim3((unsigned)grid), dim3(256), DuoLoop::LDS_BYTES, (hipStream_t)stream,
+                     (const char *)h, (const char *)w_hm, b_hm, (bf16_t *)out, B, heads, rn, scale_log2e);
+  PP_CHECK_LAUNCH("qkv_attention_kernel");
+  return 0;
 }
 
 /* Head-major qkv: see include/probpose_hip.h.  The streaming MFMA kernel only (bf16, head_dim 32 / 64 / 80, any N). */

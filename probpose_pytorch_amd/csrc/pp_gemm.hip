@@ -24,6 +24,7 @@
 #include <algorithm>
 
 #include "pp_common.h"
+#include "pp_gemm_duo.h"
 #include "pp_gemm_shared.h"
 #include "pp_gemm_forms.h"
 
@@ -1142,9 +1143,8 @@ __global__ __launch_bounds__(256, 2) void gemm_duo_kernel(GemmParams p) {
   // No start stagger of the second slot of every CU (block ids b and b + 256 share a CU on a >= 512-workgroup launch).
   // Tried because two workgroups that start together run the same phases at the same time; measured a loss at every
   // delay (units of s_sleep(127) ~ 3.9 us: fc1 87.2 / 90.9 / 101 us at 0 / 2 / 4).
-  constexpr int BM = 192, BN = 192, STAGES = 3, BK = 32, RB = 64;          // RB: bytes of K per staged row
-  constexpr int PA = 3, PB = 3, PIECES = PA + PB, TM = 6, TN = 6;           // 1-KiB pieces (16 rows) per wave per K-tile
-  constexpr int A_BYTES = BM * RB, STAGE_BYTES = (BM + BN) * RB;
+  using D = DuoLoop;
+  constexpr int BM = D::BM, BN = D::BN, BK = D::BK, PA = D::PA, PB = D::PB, TM = D::TM, TN = D::TN;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
   const int frow = lane & 15, fq = lane >> 4;
@@ -1152,16 +1152,7 @@ __global__ __launch_bounds__(256, 2) void gemm_duo_kernel(GemmParams p) {
 
   int tm, tn;
   if (p.blocked) {
-    constexpr int RM = 8;
-    const int RN = p.rn, RT = RM * RN;
-    const int nbm = (p.tiles_m + RM - 1) / RM, nbn = (p.tiles_n + RN - 1) / RN;
-    const int x = blockIdx.x & 7, j = blockIdx.x >> 3;
-    const int g = (j / RT) * 8 + x, idx = j % RT;
-    if (g >= nbm * nbn) return;
-    const int bmi = g / nbn, bni = g - bmi * nbn;
-    tm = bmi * RM + idx / RN;
-    tn = bni * RN + idx % RN;
-    if (tm >= p.tiles_m || tn >= p.tiles_n) return;
+    if (!duo_blocked_tile(blockIdx.x, p.rn, p.tiles_m, p.tiles_n, tm, tn)) return;
   } else {
     tm = blockIdx.x / p.tiles_n;
     tn = blockIdx.x - tm * p.tiles_n;
@@ -1169,82 +1160,27 @@ __global__ __launch_bounds__(256, 2) void gemm_duo_kernel(GemmParams p) {
   const int m0 = tm * BM, n0 = tn * BN;
   const int nkt = p.Kd / BK;
 
-  // ---- staging: lane -> (row in piece = lane >> 2, physical chunk = lane & 3); logical chunk = physical ^ perm
-  const int prow = lane >> 2, pchunk = lane & 3;
-  const int perm_p = (0x1230 >> (4 * ((prow >> 2) & 3))) & 3;      // {0, 3, 2, 1}[(row >> 2) & 3]
-  const int lchunk_off = (pchunk ^ perm_p) * 16;
+  // ---- the K-loop (pp_gemm_duo.h) over this tile's rows: A rows clamped to M - 1, W rows past N read a zero line
+  D duo;
+  duo.init(smem, lane, wave);
+  const int prow = duo.prow, pchunk = lane & 3;
   const char *zero_line = (const char *)g_zero_page + (((blockIdx.x * 29 + wave) * 16 + prow) & 63) * 128 + pchunk * 16;
-  const char *a_src[PA];
-  const char *w_src[PB];
-  bool w_ok[PB];
 #pragma unroll
   for (int j = 0; j < PA; ++j) {
-    const int r = (wave * PA + j) * 16 + prow;
-    a_src[j] = p.A + (size_t)min(m0 + r, p.M - 1) * p.lda * 2 + lchunk_off;
+    const int r = duo.piece_row(j);
+    duo.a_src[j] = p.A + (size_t)min(m0 + r, p.M - 1) * p.lda * 2 + duo.lchunk_off;
   }
 #pragma unroll
   for (int j = 0; j < PB; ++j) {
-    const int r = n0 + (wave * PB + j) * 16 + prow;
-    w_ok[j] = r < p.N;
-    w_src[j] = w_ok[j] ? p.W + (size_t)r * p.ldw * 2 + lchunk_off : zero_line;
+    const int r = n0 + duo.piece_row(j);
+    duo.w_ok[j] = r < p.N;
+    duo.w_src[j] = duo.w_ok[j] ? p.W + (size_t)r * p.ldw * 2 + duo.lchunk_off : zero_line;
   }
-  const unsigned lds0 = lds_offset_of(smem);
-  unsigned st_ldsA = 0, st_ldsB = 0;
-  size_t st_koff = 0;
-  auto stage_begin = [&](int kt, int buf) __attribute__((always_inline)) {
-    st_ldsA = __builtin_amdgcn_readfirstlane(lds0 + buf * STAGE_BYTES + wave * PA * 1024);
-    st_ldsB = __builtin_amdgcn_readfirstlane(lds0 + buf * STAGE_BYTES + A_BYTES + wave * PB * 1024);
-    st_koff = (size_t)kt * RB;
-  };
-  auto stage_piece = [&](auto qc) __attribute__((always_inline)) {
-    constexpr int q = decltype(qc)::value;
-    if constexpr (q < PA) {
-      glds16(a_src[q] + st_koff, st_ldsA + q * 1024);
-    } else {
-      constexpr int j = q - PA;
-      glds16(w_ok[j] ? w_src[j] + st_koff : w_src[j], st_ldsB + j * 1024);
-    }
-  };
-  auto stage_all = [&](int kt, int buf) __attribute__((always_inline)) {
-    stage_begin(kt, buf);
-    [&]<int... Q>(std::integer_sequence<int, Q...>) {
-      (stage_piece(std::integral_constant<int, Q>{}), ...);
-    }(std::make_integer_sequence<int, PIECES>{});
-  };
+  duo.init_ring(lane, wm, wn);
 
   f32x4 acc[TM][TN];
-  // fragment offsets: row (w? * 96 + 16 i + frow), chunk fq ^ perm[(frow >> 2) & 3] (i only adds multiples of 16 rows)
-  const int perm_f = (0x1230 >> (4 * ((frow >> 2) & 3))) & 3;
-  const unsigned offA = (wm * 96 + frow) * RB + ((fq ^ perm_f) << 4);
-  const unsigned offB = A_BYTES + (wn * 96 + frow) * RB + ((fq ^ perm_f) << 4);
-  auto compute = [&](int buf, auto do_stage_c) __attribute__((always_inline)) {
-    constexpr bool DO_STAGE = decltype(do_stage_c)::value;
-    const char *sb = smem + buf * STAGE_BYTES;
-    uint4 bf[TN];
-#pragma unroll
-    for (int j = 0; j < TN; ++j) bf[j] = *reinterpret_cast<const uint4 *>(sb + offB + j * 16 * RB);
-    [&]<int... I>(std::integer_sequence<int, I...>) {
-      ([&] {
-        constexpr int i = I;
-        const uint4 af = *reinterpret_cast<const uint4 *>(sb + offA + i * 16 * RB);
-        if constexpr (DO_STAGE) {
-          __builtin_amdgcn_sched_barrier(0);
-          stage_piece(std::integral_constant<int, i>{});        // PIECES == TM: one piece per MFMA group
-          __builtin_amdgcn_sched_barrier(0);
-        }
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<bf16x8 *>(&bf[j]),
-                                                              *reinterpret_cast<const bf16x8 *>(&af), acc[i][j], 0, 0, 0);
-      }(), ...);
-    }(std::make_integer_sequence<int, TM>{});
-  };
-  static_assert(PIECES == TM, "one DMA piece per MFMA group");
-
   // ---- pipeline fill, then the additive epilogue terms straight into the accumulators (residual / row bias)
-#pragma unroll
-  for (int s_ = 0; s_ < STAGES - 1; ++s_)
-    if (s_ < nkt) stage_all(s_, s_);
+  duo.fill(nkt);
   const float *Rb = p.residual;
   const float *init_base = (epi & PP_EPI_RESIDUAL) ? Rb : ((epi & PP_EPI_ROWBIAS) ? p.rowbias : nullptr);
 #pragma unroll
@@ -1265,28 +1201,7 @@ __global__ __launch_bounds__(256, 2) void gemm_duo_kernel(GemmParams p) {
   }
   __builtin_amdgcn_s_waitcnt(0x0F70);     // retire them with a wait hipcc models (see gemm_kernel): no vmcnt(0) in the loop
 
-  int buf = 0, kt = 0;
-  for (; kt + STAGES - 1 < nkt; ++kt) {
-    wait_vmcnt<(STAGES - 2) * PIECES>();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    int nb = buf + STAGES - 1;
-    if (nb >= STAGES) nb -= STAGES;
-    stage_begin(kt + STAGES - 1, nb);
-    compute(buf, std::true_type{});
-    if (++buf == STAGES) buf = 0;
-  }
-  for (; kt < nkt; ++kt) {
-    if (kt + STAGES - 1 <= nkt) {
-      wait_vmcnt<(STAGES - 2) * PIECES>();
-    } else {
-      wait_vmcnt<0>();
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    compute(buf, std::false_type{});
-    if (++buf == STAGES) buf = 0;
-  }
+  duo.run(nkt, acc);
 
   // ---- epilogue: the tile goes through the (now idle) LDS ring in column passes and leaves as whole rows (16 B per
   // lane, contiguous per row); lane (frow, fq) of a wave owns row m and 4 consecutive columns of every 16-wide tile.

@@ -38,6 +38,10 @@ SPLITK_AUX = True
 FUSE_FINAL = True
 # head-major q / k / v for head dims that are not whole cache lines (see VitPlan.__init__)
 HEADMAJOR_QKV = True
+# bf16 models with N = 192 tokens and head_dim 64 (ViT-B / ViT-L at 256x192): attn.qkv and the attention of a block run as
+# one launch (ops.qkv_attention) that keeps q, k and v in LDS; see VitPlan.__init__.  Read at plan build (the packed
+# weights) and at every forward (off: the two-kernel path, on the same plan).
+FUSE_QKV_ATTENTION = True
 
 
 def _signature(module: torch.nn.Module):
@@ -149,14 +153,30 @@ class VitPlan:
         # streaming attention kernel: the qkv GEMM writes q / k / v head-major, so one head's rows are contiguous
         self.headmajor = (HEADMAJOR_QKV and dtype == torch.bfloat16 and not fp8 and
                           (self.hd == 80 or (self.hd == 32 and self.N > 192)))
+        # one launch for attn.qkv + attention: the q, k and v rows of a head become one 192-row panel of a head-major
+        # copy of qkv.weight / qkv.bias, packed once here (the parameters are constants of the plan).  The row-major
+        # qkv_w stays as well (the two-kernel path on the same plan): + 3 C^2 bf16 per block, 42 MB at ViT-B, 151 MB
+        # at ViT-L.  The packed copy is derived state, so the plan's first eager forward checks it: see _run_blocks.
+        self.qkv_fused = (FUSE_QKV_ATTENTION and dtype == torch.bfloat16 and not fp8 and self.N == 192 and
+                          self.hd == 64 and not self.headmajor and C >= 128)
+        if self.qkv_fused:
+            for b in self.blocks:
+                b["qkv_w_hm"], b["qkv_b_hm"] = ops.pack_qkv_headmajor(b["qkv_w"], b["qkv_b"], self.heads)
+        self.qkv_checked = False
         self.ws = _Workspace()
         self._chain_stream = None
 
-    def _buffers(self, B: int) -> Dict[str, torch.Tensor]:
-        """The workspace of a batch of B crops, by name; fp8 mode adds the e4m3 twins h8 / ao8 / hid8."""
+    def _fuse_qkv(self) -> bool:
+        return self.qkv_fused and FUSE_QKV_ATTENTION
+
+    def _buffers(self, B: int, fused: bool = False) -> Dict[str, torch.Tensor]:
+        """The workspace of a batch of B crops, by name; fp8 mode adds the e4m3 twins h8 / ao8 / hid8.  No qkv buffer
+        where the fused qkv + attention launch runs."""
         dt, C = self.dtype, self.C
         cols = dict(a0=(3 * self.patch ** 2, dt), xres=(C, torch.float32), h=(C, dt), qkv=(3 * C, dt), ao=(C, dt),
                     hid=(self.hidden, dt), feats=(C, dt))
+        if fused:
+            del cols["qkv"]
         if self.fp8:
             cols.update(h8=(C, ops.FP8), ao8=(C, ops.FP8), hid8=(self.hidden, ops.FP8))
         return {k: self.ws.get(k, (B * self.N, n), t, self.device) for k, (n, t) in cols.items()}
@@ -171,7 +191,9 @@ class VitPlan:
             return self._forward_tokens(x, B)
 
     def _forward_tokens(self, x: torch.Tensor, B: int) -> torch.Tensor:
-        bufs = self._buffers(B)
+        dual = DUAL_CHAIN and not SERIALIZE_HEAD and B % 2 == 0 and B >= DUAL_CHAIN_MIN_BATCH
+        fused = self._fuse_qkv()
+        bufs = self._buffers(B, fused)
         if self.fp8:
             if not self.fp8_calibrated:
                 if torch.cuda.is_current_stream_capturing():
@@ -179,7 +201,7 @@ class VitPlan:
                                        "forward before capturing a graph")
                 self._calibrate_fp8(x, B, bufs)
             self._run_blocks(x, B, bufs, fp8=True)
-        elif DUAL_CHAIN and not SERIALIZE_HEAD and B % 2 == 0 and B >= DUAL_CHAIN_MIN_BATCH:
+        elif dual:
             # Two half-batches as two independent kernel chains on two HIP streams (row slices of the same
             # buffers, same weights).  Every kernel of the path is bulk-synchronous: all its workgroups
             # run their matrix phase together and then their store phase together, so one chain alone
@@ -191,22 +213,35 @@ class VitPlan:
             cur, s2 = torch.cuda.current_stream(self.device), self._chain_stream
             Bh, Mh = B // 2, B * self.N // 2
             offset = torch.cuda.Event()
-            self._run_blocks(x[:Bh], Bh, {k: t[:Mh] for k, t in bufs.items()}, offset_event=offset)
+            self._run_blocks(x[:Bh], Bh, {k: t[:Mh] for k, t in bufs.items()}, offset_event=offset, fused=fused)
             s2.wait_event(offset)
             with torch.cuda.stream(s2):
-                self._run_blocks(x[Bh:], Bh, {k: t[Mh:] for k, t in bufs.items()})
+                self._run_blocks(x[Bh:], Bh, {k: t[Mh:] for k, t in bufs.items()}, fused=fused)
             cur.wait_stream(s2)
+        elif fused and not self.qkv_checked and not torch.cuda.is_current_stream_capturing():
+            self._run_blocks(x, B, bufs, fused=True, check=True)
         else:
-            self._run_blocks(x, B, bufs)
+            self._run_blocks(x, B, bufs, fused=fused)
         return bufs["feats"]
 
-    def _run_blocks(self, x, B, bufs, fp8=False, observe=None, offset_event=None):
+    def _run_blocks(self, x, B, bufs, fp8=False, observe=None, offset_event=None, fused=False, check=False):
         """The launch sequence of one batch: patch embed, the blocks, the final LayerNorm into bufs["feats"].
         ``fp8``: LN and GELU write e4m3 (h8 / hid8) with the block's static scales, and qkv / fc1 / fc2 read the e4m3
         weights with their column scales; with FP8_PROJ so do attention (ao8) and proj.  ``observe(block, point, t)`` is
         called with each of the four _FP8_POINTS activations once it is enqueued (a calibration pass; it ends at the last
-        block, since nothing reads its feats)."""
-        xres, qkv = bufs["xres"], bufs["qkv"]
+        block, since nothing reads its feats).  ``fused``: attn.qkv + attention as one launch (bufs has no "qkv").
+        ``check`` (the plan's first eager fused walk): every block also runs the two launches, ops.linear on tile 14 and
+        ops.attention, on the same h into scratch tensors, and the two outputs must be the same bits in every block; one
+        synchronisation at the end, HipExtensionError otherwise (a wrong head-major copy of qkv.weight or a kernel that
+        does not do on this device what the two launches do is an error, never a silent difference).  The scratch
+        tensors (4 C bf16 per token) are freed when it returns."""
+        fused = fused and not fp8 and observe is None
+        if check:
+            M = B * self.N
+            qkv_ref = torch.empty((M, 3 * self.C), dtype=self.dtype, device=self.device)
+            ao_ref = torch.empty((M, self.C), dtype=self.dtype, device=self.device)
+            differ = torch.zeros((), dtype=torch.int64, device=self.device)
+        xres, qkv = bufs["xres"], None if fused else bufs["qkv"]
         N, heads, hd = self.N, self.heads, self.hd
         q8 = "8" if fp8 else ""
         p8 = "8" if fp8 and FP8_PROJ else ""
@@ -223,8 +258,16 @@ class VitPlan:
                 offset_event.record()      # the other chain starts here: one patch-embed GEMM + LN behind
             if observe is not None:
                 observe(b, "h1", h)
-            ops.linear(h, b["qkv_w" + q8], b["qkv_b"], out=qkv, colscale=s.get("qkv_cs"), headmajor=hm)
-            ops.attention(qkv, ao, B, N, heads, hd, out_scale=sp.get("s_ao"), headmajor=self.headmajor)
+            if fused:
+                if check:
+                    ops.linear(h, b["qkv_w"], b["qkv_b"], out=qkv_ref, tile=14)
+                    ops.attention(qkv_ref, ao_ref, B, N, heads, hd)
+                ops.qkv_attention(h, b["qkv_w_hm"], b["qkv_b_hm"], ao, B, heads)
+                if check:
+                    differ += (ao.view(torch.int16) != ao_ref.view(torch.int16)).sum()
+            else:
+                ops.linear(h, b["qkv_w" + q8], b["qkv_b"], out=qkv, colscale=s.get("qkv_cs"), headmajor=hm)
+                ops.attention(qkv, ao, B, N, heads, hd, out_scale=sp.get("s_ao"), headmajor=self.headmajor)
             if observe is not None:
                 observe(b, "ao", ao)
             ops.linear(ao, b["proj_w" + p8], b["proj_b"], out=xres, residual=xres, colscale=sp.get("proj_cs"))
@@ -238,6 +281,12 @@ class VitPlan:
             ops.linear(hid, b["fc2_w" + q8], b["fc2_b"], out=xres, residual=xres, colscale=s.get("fc2_cs"))
         if observe is None:
             ops.layernorm(xres, self.nw, self.nb, self.neps, bufs["feats"])
+        if check:
+            n = int(differ)
+            if n:
+                raise _lib.HipExtensionError(f"qkv_attention: {n} output elements differ from linear (tile 14) + attention "
+                                             f"over {len(self.blocks)} blocks (B={B}, heads={heads}, C={self.C})")
+            self.qkv_checked = True
 
     def _calibrate_fp8(self, x, B, bufs, margin: float = None):
         """One bf16 pass over the batch (the row-layout walk with an observer) recording amax of the four quantised

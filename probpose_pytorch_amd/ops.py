@@ -225,6 +225,33 @@ def attention(qkv, out, B, N, heads, hd, out_scale=None, headmajor=False):
     return out
 
 
+def pack_qkv_headmajor(qkv_w, qkv_b, heads):
+    """qkv.weight [3C, C] / qkv.bias [3C] -> (w_hm [heads*192, C], b_hm [heads*192]) for ``qkv_attention``: row
+    192 h + 64 t + d is row t C + 64 h + d of the original (t = 0, 1, 2 for q, k, v; head_dim 64), so the q, k and v
+    rows of one head are one contiguous panel of 192 rows."""
+    C = qkv_w.shape[1]
+    if qkv_w.shape[0] != 3 * C or C != 64 * heads:
+        raise ValueError(f"qkv.weight {tuple(qkv_w.shape)} is not [3C, C] with C = 64 * heads (heads = {heads})")
+    w_hm = qkv_w.reshape(3, heads, 64, C).permute(1, 0, 2, 3).reshape(3 * C, C).contiguous()
+    b_hm = qkv_b.reshape(3, heads, 64).permute(1, 0, 2).reshape(3 * C).contiguous()
+    return w_hm, b_hm
+
+
+def qkv_attention(h, w_hm, b_hm, out, B, heads):
+    """out [B*192, C] = attention(h @ qkv.weight^T + qkv.bias) per crop of 192 tokens and head of 64 dims, in one launch
+    (pp_qkv_attention_bf16); w_hm / b_hm from ``pack_qkv_headmajor``.  q, k and v are never written to memory."""
+    M, C = h.shape
+    if h.dtype != torch.bfloat16 or w_hm.dtype != torch.bfloat16 or out.dtype != torch.bfloat16 or \
+            b_hm.dtype != torch.float32:
+        raise TypeError("qkv_attention: h, w_hm and out are bf16, b_hm is f32")
+    if M != B * 192 or tuple(w_hm.shape) != (heads * 192, C) or b_hm.numel() != heads * 192 or h.stride(0) != C or \
+            out.stride(0) != C or not w_hm.is_contiguous():
+        raise ValueError("qkv_attention: h / out [B*192, C] and w_hm [heads*192, C] contiguous, b_hm [heads*192]")
+    _run("qkv_attention", 2.0 * M * 3 * C * C + 4.0 * B * heads * 192 * 192 * 64, "pp_qkv_attention_bf16", h, w_hm,
+         b_hm, out, B, heads, C)
+    return out
+
+
 def patchify(x, out, patch):
     B, _, H, W = x.shape
     _lib.launch("pp_patchify", x, out, B, H, W, patch, dtype_code(out.dtype))
