@@ -82,40 +82,47 @@ __device__ __forceinline__ void att_wait_barrier() {
   asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(PENDING) : "memory");
 }
 
-// ---- the block body as device functions, statement for statement that of attention_mfma_kernel and
-// attention_stream_kernel below; qkv_attention_kernel is built from them.  The two older kernels keep their in-line
-// copies: calling these helpers from them changes their code (profiles/device_helpers_refactor_variants.txt: operands
-// commuted, another schedule, and at the 168-register limit of three workgroups per CU a growing private segment), which
-// needs an A/B of every attention form before it may go in.  One block of KBT key tiles against a wave's QT query
-// tiles.  Ks / Vs: the K / V images in LDS ([rows][HD] bf16, chunks swizzled by
-// AttGeom<HD>::swz), the block's first key at LDS row `row0`; lane = (lrow, g).
-//
-// S^T block = K_block Q^T : sacc[kt][t] rows = keys 16 kt + 4g + r of the block, col = query.  MASK: keys >= N (global
-// key of the block's first row: key0) start at -inf.  after_tile(kt) runs behind key tile kt's MFMAs (the one-shot
-// kernel requests the rest of K / V from there).
-template <int HD, int QT, int KBT, bool MASK, typename F>
-__device__ __forceinline__ void att_scores(const char *Ks, int row0, int key0, int N,
-                                           const uint4 (&qf)[QT][AttGeom<HD>::KS], f32x4 (&sacc)[KBT][QT], int lrow,
-                                           int g, F after_tile) {
+// ---- the block body and the epilogue as device functions.  attention_mfma_kernel and qkv_attention_kernel are built
+// from them: between these two (training / fp8 and the benchmark's inference path) every statement exists once.
+// attention_stream_kernel below still carries its own in-line copy of the same statements: with the helpers its forms
+// missed the parent's times by more than the parent-against-parent spread, and two of the forms tried changed output
+// bits at one shape (profiles/attention_one_body_ab.txt), so it is left exactly as it was.  A helper that takes a functor
+// (an after_tile hook for the late DMA requests) cost attention_mfma_kernel<32, false> its fourth wave per SIMD; the
+// per-key-tile helper below, with the kernel's own loop around it, does not (profiles/attention_one_body_resources.txt).
+// One block of KBT key tiles against a wave's QT query tiles.  Ks / Vs: the K / V images in LDS ([rows][HD] bf16, chunks
+// swizzled by AttGeom<HD>::swz); lane = (lrow, g).
+
+// start of the online softmax: running max -inf, partial sum and output accumulator zero
+template <int DT, int QT>
+__device__ __forceinline__ void att_init(float (&m_run)[QT], float (&l_run)[QT], f32x4 (&oacc)[DT][QT]) {
+#pragma unroll
+  for (int t = 0; t < QT; ++t) {
+    m_run[t] = -__builtin_inff();
+    l_run[t] = 0.f;
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt) oacc[dt][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+}
+
+// one key tile of S^T = K Q^T : sacc[t] rows = keys key0 + 4g + r, col = query of tile t.  row0: the tile's first LDS row,
+// key0: its global key.  MASK: keys >= N start at -inf.
+template <int HD, int QT, bool MASK>
+__device__ __forceinline__ void att_score_tile(const char *Ks, int row0, int key0, int N,
+                                               const uint4 (&qf)[QT][AttGeom<HD>::KS], f32x4 (&sacc)[QT], int lrow, int g) {
   using G = AttGeom<HD>;
+  const f32x4 init = MASK ? att_mask_init(key0 + g * 4, N) : f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-  for (int kt = 0; kt < KBT; ++kt) {
-    const f32x4 init = MASK ? att_mask_init(key0 + kt * 16 + g * 4, N) : f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int t = 0; t < QT; ++t) sacc[t] = init;
+  const int r = row0 + lrow;
 #pragma unroll
-    for (int t = 0; t < QT; ++t) sacc[kt][t] = init;
-    const int r = row0 + kt * 16 + lrow;
+  for (int s = 0; s < G::KS; ++s) {
+    uint4 kf = make_uint4(0, 0, 0, 0);
+    if (s < G::KS - 1 || g < G::KLIVE)
+      kf = *reinterpret_cast<const uint4 *>(Ks + r * G::KROW + (G::swz(r, 4 * s + g) << 4));
 #pragma unroll
-    for (int s = 0; s < G::KS; ++s) {
-      uint4 kf = make_uint4(0, 0, 0, 0);
-      if (s < G::KS - 1 || g < G::KLIVE)
-        kf = *reinterpret_cast<const uint4 *>(Ks + r * G::KROW + (G::swz(r, 4 * s + g) << 4));
-#pragma unroll
-      for (int t = 0; t < QT; ++t)
-        sacc[kt][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8 *>(&kf),
-                                                              *reinterpret_cast<const bf16x8 *>(&qf[t][s]),
-                                                              sacc[kt][t], 0, 0, 0);
-    }
-    after_tile(kt);
+    for (int t = 0; t < QT; ++t)
+      sacc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8 *>(&kf),
+                                                        *reinterpret_cast<const bf16x8 *>(&qf[t][s]), sacc[t], 0, 0, 0);
   }
 }
 
@@ -205,42 +212,81 @@ __device__ __forceinline__ void att_pv(const char *Vs, int row0, const f32x4 (&s
   }
 }
 
-// head_dim 64 and no row guards: query tile t of a wave leaves as whole 128-byte lines.  A head's output row is ONE
-// aligned 128-byte line.  What a store costs is the lines it touches (tools/ubench/store_bw.hip), and 8 bytes per lane
-// is 16 rows x 32 B = 16 lines per 512 B.  As in gemm_quad_stream_kernel: two v_permlane16_swap_b32 per pair of dim
-// tiles give a lane 8 consecutive dims, rows lrow / lrow ^ 1 then trade halves by DPP so that one 16-byte store holds
-// the whole line of 8 rows: 2 stores of 8 lines per query tile instead of 4 stores of 16.  head_q: the head's 64
-// columns of output row q (the lane's own query; every lane takes part).
-template <int QT>
-__device__ __forceinline__ void att_store_lines64(bf16_t *head_rows, int q, int C, const f32x4 (&oacc)[4][QT], int t,
-                                                  float inv_l, int lrow, int g) {
-  unsigned w[8];
+// v in a register of its own, which the compiler cannot trace back.  The one-shot kernel's epilogue forms its query rows
+// from it: otherwise the rows computed for the Q loads are kept alive across both key blocks, one register pair per
+// query tile, and attention_mfma_kernel<64, false> at the 168-register limit spills exactly those
+__device__ __forceinline__ int att_fresh(int v) {
+  asm volatile("" : "+v"(v));
+  return v;
+}
+
+// the softmax denominator of a query: the four lanes of its column each hold a partial sum
+__device__ __forceinline__ float att_inv_l(float l) {
+  l += __shfl_xor(l, 16, 64);
+  l += __shfl_xor(l, 32, 64);
+  return 1.0f / l;
+}
+
+// the bf16 store of query tile t, 8 bytes per lane (dims 16 dt + 4 g .. + 3 per dim tile); orow: the query's head row
+template <int DT, int QT>
+__device__ __forceinline__ void att_store8(bf16_t *orow, const f32x4 (&oacc)[DT][QT], int t, float inv_l, int g) {
 #pragma unroll
-  for (int dt = 0; dt < 4; ++dt) {
+  for (int dt = 0; dt < DT; ++dt) {
+    uint2 pk;
+    pk.x = pack_bf16x2(oacc[dt][t][0] * inv_l, oacc[dt][t][1] * inv_l);
+    pk.y = pack_bf16x2(oacc[dt][t][2] * inv_l, oacc[dt][t][3] * inv_l);
+    *reinterpret_cast<uint2 *>(orow + dt * 16 + g * 4) = pk;
+  }
+}
+
+// the bf16 store of query tile t, 16 bytes per lane (head_dim 64 / 80).  What a store costs is the 128-byte lines it
+// touches (tools/ubench/store_bw.hip): 8 bytes per lane is 16 rows x 32 B = 16 lines per 512 B.  As in
+// gemm_quad_stream_kernel: two v_permlane16_swap_b32 per pair of dim tiles give a lane 8 consecutive dims (64 B per row
+// and store); where there are two pairs, rows lrow / lrow ^ 1 trade one each by DPP so that a store holds 128 contiguous
+// bytes of 8 rows -- at head_dim 64 a head's output row is ONE aligned 128-byte line: 2 stores of 8 lines per query tile
+// instead of 4 stores of 16.  head0: the head's columns of the crop's row 0; q: the lane's own query.  Every lane takes
+// part in the exchanges: the exchanged chunks belong to rows q & ~1 and q | 1.  GUARD: rows >= N hold garbage and are
+// not stored.
+template <int HD, bool GUARD, int QT>
+__device__ __forceinline__ void att_store16(bf16_t *head0, int q, int C, int N, const f32x4 (&oacc)[AttGeom<HD>::DT][QT],
+                                            int t, float inv_l, int lrow, int g) {
+  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+  constexpr int DT = AttGeom<HD>::DT;
+  constexpr int NP = DT / 2;                  // pairs of dim tiles
+  static_assert(NP >= 2, "head_dim 32 keeps the 8-byte store");
+  unsigned w[2 * DT];
+#pragma unroll
+  for (int dt = 0; dt < DT; ++dt) {
     w[2 * dt] = pack_bf16x2(oacc[dt][t][0] * inv_l, oacc[dt][t][1] * inv_l);
     w[2 * dt + 1] = pack_bf16x2(oacc[dt][t][2] * inv_l, oacc[dt][t][3] * inv_l);
   }
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-  u32x4 PQ[2];
+  u32x4 ch[NP];
 #pragma unroll
-  for (int jp = 0; jp < 2; ++jp) {       // dim tiles 2 jp, 2 jp + 1: even g -> dims 4 g .. + 7 of tile 2 jp, odd g -> of tile 2 jp + 1
+  for (int jp = 0; jp < NP; ++jp) {       // even g: dims 4 g .. + 7 of tile 2 jp; odd g: dims 4 (g - 1) .. + 7 of tile 2 jp + 1
     const auto r0 = __builtin_amdgcn_permlane16_swap(w[4 * jp], w[4 * jp + 2], false, false);
     const auto r1 = __builtin_amdgcn_permlane16_swap(w[4 * jp + 1], w[4 * jp + 3], false, false);
-    PQ[jp] = u32x4{r0[0], r1[0], r0[1], r1[1]};
+    ch[jp] = u32x4{r0[0], r1[0], r0[1], r1[1]};
   }
   const bool odd = (lrow & 1) != 0;
-  u32x4 X, Y;
+  const int lane_dim = (g & 1) ? 16 + (g - 1) * 4 : g * 4;
 #pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const unsigned give = odd ? PQ[0][e] : PQ[1][e];                                   // what lane lrow ^ 1 needs
-    const unsigned got = (unsigned)__builtin_amdgcn_mov_dpp((int)give, 0xB1, 0xF, 0xF, true);   // quad_perm [1, 0, 3, 2]
-    X[e] = odd ? got : PQ[0][e];       // the even row: dims 0 .. 31 from the even lane, 32 .. 63 from the odd lane
-    Y[e] = odd ? PQ[1][e] : got;       // the odd row
+  for (int pp = 0; pp < NP / 2; ++pp) {
+    u32x4 X, Y;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const unsigned give = odd ? ch[2 * pp][e] : ch[2 * pp + 1][e];                     // what lane lrow ^ 1 needs
+      const unsigned got = (unsigned)__builtin_amdgcn_mov_dpp((int)give, 0xB1, 0xF, 0xF, true);   // quad_perm [1, 0, 3, 2]
+      X[e] = odd ? got : ch[2 * pp][e];       // the even row: the first 32 dims from the even lane, the next 32 from the odd lane
+      Y[e] = odd ? ch[2 * pp + 1][e] : got;   // the odd row
+    }
+    const int dim = (2 * pp + (odd ? 1 : 0)) * 32 + lane_dim;
+    if (!GUARD || (q & ~1) < N) *reinterpret_cast<u32x4 *>(head0 + (size_t)(q & ~1) * C + dim) = X;
+    if (!GUARD || (q | 1) < N) *reinterpret_cast<u32x4 *>(head0 + (size_t)(q | 1) * C + dim) = Y;
   }
-  const int lane_dim = ((g & 1) ? 16 + (g - 1) * 4 : g * 4) + (odd ? 32 : 0);
-  bf16_t *even_row = head_rows + (size_t)(q & ~1) * C + lane_dim;
-  *reinterpret_cast<u32x4 *>(even_row) = X;
-  *reinterpret_cast<u32x4 *>(even_row + C) = Y;
+  if (!GUARD || q < N) {
+    if constexpr (NP & 1) *reinterpret_cast<u32x4 *>(head0 + (size_t)q * C + (NP - 1) * 32 + lane_dim) = ch[NP - 1];
+    if constexpr (DT & 1) *reinterpret_cast<uint2 *>(head0 + (size_t)q * C + (DT - 1) * 16 + g * 4) = uint2{w[2 * DT - 2], w[2 * DT - 1]};
+  }
 }
 
 // The staging is issued as Q, then groups of 12 one-KiB pieces (3 per wave) in the order the products consume them
@@ -310,33 +356,15 @@ __global__ __launch_bounds__(256, 3) void attention_mfma_kernel(const bf16_t *__
   constexpr int KB_TILES = AT_NT / 2;  // 6 key tiles per block
   float m_run[AT_QT], l_run[AT_QT];
   f32x4 oacc[G::DT][AT_QT];
-#pragma unroll
-  for (int t = 0; t < AT_QT; ++t) {
-    m_run[t] = -__builtin_inff();
-    l_run[t] = 0.f;
-#pragma unroll
-    for (int dt = 0; dt < G::DT; ++dt) oacc[dt][t] = f32x4{0.f, 0.f, 0.f, 0.f};
-  }
+  att_init(m_run, l_run, oacc);
 #pragma unroll
   for (int kb = 0; kb < 2; ++kb) {
     if (kb == 1) att_wait_barrier<(AT_HD == 64) ? 3 : 0>();        // K (hd 32: K and V) of block 1
-    // S^T block = K_block Q^T : sacc[kt][t] rows = keys 96*kb + 16*kt + 4g + r, col = query
     f32x4 sacc[KB_TILES][AT_QT];
 #pragma unroll
     for (int kt = 0; kt < KB_TILES; ++kt) {
-      const f32x4 init = FULL ? f32x4{0.f, 0.f, 0.f, 0.f} : att_mask_init((kb * KB_TILES + kt) * 16 + g * 4, N);
-#pragma unroll
-      for (int t = 0; t < AT_QT; ++t) sacc[kt][t] = init;
-      const int r = (kb * KB_TILES + kt) * 16 + lrow;
-#pragma unroll
-      for (int s = 0; s < G::KS; ++s) {
-        const uint4 kf = *reinterpret_cast<const uint4 *>(Ks + r * AT_KROW + (G::swz(r, 4 * s + g) << 4));
-#pragma unroll
-        for (int t = 0; t < AT_QT; ++t)
-          sacc[kt][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8 *>(&kf),
-                                                                *reinterpret_cast<const bf16x8 *>(&qf[t][s]),
-                                                                sacc[kt][t], 0, 0, 0);
-      }
+      const int key0 = (kb * KB_TILES + kt) * 16;
+      att_score_tile<AT_HD, AT_QT, !FULL>(Ks, key0, key0, N, qf, sacc[kt], lrow, g);
       // the rest of K / V is requested here, spread over the first product, so that no wave sits in the (memory-
       // throttled) issue of all 18 loads before it computes
       if (kb == 0) {
@@ -344,97 +372,21 @@ __global__ __launch_bounds__(256, 3) void attention_mfma_kernel(const bf16_t *__
         for (int i = kt * NLATE / KB_TILES; i < (kt + 1) * NLATE / KB_TILES; ++i) issue_piece(1 + i / 3, i % 3);
       }
     }
-    // online softmax over this block's keys, per query column.  VALU diet (this phase, not the MFMAs,
-    // bounds the kernel): padded keys are masked through the accumulator init (below), scores are
-    // pre-scaled by c = log2(e)/sqrt(hd) so each probability is one FMA + one raw v_exp_f32.
-#pragma unroll
-    for (int t = 0; t < AT_QT; ++t) {
-      float mb = sacc[0][t][0];
-#pragma unroll
-      for (int kt = 0; kt < KB_TILES; ++kt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) mb = fmaxf(mb, sacc[kt][t][r]);
-      mb = fmaxf(mb, __shfl_xor(mb, 16, 64));
-      mb = fmaxf(mb, __shfl_xor(mb, 32, 64));
-      const float m_new = fmaxf(m_run[t], mb * scale_log2e);   // running max of the SCALED scores; finite
-      const float alpha = __builtin_amdgcn_exp2f(m_run[t] - m_new);  // block 0: exp2(-inf) = 0
-      // two scores per instruction: v_pk_fma_f32 for the exponent, v_pk_add_f32 for the partial sums
-      att_f32x2 l2 = {0.f, 0.f};
-      const att_f32x2 c2 = {scale_log2e, scale_log2e}, nm2 = {-m_new, -m_new};
-#pragma unroll
-      for (int kt = 0; kt < KB_TILES; ++kt)
-#pragma unroll
-        for (int r = 0; r < 4; r += 2) {
-          const att_f32x2 e = __builtin_elementwise_fma((att_f32x2){sacc[kt][t][r], sacc[kt][t][r + 1]}, c2, nm2);
-          const att_f32x2 pv = {__builtin_amdgcn_exp2f(e.x), __builtin_amdgcn_exp2f(e.y)};
-          sacc[kt][t][r] = pv.x;
-          sacc[kt][t][r + 1] = pv.y;
-          l2 += pv;
-        }
-      const float l = l2.x + l2.y;
-      l_run[t] = l_run[t] * alpha + l;
-      m_run[t] = m_new;
-#pragma unroll
-      for (int dt = 0; dt < G::DT; ++dt) {
-        oacc[dt][t][0] *= alpha; oacc[dt][t][1] *= alpha; oacc[dt][t][2] *= alpha; oacc[dt][t][3] *= alpha;
-      }
-    }
-    // O^T += V_block^T P_block^T : rows = dims 16*dt + 4g + r, col = query
+    att_softmax<G::DT, AT_QT, KB_TILES>(sacc, m_run, l_run, oacc, scale_log2e);
     if constexpr (AT_HD == 64) {
       if (kb == 0) att_wait_barrier<6>(); else att_wait_barrier<0>();   // V of this block
     }
-#pragma unroll
-    for (int u = 0; u < KB_TILES / 2; ++u) {  // 32 keys per step
-      uint4 pf[AT_QT];
-#pragma unroll
-      for (int t = 0; t < AT_QT; ++t) {
-        pf[t].x = pack_bf16x2(sacc[2 * u][t][0], sacc[2 * u][t][1]);
-        pf[t].y = pack_bf16x2(sacc[2 * u][t][2], sacc[2 * u][t][3]);
-        pf[t].z = pack_bf16x2(sacc[2 * u + 1][t][0], sacc[2 * u + 1][t][1]);
-        pf[t].w = pack_bf16x2(sacc[2 * u + 1][t][2], sacc[2 * u + 1][t][3]);
-      }
-#pragma unroll
-      for (int dt = 0; dt < G::DT; ++dt) {
-        // A operand = V^T fragment: lane (dim = lrow, g) needs keys {4g..4g+3} and {16+4g..16+4g+3}
-        // of this 32-key step for its dim.  Each 16-lane group g issues one transposing read per key
-        // quartet: lane 4q+p of the group addresses row (key) q, dims 4p..4p+3 of the 16-dim block;
-        // lane i receives dim i of the 4 keys.  (EXEC is all ones here; addresses are 8-B aligned.)
-        const int tq = lrow >> 2, tp = lrow & 3;
-        const int key0 = kb * (KB_TILES * 16) + 32 * u + 4 * g + tq;
-        const int ch = 2 * dt + (tp >> 1);
-        const int a0 = key0 * AT_KROW + (G::swz(key0, ch) << 4) + (tp & 1) * 8;
-        const int key1 = key0 + 16;
-        const int a1 = key1 * AT_KROW + (G::swz(key1, ch) << 4) + (tp & 1) * 8;
-        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-            (__attribute__((address_space(3))) s16x4 *)(Vs + a0));
-        const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-            (__attribute__((address_space(3))) s16x4 *)(Vs + a1));
-        uint4 vf;
-        vf.x = (unsigned)(unsigned short)lo[0] | ((unsigned)(unsigned short)lo[1] << 16);
-        vf.y = (unsigned)(unsigned short)lo[2] | ((unsigned)(unsigned short)lo[3] << 16);
-        vf.z = (unsigned)(unsigned short)hi[0] | ((unsigned)(unsigned short)hi[1] << 16);
-        vf.w = (unsigned)(unsigned short)hi[2] | ((unsigned)(unsigned short)hi[3] << 16);
-#pragma unroll
-        for (int t = 0; t < AT_QT; ++t)
-          oacc[dt][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8 *>(&vf),
-                                                                *reinterpret_cast<const bf16x8 *>(&pf[t]),
-                                                                oacc[dt][t], 0, 0, 0);
-      }
-    }
+    att_pv<AT_HD, AT_QT, KB_TILES>(Vs, kb * (KB_TILES * 16), sacc, oacc, lrow, g);
   }
+  const int lrow_e = att_fresh(lrow);       // the epilogue's own copy: see att_fresh
   float inv_l[AT_QT];
 #pragma unroll
-  for (int t = 0; t < AT_QT; ++t) {
-    float l = l_run[t];
-    l += __shfl_xor(l, 16, 64);
-    l += __shfl_xor(l, 32, 64);
-    inv_l[t] = 1.0f / l;
-  }
+  for (int t = 0; t < AT_QT; ++t) inv_l[t] = att_inv_l(l_run[t]);
 
-  // ---- store: lane holds 4 consecutive dims of one query -> 8-byte stores
+  // ---- store
 #pragma unroll
   for (int t = 0; t < AT_QT; ++t) {
-    const int q = q0 + t * 16 + lrow;
+    const int q = q0 + t * 16 + lrow_e;
     if (!FULL && q >= N) continue;
     if (fp8_inv_scale > 0.f) {   // out is an e4m3 byte tensor [B*N, C]
       unsigned char *orow8 = reinterpret_cast<unsigned char *>(out) + ((size_t)b * N + q) * C + h * AT_HD;
@@ -442,49 +394,10 @@ __global__ __launch_bounds__(256, 3) void attention_mfma_kernel(const bf16_t *__
       att_store_fp8(orow8, oacc, t, sc, g);
       continue;
     }
-    bf16_t *orow = out + ((size_t)b * N + q) * C + h * AT_HD;
-    if constexpr (G::DT == 4 && FULL) {
-      // head_dim 64: a head's output row is ONE aligned 128-byte line.  What a store costs is the lines it touches
-      // (tools/ubench/store_bw.hip), and 8 bytes per lane is 16 rows x 32 B = 16 lines per 512 B.  As in
-      // gemm_quad_stream_kernel: two v_permlane16_swap_b32 per pair of dim tiles give a lane 8 consecutive dims, rows
-      // lrow / lrow ^ 1 then trade halves by DPP so that one 16-byte store holds the whole line of 8 rows: 2 stores of
-      // 8 lines per query tile instead of 4 stores of 16.
-      unsigned w[8];
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) {
-        w[2 * dt] = pack_bf16x2(oacc[dt][t][0] * inv_l[t], oacc[dt][t][1] * inv_l[t]);
-        w[2 * dt + 1] = pack_bf16x2(oacc[dt][t][2] * inv_l[t], oacc[dt][t][3] * inv_l[t]);
-      }
-      typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-      u32x4 PQ[2];
-#pragma unroll
-      for (int jp = 0; jp < 2; ++jp) {       // dim tiles 2 jp, 2 jp + 1: even g -> dims 4 g .. + 7 of tile 2 jp, odd g -> of tile 2 jp + 1
-        const auto r0 = __builtin_amdgcn_permlane16_swap(w[4 * jp], w[4 * jp + 2], false, false);
-        const auto r1 = __builtin_amdgcn_permlane16_swap(w[4 * jp + 1], w[4 * jp + 3], false, false);
-        PQ[jp] = u32x4{r0[0], r1[0], r0[1], r1[1]};
-      }
-      const bool odd = (lrow & 1) != 0;
-      u32x4 X, Y;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const unsigned give = odd ? PQ[0][e] : PQ[1][e];                                   // what lane lrow ^ 1 needs
-        const unsigned got = (unsigned)__builtin_amdgcn_mov_dpp((int)give, 0xB1, 0xF, 0xF, true);   // quad_perm [1, 0, 3, 2]
-        X[e] = odd ? got : PQ[0][e];       // the even row: dims 0 .. 31 from the even lane, 32 .. 63 from the odd lane
-        Y[e] = odd ? PQ[1][e] : got;       // the odd row
-      }
-      const int lane_dim = ((g & 1) ? 16 + (g - 1) * 4 : g * 4) + (odd ? 32 : 0);
-      bf16_t *even_row = out + ((size_t)b * N + (q & ~1)) * C + h * AT_HD + lane_dim;
-      *reinterpret_cast<u32x4 *>(even_row) = X;
-      *reinterpret_cast<u32x4 *>(even_row + C) = Y;
-      continue;
-    }
-#pragma unroll
-    for (int dt = 0; dt < G::DT; ++dt) {
-      uint2 pk;
-      pk.x = pack_bf16x2(oacc[dt][t][0] * inv_l[t], oacc[dt][t][1] * inv_l[t]);
-      pk.y = pack_bf16x2(oacc[dt][t][2] * inv_l[t], oacc[dt][t][3] * inv_l[t]);
-      *reinterpret_cast<uint2 *>(orow + dt * 16 + g * 4) = pk;
-    }
+    if constexpr (G::DT == 4 && FULL)       // whole 128-byte lines, 16 bytes per lane
+      att_store16<AT_HD, false>(out + (size_t)b * N * C + h * AT_HD, q, C, N, oacc, t, inv_l[t], lrow_e, g);
+    else
+      att_store8(out + ((size_t)b * N + q) * C + h * AT_HD, oacc, t, inv_l[t], g);
   }
 }
 
@@ -846,20 +759,17 @@ __global__ __launch_bounds__(256, 2) void qkv_attention_kernel(const char *__res
   constexpr int KB_TILES = AT_NT / 2;
   float m_run[AT_QT], l_run[AT_QT];
   f32x4 oacc[G::DT][AT_QT];
-#pragma unroll
-  for (int t = 0; t < AT_QT; ++t) {
-    m_run[t] = -__builtin_inff();
-    l_run[t] = 0.f;
-#pragma unroll
-    for (int dt = 0; dt < G::DT; ++dt) oacc[dt][t] = f32x4{0.f, 0.f, 0.f, 0.f};
-  }
+  att_init(m_run, l_run, oacc);
 #pragma unroll
   for (int kb = 0; kb < 2; ++kb) {
     f32x4 sacc[KB_TILES][AT_QT];
     // the scheduling fences stand where attention_mfma_kernel has its counted waits: without them the K and V
     // fragment reads of both blocks are hoisted to the front until the register file is full (68 bytes of scratch)
-    att_scores<64, AT_QT, KB_TILES, false>(Ks, kb * (KB_TILES * 16), kb * (KB_TILES * 16), AT_NMAX, qf, sacc, lrow, g,
-                                           [](int) {});
+#pragma unroll
+    for (int kt = 0; kt < KB_TILES; ++kt) {
+      const int key0 = (kb * KB_TILES + kt) * 16;
+      att_score_tile<64, AT_QT, false>(Ks, key0, key0, AT_NMAX, qf, sacc[kt], lrow, g);
+    }
     __builtin_amdgcn_sched_barrier(0);
     att_softmax<G::DT, AT_QT, KB_TILES>(sacc, m_run, l_run, oacc, scale_log2e);
     __builtin_amdgcn_sched_barrier(0);
@@ -867,12 +777,9 @@ __global__ __launch_bounds__(256, 2) void qkv_attention_kernel(const char *__res
     __builtin_amdgcn_sched_barrier(0);
   }
 #pragma unroll
-  for (int t = 0; t < AT_QT; ++t) {
-    float l = l_run[t];
-    l += __shfl_xor(l, 16, 64);
-    l += __shfl_xor(l, 32, 64);
-    att_store_lines64<AT_QT>(out + (size_t)b * AT_NMAX * C + h * 64, q0 + t * 16 + lrow, C, oacc, t, 1.0f / l, lrow, g);
-  }
+  for (int t = 0; t < AT_QT; ++t)
+    att_store16<64, false>(out + (size_t)b * AT_NMAX * C + h * 64, q0 + t * 16 + lrow, C, AT_NMAX, oacc, t,
+                           att_inv_l(l_run[t]), lrow, g);
 }
 
 }  // namespace pp

@@ -2,16 +2,30 @@
 """A/B of the qkv projection + attention of one ViT block (bf16, N = 192, head_dim 64): ops.linear on the autotuned tile
 followed by ops.attention, against the one launch of ops.qkv_attention.  One process, random h and weights, HIP events,
 7 interleaved rounds of 10 launches, medians; also whether the two outputs are bit-equal.
-usage: qkv_attention_ab.py [> profiles/qkv_attention_ab.txt]"""
+With two builds named (`shipped`, or a lib/exp/*.so of tools/build_exp.sh) it times pp_qkv_attention_bf16 of the one
+against the other instead, same method, and checks that their outputs are the same bits; two builds of one source give
+the spread.
+usage: qkv_attention_ab.py [<build a> <build b>] [> profiles/qkv_attention_ab.txt]"""
+import ctypes
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
-from probpose_pytorch_amd import ops
+from probpose_pytorch_amd import _lib, ops
 
 ROUNDS, LAUNCHES = 7, 10
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BUILDS = sys.argv[1:3]
+if len(BUILDS) not in (0, 2) or len(set(BUILDS)) != len(BUILDS):
+    sys.exit(__doc__)
+
+
+def load(name):
+    L = ctypes.CDLL(_lib.LIB_PATH if name == "shipped" else os.path.join(ROOT, "probpose_pytorch_amd", "lib", "exp", name))
+    L.pp_qkv_attention_bf16.restype, L.pp_qkv_attention_bf16.argtypes = _lib._SIGNATURES["pp_qkv_attention_bf16"]
+    return L
 
 
 def timed(fn):
@@ -44,6 +58,24 @@ for name, B, heads in [("vit_b bs64", 64, 12), ("vit_l bs256", 256, 16)]:
     ops.AUTOTUNE = False
     tile = next(iter(ops._TUNE_CACHE.values()))
     ops._TUNE_CACHE.clear()
+    if BUILDS:
+        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        outs = {k: torch.zeros_like(out1) for k in BUILDS}
+        calls = {k: (lambda L=load(k), o=outs[k]: L.pp_qkv_attention_bf16(h.data_ptr(), w_hm.data_ptr(), b_hm.data_ptr(),
+                                                                            o.data_ptr(), B, heads, C, st)) for k in BUILDS}
+        assert all(c() == 0 for c in calls.values())
+        times = {k: [] for k in BUILDS}
+        for _ in range(ROUNDS):
+            for k, fn in calls.items():
+                times[k].append(timed(fn))
+        torch.cuda.synchronize()
+        same = torch.equal(*(o.view(torch.int16) for o in outs.values()))
+        print(f"{name}: B={B} heads={heads} C={C}, pp_qkv_attention_bf16")
+        for k, v in times.items():
+            print(f"  {k:22s} {median(v):8.2f}   (min {min(v):.2f}, max {max(v):.2f})")
+        a, b_ = (median(times[k]) for k in BUILDS)
+        print(f"  {BUILDS[1]} against {BUILDS[0]}: {b_ - a:+.2f} us ({(b_ / a - 1) * 100:+.2f} %); outputs bit-equal: {same}")
+        continue
     runs = {
         f"linear (tile {tile})": lambda: ops.linear(h, w, b, out=qkv, tile=tile),
         "attention": lambda: ops.attention(qkv, out2, B, N, heads, 64),
