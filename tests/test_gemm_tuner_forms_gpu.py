@@ -112,8 +112,9 @@ def _launch(ops, c, tile, template):
     return buf
 
 
-def _sweep_call(ops, c, forms, device):
-    """Launch every form on call c and compare each result with the float64 restatement: (accepted forms, failures)."""
+def _sweep_call(ops, c, forms, device, check=None):
+    """Launch every form on call c and compare each result with the float64 restatement: (accepted forms, failures).
+    check(tile, verdict, buffer from C on, written): a caller's further conditions; it may clear verdict.ok."""
     shape, odt, align = c["out_like"]
     esz = torch.empty((), dtype=odt).element_size()
     numel = 1
@@ -141,6 +142,8 @@ def _sweep_call(ops, c, forms, device):
         if not torch.equal(buf[:lead].view(bits), template[:lead].view(bits)):
             v.ok = False
             v.note += " (front guard written)"
+        if check is not None:
+            check(tile, v, buf[lead:], written)
         print(f"  {_name(c):64s} form {tile:2d}: {v}")
         if not v.ok:
             failures.append(f"{_name(c)} form {tile}: {v}")
