@@ -15,7 +15,7 @@ from typing import Dict, Optional, Sequence, Tuple
 
 import torch
 
-from . import _lib, ops, pack
+from . import _lib, head_calls, ops, pack
 from ._buffers import CaptureCache
 from .ops import EPI_GELU, EPI_OUT_F32, EPI_RELU
 
@@ -368,6 +368,7 @@ class HeadGeometry:
             ks = pool.kernel_size
             self.pools.append((int(ks), int(ks)) if isinstance(ks, int) else (int(ks[0]), int(ks[1])))
         self._tables = CaptureCache(8)      # batch sizes vary per frame in inference; captured entries stay
+        self.grad_tables = CaptureCache(64)  # the training backward's data-gradient tables (head_train.py)
 
     # gather/scatter tables depend on (B, h, w) only
     def _tables_for(self, B: int, h: int, w: int) -> dict:
@@ -479,9 +480,8 @@ class HeadPlan(HeadGeometry):
             return self._forward(feats, B, h, w)
 
     def _forward(self, feats: torch.Tensor, B: int, h: int, w: int):
-        dev, dt, C, K = self.device, self.dtype, self.C, self.K
+        dev, K = self.device, self.K
         tb = self._tables_for(B, h, w)
-        g = self.ws.get
         # ---- aux branches on a second HIP stream: after their first conv they are long-K GEMMs over a
         # few rows (M = B*16, B*4) that cannot fill 256 CUs; the independent deconvolution branch fills
         # the idle CUs meanwhile.  Fork/join by events, so the pair is graph-capturable.
@@ -493,88 +493,71 @@ class HeadPlan(HeadGeometry):
         aux_stream = torch.cuda.current_stream(dev) if SERIALIZE_HEAD else self._aux_stream
         aux_stream.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(aux_stream):
-            a, ah, aw = feats, h, w
-            for i, (p, (ro, _, _)) in enumerate(zip(self.pools, tb["aux"])):
-                M = B * ah * aw
+            self._aux_branch(feats, B, h, w, tb, aux)
+        self._heatmap_branch(feats, B, h, w, tb, heat)
+        # ---- join the aux-branch stream (forked above)
+        torch.cuda.current_stream(dev).wait_stream(aux_stream)
+        return (heat, *(aux[i].reshape(B, K, 1, 1) for i in range(4)))
+
+    def _aux_branch(self, feats, B, h, w, tb, aux):
+        dev, dt, C = self.device, self.dtype, self.C
+        g = self.ws.get
+        a, ah, aw = feats, h, w
+        for i, (p, (ro, _, _)) in enumerate(zip(self.pools, tb["aux"])):
+            M = B * ah * aw
+            kh, kw, oh, ow = pack.pool_out(ah, aw, p)
+            pooled = g(f"aux_pool{i}", (B * oh * ow, 4 * C), dt, dev)
+            split = head_calls.aux_split(i) if i > 0 and SPLITK_AUX else 1
+            if split > 1:
+                # rows leading ([split * M, 4C], partial s = rows [s * M, (s + 1) * M)): the workspace key does
+                # not hold M, so one allocation serves every batch size up to the largest seen
+                parts = g(f"aux_part{i}", (split * M, 4 * C), torch.float32, dev).view(split, M, 4 * C)
+                ops.gemm(a, self.aux_w[i], parts, **head_calls.aux_stage(M, C, split=split), rowoff=ro,
+                         epilogue=EPI_OUT_F32)
+                ops.maxpool_relu_sum(parts, self.aux_b[i].reshape(-1), pooled, B, ah, aw, 4 * C, kh, kw)
+            else:
                 conv = g(f"aux_conv{i}", (M, 4 * C), dt, dev)
-                if i == 0:
-                    ops.gemm(a, self.aux_w[0], conv, M=M, N=4 * C, Kd=9 * C, lda=C, ldw=9 * C, ldc=4 * C,
-                             bias=self.aux_b[0], rowoff=ro, seg_len=C)
-                    split = 1
-                else:
-                    # few rows (16 B, then 4 B) against K = 9 C: split the taps over workgroups when the plain launch
-                    # would leave most CUs idle behind 108 sequential K-tiles (S f32 partials, summed in the pooling)
-                    # The split is a property of the LAYER (3 for the first pooled stage, 9 from the second on), never
-                    # of the batch size: a crop's outputs stay bit-identical whatever batch it is computed in (the
-                    # partial-sum order would otherwise change with B).  At large batches the partials cost ~0.2 % of
-                    # the step.
-                    split = (3 if i == 1 else 9) if SPLITK_AUX else 1
-                    if split == 1:
-                        ops.gemm(a, self.aux_w[i], conv, M=M, N=C, Kd=9 * C, lda=4 * C, ldw=9 * C, ldc=4 * C,
-                                 bias=self.aux_b[i], rowoff=ro, seg_len=C, batch=4, strideA=C, strideW=C * 9 * C,
-                                 strideC=C, strideBias=C)
-                    else:
-                        # rows leading ([split * M, 4C], partial s = rows [s * M, (s + 1) * M)): the workspace key does
-                        # not hold M, so one allocation serves every batch size up to the largest seen
-                        parts = g(f"aux_part{i}", (split * M, 4 * C), torch.float32, dev).view(split, M, 4 * C)
-                        taps = 9 // split
-                        ops.gemm(a, self.aux_w[i], parts, M=M, N=C, Kd=taps * C, lda=4 * C, ldw=9 * C, ldc=4 * C,
-                                 rowoff=ro, seg_len=C, batch=4, strideA=C, strideW=C * 9 * C, strideC=C,
-                                 epilogue=EPI_OUT_F32, splitk=split, strideW_k=taps * C, strideRowoff_k=taps * M,
-                                 strideC_k=M * 4 * C)
-                kh, kw, oh, ow = pack.pool_out(ah, aw, p)
-                pooled = g(f"aux_pool{i}", (B * oh * ow, 4 * C), dt, dev)
-                if split > 1:
-                    ops.maxpool_relu_sum(parts, self.aux_b[i].reshape(-1), pooled, B, ah, aw, 4 * C, kh, kw)
-                else:
-                    ops.maxpool_relu(conv, pooled, B, ah, aw, 4 * C, kh, kw)
-                a, ah, aw = pooled, oh, ow
-            ops.aux_tail(a, self.tail_w, self.tail_b, aux, B, C, K)
-        # ---- heatmap branch
-        x, hh, ww, cin = feats, h, w, C
+                call = head_calls.aux_stage0(M, C) if i == 0 else head_calls.aux_stage(M, C)
+                ops.gemm(a, self.aux_w[i], conv, **call, bias=self.aux_b[i], rowoff=ro)
+                ops.maxpool_relu(conv, pooled, B, ah, aw, 4 * C, kh, kw)
+            a, ah, aw = pooled, oh, ow
+        ops.aux_tail(a, self.tail_w, self.tail_b, aux, B, C, self.K)
+
+    def _heatmap_branch(self, feats, B, h, w, tb, heat):
+        dev, dt, K = self.device, self.dtype, self.K
+        g = self.ws.get
+        x, hh, ww, cin = feats, h, w, self.C
         f = self.final
         clamp = self.normalize is None
         fused_final = final_done = False
         for li, (d, (ro, rm, _, _)) in enumerate(zip(self.deconvs, tb["deconv"])):
             M = B * hh * ww
-            last = li == len(self.deconvs) - 1
-            if (FUSE_FINAL and last and not self.convs and f is not None and dt == torch.bfloat16 and d["cout"] == 256
-                    and f["k"] == 1 and K <= 32):
+            ends = li == len(self.deconvs) - 1 and not self.convs
+            if (FUSE_FINAL and ends and f is not None and dt == torch.bfloat16 and d["cout"] == 256 and f["k"] == 1
+                    and K <= 32):
                 # the last deconvolution's epilogue applies the final 1x1 layer itself: its 256-channel output
                 # (100 MB at bs 64) is never stored, and the final-layer launch is gone
-                ops.gemm(x, d["w"], heat, M=M, N=256, Kd=4 * cin, lda=cin, ldw=4 * cin, ldc=256, bias=d["b"],
-                         rowoff=ro, seg_len=cin, out_rowmap=rm, batch=4, strideW=256 * 4 * cin, strideRowoff=4 * M,
-                         strideRowmap=M, epilogue=EPI_RELU,
-                         fuse_final=(f["w"], f["b"], K, 4 * hh * ww, self.temperature, clamp))
-                fused_final = True
-                hh, ww, cin = 2 * hh, 2 * ww, 256
-                break
-            if f is None and last and not self.convs:
+                out, fused_final = heat, True
+                tail = dict(fuse_final=(f["w"], f["b"], K, 4 * hh * ww, self.temperature, clamp))
+            elif f is None and ends:
                 # Identity final layer: this layer's ReLU'd outputs are the maps -> /T, clamp, NCHW store in its epilogue
-                ops.gemm(x, d["w"], heat, M=M, N=K, Kd=4 * cin, lda=cin, ldw=4 * cin, ldc=K, bias=d["b"], rowoff=ro,
-                         seg_len=cin, out_rowmap=rm, batch=4, strideW=K * 4 * cin, strideRowoff=4 * M, strideRowmap=M,
-                         strideBias=0, epilogue=EPI_RELU, heatmap=(K, 4 * hh * ww, self.temperature, clamp))
-                final_done = True
-                hh, ww, cin = 2 * hh, 2 * ww, K
-                break
-            out = g(f"deconv{li}", (4 * M, d["cout"]), dt, dev)
-            ops.gemm(x, d["w"], out, M=M, N=d["cout"], Kd=4 * cin, lda=cin, ldw=4 * cin, ldc=d["cout"],
-                     bias=d["b"], rowoff=ro, seg_len=cin, out_rowmap=rm, batch=4,
-                     strideW=d["cout"] * 4 * cin, strideRowoff=4 * M, strideRowmap=M, epilogue=EPI_RELU)
+                out, final_done = heat, True
+                tail = dict(heatmap=(K, 4 * hh * ww, self.temperature, clamp))
+            else:
+                out, tail = g(f"deconv{li}", (4 * M, d["cout"]), dt, dev), {}
+            ops.gemm(x, d["w"], out, **head_calls.deconv(M, cin, d["cout"]), bias=d["b"], rowoff=ro, out_rowmap=rm,
+                     epilogue=EPI_RELU, **tail)
             x, hh, ww, cin = out, 2 * hh, 2 * ww, d["cout"]
         for li, (c, ro) in enumerate(zip(self.convs, tb["conv"])):
             M = B * hh * ww
-            kk = c["k"] * c["k"]
             if f is None and li == len(self.convs) - 1:
-                ops.gemm(x, c["w"], heat, M=M, N=K, Kd=kk * cin, lda=cin, ldw=kk * cin, ldc=K, bias=c["b"], rowoff=ro,
-                         seg_len=cin, epilogue=EPI_RELU, heatmap=(K, hh * ww, self.temperature, clamp))
-                final_done = True
-                break
-            out = g(f"conv{li}", (M, c["cout"]), dt, dev)
-            ops.gemm(x, c["w"], out, M=M, N=c["cout"], Kd=kk * cin, lda=cin, ldw=kk * cin, ldc=c["cout"],
-                     bias=c["b"], rowoff=ro, seg_len=cin, epilogue=EPI_RELU)
+                out, final_done = heat, True
+                tail = dict(heatmap=(K, hh * ww, self.temperature, clamp))
+            else:
+                out, tail = g(f"conv{li}", (M, c["cout"]), dt, dev), {}
+            ops.gemm(x, c["w"], out, **head_calls.conv(M, cin, c["cout"], c["k"]), bias=c["b"], rowoff=ro,
+                     epilogue=EPI_RELU, **tail)
             x, cin = out, c["cout"]
-        M = B * hh * ww
         assert heat.shape == (B, K, hh, ww)
         if f is None and not final_done:
             # no deconv, no conv, no final layer: the maps are the input features themselves (degenerate but constructible)
@@ -588,15 +571,10 @@ class HeadPlan(HeadGeometry):
         elif f["k"] == 1 and final_heatmap_fits(cin, K, dt):
             ops.final_heatmap(x, f["w"], f["b"], heat, B, hh * ww, cin, K, self.temperature, clamp=clamp)
         else:
-            kk = f["k"] * f["k"]
-            ops.gemm(x, f["w"], heat, M=M, N=K, Kd=kk * cin, lda=cin, ldw=kk * cin, ldc=K, bias=f["b"],
-                     rowoff=tb["final"], seg_len=cin, heatmap=(K, hh * ww, self.temperature, clamp))
+            ops.gemm(x, f["w"], heat, **head_calls.conv(B * hh * ww, cin, K, f["k"]), bias=f["b"], rowoff=tb["final"],
+                     heatmap=(K, hh * ww, self.temperature, clamp))
         if not clamp:
             ops.sparsemax_rows(heat.view(B * K, hh * ww), self.normalize)
-        # ---- join the aux-branch stream (forked above)
-        torch.cuda.current_stream(dev).wait_stream(aux_stream)
-        return (heat, aux[0].reshape(B, K, 1, 1), aux[1].reshape(B, K, 1, 1), aux[2].reshape(B, K, 1, 1),
-                aux[3].reshape(B, K, 1, 1))
 
 
 def build_head_plan(head, dtype, device):

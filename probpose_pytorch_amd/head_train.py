@@ -10,16 +10,14 @@ rebuild of the eval ``HeadPlan``); the gather / scatter tables are ``engine.Head
 from __future__ import annotations
 
 import weakref
-from typing import Dict, List
+from typing import List
 
 import torch
 from torch import nn
 
-from . import _lib, engine, ops, pack
+from . import _lib, engine, head_calls, ops, pack
+from .head_calls import KTILE  # noqa: F401  (the heatmap gradient's channel pitch; tests read it here)
 from .ops import EPI_OUT_F32
-
-AUX_NAMES = engine.AUX_NAMES
-KTILE = 64         # the heatmap gradient's channel pitch is a whole number of pp_gemm K-tiles in both compute dtypes
 
 
 def check_trainable(head) -> None:
@@ -52,36 +50,18 @@ def head_parameters(head) -> List[nn.Parameter]:
     for i in range(0, len(layers), 3):
         ps += [layers[i].weight, layers[i + 1].weight, layers[i + 1].bias]
     ps += [head.final_layer.weight, head.final_layer.bias]
-    for name in AUX_NAMES:
+    for name in engine.AUX_NAMES:
         ps += list(getattr(head, name + "_layers").parameters())
     return ps
-
-
-class _Geometry(engine.HeadGeometry):
-    """The head's layer dimensions and tables, plus what only the backward reads: the deconvolution's parity index and
-    a cache of its data-gradient tables."""
-
-    def __init__(self, head, device):
-        super().__init__(head, device)
-        self._extra: Dict[tuple, object] = {}
-        self.KY, self.KX = (t.to(device) for t in pack.deconv_parity_index(4))
-
-    def extra(self, key, make):
-        t = self._extra.get(key)
-        if t is None:
-            if len(self._extra) >= 64:
-                self._extra.pop(next(iter(self._extra)))
-            t = self._extra[key] = make()
-        return t
 
 
 _GEOM: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()
 
 
-def _geometry(head, device) -> _Geometry:
+def _geometry(head, device) -> engine.HeadGeometry:
     g = _GEOM.get(head)
     if g is None or g.device != device:
-        g = _GEOM[head] = _Geometry(head, device)
+        g = _GEOM[head] = engine.HeadGeometry(head, device)
     return g
 
 
@@ -92,7 +72,10 @@ def _bn_stats(bn, y, M, Cc, gammas, betas, rms, rvs):
     dev = y.device
     st = torch.empty((4, Cc), dtype=torch.float32, device=dev)
     ws = torch.empty(ops.bn_workspace_bytes(M, Cc), dtype=torch.uint8, device=dev)
-    cat = (lambda ts: ts[0] if len(ts) == 1 else torch.cat(ts)) if gammas else None
+
+    def cat(ts):
+        return ts[0] if len(ts) == 1 else torch.cat(ts)
+
     gamma = cat([g.detach() for g in gammas]) if gammas[0] is not None else None
     beta = cat([b.detach() for b in betas]) if betas[0] is not None else None
     track = rms[0] is not None
@@ -100,12 +83,11 @@ def _bn_stats(bn, y, M, Cc, gammas, betas, rms, rvs):
     rv = cat(rvs) if track else None
     ops.bn_train_stats(y, M, Cc, gamma, beta, bn.eps, bn.momentum if track else 0.0, rm, rv, st[0], st[1], st[2],
                        st[3], ws)
-    if track:
-        if len(rms) > 1:
-            n = Cc // len(rms)
-            for i, (a, b) in enumerate(zip(rms, rvs)):
-                a.copy_(rm[i * n:(i + 1) * n])
-                b.copy_(rv[i * n:(i + 1) * n])
+    if track and len(rms) > 1:
+        n = Cc // len(rms)
+        for i, (a, b) in enumerate(zip(rms, rvs)):
+            a.copy_(rm[i * n:(i + 1) * n])
+            b.copy_(rv[i * n:(i + 1) * n])
     return st, gamma
 
 
@@ -155,12 +137,9 @@ class _HeadTrainFn(torch.autograd.Function):
             dc, bn = layers[3 * li], layers[3 * li + 1]
             cin, cout = d["cin"], d["cout"]
             M = B * hh * ww
-            wp = dc.weight.detach().permute(1, 2, 3, 0)[:, geo.KY, geo.KX, :].permute(1, 0, 2, 3)
-            wp = wp.reshape(4, cout, 4 * cin).to(dt).contiguous()
+            wp = pack.pack_deconv_parities(dc.weight.detach(), 4).to(dt).contiguous()
             y = torch.empty((4 * M, cout), dtype=torch.float32, device=dev)
-            ops.gemm(xin, wp, y, M=M, N=cout, Kd=4 * cin, lda=cin, ldw=4 * cin, ldc=cout, rowoff=ro, seg_len=cin,
-                     out_rowmap=rm, batch=4, strideW=cout * 4 * cin, strideRowoff=4 * M, strideRowmap=M,
-                     epilogue=EPI_OUT_F32)
+            ops.gemm(xin, wp, y, **head_calls.deconv(M, cin, cout), rowoff=ro, out_rowmap=rm, epilogue=EPI_OUT_F32)
             st, gamma = _bn_stats(bn, y, 4 * M, cout, [bn.weight], [bn.bias], [bn.running_mean], [bn.running_var])
             xo = torch.empty((4 * M, cout), dtype=dt, device=dev)
             ops.bn_apply_relu(y, 4 * M, cout, st[2], st[3], xo)
@@ -177,14 +156,14 @@ class _HeadTrainFn(torch.autograd.Function):
         if engine.final_heatmap_fits(cin, K, dt):
             ops.final_heatmap(xin, fw, fb, v, B, HW, cin, K, T, clamp=False)
         else:
-            ops.gemm(xin, fw, v, M=B * HW, N=K, Kd=cin, lda=cin, ldw=cin, ldc=K, bias=fb, heatmap=(K, HW, T, False))
+            ops.gemm(xin, fw, v, **head_calls.conv(B * HW, cin, K, 1), bias=fb, heatmap=(K, HW, T, False))
         scale = 1.0 if head.normalize is None else float(head.normalize)
         if head.normalize is not None:
             ops.sparsemax_rows(v.view(B * K, HW), 1.0)       # v <- Sparsemax(logits / T), kept for the backward
         heat = ops.heat_clamp(v, torch.empty_like(v), scale)
         S.update(dec=dec, feat=xin, p=v, HW=HW, HH=HH, WW=WW, scale=scale, fw=fw)
         # ---- aux branches: [conv3x3 -> train BN -> MaxPool -> ReLU] x n -> conv1x1 -> Sigmoid / ReLU
-        seqs = [list(getattr(head, n + "_layers")) for n in AUX_NAMES]
+        seqs = [list(getattr(head, n + "_layers")) for n in engine.AUX_NAMES]
         a, ah, aw = tokens, h, w
         aux_st = []
         for i, (p, (ro, _, _)) in enumerate(zip(geo.pools, tb["aux"])):
@@ -192,17 +171,11 @@ class _HeadTrainFn(torch.autograd.Function):
             convs = [s[4 * i] for s in seqs]
             bns = [s[4 * i + 1] for s in seqs]
             y = torch.empty((M, 4 * C), dtype=torch.float32, device=dev)
-            if i == 0:
-                w0 = torch.cat([pack.conv_taps_major(cv.weight.detach()) for cv in convs]).to(dt).contiguous()
-                b0 = torch.cat([cv.bias.detach() for cv in convs]).float().contiguous()
-                ops.gemm(a, w0, y, M=M, N=4 * C, Kd=9 * C, lda=C, ldw=9 * C, ldc=4 * C, bias=b0, rowoff=ro, seg_len=C,
-                         epilogue=EPI_OUT_F32)
-            else:
-                wi = torch.stack([pack.conv_taps_major(cv.weight.detach()) for cv in convs]).to(dt).contiguous()
-                bi = torch.stack([cv.bias.detach() for cv in convs]).float().contiguous()
-                ops.gemm(a, wi, y, M=M, N=C, Kd=9 * C, lda=4 * C, ldw=9 * C, ldc=4 * C, bias=bi, rowoff=ro,
-                         seg_len=C, batch=4, strideA=C, strideW=C * 9 * C, strideC=C, strideBias=C,
-                         epilogue=EPI_OUT_F32)
+            # stage 0 shares its input: the branches' weights one under the other; later stages: batch entries
+            join, call = (torch.cat, head_calls.aux_stage0) if i == 0 else (torch.stack, head_calls.aux_stage)
+            wi = join([pack.conv_taps_major(cv.weight.detach()) for cv in convs]).to(dt).contiguous()
+            bi = join([cv.bias.detach() for cv in convs]).float().contiguous()
+            ops.gemm(a, wi, y, **call(M, C), bias=bi, rowoff=ro, epilogue=EPI_OUT_F32)
             st, gamma = _bn_stats(bns[0], y, M, 4 * C, [b.weight for b in bns], [b.bias for b in bns],
                                   [b.running_mean for b in bns], [b.running_var for b in bns])
             _bump(bns)
@@ -219,8 +192,7 @@ class _HeadTrainFn(torch.autograd.Function):
         S.update(aux=aux_st, pooled=a, tw=tw, aux_out=aux)
         ctx.head = head
         ctx.set_materialize_grads(False)
-        outs = [heat] + [aux[i].reshape(B, K, 1, 1).clone() for i in range(4)]
-        return tuple(outs)
+        return (heat, *(aux[i].reshape(B, K, 1, 1).clone() for i in range(4)))
 
     @staticmethod
     @torch.autograd.function.once_differentiable
@@ -231,154 +203,148 @@ class _HeadTrainFn(torch.autograd.Function):
         pidx = {id(p): i for i, p in enumerate(params)}
         grads = [None] * len(params)
         x_needs = need[1]          # NCHW x, or channels-last tokens that carry a gradient (a training backbone)
+        dt, f32, dev = head.compute_dtype, torch.float32, S["tokens"].device
+        B, h, w, C, K = S["B"], S["h"], S["w"], head.in_channels, head.out_channels
+        geo = _geometry(head, dev)
 
-        def wants(p):
-            return p is not None and need[4 + pidx[id(p)]]
+        def wants(*ps):
+            return any(p is not None and need[4 + pidx[id(p)]] for p in ps)
 
         def put(p, g):
             if wants(p):
                 grads[pidx[id(p)]] = g.reshape(p.shape).to(p.dtype)
 
-        dt = head.compute_dtype
-        B, h, w = S["B"], S["h"], S["w"]
-        C, K = head.in_channels, head.out_channels
-        dev = S["tokens"].device
-        geo = _geometry(head, dev)
-        layers = list(head.deconv_layers)
-        gtok = None
-        # ---- heatmap branch
-        dec = S["dec"]
-        dec_need = [any(wants(p) for p in (layers[3 * i].weight, layers[3 * i + 1].weight, layers[3 * i + 1].bias))
-                    for i in range(len(dec))]
-        below = [x_needs or any(dec_need[:i]) for i in range(len(dec) + 1)]     # below[i]: layer i's input needs grad
-        fl = head.final_layer
-        if g_heat is not None and (wants(fl.weight) or wants(fl.bias) or below[len(dec)]):
+        def bn_backward(g, s, M, Cc, bns, **mode):
+            """dY (compute dtype) of a train-mode BN under the gradient g of what follows it; puts the BNs' gradients."""
+            dY = torch.empty((M, Cc), dtype=dt, device=dev)
+            dgb = torch.empty((2, Cc), dtype=f32, device=dev)
+            ws = torch.empty(ops.bn_workspace_bytes(M, Cc), dtype=torch.uint8, device=dev)
+            st = s["st"]
+            ops.bn_train_backward(g, s["y"], M, Cc, st[0], st[1], s["gamma"], dY, ws, dgamma=dgb[0], dbeta=dgb[1], **mode)
+            n = Cc // len(bns)
+            for bi, bn in enumerate(bns):
+                put(bn.weight, dgb[0, bi * n:(bi + 1) * n])
+                put(bn.bias, dgb[1, bi * n:(bi + 1) * n])
+            return dY
+
+        def heatmap_backward():
+            """The heatmap branch, final layer down to the tokens: their f32 gradient [B*h*w, C], or None when x needs
+            none (or no heatmap gradient came in)."""
+            layers = list(head.deconv_layers)
+            dec = S["dec"]
+            n = len(dec)
+            dec_need = [wants(layers[3 * i].weight, layers[3 * i + 1].weight, layers[3 * i + 1].bias) for i in range(n)]
+            below = [x_needs or any(dec_need[:i]) for i in range(n + 1)]     # below[i]: layer i's input needs grad
+            fl = head.final_layer
+            if g_heat is None or not (wants(fl.weight, fl.bias) or below[n]):
+                return None
             HW, M = S["HW"], B * S["HW"]
-            KPAD = -(-K // KTILE) * KTILE
+            cin = geo.final["cin"]
+            KPAD = head_calls.kpad(K)
             dz = torch.empty((M, KPAD), dtype=dt, device=dev)
             ops.heat_tail_backward(S["p"], g_heat.contiguous().float(), B, K, HW, S["scale"],
                                    head.normalize is not None, float(head.temperature), dz)
-            feat, cin = S["feat"], geo.final["cin"]
-            if wants(fl.weight) or wants(fl.bias):
-                dWf = torch.empty((K, cin), dtype=torch.float32, device=dev)
-                dbf = torch.empty((K,), dtype=torch.float32, device=dev)
-                _wgrad(dz, feat, dWf, M=M, N=K, Kd=cin, ldd=KPAD, lda=cin, dB=dbf)
+            if wants(fl.weight, fl.bias):
+                dWf = torch.empty((K, cin), dtype=f32, device=dev)
+                dbf = torch.empty((K,), dtype=f32, device=dev)
+                _wgrad(dz, S["feat"], dWf, **dict(head_calls.wgrad_of(head_calls.conv(M, cin, K, 1)), ldd=KPAD), dB=dbf)
                 put(fl.weight, dWf)
                 put(fl.bias, dbf)
-            if below[len(dec)]:
-                wt = torch.zeros((cin, KPAD), dtype=dt, device=dev)
-                wt[:, :K] = S["fw"].t()
-                gf = torch.empty((M, cin), dtype=torch.float32, device=dev)
-                ops.gemm(dz, wt, gf, M=M, N=cin, Kd=KPAD, lda=KPAD, ldw=KPAD, ldc=cin, epilogue=EPI_OUT_F32)
-                for li in range(len(dec) - 1, -1, -1):
-                    d = dec[li]
-                    dc, bn = layers[3 * li], layers[3 * li + 1]
-                    M = B * d["hh"] * d["ww"]
-                    cin, cout = d["cin"], d["cout"]
-                    dY = torch.empty((4 * M, cout), dtype=dt, device=dev)
-                    dgb = torch.empty((2, cout), dtype=torch.float32, device=dev)
-                    ws = torch.empty(ops.bn_workspace_bytes(4 * M, cout), dtype=torch.uint8, device=dev)
-                    st = d["st"]
-                    ops.bn_train_backward(gf, d["y"], 4 * M, cout, st[0], st[1], d["gamma"], dY, ws, mode=1,
-                                          scale=st[2], shift=st[3], dgamma=dgb[0], dbeta=dgb[1])
-                    put(bn.weight, dgb[0])
-                    put(bn.bias, dgb[1])
-                    if wants(dc.weight):
-                        dwp = torch.empty((4, cout, 4 * cin), dtype=torch.float32, device=dev)
-                        _wgrad(dY, d["x"], dwp, M=M, N=cout, Kd=4 * cin, ldd=cout, rowoff=d["ro"], seg_len=cin,
-                               dy_rowmap=d["rm"], batch=4, strideRowoff=4 * M, strideRowmap=M,
-                               strideDW=cout * 4 * cin)
-                        dw = torch.empty((cout, 4, 4, cin), dtype=torch.float32, device=dev)
-                        dw[:, geo.KY, geo.KX, :] = dwp.view(4, cout, 4, cin).permute(1, 0, 2, 3)
-                        put(dc.weight, dw.permute(3, 0, 1, 2))
-                    if not below[li]:
-                        break
-                    tab = geo.extra(("dgrad", B, d["hh"], d["ww"], cout),
-                                    lambda: pack.deconv_data_grad_table(B, d["hh"], d["ww"], 4, cout).to(dev))
-                    wt = pack.deconv_data_grad_weights(dc.weight.detach()).to(dt).contiguous()
-                    gf = torch.empty((M, cin), dtype=torch.float32, device=dev)
-                    ops.gemm(dY, wt, gf, M=M, N=cin, Kd=16 * cout, lda=cout, ldw=16 * cout, ldc=cin, rowoff=tab,
-                             seg_len=cout, epilogue=EPI_OUT_F32)
-                if x_needs:
-                    gtok = gf
-        # ---- aux branches
-        seqs = [list(getattr(head, n + "_layers")) for n in AUX_NAMES]
-        gs = (g_prob, g_vis, g_oks, g_err)
-        into_x = [x_needs and not head.detach_probability, x_needs and not head.detach_visibility, False, False]
-        aux = S["aux"]
-        n = len(aux)
-        stage_need = [[any(wants(p) for p in (s[4 * i].weight, s[4 * i].bias, s[4 * i + 1].weight,
-                                              s[4 * i + 1].bias)) for s in seqs] for i in range(n)]
-        tail_need = [wants(s[-2].weight) or wants(s[-2].bias) for s in seqs]
-        abelow = [any(any(stage_need[j]) for j in range(i)) or (any(into_x) and i >= 0) for i in range(n + 1)]
-        if any(g is not None for g in gs) and (any(tail_need) or abelow[n]):
+            if not below[n]:
+                return None
+            wt = torch.zeros((cin, KPAD), dtype=dt, device=dev)
+            wt[:, :K] = S["fw"].t()
+            gf = torch.empty((M, cin), dtype=f32, device=dev)
+            ops.gemm(dz, wt, gf, **head_calls.final_dgrad(M, cin, K), epilogue=EPI_OUT_F32)
+            for li in range(n - 1, -1, -1):
+                d = dec[li]
+                dc, bn = layers[3 * li], layers[3 * li + 1]
+                M = B * d["hh"] * d["ww"]
+                cin, cout = d["cin"], d["cout"]
+                dY = bn_backward(gf, d, 4 * M, cout, [bn], mode=1, scale=d["st"][2], shift=d["st"][3])
+                if wants(dc.weight):
+                    dwp = torch.empty((4, cout, 4 * cin), dtype=f32, device=dev)
+                    _wgrad(dY, d["x"], dwp, **head_calls.wgrad_of(head_calls.deconv(M, cin, cout)), rowoff=d["ro"],
+                           dy_rowmap=d["rm"])
+                    put(dc.weight, pack.unpack_deconv_parities(dwp))
+                if not below[li]:
+                    break
+                tab = geo.grad_tables.get(("dgrad", B, d["hh"], d["ww"], cout),
+                                          lambda: pack.deconv_data_grad_table(B, d["hh"], d["ww"], 4, cout).to(dev))
+                wt = pack.deconv_data_grad_weights(dc.weight.detach()).to(dt).contiguous()
+                gf = torch.empty((M, cin), dtype=f32, device=dev)
+                ops.gemm(dY, wt, gf, **head_calls.deconv_dgrad(M, cin, cout), rowoff=tab, epilogue=EPI_OUT_F32)
+            return gf if x_needs else None
+
+        def aux_backward(gtok):
+            """The four aux branches, tails down to the first stage; the branches that reach x add their token gradient
+            to gtok (or write it, gtok None).  Returns the tokens' gradient so far."""
+            seqs = [list(getattr(head, n + "_layers")) for n in engine.AUX_NAMES]
+            gs = (g_prob, g_vis, g_oks, g_err)
+            into_x = [x_needs and not head.detach_probability, x_needs and not head.detach_visibility, False, False]
+            aux = S["aux"]
+            n = len(aux)
+            stage_need = [[wants(s[4 * i].weight, s[4 * i].bias, s[4 * i + 1].weight, s[4 * i + 1].bias) for s in seqs]
+                          for i in range(n)]
+            tail_need = [wants(s[-2].weight, s[-2].bias) for s in seqs]
+            below = [any(any(stage_need[j]) for j in range(i)) or any(into_x) for i in range(n + 1)]
+            if all(g is None for g in gs) or not (any(tail_need) or below[n]):
+                return gtok
             gaux = torch.stack([g.reshape(B, K).float() if g is not None else
-                                torch.zeros((B, K), dtype=torch.float32, device=dev) for g in gs]).contiguous()
-            dWt = torch.empty((4, K, C), dtype=torch.float32, device=dev) if any(tail_need) else None
-            dbt = torch.empty((4, K), dtype=torch.float32, device=dev) if any(tail_need) else None
-            dpool = torch.empty((B, 4 * C), dtype=torch.float32, device=dev) if abelow[n] else None
+                                torch.zeros((B, K), dtype=f32, device=dev) for g in gs]).contiguous()
+            dWt = torch.empty((4, K, C), dtype=f32, device=dev) if any(tail_need) else None
+            dbt = torch.empty((4, K), dtype=f32, device=dev) if any(tail_need) else None
+            dpool = torch.empty((B, 4 * C), dtype=f32, device=dev) if below[n] else None
             ops.aux_tail_backward(S["pooled"], S["tw"], S["aux_out"], gaux, B, C, K, dWt, dbt, dpool)
-            for bi, s in enumerate(seqs):
-                if tail_need[bi]:
-                    put(s[-2].weight, dWt[bi])
-                    put(s[-2].bias, dbt[bi])
+            for bi, s in enumerate(seqs if any(tail_need) else ()):
+                put(s[-2].weight, dWt[bi])
+                put(s[-2].bias, dbt[bi])
             for i in range(n - 1, -1, -1):
-                if not abelow[i + 1]:
+                if not below[i + 1]:
                     break
                 a = aux[i]
                 M = B * a["ah"] * a["aw"]
-                st = a["st"]
-                dY = torch.empty((M, 4 * C), dtype=dt, device=dev)
-                dgb = torch.empty((2, 4 * C), dtype=torch.float32, device=dev)
-                ws = torch.empty(ops.bn_workspace_bytes(M, 4 * C), dtype=torch.uint8, device=dev)
-                ops.bn_train_backward(dpool, a["y"], M, 4 * C, st[0], st[1], a["gamma"], dY, ws, mode=2,
-                                      argmax=a["argmax"], pool=(B, a["ah"], a["aw"], a["kh"], a["kw"]),
-                                      dgamma=dgb[0], dbeta=dgb[1])
-                dW = torch.empty((4, C, 9 * C), dtype=torch.float32, device=dev)
-                dB = torch.empty((4, C), dtype=torch.float32, device=dev)
-                wneed = [wants(s[4 * i].weight) or wants(s[4 * i].bias) for s in seqs]
-                for b0, b1 in _runs(wneed):
-                    if i == 0:
-                        _wgrad(dY[:, b0 * C:], a["x"], dW[b0:b1].view(-1, 9 * C), M=M, N=(b1 - b0) * C, Kd=9 * C,
-                               ldd=4 * C, rowoff=a["ro"], seg_len=C, dB=dB[b0:b1].view(-1))
-                    else:
-                        _wgrad(dY[:, b0 * C:], a["x"][:, b0 * C:], dW[b0:b1], M=M, N=C, Kd=9 * C, ldd=4 * C,
-                               rowoff=a["ro"], seg_len=C, batch=b1 - b0, strideDY=C, strideA=C, strideDW=C * 9 * C,
-                               dB=dB[b0:b1], strideDB=C)
-                for bi, s in enumerate(seqs):
-                    cv, bn = s[4 * i], s[4 * i + 1]
-                    if wneed[bi]:
-                        put(cv.weight, dW[bi].view(C, 3, 3, C).permute(0, 3, 1, 2))
-                        put(cv.bias, dB[bi])
-                    put(bn.weight, dgb[0, bi * C:(bi + 1) * C])
-                    put(bn.bias, dgb[1, bi * C:(bi + 1) * C])
-                if i > 0 and abelow[i]:
-                    wt = torch.stack([pack.conv3x3_data_grad_weights(s[4 * i].weight.detach()) for s in seqs])
+                convs = [s[4 * i] for s in seqs]
+                dY = bn_backward(dpool, a, M, 4 * C, [s[4 * i + 1] for s in seqs], mode=2, argmax=a["argmax"],
+                                 pool=(B, a["ah"], a["aw"], a["kh"], a["kw"]))
+                dW = torch.empty((4, C, 9 * C), dtype=f32, device=dev)
+                dB = torch.empty((4, C), dtype=f32, device=dev)
+                wneed = [wants(cv.weight, cv.bias) for cv in convs]
+                for b0, b1 in _runs(wneed):         # the branches [b0, b1): the stage's descriptor with b1 - b0 branches
+                    call = head_calls.aux_stage0 if i == 0 else head_calls.aux_stage
+                    _wgrad(dY[:, b0 * C:], a["x"] if i == 0 else a["x"][:, b0 * C:], dW[b0:b1], dB=dB[b0:b1],
+                           rowoff=a["ro"], **head_calls.wgrad_of(call(M, C, b1 - b0)))
+                for bi, cv in enumerate(convs):
+                    put(cv.weight, dW[bi].view(C, 3, 3, C).permute(0, 3, 1, 2))
+                    put(cv.bias, dB[bi])
+                if i > 0 and below[i]:
+                    # the data gradient has the forward's dimensions: the same descriptor over flipped weights
+                    wt = torch.stack([pack.conv3x3_data_grad_weights(cv.weight.detach()) for cv in convs])
                     wt = wt.to(dt).contiguous()
-                    dpool = torch.empty((M, 4 * C), dtype=torch.float32, device=dev)
-                    ops.gemm(dY, wt, dpool, M=M, N=C, Kd=9 * C, lda=4 * C, ldw=9 * C, ldc=4 * C, rowoff=a["ro"],
-                             seg_len=C, batch=4, strideA=C, strideW=C * 9 * C, strideC=C, epilogue=EPI_OUT_F32)
+                    dpool = torch.empty((M, 4 * C), dtype=f32, device=dev)
+                    ops.gemm(dY, wt, dpool, **head_calls.aux_stage(M, C), rowoff=a["ro"], epilogue=EPI_OUT_F32)
                 elif i == 0 and any(into_x):
                     brs = [bi for bi in range(4) if into_x[bi]]
-                    tab = geo.extra(("aux0", B, h, w, tuple(brs)), lambda: _aux0_dgrad_table(B, h, w, C, brs, dev))
-                    wt = torch.stack([pack.conv3x3_data_grad_weights(seqs[bi][0].weight.detach()).view(C, 9, C)
+                    tab = geo.grad_tables.get(("aux0", B, h, w, tuple(brs)),
+                                              lambda: _aux0_dgrad_table(B, h, w, C, brs, dev))
+                    wt = torch.stack([pack.conv3x3_data_grad_weights(convs[bi].weight.detach()).view(C, 9, C)
                                       for bi in brs], dim=2).reshape(C, 9 * len(brs) * C).to(dt).contiguous()
-                    if gtok is None:
-                        gtok = torch.empty((M, C), dtype=torch.float32, device=dev)
-                        ops.gemm(dY, wt, gtok, M=M, N=C, Kd=9 * len(brs) * C, lda=4 * C, ldw=9 * len(brs) * C,
-                                 ldc=C, rowoff=tab, seg_len=C, epilogue=EPI_OUT_F32)
-                    else:
-                        ops.gemm(dY, wt, gtok, M=M, N=C, Kd=9 * len(brs) * C, lda=4 * C, ldw=9 * len(brs) * C,
-                                 ldc=C, rowoff=tab, seg_len=C, residual=gtok, epilogue=EPI_OUT_F32)
+                    out = gtok if gtok is not None else torch.empty((M, C), dtype=f32, device=dev)
+                    ops.gemm(dY, wt, out, **head_calls.aux0_dgrad(M, C, len(brs)), rowoff=tab, residual=gtok,
+                             epilogue=EPI_OUT_F32)       # added to the heatmap branch's token gradient in place
+                    gtok = out
+            return gtok
+
+        gtok = aux_backward(heatmap_backward())
         gx = None
         if x_needs and not S["nchw"]:
             # the token gradient as it is, f32 [B*h*w, C] (autograd casts it to the tokens' dtype)
-            gx = gtok if gtok is not None else torch.zeros((B * h * w, C), dtype=torch.float32, device=dev)
+            gx = gtok if gtok is not None else torch.zeros((B * h * w, C), dtype=f32, device=dev)
         elif x_needs:
             if gtok is None:
-                gx = torch.zeros((B, C, h, w), dtype=torch.float32, device=dev)
+                gx = torch.zeros((B, C, h, w), dtype=f32, device=dev)
             else:
-                gx = torch.empty((B, C, h, w), dtype=torch.float32, device=dev)
+                gx = torch.empty((B, C, h, w), dtype=f32, device=dev)
                 ops.tokens_to_nchw(gtok, gx, B, h * w, C)
         return (None, gx, None, None, *grads)
 
@@ -398,24 +364,20 @@ def train_forward(head, x: torch.Tensor = None, tokens: torch.Tensor = None, geo
     """The train-mode forward of ``head``: from an NCHW feature map ``x`` or from channels-last ``tokens`` [B*h*w, C]
     in the compute dtype, geom = (B, h, w); the gradient reaches either when it requires grad."""
     check_trainable(head)
-    params = head_parameters(head)
+    inp = x if x is not None else tokens
+    _lib.require_device(inp)
     if x is not None:
-        _lib.require_device(x)
         B, C, h, w = x.shape
         if C != head.in_channels:
             raise ValueError(f"ProbMapHead: expected {head.in_channels} channels, got {C}")
-        inp, is_nchw, shape = x, True, (B, C, h, w)
-        dev = x.device
     else:
-        _lib.require_device(tokens)
         B, h, w = geom
         if tokens.dtype != head.compute_dtype:
             raise TypeError(f"tokens are {tokens.dtype}, the head computes in {head.compute_dtype}")
         inp = tokens if tokens.requires_grad else tokens.detach()
-        is_nchw, shape = False, (B, head.in_channels, h, w)
-        dev = tokens.device
+    params = head_parameters(head)
     for p in params:
-        if p.device != dev:
-            raise ValueError(f"ProbMapHead parameters are on {p.device}, the input on {dev}: move the head first")
-    with torch.cuda.device(dev):
-        return _HeadTrainFn.apply(head, inp, is_nchw, shape, *params)
+        if p.device != inp.device:
+            raise ValueError(f"ProbMapHead parameters are on {p.device}, the input on {inp.device}: move the head first")
+    with torch.cuda.device(inp.device):
+        return _HeadTrainFn.apply(head, inp, x is not None, (B, head.in_channels, h, w), *params)

@@ -11,6 +11,7 @@ backbone and head.
 """
 from __future__ import annotations
 
+import functools
 from typing import List, Optional, Sequence, Tuple
 
 import torch
@@ -87,22 +88,49 @@ def deconv_geometry(k: int) -> Tuple[int, int]:
     raise ValueError(f"Unsupported kernel size {k} for deconvlutional layers in ProbMapHead")
 
 
-def pack_deconv_parities(w: torch.Tensor, k: int) -> torch.Tensor:
-    """ConvTranspose2d weight (Cin, Cout, k, k) [BN already folded on dim 1] ->
-    (4, Cout, 4*Cin): parity p = py*2+px, K index = (a*2+b)*Cin + ci for axis taps a (y), b (x)."""
-    Cin, Cout = w.shape[0], w.shape[1]
+def deconv_parity_index(k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(KY, KX) int64 [4 parities, 4 taps]: the kernel position of parity p = py*2+px, tap t = a*2+b (axis taps a in y,
+    b in x) in pack_deconv_parities' layout, packed[p, co, t*Cin + ci] = w[ci, co, KY[p, t], KX[p, t]]; -1 where the
+    parity has no such tap (k = 3, 2: a zero weight).  k = 4: every kernel position appears exactly once."""
     pad, _ = deconv_geometry(k)
     taps = deconv_axis_taps(k, pad)
-    out = torch.zeros((4, Cout, 4 * Cin), dtype=w.dtype)
+    KY = torch.full((4, 4), -1, dtype=torch.long)
+    KX = torch.full((4, 4), -1, dtype=torch.long)
     for py in (0, 1):
         for px in (0, 1):
             for a, (_, ky) in enumerate(taps[py]):
                 for b, (_, kx) in enumerate(taps[px]):
-                    if ky is None or kx is None:
-                        continue
-                    t = a * 2 + b
-                    out[py * 2 + px, :, t * Cin:(t + 1) * Cin] = w[:, :, ky, kx].t()
-    return out
+                    if ky is not None and kx is not None:
+                        KY[py * 2 + px, a * 2 + b], KX[py * 2 + px, a * 2 + b] = ky, kx
+    return KY, KX
+
+
+@functools.lru_cache(maxsize=None)
+def _parity_index_on(k: int, device):
+    """deconv_parity_index on ``device`` with absent taps at position 0, and their mask (None: every tap is there)."""
+    KY, KX = deconv_parity_index(k)
+    ok = KY >= 0
+    return KY.clamp(min=0).to(device), KX.clamp(min=0).to(device), (None if bool(ok.all()) else ok.to(device))
+
+
+def pack_deconv_parities(w: torch.Tensor, k: int) -> torch.Tensor:
+    """ConvTranspose2d weight (Cin, Cout, k, k) [BN already folded on dim 1], on any device ->
+    (4, Cout, 4*Cin): parity p = py*2+px, K index = (a*2+b)*Cin + ci for axis taps a (y), b (x)."""
+    Cin, Cout = w.shape[0], w.shape[1]
+    KY, KX, ok = _parity_index_on(k, w.device)
+    taps = w.permute(1, 2, 3, 0)[:, KY, KX, :]                                  # [Cout, 4 parities, 4 taps, Cin]
+    if ok is not None:
+        taps = torch.where(ok[None, :, :, None], taps, taps.new_zeros(()))
+    return taps.permute(1, 0, 2, 3).reshape(4, Cout, 4 * Cin).contiguous()
+
+
+def unpack_deconv_parities(dwp: torch.Tensor) -> torch.Tensor:
+    """The inverse of pack_deconv_parities at k = 4, for the weight gradient: (4, Cout, 4*Cin) -> (Cin, Cout, 4, 4)."""
+    Cout, Cin = dwp.shape[1], dwp.shape[2] // 4
+    KY, KX, _ = _parity_index_on(4, dwp.device)
+    dw = torch.empty((Cout, 4, 4, Cin), dtype=dwp.dtype, device=dwp.device)
+    dw[:, KY, KX, :] = dwp.view(4, Cout, 4, Cin).permute(1, 0, 2, 3)
+    return dw.permute(3, 0, 1, 2)
 
 
 def deconv_tables(B: int, h: int, w: int, k: int, row_stride: int):
@@ -188,20 +216,3 @@ def deconv_data_grad_table(B: int, h: int, w: int, k: int, row_stride: int) -> t
     t = torch.stack(taps)
     assert t.max().item() < 2 ** 31
     return t.to(torch.int32).contiguous()
-
-
-def deconv_parity_index(k: int) -> Tuple[torch.Tensor, torch.Tensor]:
-    """(KY, KX) int64 [4 parities, 4 taps]: kernel position of parity p, tap t in pack_deconv_parities' layout, so that
-    packed[p, co, t*Cin + ci] = w[ci, co, KY[p, t], KX[p, t]] (k = 4: every kernel position appears exactly once)."""
-    if k != 4:
-        raise NotImplementedError(f"deconvolution kernel {k}: the training path packs kernel 4 only")
-    pad, _ = deconv_geometry(k)
-    taps = deconv_axis_taps(k, pad)
-    KY = torch.zeros((4, 4), dtype=torch.long)
-    KX = torch.zeros((4, 4), dtype=torch.long)
-    for py in (0, 1):
-        for px in (0, 1):
-            for a, (_, ky) in enumerate(taps[py]):
-                for b, (_, kx) in enumerate(taps[px]):
-                    KY[py * 2 + px, a * 2 + b], KX[py * 2 + px, a * 2 + b] = ky, kx
-    return KY, KX

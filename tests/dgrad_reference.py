@@ -1,12 +1,14 @@
-"""The pp_gemm calls that only a training step makes, built the way head_train.py and vit_train.py build them, each
-with its ground truth from torch autograd in float64 on the layer itself.
+"""The pp_gemm calls that only a training step makes, built from what head_train.py and vit_train.py build them from
+(the head's dimension keywords are head_calls' descriptors, the product's own), each with its ground truth from torch
+autograd in float64 on the layer itself: the independent side.
 
 A builder takes layer parameters, an output gradient (or, for the train-mode forward, an input) and the operand dtype,
 and returns a ``Call``: ``kw`` holds the keyword arguments of ``ops.gemm`` with A, W and out among them (what
 tests/gemm_reference.py restates and what a GPU test launches), ``truth`` the float64 result shaped like ``out``.
 Weights and tables come from the product's own packers (pack.conv3x3_data_grad_weights, pack.deconv_data_grad_weights,
-pack.deconv_data_grad_table, head_train._aux0_dgrad_table, vit_train._wt, ops.linear), looked up through their modules
-at call time, so that ``planted(fault)`` can swap one of them for a wrong one: FAULTS lists those, each with the call
+pack.deconv_data_grad_table, head_train._aux0_dgrad_table, vit_train._wt, ops.linear) and the descriptors from
+head_calls, all looked up through their modules at call time, so that ``planted(fault)`` can swap one of them for a
+wrong one: FAULTS lists those, each with the call
 kinds whose comparison with the truth it must fail.  The truth is computed from the operands as the kernel reads them
 (rounded to the operand dtype first), so on integer data it is exact and the restatement must equal it bit for bit.
 
@@ -21,7 +23,7 @@ from dataclasses import dataclass
 import torch
 import torch.nn.functional as F
 
-from probpose_pytorch_amd import head_train, ops, pack, vit_train
+from probpose_pytorch_amd import head_calls, head_train, ops, pack, vit_train
 from tests import gemm_reference as gr
 
 EPI_OUT_F32 = gr.EPI_OUT_F32
@@ -59,15 +61,14 @@ def final_dgrad(weight, dz, dt) -> Call:
     """The final 1x1 layer's data gradient.  weight: final_layer.weight (K, cin, 1, 1); dz [M, KPAD]: the heatmap
     gradient at head_train's channel pitch (columns from K on meet the weight's zero padding: any finite value)."""
     K, cin = weight.shape[:2]
-    KPAD = -(-K // head_train.KTILE) * head_train.KTILE
+    KPAD = head_calls.kpad(K)
     M = dz.shape[0]
     assert dz.shape[1] == KPAD
     fw = weight.detach().reshape(K, cin).to(dt).contiguous()
     wt = torch.zeros((cin, KPAD), dtype=dt)
     wt[:, :K] = fw.t()
     A = dz.to(dt).contiguous()
-    kw = dict(A=A, W=wt, out=torch.empty((M, cin), dtype=f32), M=M, N=cin, Kd=KPAD, lda=KPAD, ldw=KPAD, ldc=cin,
-              epilogue=EPI_OUT_F32)
+    kw = dict(head_calls.final_dgrad(M, cin, K), A=A, W=wt, out=torch.empty((M, cin), dtype=f32), epilogue=EPI_OUT_F32)
     return Call("final", kw, _input_grad(lambda x: F.linear(x, fw.double()), (M, cin), A[:, :K]))
 
 
@@ -80,8 +81,8 @@ def deconv_dgrad(weight, dY, dt) -> Call:
     tab = pack.deconv_data_grad_table(B, h, w, 4, cout)
     wt = pack.deconv_data_grad_weights(weight.detach()).to(dt).contiguous()
     A = rows(dY).to(dt)
-    kw = dict(A=A, W=wt, out=torch.empty((M, cin), dtype=f32), M=M, N=cin, Kd=16 * cout, lda=cout, ldw=16 * cout,
-              ldc=cin, rowoff=tab, seg_len=cout, epilogue=EPI_OUT_F32)
+    kw = dict(head_calls.deconv_dgrad(M, cin, cout), A=A, W=wt, out=torch.empty((M, cin), dtype=f32), rowoff=tab,
+              epilogue=EPI_OUT_F32)
     w64 = weight.detach().to(dt).double()
     g = _input_grad(lambda x: F.conv_transpose2d(x, w64, stride=2, padding=1), (B, cin, h, w), dY.to(dt))
     return Call("deconv", kw, rows(g))
@@ -102,8 +103,8 @@ def aux_stage_dgrad(weights, dY, dt) -> Call:
     ro = pack.conv_gather_table(B, h, w, 3, 3, 1, 1, 4 * C)
     wt = torch.stack([pack.conv3x3_data_grad_weights(wb.detach()) for wb in weights]).to(dt).contiguous()
     A = rows(dY).to(dt)
-    kw = dict(A=A, W=wt, out=torch.empty((M, 4 * C), dtype=f32), M=M, N=C, Kd=9 * C, lda=4 * C, ldw=9 * C, ldc=4 * C,
-              rowoff=ro, seg_len=C, batch=4, strideA=C, strideW=C * 9 * C, strideC=C, epilogue=EPI_OUT_F32)
+    kw = dict(head_calls.aux_stage(M, C), A=A, W=wt, out=torch.empty((M, 4 * C), dtype=f32), rowoff=ro,
+              epilogue=EPI_OUT_F32)
     g = torch.cat([_conv_input_grad(wb, dY[:, b * C:(b + 1) * C], dt) for b, wb in enumerate(weights)], dim=1)
     return Call("aux_stage", kw, rows(g))
 
@@ -119,8 +120,7 @@ def aux0_dgrad(weights, dY, brs, dt, prior=None) -> Call:
     wt = torch.stack([pack.conv3x3_data_grad_weights(weights[bi].detach()).view(C, 9, C) for bi in brs],
                      dim=2).reshape(C, 9 * len(brs) * C).to(dt).contiguous()
     A = rows(dY).to(dt)
-    Kd = 9 * len(brs) * C
-    kw = dict(A=A, W=wt, M=M, N=C, Kd=Kd, lda=4 * C, ldw=Kd, ldc=C, rowoff=tab, seg_len=C, epilogue=EPI_OUT_F32)
+    kw = dict(head_calls.aux0_dgrad(M, C, len(brs)), A=A, W=wt, rowoff=tab, epilogue=EPI_OUT_F32)
     g = sum(rows(_conv_input_grad(weights[bi], dY[:, bi * C:(bi + 1) * C], dt)) for bi in brs)
     if prior is None:
         kw["out"] = torch.empty((M, C), dtype=f32)
@@ -221,7 +221,7 @@ def make(kind: str, case, dt, ints: bool, seed: int = 0) -> Call:
 
     if kind == "final":
         K, M, cin = case
-        KPAD = -(-K // head_train.KTILE) * head_train.KTILE
+        KPAD = head_calls.kpad(K)
         return final_dgrad(draw((K, cin, 1, 1), KPAD ** -0.5), draw((M, KPAD)), dt)
     if kind == "deconv":
         B, h, w, cin, cout = case
@@ -279,6 +279,11 @@ def _reversed_branches(real):
     return lambda B, h, w, C, brs, dev: real(B, h, w, C, list(reversed(brs)), dev)
 
 
+def _with(**wrong):
+    """A head_calls descriptor with some keywords replaced: wrong[key](the right value) -> the wrong one."""
+    return lambda real: lambda *a, **k: {key: (wrong[key](v) if key in wrong else v) for key, v in real(*a, **k).items()}
+
+
 _CONV_KINDS = ("aux_stage", "aux0", "aux0_resid")
 # name: (module, attribute, wrong function or a wrapper of the real one, wraps the real one?, the kinds it must fail)
 FAULTS = {
@@ -294,6 +299,13 @@ FAULTS = {
     "conv table -1 as offset 0": (pack, "conv_gather_table", _pad_as_row_zero, True, _CONV_KINDS),
     "aux-0 table -1 as offset 0": (head_train, "_aux0_dgrad_table", _pad_as_row_zero, True, ("aux0", "aux0_resid")),
     "aux-0 branch order reversed": (head_train, "_aux0_dgrad_table", _reversed_branches, True, ("aux0", "aux0_resid")),
+    # one per head_calls descriptor these builders use: the comparison sees the product's call, not a transcription
+    "final dgrad weight pitch short": (head_calls, "final_dgrad", _with(ldw=lambda v: v - 16), True, ("final",)),
+    "deconv dgrad last tap dropped": (head_calls, "deconv_dgrad", _with(Kd=lambda v: v - v // 16), True, ("deconv",)),
+    "aux stage strideC wrong": (head_calls, "aux_stage", _with(strideC=lambda v: v // 2), True, ("aux_stage",)),
+    "aux stage strideW wrong": (head_calls, "aux_stage", _with(strideW=lambda v: v // 9), True, ("aux_stage",)),
+    "aux-0 dgrad last segment dropped": (head_calls, "aux0_dgrad", _with(Kd=lambda v: v - 64), True,
+                                         ("aux0", "aux0_resid")),
     "_wt not transposed": (vit_train, "_wt", lambda p, dt: p.detach().to(dt).contiguous(), False, ("proj_dgrad",)),
 }
 
@@ -302,7 +314,7 @@ FAULTS = {
 # a missing flip cannot be seen), square layers where two axes are swapped, two branches where their order is
 FAULT_CASES = {
     "deconv": (2, 3, 2, 64, 64), "aux_stage": (2, 5, 3, 64), "aux0": ((2, 5, 3, 64), (0, 1)),
-    "aux0_resid": ((2, 5, 3, 64), (0, 1)), "proj_dgrad": (70, 64, 256),
+    "aux0_resid": ((2, 5, 3, 64), (0, 1)), "proj_dgrad": (70, 64, 256), "final": (17, 30, 64),
 }
 
 

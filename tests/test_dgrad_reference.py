@@ -79,3 +79,12 @@ def test_every_issue_fault_is_listed():
         if kind != "proj_dgrad":
             geo = case[0] if kind.startswith("aux0") else case
             assert geo[1] >= 2 and geo[2] >= 2
+
+
+def test_every_head_descriptor_the_builders_use_has_a_planted_fault():
+    """The builders take their dimension keywords from head_calls: a wrong descriptor must fail the comparison, or
+    the tests would hold the product to itself."""
+    from probpose_pytorch_amd import head_calls
+    planted = {f[1]: f[4] for f in DR.FAULTS.values() if f[0] is head_calls}
+    assert planted == {"final_dgrad": ("final",), "deconv_dgrad": ("deconv",), "aux_stage": ("aux_stage",),
+                       "aux0_dgrad": ("aux0", "aux0_resid")}

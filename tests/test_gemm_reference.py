@@ -1,6 +1,6 @@
 """CPU tests of the float64 pp_gemm restatement (tests/gemm_reference.py) and of its comparator.
 
-(1) The restatement, driven with the tables pack.py builds and the arguments the engine passes, equals torch's own
+(1) The restatement, driven with the tables pack.py builds and the head layers' own calls (head_calls), equals torch's own
 operators (F.linear, F.conv2d with its zero padding, F.conv_transpose2d, the head-major permute, the NCHW heatmap
 store).  Operands are small integers, so every product and sum is exact and equality is exact.
 (2) The comparator rejects what a broken tile would leave behind: a K-tile missing from one 16x16 block, two
@@ -9,7 +9,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from probpose_pytorch_amd import pack
+from probpose_pytorch_amd import head_calls, pack
 from tests import gemm_reference as gr
 
 BF16, F32 = torch.bfloat16, torch.float32
@@ -74,8 +74,7 @@ def test_conv3x3_gather_stage0_and_batched_branches_equal_conv2d():
     Wp0 = pack.conv_taps_major(wt0).to(BF16)
     ro0 = pack.conv_gather_table(B, h, w, 3, 3, 1, 1, C)
     out = torch.empty((M, 4 * C), dtype=BF16)
-    ref, written = _run(dict(A=x0, W=Wp0, out=out, M=M, N=4 * C, Kd=9 * C, lda=C, ldw=9 * C, ldc=4 * C, bias=b0,
-                             rowoff=ro0, seg_len=C))
+    ref, written = _run(dict(head_calls.aux_stage0(M, C), A=x0, W=Wp0, out=out, bias=b0, rowoff=ro0))
     want = F.conv2d(x0.double().reshape(B, h, w, C).permute(0, 3, 1, 2), wt0.double(), b0.double(), padding=1)
     assert torch.equal(ref.reshape(M, 4 * C), want.permute(0, 2, 3, 1).reshape(M, 4 * C)) and written.all()
     # stage >= 1: batch = 4 branches
@@ -84,8 +83,7 @@ def test_conv3x3_gather_stage0_and_batched_branches_equal_conv2d():
     bias = _int((4, C), 6, dtype=F32)
     Wp = torch.stack([pack.conv_taps_major(wt[i]) for i in range(4)]).to(BF16)
     ro = pack.conv_gather_table(B, h, w, 3, 3, 1, 1, 4 * C)
-    ref, written = _run(dict(A=x, W=Wp, out=out, M=M, N=C, Kd=9 * C, lda=4 * C, ldw=9 * C, ldc=4 * C, bias=bias,
-                             rowoff=ro, seg_len=C, batch=4, strideA=C, strideW=C * 9 * C, strideC=C, strideBias=C))
+    ref, written = _run(dict(head_calls.aux_stage(M, C), A=x, W=Wp, out=out, bias=bias, rowoff=ro))
     ref = ref.reshape(M, 4 * C)
     for i in range(4):
         xi = x[:, i * C:(i + 1) * C].double().reshape(B, h, w, C).permute(0, 3, 1, 2)
@@ -106,9 +104,8 @@ def test_splitk_partials_sum_to_the_convolution(split):
     ro = pack.conv_gather_table(B, h, w, 3, 3, 1, 1, 4 * C)
     taps = 9 // split
     parts = torch.empty((split, M, 4 * C), dtype=F32)
-    ref, written = _run(dict(A=x, W=Wp, out=parts, M=M, N=C, Kd=taps * C, lda=4 * C, ldw=9 * C, ldc=4 * C, rowoff=ro,
-                             seg_len=C, batch=4, strideA=C, strideW=C * 9 * C, strideC=C, epilogue=gr.EPI_OUT_F32,
-                             splitk=split, strideW_k=taps * C, strideRowoff_k=taps * M, strideC_k=M * 4 * C))
+    ref, written = _run(dict(head_calls.aux_stage(M, C, split=split), A=x, W=Wp, out=parts, rowoff=ro,
+                             epilogue=gr.EPI_OUT_F32))
     assert written.all()
     ref = ref.reshape(split, M, 4 * C)
     total = ref.sum(0)
@@ -135,13 +132,35 @@ def test_deconv_parities_with_row_scatter_equal_conv_transpose2d(k):
     Wp = pack.pack_deconv_parities(wt, k).to(BF16)
     ro, rm = pack.deconv_tables(B, h, w, k, Cin)
     out = torch.empty((4 * M, Cout), dtype=BF16)
-    ref, written = _run(dict(A=x, W=Wp, out=out, M=M, N=Cout, Kd=4 * Cin, lda=Cin, ldw=4 * Cin, ldc=Cout, bias=bias,
-                             rowoff=ro, seg_len=Cin, out_rowmap=rm, batch=4, strideW=Cout * 4 * Cin, strideRowoff=4 * M,
-                             strideRowmap=M, epilogue=gr.EPI_RELU))
+    ref, written = _run(dict(head_calls.deconv(M, Cin, Cout), A=x, W=Wp, out=out, bias=bias, rowoff=ro, out_rowmap=rm,
+                             epilogue=gr.EPI_RELU))
     pad, op = pack.deconv_geometry(k)
     want = F.relu(F.conv_transpose2d(x.double().reshape(B, h, w, Cin).permute(0, 3, 1, 2), wt.double(), bias.double(),
                                      stride=2, padding=pad, output_padding=op))
     assert torch.equal(ref.reshape(4 * M, Cout), want.permute(0, 2, 3, 1).reshape(4 * M, Cout)) and written.all()
+
+
+@pytest.mark.parametrize("fn,key,wrong,test,arg", [
+    ("deconv", "strideRowoff", lambda v: v // 2, "test_deconv_parities_with_row_scatter_equal_conv_transpose2d", 4),
+    ("aux_stage0", "Kd", lambda v: v - v // 9, "test_conv3x3_gather_stage0_and_batched_branches_equal_conv2d", None),
+    ("aux_stage", "strideC", lambda v: v // 2, "test_conv3x3_gather_stage0_and_batched_branches_equal_conv2d", None),
+    ("aux_stage", "strideRowoff_k", lambda v: 0, "test_splitk_partials_sum_to_the_convolution", 3),
+    ("conv", "Kd", lambda v: v // 2, "test_heatmap_epilogue_is_the_nchw_store_over_temperature", True),
+], ids=lambda v: v if isinstance(v, str) and not v.startswith("test_") else None)
+def test_a_wrong_head_descriptor_fails_its_comparison(monkeypatch, fn, key, wrong, test, arg):
+    """The cases above hold head_calls' own descriptors, so they must notice a wrong one (they are not circular)."""
+    run = globals()[test]
+    args = () if arg is None else (arg,)
+    run(*args)
+    real = getattr(head_calls, fn)
+
+    def faulty(*a, **k):
+        kw = real(*a, **k)
+        return dict(kw, **{key: wrong(kw[key])}) if key in kw else kw
+
+    monkeypatch.setattr(head_calls, fn, faulty)
+    with pytest.raises(AssertionError):
+        run(*args)
 
 
 def test_headmajor_layout_is_the_permuted_projection():
@@ -163,8 +182,7 @@ def test_heatmap_epilogue_is_the_nchw_store_over_temperature(clamp):
     x, W = _int((B * HW, Cin), 1), _int((K, Cin), 2)
     b = _int((K,), 3, dtype=F32)
     out = torch.empty((B, K, HW), dtype=F32)
-    ref, written = _run(dict(A=x, W=W, out=out, M=B * HW, N=K, Kd=Cin, lda=Cin, ldw=Cin, ldc=K, bias=b,
-                             heatmap=(K, HW, T, clamp)))
+    ref, written = _run(dict(head_calls.conv(B * HW, Cin, K, 1), A=x, W=W, out=out, bias=b, heatmap=(K, HW, T, clamp)))
     want = ((x.double() @ W.double().t() + b.double()) / T).reshape(B, HW, K).permute(0, 2, 1)
     if clamp:
         want = want.clamp(0, 1)

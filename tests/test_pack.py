@@ -27,6 +27,33 @@ def test_deconv_parities_reproduce_conv_transpose(k):
     torch.testing.assert_close(got, ref, rtol=1e-5, atol=1e-5)
 
 
+@pytest.mark.parametrize("k", [4, 3, 2])
+def test_deconv_parity_index_is_the_packed_layout(k):
+    """packed[p, co, t*Cin + ci] = w[ci, co, KY[p, t], KX[p, t]], a plain +0.0 where the parity has no tap t (whatever
+    the weight holds); at k = 4 every kernel position appears once and unpack_deconv_parities is the inverse."""
+    Cin, Cout = 3, 5
+    wt = torch.randn((Cin, Cout, k, k), generator=torch.Generator().manual_seed(k))
+    wt[0, 0, 0, 0], wt[1, 1, -1, -1], wt[2, 2, 0, -1] = float("inf"), float("nan"), -1.0
+    KY, KX = pack.deconv_parity_index(k)
+    ok = KY >= 0
+    assert torch.equal(ok, KX >= 0)
+    Wp = pack.pack_deconv_parities(wt, k)
+    assert Wp.shape == (4, Cout, 4 * Cin) and Wp.is_contiguous() and Wp.dtype == wt.dtype
+    assert int(ok.sum()) == k * k and len({(int(y), int(x)) for y, x in zip(KY[ok], KX[ok])}) == k * k
+    zero = torch.zeros(Cin).view(torch.int32)
+    for p in range(4):
+        for t in range(4):
+            got = Wp[p, :, t * Cin:(t + 1) * Cin]
+            if ok[p, t]:
+                assert torch.equal(got.view(torch.int32), wt[:, :, KY[p, t], KX[p, t]].t().contiguous().view(torch.int32))
+            else:
+                assert all(torch.equal(row.view(torch.int32), zero) for row in got.contiguous())
+    if k == 4:
+        assert bool(ok.all())
+        back = pack.unpack_deconv_parities(Wp)
+        assert torch.equal(back.contiguous().view(torch.int32), wt.view(torch.int32))
+
+
 def test_deconv_geometry_rejects_other_kernel_sizes():
     with pytest.raises(ValueError):
         pack.deconv_geometry(5)                        # reference head.py:452-457

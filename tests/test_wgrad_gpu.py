@@ -27,7 +27,7 @@ import time
 import pytest
 import torch
 
-from probpose_pytorch_amd import pack
+from probpose_pytorch_amd import head_calls, pack
 from tests import wgrad_reference as WR
 
 pytestmark = pytest.mark.gpu
@@ -146,9 +146,8 @@ def _build(spec, dt, ints, seed):
     if "aux" in spec:           # head_train.py's later aux stages: column blocks of [M, 4C] rows, one table for all
         B, h, w, Cc, _ = spec["aux"]
         ro = pack.conv_gather_table(B, h, w, 3, 3, 1, 1, 4 * Cc)
-        return dict(dY=_place(draw(M * 4 * Cc), 0), A=_place(draw(M * 4 * Cc), 0), M=M, N=Cc, Kd=9 * Cc, ldd=4 * Cc,
-                    rowoff=ro.reshape(-1).cuda(), seg_len=Cc, batch=batch, strideDY=Cc, strideA=Cc,
-                    strideDW=Cc * 9 * Cc, strideDB=Cc), True
+        return dict(head_calls.wgrad_of(head_calls.aux_stage(M, Cc, batch)), dY=_place(draw(M * 4 * Cc), 0),
+                    A=_place(draw(M * 4 * Cc), 0), rowoff=ro.reshape(-1).cuda()), True
     off = spec.get("off", (0, 0, 0))
     ldd = spec.get("ldd", N)
     many = batch > 1

@@ -6,7 +6,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from probpose_pytorch_amd import pack
+from probpose_pytorch_amd import head_calls, pack
 from tests import wgrad_reference as WR
 
 F64_TOL = 1e-12        # relative to the largest gradient element: float64 sums of at most a few thousand terms
@@ -41,7 +41,7 @@ def test_conv3x3_weight_and_bias_gradient():
     gw, gb = torch.autograd.grad(F.conv2d(x, wt, bs, padding=1), (wt, bs), dy)
     ro = pack.conv_gather_table(B, h, w, 3, 3, 1, 1, C)
     assert int((ro < 0).sum()) > 0
-    kw = dict(dY=_rows(dy), A=_rows(x), M=B * h * w, N=Co, Kd=9 * C, ldd=Co, rowoff=ro, seg_len=C)
+    kw = dict(head_calls.wgrad_of(head_calls.conv(B * h * w, C, Co, 3)), dY=_rows(dy), A=_rows(x), rowoff=ro)
     dW, dB = _run(kw, (Co, 9 * C), (Co,))
     assert _close(dW.view(Co, 3, 3, C).permute(0, 3, 1, 2), gw) and _close(dB, gb)
     # the gathered operand is pack.gather_rows' (the forward GEMM's A)
@@ -58,13 +58,9 @@ def test_deconv4x4_weight_gradient_through_the_parity_scatter():
     (gw,) = torch.autograd.grad(F.conv_transpose2d(x, wt, stride=2, padding=1), (wt,), dy)
     M = B * h * w
     ro, rm = pack.deconv_tables(B, h, w, 4, ci)
-    kw = dict(dY=_rows(dy), A=_rows(x), M=M, N=co, Kd=4 * ci, ldd=co, rowoff=ro, seg_len=ci, dy_rowmap=rm, batch=4,
-              strideRowoff=4 * M, strideRowmap=M, strideDW=co * 4 * ci)
+    kw = dict(head_calls.wgrad_of(head_calls.deconv(M, ci, co)), dY=_rows(dy), A=_rows(x), rowoff=ro, dy_rowmap=rm)
     dwp, _ = _run(kw, (4, co, 4 * ci))
-    KY, KX = pack.deconv_parity_index(4)
-    dw = torch.empty((co, 4, 4, ci), dtype=torch.float64)
-    dw[:, KY, KX, :] = dwp.view(4, co, 4, ci).permute(1, 0, 2, 3)       # head_train.py's scatter
-    assert _close(dw.permute(3, 0, 1, 2), gw)
+    assert _close(pack.unpack_deconv_parities(dwp), gw)                  # head_train.py's scatter
 
 
 def test_linear_plain_form():
@@ -99,8 +95,8 @@ def test_batched_aux_form_equals_four_convolutions():
     dy = torch.randn((B, 4 * C, h, w), generator=gen, dtype=torch.float64)
     ro = pack.conv_gather_table(B, h, w, 3, 3, 1, 1, 4 * C)
     for b0, b1 in ((0, 4), (1, 3)):
-        kw = dict(dY=_rows(dy)[:, b0 * C:], A=_rows(x)[:, b0 * C:], M=M, N=C, Kd=9 * C, ldd=4 * C, rowoff=ro, seg_len=C,
-                  batch=b1 - b0, strideDY=C, strideA=C, strideDW=C * 9 * C, strideDB=C)
+        kw = dict(head_calls.wgrad_of(head_calls.aux_stage(M, C, b1 - b0)), dY=_rows(dy)[:, b0 * C:],
+                  A=_rows(x)[:, b0 * C:], rowoff=ro)
         dW, dB = _run(kw, (b1 - b0, C, 9 * C), (b1 - b0, C))
         for br in range(b0, b1):
             wt = torch.zeros((C, C, 3, 3), dtype=torch.float64, requires_grad=True)
