@@ -11,17 +11,9 @@ import pytest
 import torch
 
 from oracle import frontend_oracle as fo
+from tests.frontend_forms import frame as _frame
 
 SIZE = (192, 256)   # [w, h]
-
-
-def _frame(h, w, seed):
-    rng = np.random.default_rng(seed)
-    base = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
-    yy, xx = np.mgrid[0:h, 0:w]
-    smooth = ((np.sin(xx / 17.0) + np.cos(yy / 23.0)) * 60 + 128).clip(0, 255).astype(np.uint8)
-    base[: h // 2] = (base[: h // 2] // 4 + smooth[: h // 2, :, None] * 3 // 4).astype(np.uint8)
-    return base
 
 
 BOXES = [
