@@ -14,13 +14,12 @@ them; sequence + dataflow + stage values cover the chain by induction.
 The models are fp8_walk_reference.MODELS (A: C 128, head dim 64, M = 60 rows; B: C 256, head dim 32, N = 15; C = 192
 is refused by the fp8 GEMM, whose K comes in multiples of 128), with the conditioned states of
 fp8_walk_reference.condition_state; the input condition is asserted on every restatement used."""
-import contextlib
-
 import pytest
 import torch
 
 from tests import fp8_walk_reference as fw
 from tests import gemm_reference as gr
+from tests.walk_recording import VIT_OPS, recording
 
 pytestmark = pytest.mark.gpu
 
@@ -34,62 +33,6 @@ def ops(built_lib):
     assert torch.cuda.is_available()
     from probpose_pytorch_amd import ops as o
     return o
-
-
-@contextlib.contextmanager
-def recording(ops):
-    """ops.layernorm / ops.linear / ops.attention (and the patch-embed ops.gemm) wrapped: every launch's tensor
-    arguments are cloned before the call and its output after it, with their addresses and the scalars as passed."""
-    rec = []
-    real = {k: getattr(ops, k) for k in ("layernorm", "linear", "attention", "gemm")}
-    inside_linear = [False]
-
-    def entry(op, args, scalars, out, call):
-        assert all(t.is_contiguous() for t in args.values() if t is not None) and out.is_contiguous()
-        e = dict(op=op, args={k: t.clone() for k, t in args.items() if t is not None}, scalars=scalars,
-                 ptrs={k: t.data_ptr() for k, t in dict(args, out=out).items() if t is not None},
-                 meta={k: (t.dtype, tuple(t.shape)) for k, t in dict(args, out=out).items() if t is not None})
-        r = call()
-        e["out"] = out.clone()
-        rec.append(e)
-        return r
-
-    def layernorm(x, gamma, beta, eps, out, out_scale=None):
-        return entry("layernorm", dict(x=x, gamma=gamma, beta=beta), dict(eps=eps, out_scale=out_scale), out,
-                     lambda: real["layernorm"](x, gamma, beta, eps, out, out_scale=out_scale))
-
-    def linear(x, w, bias=None, *, out=None, epilogue=0, residual=None, colscale=None, out_scale=None, headmajor=None,
-               **kw):
-        assert out is not None and not kw, "the walk hands every linear its output buffer"
-
-        def call():
-            inside_linear[0] = True
-            try:
-                return real["linear"](x, w, bias, out=out, epilogue=epilogue, residual=residual, colscale=colscale,
-                                      out_scale=out_scale, headmajor=headmajor)
-            finally:
-                inside_linear[0] = False
-        return entry("linear", dict(x=x, w=w, bias=bias, residual=residual, colscale=colscale),
-                     dict(epilogue=epilogue, out_scale=out_scale, headmajor=headmajor), out, call)
-
-    def attention(qkv, out, B, N, heads, hd, out_scale=None, headmajor=False):
-        return entry("attention", dict(qkv=qkv), dict(B=B, N=N, heads=heads, hd=hd, out_scale=out_scale,
-                                                      headmajor=headmajor), out,
-                     lambda: real["attention"](qkv, out, B, N, heads, hd, out_scale=out_scale, headmajor=headmajor))
-
-    def gemm(A, W, out, **kw):
-        if inside_linear[0]:
-            return real["gemm"](A, W, out, **kw)
-        assert kw.get("rowbias") is not None, "a GEMM outside ops.linear that is not the patch embedding"
-        return entry("patch_embed", {}, {}, out, lambda: real["gemm"](A, W, out, **kw))
-
-    try:
-        for k, f in dict(layernorm=layernorm, linear=linear, attention=attention, gemm=gemm).items():
-            setattr(ops, k, f)
-        yield rec
-    finally:
-        for k, f in real.items():
-            setattr(ops, k, f)
 
 
 class Rig:
@@ -122,7 +65,7 @@ class Rig:
         return self.model.model._plan(self.xs["x1"].device)
 
     def forward(self, x):
-        with recording(self.ops) as rec, torch.no_grad():
+        with recording(self.ops, VIT_OPS) as rec, torch.no_grad():
             tok = self.model.model.forward_tokens(x).clone()
         torch.cuda.synchronize()
         return rec, tok
