@@ -368,6 +368,35 @@ int pp_dataset_ground_truth_affine(const float *kpts_raw, const float *kp_affine
                                    unsigned char *keypoints_visible, float *keypoints_visibility, void *stream);
 
 /* ------------------------------------------------------------------------
+ * The pixel steps behind the warp (Augment's blur_* / median_* / erase_* settings): a box or median
+ * blur, then coarse dropout, one launch for the batch.
+ *
+ * records [n, 24] int32 per sample: {kind, k, n_holes, fill (f32 bits), 4 x {x0, y0, x1, y1}, 4 x 0}.  in and out are
+ * [n, 3, in_h, in_w] f32, the warp's layout.  Per sample and channel, in this order:
+ *   1. filter (filters = 1 only).  kind 1: the mean of the k x k window in float32 (k * k - 1 additions, one division
+ *      by k * k).  kind 2: the median of the k x k window, an element of the window, so exact.  Both with reflect-101
+ *      borders: index -i reads i, index W - 1 + i reads W - 1 - i.  kind 0: a copy (its k is 0).
+ *   2. holes: every pixel inside any of the first n_holes half-open rectangles [x0, x1) x [y0, y1) becomes fill.
+ * filters = 0: the kind fields are not read and only the holes are written; in == out is allowed, and a workgroup
+ * whose PP_AUGMENT_POST_TILE_W x PP_AUGMENT_POST_TILE_H tile meets no hole writes nothing.  filters = 1 requires that
+ * in and out do not overlap.  128-bit stores where in_w % 4 == 0 and both buffers are 16-byte aligned, scalar stores
+ * otherwise.  No load leaves `in`, whatever the records hold.
+ *
+ * pp_augment_post refuses on the host, before any launch: null or misaligned (not 4-byte) buffers, n, in_w or in_h
+ * below 1, a mode other than 0 and 1, 2^31 or more elements, and the overlaps above.
+ *
+ * pp_augment_post_check (HOST, no GPU needed) refuses what the launch cannot check on device memory: a kind outside
+ * 0..2; a k that is even, not one of 3, 5, 7 (box) or 3, 5 (median), above min(in_w, in_h), or not 0 with kind 0;
+ * n_holes outside 0..4; one of the first n_holes rectangles that is empty or leaves the crop; a fill that is not
+ * finite; a non-zero reserved word; any kind != 0 when filters = 0.
+ * ---------------------------------------------------------------------- */
+#define PP_AUGMENT_POST_TILE_W 64
+#define PP_AUGMENT_POST_TILE_H 16
+int pp_augment_post_check(int n, const int *records, int in_w, int in_h, int filters);
+int pp_augment_post(const float *in, const int *records, int n, int in_w, int in_h, int filters, float *out,
+                    void *stream);
+
+/* ------------------------------------------------------------------------
  * Flip test at inference (ProbPoseModel(..., flip_pairs=...)).  float32 only.
  *
  * pp_hflip_pair: x [B,C,H,W] -> out [2B,C,H,W]: out[b] = x[b] and out[B + b, c, y, u] = x[b, c, y, W - 1 - u], the

@@ -102,6 +102,8 @@ _SIGNATURES = {
     "pp_augment_check": (C.c_int, [_i, _vp, C.c_longlong, _vp, _vp, _i, _vp]),
     "pp_augment_warp": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "pp_dataset_ground_truth_affine": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _f] + [_vp] * 7),
+    "pp_augment_post_check": (C.c_int, [_i, _vp, _i, _i, _i]),
+    "pp_augment_post": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "pp_hflip_pair": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "pp_flip_merge": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "pp_oks_heatmap_loss": (C.c_int, [_vp, _vp, _vp, _i, _vp, C.c_longlong, C.c_longlong, _i, _i] + [_f] * 4
@@ -165,6 +167,7 @@ _SIGNATURES = {
     "pp_viz_colorize": (C.c_int, [_vp, _vp, C.c_longlong, _i, _i, _vp, _i, _vp]),
 }
 PP_VIZ_MAX_SIDE = 8192
+PP_AUGMENT_POST_TILE_W, PP_AUGMENT_POST_TILE_H, PP_AUGMENT_POST_WORDS = 64, 16, 24
 PP_EMA_LERP_F32, PP_EMA_COPY_WORDS = 0, 1
 PP_COCO_GT_CROWD, PP_COCO_GT_NO_VISIBLE = 1, 2
 PP_POSENMS_HARD, PP_POSENMS_SOFT_GAUSSIAN, PP_POSENMS_SOFT_LINEAR = 0, 1, 2

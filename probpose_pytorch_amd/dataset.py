@@ -18,6 +18,11 @@ worker draws the sample's parameters from a counter-based generator keyed by (se
 rectangle of the transformed box; ``collate`` folds the geometry into two 2x3 matrices per sample and replaces launches
 one and two by ``pp_augment_warp`` (bilinear) and ``pp_dataset_ground_truth_affine`` (csrc/pp_augment.hip).  With
 ``augment=None`` nothing changes.
+
+``Augment`` has three more steps, off by default: a half-body crop replaces the sample's box in the worker
+before anything else looks at it; a box or median blur and random erasing ride along as one int32 record per sample
+(a sixth tuple entry) and cost one more launch, ``pp_augment_post`` (csrc/pp_augment_post.hip), between the warp and
+the keypoint kernel.
 """
 from __future__ import annotations
 
@@ -104,7 +109,24 @@ class Augment:
     n.x = -n.x; p = (n.x * bw * s, n.y * bh * s); the source point is centre + (tx * bw, ty * bh) + R(theta) p in image
     pixels with pixel centres at half-integers, R(theta) = [[cos, -sin], [sin, cos]].  The box is stretched to the
     input size as the un-augmented path stretches it; the rotation is a rotation in image space.  The pixels are
-    bilinear, not LANCZOS: identity parameters give the un-augmented geometry, not its bits."""
+    bilinear, not LANCZOS: identity parameters give the un-augmented geometry, not its bits.
+
+    Three more steps, all off by default:
+
+    half_body_prob, upper_body, half_body_min_keypoints, half_body_padding
+                 with probability half_body_prob a sample with at least half_body_min_keypoints labelled keypoints
+                 (v > 0) is cut around its upper body (the indices of ``upper_body``) or its lower body (every other
+                 index below K): see ``half_body_box``.  Every keypoint keeps its label; those outside the new crop
+                 come out with in_image = 0.
+    blur_prob, blur_kernel (lo, hi)
+                 box blur of the warped crop: the mean of a k x k window, k uniform over the odd sizes in [lo, hi]
+                 (3, 5, 7), reflect-101 borders
+    median_prob, median_kernel (lo, hi)
+                 median blur instead, sizes 3 and 5; blur_prob + median_prob <= 1, a sample gets at most one of them
+    erase_prob, erase_holes (lo, hi), erase_size (lo, hi), erase_fill
+                 with probability erase_prob, lo..hi rectangles (at most 4) of the crop are set to erase_fill, the
+                 width and the height of each an independent uniform fraction in erase_size of the crop's
+    Blur and erasing act on the pixels after the warp and change no label (``draw_post``)."""
     flip_pairs: Sequence[Tuple[int, int]] = ()
     flip_prob: float = 0.5
     scale: Tuple[float, float] = (0.75, 1.25)
@@ -114,6 +136,18 @@ class Augment:
     brightness: float = 0.2
     contrast: float = 0.2
     seed: int = 0
+    half_body_prob: float = 0.0
+    upper_body: Sequence[int] = ()
+    half_body_min_keypoints: int = 9
+    half_body_padding: float = 1.5
+    blur_prob: float = 0.0
+    blur_kernel: Tuple[int, int] = (3, 7)
+    median_prob: float = 0.0
+    median_kernel: Tuple[int, int] = (3, 5)
+    erase_prob: float = 0.0
+    erase_holes: Tuple[int, int] = (1, 1)
+    erase_size: Tuple[float, float] = (0.2, 0.4)
+    erase_fill: float = 0.0
 
     def __post_init__(self):
         object.__setattr__(self, "flip_pairs", tuple((int(i), int(j)) for i, j in self.flip_pairs))
@@ -124,6 +158,38 @@ class Augment:
             raise ValueError("Augment: flip_prob and rotate_prob are probabilities")
         if self.shift < 0 or self.brightness < 0 or self.contrast < 0 or self.rotate_deg < 0 or self.seed < 0:
             raise ValueError("Augment: shift, brightness, contrast, rotate_deg and seed must not be negative")
+        object.__setattr__(self, "upper_body", tuple(int(i) for i in self.upper_body))
+        object.__setattr__(self, "erase_size", (float(self.erase_size[0]), float(self.erase_size[1])))
+        object.__setattr__(self, "erase_fill", float(self.erase_fill))
+        for name in ("half_body_prob", "blur_prob", "median_prob", "erase_prob"):
+            if not 0 <= getattr(self, name) <= 1:
+                raise ValueError(f"Augment: {name}={getattr(self, name)} is not a probability")
+        if self.blur_prob + self.median_prob > 1:
+            raise ValueError("Augment: blur_prob + median_prob exceeds 1 (a sample gets one filter at most)")
+        for name, allowed in (("blur_kernel", (3, 5, 7)), ("median_kernel", (3, 5))):
+            lo, hi = getattr(self, name)
+            if lo != int(lo) or hi != int(hi) or int(lo) not in allowed or int(hi) not in allowed or lo > hi:
+                raise ValueError(f"Augment: {name}={(lo, hi)}; expected lo <= hi, both of the odd sizes {allowed}")
+            object.__setattr__(self, name, (int(lo), int(hi)))
+        lo, hi = self.erase_holes
+        if lo != int(lo) or hi != int(hi) or not 1 <= lo <= hi <= 4:
+            raise ValueError(f"Augment: erase_holes={(lo, hi)}; expected 1 <= lo <= hi <= 4")
+        object.__setattr__(self, "erase_holes", (int(lo), int(hi)))
+        if not 0 < self.erase_size[0] <= self.erase_size[1] <= 1:
+            raise ValueError(f"Augment: erase_size={self.erase_size}; expected 0 < lo <= hi <= 1")
+        if not math.isfinite(self.erase_fill) or not math.isfinite(float(np.float32(self.erase_fill))):
+            raise ValueError(f"Augment: erase_fill={self.erase_fill} is not a finite float32")
+        if self.half_body_prob > 0 and not self.upper_body:
+            raise ValueError("Augment: half_body_prob > 0 needs the keypoint indices of upper_body")
+        if any(i < 0 for i in self.upper_body) or len(set(self.upper_body)) != len(self.upper_body):
+            raise ValueError(f"Augment: upper_body={self.upper_body}; expected distinct indices, none negative")
+        if self.half_body_min_keypoints < 0 or not self.half_body_padding > 0:
+            raise ValueError("Augment: half_body_min_keypoints must not be negative and half_body_padding must be positive")
+
+    @property
+    def post(self) -> bool:
+        """Does a sample carry a ``draw_post`` record (any of blur, median blur and erasing switched on)?"""
+        return self.blur_prob > 0 or self.median_prob > 0 or self.erase_prob > 0
 
     def draw(self, epoch: int, idx: int) -> np.ndarray:
         """float64 [flip (0 or 1), s, theta (radians), tx, ty, c, b] of sample ``idx`` in epoch ``epoch``: a pure
@@ -136,6 +202,72 @@ class Augment:
                          (2.0 * r[4] - 1.0) * self.shift, (2.0 * r[5] - 1.0) * self.shift,
                          1.0 + (2.0 * r[6] - 1.0) * self.contrast, (2.0 * r[7] - 1.0) * self.brightness],
                         dtype=np.float64)
+
+    def _uniforms(self, epoch: int, idx: int, stream: int, count: int) -> np.ndarray:
+        """``count`` uniforms of sample ``idx`` in epoch ``epoch`` from the counter [epoch, idx, stream, 0]; stream 0
+        is ``draw``'s, so the streams here never change what ``draw`` returns."""
+        return np.random.Generator(np.random.Philox(key=int(self.seed),
+                                                    counter=[int(epoch), int(idx), int(stream), 0])).random(count)
+
+    def half_body_box(self, epoch: int, idx: int, keypoints, bbox) -> np.ndarray:
+        """float64 [x, y, w, h]: the box of sample ``idx`` in epoch ``epoch``, a pure function of (seed, epoch, idx)
+        and the sample's annotation.  Two uniforms from the counter [epoch, idx, 2, 0], whatever the settings.
+
+        The sample qualifies when r0 < half_body_prob and it has at least half_body_min_keypoints labelled keypoints
+        (v > 0).  With >= 2 labelled upper-body and >= 3 labelled lower-body keypoints the upper body is taken when
+        r1 < 0.7, else the lower; with only one half sufficient, that half; else, or when the sample does not
+        qualify, ``bbox`` is returned as it is.  The new box is centred on the midpoint of the extents of the chosen
+        labelled keypoints, each side max(extent * half_body_padding, 0.25 * the original side), and is not clipped
+        to the frame (the region crop pads with zero)."""
+        r = self._uniforms(epoch, idx, 2, 2)
+        bbox = np.array(bbox, dtype=np.float64).reshape(4)
+        kps = np.asarray(keypoints, dtype=np.float64).reshape(-1, 3)
+        K = kps.shape[0]
+        if any(i >= K for i in self.upper_body):
+            raise ValueError(f"Augment: upper_body={self.upper_body} names a keypoint outside 0..{K - 1}")
+        labelled = kps[:, 2] > 0
+        if not (r[0] < self.half_body_prob and int(labelled.sum()) >= self.half_body_min_keypoints):
+            return bbox
+        is_upper = np.zeros(K, dtype=bool)
+        is_upper[list(self.upper_body)] = True
+        upper, lower = labelled & is_upper, labelled & ~is_upper
+        upper_ok, lower_ok = int(upper.sum()) >= 2, int(lower.sum()) >= 3
+        if upper_ok and lower_ok:
+            chosen = upper if r[1] < 0.7 else lower
+        elif upper_ok or lower_ok:
+            chosen = upper if upper_ok else lower
+        else:
+            return bbox
+        lo, hi = kps[chosen, :2].min(0), kps[chosen, :2].max(0)
+        centre = (lo + hi) / 2
+        side = np.maximum((hi - lo) * self.half_body_padding, 0.25 * bbox[2:])
+        return np.concatenate([centre - side / 2, side])
+
+    def draw_post(self, epoch: int, idx: int, input_size) -> np.ndarray:
+        """int32 [24], the record of sample ``idx`` in epoch ``epoch`` that ``pp_augment_post`` takes: {kind, k,
+        n_holes, fill (float32 bits), 4 x {x0, y0, x1, y1}, 4 x 0}; kind 0 none (k = 0), 1 box blur, 2 median blur;
+        the rectangles half-open, in pixels of the in_w x in_h crop.  Twenty uniforms from the counter
+        [epoch, idx, 1, 0], whatever the settings: r0 the kind, r1 the size, r2 and r3 whether and how many holes,
+        r[4 + 4 j .. 7 + 4 j] width, height, x0 and y0 of hole j."""
+        r = self._uniforms(epoch, idx, 1, 20)
+        in_w, in_h = int(input_size[0]), int(input_size[1])
+        rec = np.zeros(24, dtype=np.int32)
+        kind = 1 if r[0] < self.blur_prob else 2 if r[0] < self.blur_prob + self.median_prob else 0
+        if kind:
+            lo, hi = self.blur_kernel if kind == 1 else self.median_kernel
+            sizes = list(range(lo, hi + 1, 2))
+            rec[0], rec[1] = kind, sizes[min(int(r[1] * len(sizes)), len(sizes) - 1)]
+        lo, hi = self.erase_holes
+        rec[2] = lo + min(int(r[3] * (hi - lo + 1)), hi - lo) if r[2] < self.erase_prob else 0
+        rec[3] = np.float32(self.erase_fill).view(np.int32)
+        elo, ehi = self.erase_size
+        for j in range(int(rec[2])):
+            rw, rh, rx, ry = r[4 + 4 * j:8 + 4 * j]
+            w = min(max(int(round((elo + rw * (ehi - elo)) * in_w)), 1), in_w)
+            h = min(max(int(round((elo + rh * (ehi - elo)) * in_h)), 1), in_h)
+            x0, y0 = min(int(rx * (in_w - w + 1)), in_w - w), min(int(ry * (in_h - h + 1)), in_h - h)
+            rec[4 + 4 * j:8 + 4 * j] = (x0, y0, x0 + w, y0 + h)
+        return rec
 
     def permutation(self, K: int) -> np.ndarray:
         """int32 [K]: the keypoint that output slot k of a flipped sample reads."""
@@ -232,17 +364,25 @@ class YOLOPoseDataset(Dataset):
     def __getitem__(self, idx):
         """CPU only.  Without ``augment``: ``plain_item(idx)``.  With it: (region, keypoints, bbox, origin, params),
         where params float64 (7,) is ``augment.draw(epoch, idx)``, region the uint8 (h, w, 3) pixels of ``image.crop``
-        of ``augment_region(bbox, params)`` (zero outside the frame) and origin int64 (2,) that rectangle's corner."""
+        of ``augment_region(bbox, params)`` (zero outside the frame) and origin int64 (2,) that rectangle's corner.
+        With ``augment.half_body_prob`` above 0, bbox is ``augment.half_body_box(epoch, idx, keypoints, bbox)`` here and
+        in everything after it.  With any of blur, median blur and erasing switched on, a sixth entry follows: the
+        int32 (24,) record ``augment.draw_post(epoch, idx, input size)``."""
         if getattr(self, "augment", None) is None:
             return self.plain_item(idx)
         ann = self.annotations[idx]
         bbox = np.asarray(ann["bbox"], dtype=np.float64)
+        keypoints = np.array(ann["keypoints"], dtype=np.float32).reshape(-1, 3)
+        if self.augment.half_body_prob > 0:
+            bbox = self.augment.half_body_box(self.epoch, idx, keypoints, bbox)
         params = self.augment.draw(self.epoch, idx)
         x0, y0, x1, y1 = augment_region(bbox, params)
         with PIL.Image.open(ann["image_path"]) as im:
             region = np.asarray(im.convert("RGB").crop((x0, y0, x1, y1)), dtype=np.uint8)
-        return (np.ascontiguousarray(region), np.array(ann["keypoints"], dtype=np.float32).reshape(-1, 3), bbox,
-                np.array([x0, y0], dtype=np.int64), params)
+        item = (np.ascontiguousarray(region), keypoints, bbox, np.array([x0, y0], dtype=np.int64), params)
+        if self.augment.post:
+            item += (self.augment.draw_post(self.epoch, idx, self._input_size()),)
+        return item
 
     def plain_item(self, idx):
         """CPU only.  Returns (region, keypoints, bbox): the uint8 (h, w, 3) pixels of ``image.crop`` of the rounded
@@ -279,6 +419,8 @@ class YOLOPoseDataset(Dataset):
     def _collate_device(self, samples):
         if len(samples) and len(samples[0]) == 5:
             return self._launch_augmented(*self._upload_augmented(samples))
+        if len(samples) and len(samples[0]) == 6:
+            return self._launch_post(*self._upload_post(samples))
         return self._launch(*self._upload(samples))
 
     def _pack(self, samples, fields):
@@ -363,20 +505,22 @@ class YOLOPoseDataset(Dataset):
             self._perm = (K, dev, perm, torch.from_numpy(perm).to(dev))
         return self._perm[2], self._perm[3]
 
-    def _upload_augmented(self, samples):
+    def _upload_augmented(self, samples, fields=5):
         """Host half of the augmented ``collate``: pack the regions (copy 1); build the source records, the two
-        matrices per sample in float64 and the keypoints into the meta buffer (copy 2); have the library check them."""
+        matrices per sample in float64 and the keypoints into the meta buffer (copy 2); have the library check them.
+        With ``fields=6`` (``_upload_post``) the samples' ``draw_post`` records follow the keypoints in copy 2."""
         _lib.require_device()
         if self.augment is None:
             raise ValueError("YOLOPoseDataset.collate: augmented samples, but the dataset has augment=None")
-        B, K, shapes, offs, total, d_src = self._pack(samples, 5)
+        B, K, shapes, offs, total, d_src = self._pack(samples, fields)
         perm, d_perm = self._permutation(K, d_src.device)
         # copy 2: [B x 4 i64 source records][B x 8 f64 pixel matrix, c, b][B x 8 f32 keypoint matrix, flip, 0][keypoints]
         params = np.stack([s[4] for s in samples])
         pixel, keypoint = augment_matrices(np.stack([s[2] for s in samples]), np.stack([s[3] for s in samples]),
                                            params, self._input_size())
         warp_off, aff_off, kp_off = 32 * B, 96 * B, 128 * B
-        meta_bytes = kp_off + 12 * B * K
+        post_off = kp_off + 12 * B * K
+        meta_bytes = post_off + (4 * _lib.PP_AUGMENT_POST_WORDS * B if fields == 6 else 0)
         slot = self._staging.take(meta_bytes)
         host = slot[0].numpy()
         host[:warp_off].view(np.int64).reshape(B, 4)[:] = [[off, w, h, 3 * w] for off, (h, w) in zip(offs, shapes)]
@@ -384,9 +528,15 @@ class YOLOPoseDataset(Dataset):
         warp[:, :6], warp[:, 6], warp[:, 7] = pixel.reshape(B, 6), params[:, 5], params[:, 6]
         aff = host[aff_off:kp_off].view(np.float32).reshape(B, 8)
         aff[:, :6], aff[:, 6], aff[:, 7] = keypoint.reshape(B, 6), params[:, 0], 0.0
-        host[kp_off:meta_bytes].view(np.float32).reshape(B, K, 3)[:] = [s[1] for s in samples]
+        host[kp_off:post_off].view(np.float32).reshape(B, K, 3)[:] = [s[1] for s in samples]
         base = slot[0].data_ptr()
         _lib.call("pp_augment_check", B, base, total, base + warp_off, base + aff_off, K, perm)
+        if fields == 6:
+            for s in samples:
+                if s[5].shape != (_lib.PP_AUGMENT_POST_WORDS,) or s[5].dtype != np.int32:
+                    raise ValueError(f"YOLOPoseDataset.collate: a post record of shape {s[5].shape}, dtype {s[5].dtype}")
+            host[post_off:meta_bytes].view(np.int32).reshape(B, _lib.PP_AUGMENT_POST_WORDS)[:] = [s[5] for s in samples]
+            _lib.call("pp_augment_post_check", B, base + post_off, *self._input_size(), self._post_filters())
         d_meta = torch.empty(meta_bytes, dtype=torch.uint8, device=d_src.device)
         d_meta.copy_(slot[0][:meta_bytes], non_blocking=True)
         slot[1].record()
@@ -400,6 +550,29 @@ class YOLOPoseDataset(Dataset):
         with torch.cuda.device(d_src.device):
             _lib.launch("pp_augment_warp", d_src, meta, meta + 32 * B, B, in_w, in_h, img)
         return self._ground_truth(img, B, K, "pp_dataset_ground_truth_affine", meta + 128 * B, meta + 96 * B, d_perm)
+
+    # ---- the augmented batch with blur / erasing: the records ride on copy 2, one launch more behind the warp ---------
+    def _post_filters(self):
+        """``pp_augment_post``'s mode: 1 when a sample can carry a filter, else 0 (holes only, in place)."""
+        return 1 if self.augment.blur_prob > 0 or self.augment.median_prob > 0 else 0
+
+    def _upload_post(self, samples):
+        """Host half of ``collate`` for 6-tuples: ``_upload_augmented`` with the records appended to copy 2, checked on
+        the host (``pp_augment_post_check``) before the copy is issued."""
+        return self._upload_augmented(samples, fields=6)
+
+    def _launch_post(self, d_src, d_meta, d_perm, B, K):
+        """Device half of ``collate`` for 6-tuples: warp, blur / holes, keypoints and flags, maps.  Holes alone are
+        written in place into the warp's output; a filter writes a second tensor, which becomes img."""
+        in_w, in_h = self._input_size()
+        meta = d_meta.data_ptr()
+        filters = self._post_filters()
+        img = torch.empty((B, 3, in_h, in_w), dtype=torch.float32, device=d_src.device)
+        out = torch.empty_like(img) if filters else img
+        with torch.cuda.device(d_src.device):
+            _lib.launch("pp_augment_warp", d_src, meta, meta + 32 * B, B, in_w, in_h, img)
+            _lib.launch("pp_augment_post", img, meta + 128 * B + 12 * B * K, B, in_w, in_h, filters, out)
+        return self._ground_truth(out, B, K, "pp_dataset_ground_truth_affine", meta + 128 * B, meta + 96 * B, d_perm)
 
     def loader(self, batch_size, shuffle=False, num_workers=0, **kw):
         """A DataLoader over this dataset whose batches are ``collate``'s.  The workers do file reading, decoding and

@@ -15,7 +15,11 @@ from a seeded 1080p frame (what `__getitem__` hands over), held in memory: no fi
 `--augment` adds the augmented batch (Augment defaults with shift 0.1 and eight flip pairs; the regions are the bounding
 rectangles of the transformed boxes, cut from the same frame) to the same process, its windows alternating with the
 un-augmented ones: the three launches together and one by one (warp, keypoints, maps; the LANCZOS launch it replaces
-beside the warp), a whole collate() in HIP-event and in host time, and the warp's store bandwidth.
+beside the warp), a whole collate() in HIP-event and in host time, and the warp's store bandwidth.  Behind the warp
+window of the same run it times the blur / erasing launch (pp_augment_post) on the warp's output in three
+variants: erase-only in place (one hole per sample of Augment's default erase_size), a 7x7 box blur of every sample
+and a 5x5 median of every sample, both into a second tensor; and a whole collate() of 6-tuples with blur, median blur
+and erasing switched on.
 """
 import argparse
 import json
@@ -124,7 +128,25 @@ def main():
         for _ in range(args.warmup):
             ds.collate(aug_samples)
         torch.cuda.synchronize()
-        aug = dict(device=[], copies=[], host=[], warp=[], keypoints=[], maps=[], lanczos=[])
+        aug = dict(device=[], copies=[], host=[], warp=[], keypoints=[], maps=[], lanczos=[], erase=[], box7=[],
+                   median5=[], post_host=[], post_copies=[])
+        eraser = Augment(erase_prob=1.0)
+        post_records = dict(
+            erase=np.stack([eraser.draw_post(0, i, INPUT) for i in range(B)]),
+            box7=np.tile(np.array([1, 7] + [0] * 22, dtype=np.int32), (B, 1)),
+            median5=np.tile(np.array([2, 5] + [0] * 22, dtype=np.int32), (B, 1)))
+        for name, rec in post_records.items():
+            _lib.call("pp_augment_post_check", B, rec, INPUT[0], INPUT[1], 0 if name == "erase" else 1)
+        d_records = {name: torch.from_numpy(rec).cuda() for name, rec in post_records.items()}
+        post_ds = YOLOPoseDataset.__new__(YOLOPoseDataset)
+        post_ds.__dict__.update(ds.__dict__)
+        post_ds._staging, post_ds._perm = PinnedStaging(), None
+        post_ds.augment = Augment(flip_pairs=ds.augment.flip_pairs, shift=0.1, blur_prob=0.3, median_prob=0.3,
+                                  erase_prob=0.5, erase_holes=(1, 4))
+        post_samples = [s + (post_ds.augment.draw_post(0, i, INPUT),) for i, s in enumerate(aug_samples)]
+        for _ in range(args.warmup):
+            post_ds.collate(post_samples)
+        torch.cuda.synchronize()
         L, pm = _lib.lib(), ds.codec.probmap
         sx, sy = (float(v) for v in np.asarray(pm.scale_factor, dtype=np.float32))
 
@@ -151,6 +173,12 @@ def main():
             aug["device"].append(window(lambda: ds._launch_augmented(*up_a)))
             aug["warp"].append(window(lambda: L.pp_augment_warp(_lib.ptr(d_src), meta, meta + 32 * B, B, INPUT[0],
                                                                 INPUT[1], _lib.ptr(img), _lib.stream_ptr())))
+            img2 = torch.empty_like(img)
+            aug["erase"].append(window(lambda: L.pp_augment_post(_lib.ptr(img), _lib.ptr(d_records["erase"]), B, INPUT[0],
+                                                                 INPUT[1], 0, _lib.ptr(img), _lib.stream_ptr())))
+            for name in ("box7", "median5"):
+                aug[name].append(window(lambda: L.pp_augment_post(_lib.ptr(img), _lib.ptr(d_records[name]), B, INPUT[0],
+                                                                  INPUT[1], 1, _lib.ptr(img2), _lib.stream_ptr())))
             aug["lanczos"].append(window(lambda: frontend.crop_resize_multi(up_plain[0], up_plain[1], B, up_plain[4],
                                                                             up_plain[5], INPUT)))
             aug["keypoints"].append(window(lambda: L.pp_dataset_ground_truth_affine(
@@ -170,6 +198,17 @@ def main():
             aug["host"].append((t1 - t0) * 1e3 / args.steps)
             aug["copies"].append(a.elapsed_time(b) / args.steps)
             aug["bytes"] = (int(d_src.numel()), int(d_meta.numel()))
+            torch.cuda.synchronize()
+            a, b = ev(), ev()
+            t0 = time.perf_counter()
+            a.record()
+            for _ in range(args.steps):
+                post_ds.collate(post_samples)
+            b.record()
+            t1 = time.perf_counter()
+            b.synchronize()
+            aug["post_host"].append((t1 - t0) * 1e3 / args.steps)
+            aug["post_copies"].append(a.elapsed_time(b) / args.steps)
         up = ds._upload(samples)
         torch.cuda.synchronize()
         a, b = ev(), ev()
@@ -212,6 +251,15 @@ def main():
             maps=stats(aug["maps"]), device_collate_with_copies=stats(aug["copies"]),
             host_collate_wall=stats(aug["host"]),
             warp_store_TB_per_s=round(image_bytes / (statistics.median(aug["warp"]) * 1e-3) / 1e12, 3))
+        warp_ms = statistics.median(aug["warp"])
+        res["augment"]["post"] = dict(
+            erase_only_in_place=stats(aug["erase"]), box_k7=stats(aug["box7"]), median_k5=stats(aug["median5"]),
+            ratio_to_warp={k: round(statistics.median(aug[k]) / warp_ms, 3) for k in ("erase", "box7", "median5")},
+            box_k7_read_plus_write_TB_per_s=round(2 * image_bytes / (statistics.median(aug["box7"]) * 1e-3) / 1e12, 3),
+            median_k5_read_plus_write_TB_per_s=round(2 * image_bytes / (statistics.median(aug["median5"]) * 1e-3) / 1e12,
+                                                     3),
+            settings=dict(blur_prob=0.3, median_prob=0.3, erase_prob=0.5, erase_holes=[1, 4]),
+            device_collate_with_copies=stats(aug["post_copies"]), host_collate_wall=stats(aug["post_host"]))
     line = json.dumps(res)
     print(line)
     if args.out:
