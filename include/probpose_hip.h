@@ -897,6 +897,48 @@ int pp_track_assign_optimal(int n_str, int K, int max_tracks, long long Dtot, co
                             void *slot_of, void *te, void *total, void *stream);
 
 /* ------------------------------------------------------------------------
+ * Motion prediction and the low-score second pass (PoseTracker(predict=..., high_thr=..., birth_thr=...), DESIGN
+ * §4.7i).  Each entry stands in for one of the three launches of an update; the state block does not change.
+ *
+ * pp_track_oks_predicted: pp_track_oks with the slot's pose moved to time t by the speed of its One-Euro filter.  For
+ *   a live slot j and keypoint k, e = j K + k, float64, every step one IEEE basic operation, unfused:
+ *     dt = t - t_last[j]; if dt > max_dt then dt = max_dt           (pp_track_boxes' step 3; max_dt = +inf is allowed)
+ *     p_c = init[e] ? xhat[2e+c] + dxhat[2e+c] * dt : kp[2e+c]      (the product, then the sum, per coordinate c)
+ *   and the pair OKS takes p in place of the slot's stored raw keypoints; the slot's stored visibilities and area are
+ *   used as in pp_track_oks, a free slot gives 0.  One lane per pair, the same grid.
+ *   Refused on the host like pp_track_oks, and also: t not finite, max_dt negative or NaN.
+ *
+ * pp_track_assign_staged: pp_track_assign in two stages by detection score, with births gated by score.  score f64
+ *   [Dtot] in visiting order (descending within a stream, so the detections with score >= high_thr are a prefix of
+ *   their stream: n_high of them); dropped uint8 [Dtot]; the other arguments and outputs are pp_track_assign's.
+ *   Per stream, with "live" and "age" as they are when the call begins:
+ *     stage 1: rows are detections 0 .. n_high-1, columns the live slots, the threshold is match_thr;
+ *     stage 2: rows are detections n_high .. D-1, columns the live slots that stage 1 did not take and whose
+ *       age <= low_max_age, the threshold is low_match_thr.
+ *   Within a stage, optimal = 0: each row in turn takes the column not yet taken with the largest OKS (the lowest slot
+ *   on equal OKS) if that OKS is > the threshold (pp_track_assign's rule).  optimal = 1: the rows take the columns by
+ *   pp_track_assign_optimal's steps 1 - 3 with m = max(rows of the stage, T), q = 0 for a slot that is not a column of
+ *   the stage and the stage's threshold in place of match_thr; the stages are solved one after the other.
+ *   Then ageing as in pp_track_assign (every live slot taken in neither stage).  Then each unmatched detection with
+ *   score >= birth_thr, in visiting order, takes the lowest free slot with id = next_id++, or none (overflow += 1).
+ *   Every other unmatched detection is dropped: ids = -1, match_oks = 0, born = 0, slot_of = -1, te = 0, dropped = 1,
+ *   and overflow does not count it; dropped = 0 for every other detection.  high_thr = birth_thr = -inf is
+ *   pp_track_assign (optimal = 0) or pp_track_assign_optimal (optimal = 1) bit for bit.
+ *   Refused on the host like pp_track_assign, and also: high_thr or birth_thr NaN, low_match_thr outside [0, 1),
+ *   low_max_age < 0, optimal neither 0 nor 1, and with optimal = 1 max_tracks or a stream's detections above
+ *   PP_TRACK_OPT_MAX.
+ * ---------------------------------------------------------------------- */
+int pp_track_oks_predicted(int n_str, int K, int max_tracks, long long Dtot, const long long *host_off,
+                           const void *det_stream, const void *blocks, const void *kpts, const void *vis,
+                           const void *area, const void *vars, double vis_thr, double t, double max_dt, void *oks,
+                           void *stream);
+int pp_track_assign_staged(int n_str, int K, int max_tracks, long long Dtot, const long long *host_off,
+                           const void *off, const void *blocks, const void *oks, const void *area, const void *score,
+                           double match_thr, double high_thr, double low_match_thr, int low_max_age, double birth_thr,
+                           int optimal, int max_age, double t, double t_prev, void *ids, void *match_oks, void *born,
+                           void *slot_of, void *te, void *dropped, void *stream);
+
+/* ------------------------------------------------------------------------
  * Track-driven person boxes (PoseTracker.propose_boxes): the tracker's state read back out as the box
  * each track's person is expected in at time t, one launch, one lane per (stream, slot) with a serial loop over the
  * slot's K keypoints.  It writes no state; no atomics, no LDS, no barrier, plain vector stores: the same bits on every

@@ -152,6 +152,9 @@ _SIGNATURES = {
     "pp_track_oks": (C.c_int, [_i, _i, _i, C.c_longlong] + [_vp] * 7 + [_d, _vp, _vp]),
     "pp_track_assign": (C.c_int, [_i, _i, _i, C.c_longlong] + [_vp] * 5 + [_d, _i, _d, _d] + [_vp] * 6),
     "pp_track_assign_optimal": (C.c_int, [_i, _i, _i, C.c_longlong] + [_vp] * 5 + [_d, _i, _d, _d] + [_vp] * 7),
+    "pp_track_oks_predicted": (C.c_int, [_i, _i, _i, C.c_longlong] + [_vp] * 7 + [_d, _d, _d, _vp, _vp]),
+    "pp_track_assign_staged": (C.c_int, [_i, _i, _i, C.c_longlong] + [_vp] * 6 + [_d, _d, _d, _i, _d, _i, _i, _d, _d]
+                               + [_vp] * 7),
     "pp_track_filter": (C.c_int, [_i, _i, C.c_longlong] + [_vp] * 4 + [_d] + [_vp] * 3 + [_i, _d, _d, _d, _vp, _vp]),
     "pp_track_boxes": (C.c_int, [_i, _i, _i, _vp, _d, _i, _d, _i, _i, _d, _i, _i, _d, _d, _d] + [_vp] * 4 + [_d]
                        + [_vp] * 5),

@@ -1,7 +1,8 @@
 // What the association kernels share (pp_posenms.hip, pp_track.hip, pp_trackeval.hip), each written once:
 //
 //   pair_oks    the pair OKS of DESIGN §4.7c, the gauges' operations in the gauges' order.  The library is compiled
-//               -ffp-contract=off, which is what keeps these the gauges' bits up to exp().
+//               -ffp-contract=off, which is what keeps these the gauges' bits up to exp().  pair_oks_of is the loop
+//               itself, over how the second pose's coordinates are had (stored, or a track's predicted ones).
 //   sap_solve   the shortest-augmenting-path solver of DESIGN §4.7f (the rule: include/probpose_hip.h,
 //               tests/trackopt_reference.py): a device template over the number of columns NC a lane owns (lane j % 64
 //               owns column j) and over how the weights of a row are fetched.  v, minv, way, the used bits, the held
@@ -18,22 +19,32 @@
 
 namespace pp {
 
-// OKS of detections a (the pivot) and b of one image; vis_a == nullptr: every keypoint counts
-__device__ __forceinline__ double pair_oks(int K, const double *__restrict__ ka, const double *__restrict__ kb,
-                                           const double *__restrict__ vis_a, const double *__restrict__ vis_b,
-                                           double vis_thr, double area_a, double area_b,
-                                           const double *__restrict__ vars) {
+// The pair loop: OKS of detection a (the pivot) and a second pose whose keypoint k has the coordinates b(k, 0) and
+// b(k, 1); vis_a == nullptr: every keypoint counts
+template <typename Second>
+__device__ __forceinline__ double pair_oks_of(int K, const double *__restrict__ ka, const Second &b,
+                                              const double *__restrict__ vis_a, const double *__restrict__ vis_b,
+                                              double vis_thr, double area_a, double area_b,
+                                              const double *__restrict__ vars) {
   const double size = (area_a + area_b) / 2.0 + DBL_EPSILON;
   double sum = 0.0;
   int n = 0;
   for (int k = 0; k < K; ++k) {
     if (vis_a && !(vis_a[k] > vis_thr && vis_b[k] > vis_thr)) continue;
-    const double dx = ka[2 * k] - kb[2 * k], dy = ka[2 * k + 1] - kb[2 * k + 1];
+    const double dx = ka[2 * k] - b(k, 0), dy = ka[2 * k + 1] - b(k, 1);
     const double e = (dx * dx + dy * dy) / vars[k] / size / 2.0;
     sum += exp(-e);
     ++n;
   }
   return n ? sum / (double)n : 0.0;
+}
+
+// OKS of detections a (the pivot) and b of one image
+__device__ __forceinline__ double pair_oks(int K, const double *__restrict__ ka, const double *__restrict__ kb,
+                                           const double *__restrict__ vis_a, const double *__restrict__ vis_b,
+                                           double vis_thr, double area_a, double area_b,
+                                           const double *__restrict__ vars) {
+  return pair_oks_of(K, ka, [kb](int k, int c) { return kb[2 * k + c]; }, vis_a, vis_b, vis_thr, area_a, area_b, vars);
 }
 
 constexpr long long kSapInf = 1ll << 62;

@@ -21,9 +21,17 @@
 //                        its v, minv, way, used bit, the row it holds and that row's u are registers of that lane; a
 //                        step is one coalesced load of the scanned row's OKS (a row's first step: loaded a row ahead)
 //                        and one wave_argmin_i64.  The loop is pp_assoc.h's sap_solve statement for statement, kept
-//                        written out here for the row-ahead load (the header says what calling sap_solve cost); the
+//                        written out here, in track_optimal_rows, for the row-ahead load (the header says what calling
+//                        sap_solve cost; the function takes a row range, a column mask and a threshold, so that the
+//                        staged kernel runs the same statements once per stage); the
 //                        shuffle sap_fetch and the constants are the header's.  Ageing, births and the matched pair's
 //                        stores are the greedy kernel's own functions.
+//   track_oks_predicted_kernel   track_oks_kernel with the slot's pose moved to the call's time by its One-Euro speed
+//                        (DESIGN §4.7i): both are track_oks_lane, the pair loop is pp_assoc.h's pair_oks_of.
+//   track_assign_staged_kernel   the launch shape, layout and outputs of track_assign_kernel with the association in
+//                        two stages by score and births gated by score (§4.7i).  A stage is track_greedy_rows, the
+//                        greedy kernel's own walk, or track_optimal_rows, the optimal kernel's own loop on the stage's
+//                        rows and column mask; ageing and births are track_age_and_bear.
 //   track_filter_kernel  one lane per (detection, keypoint): reads the slot the assign kernel gave the detection, applies
 //                        the One-Euro step (or initialises, or passes the raw value through) and writes the output, the
 //                        filter state and the slot's raw keypoint and visibility.  A slot belongs to at most one
@@ -76,10 +84,15 @@ __device__ __forceinline__ TrackState track_state(long long base, int T, int K) 
   return s;
 }
 
-__global__ __launch_bounds__(kTrackThreads) void track_oks_kernel(
-    int K, int T, long long Dtot, const long long *__restrict__ det_stream, const long long *__restrict__ blocks,
-    const double *__restrict__ kpts, const double *__restrict__ vis, const double *__restrict__ area,
-    const double *__restrict__ vars, double vis_thr, double *__restrict__ oks) {
+// The lane of pair i = (detection d, slot j) of both OKS kernels.  kPredict: the slot's pose is where its One-Euro
+// filter expects it at time t (the two statements of track_boxes_kernel for dt, then one multiply and one add per
+// coordinate), the stored raw keypoint where the filter holds nothing for it; otherwise the stored raw keypoints.
+template <bool kPredict>
+__device__ __forceinline__ void track_oks_lane(int K, int T, long long Dtot, const long long *__restrict__ det_stream,
+                                               const long long *__restrict__ blocks, const double *__restrict__ kpts,
+                                               const double *__restrict__ vis, const double *__restrict__ area,
+                                               const double *__restrict__ vars, double vis_thr, double t, double max_dt,
+                                               double *__restrict__ oks) {
   const long long i = (long long)blockIdx.x * kTrackThreads + threadIdx.x;
   if (i >= Dtot * T) return;
   const long long d = i / T;
@@ -89,9 +102,35 @@ __global__ __launch_bounds__(kTrackThreads) void track_oks_kernel(
     oks[i] = 0.0;
     return;
   }
-  const double *ka = kpts + d * K * 2, *kb = st.kp + (long long)j * K * 2;
-  const double *va = vis ? vis + d * K : nullptr, *vb = st.vis + (long long)j * K;
-  oks[i] = pair_oks(K, ka, kb, va, vb, vis_thr, area[d], st.area[j], vars);   // the detection as the pivot
+  const long long e0 = (long long)j * K;
+  const double *ka = kpts + d * K * 2, *kb = st.kp + e0 * 2;
+  const double *va = vis ? vis + d * K : nullptr, *vb = st.vis + e0;
+  if constexpr (kPredict) {
+    double dt = t - st.t_last[j];
+    if (dt > max_dt) dt = max_dt;
+    const double *xh = st.xhat + e0 * 2, *dxh = st.dxhat + e0 * 2;
+    const unsigned char *init = st.init + e0;
+    const auto expected = [=](int k, int c) {
+      return init[k] ? xh[2 * k + c] + dxh[2 * k + c] * dt : kb[2 * k + c];
+    };
+    oks[i] = pair_oks_of(K, ka, expected, va, vb, vis_thr, area[d], st.area[j], vars);
+  } else {
+    oks[i] = pair_oks(K, ka, kb, va, vb, vis_thr, area[d], st.area[j], vars);   // the detection as the pivot
+  }
+}
+
+__global__ __launch_bounds__(kTrackThreads) void track_oks_kernel(
+    int K, int T, long long Dtot, const long long *__restrict__ det_stream, const long long *__restrict__ blocks,
+    const double *__restrict__ kpts, const double *__restrict__ vis, const double *__restrict__ area,
+    const double *__restrict__ vars, double vis_thr, double *__restrict__ oks) {
+  track_oks_lane<false>(K, T, Dtot, det_stream, blocks, kpts, vis, area, vars, vis_thr, 0.0, 0.0, oks);
+}
+
+__global__ __launch_bounds__(kTrackThreads) void track_oks_predicted_kernel(
+    int K, int T, long long Dtot, const long long *__restrict__ det_stream, const long long *__restrict__ blocks,
+    const double *__restrict__ kpts, const double *__restrict__ vis, const double *__restrict__ area,
+    const double *__restrict__ vars, double vis_thr, double t, double max_dt, double *__restrict__ oks) {
+  track_oks_lane<true>(K, T, Dtot, det_stream, blocks, kpts, vis, area, vars, vis_thr, t, max_dt, oks);
 }
 
 // What the lanes of a stream's wave share between the association modes.  The per-detection outputs of the assign
@@ -191,6 +230,41 @@ __device__ __forceinline__ void track_slot_masks(const TrackState &st, int lane,
   }
 }
 
+// The greedy walk of §4.7d over the stream's detections p0 .. p1-1 in visiting order: each takes, among the lane-owned
+// slots of `cols` not yet taken, the one with the largest OKS (the lowest on equal OKS) if that OKS is > thr, and is
+// marked unmatched otherwise.
+__device__ __forceinline__ void track_greedy_rows(const TrackState &st, const TrackOut &out, int lane, long long d0,
+                                                  int p0, int p1, int T, const double *__restrict__ oks,
+                                                  unsigned long long cols, double thr, unsigned long long &taken,
+                                                  unsigned long long &unmatched) {
+  for (int p = p0; p < p1; ++p) {
+    const double *row = oks + (d0 + p) * T;
+    double best = -INFINITY;
+    int best_j = INT_MAX;
+    unsigned long long cand = cols & ~taken;
+    while (cand) {                                        // ascending slots: the lowest of the lane's on equal OKS
+      const int s = __builtin_ctzll(cand);
+      cand &= cand - 1;
+      const int j = s * 64 + lane;
+      const double v = row[j];
+      if (v > best) {
+        best = v;
+        best_j = j;
+      }
+    }
+    const double top = wave_max(best);
+    const int pick = wave_min(best_j != INT_MAX && best == top ? best_j : INT_MAX);
+    if (pick != INT_MAX && top > thr) {                   // wave-uniform
+      if (lane == (pick & 63)) {
+        taken |= 1ull << (pick >> 6);
+        track_take(st, out, d0 + p, pick, top);
+      }
+    } else if (lane == (p & 63)) {
+      unmatched |= 1ull << (p >> 6);
+    }
+  }
+}
+
 __global__ __launch_bounds__(64 * kTrackWaves) void track_assign_kernel(
     int n_str, int K, int T, const long long *__restrict__ off, const long long *__restrict__ blocks,
     const double *__restrict__ oks, const double *__restrict__ area, double match_thr, int max_age, double t,
@@ -209,34 +283,7 @@ __global__ __launch_bounds__(64 * kTrackWaves) void track_assign_kernel(
   // detections p with p % 64 == lane are unmatched
   unsigned long long valid, live, taken = 0, unmatched = 0;
   track_slot_masks(st, lane, T, valid, live);
-
-  // association: the detections in visiting order
-  for (int p = 0; p < D; ++p) {
-    const double *row = oks + (d0 + p) * T;
-    double best = -INFINITY;
-    int best_j = INT_MAX;
-    unsigned long long cand = live & ~taken;
-    while (cand) {                                        // ascending slots: the lowest of the lane's on equal OKS
-      const int s = __builtin_ctzll(cand);
-      cand &= cand - 1;
-      const int j = s * 64 + lane;
-      const double v = row[j];
-      if (v > best) {
-        best = v;
-        best_j = j;
-      }
-    }
-    const double top = wave_max(best);
-    const int pick = wave_min(best_j != INT_MAX && best == top ? best_j : INT_MAX);
-    if (pick != INT_MAX && top > match_thr) {             // wave-uniform
-      if (lane == (pick & 63)) {
-        taken |= 1ull << (pick >> 6);
-        track_take(st, out, d0 + p, pick, top);
-      }
-    } else if (lane == (p & 63)) {
-      unmatched |= 1ull << (p >> 6);
-    }
-  }
+  track_greedy_rows(st, out, lane, d0, 0, D, T, oks, live, match_thr, taken, unmatched);
   track_age_and_bear(st, out, lane, d0, D, max_age, valid, live, taken, unmatched);
 }
 
@@ -256,22 +303,19 @@ __device__ __forceinline__ void opt_load_row(const double *row, int lane, unsign
   for (int s = 0; s < kOptCols; ++s) x[s] = ((live >> s) & 1ull) ? row[s * 64 + lane] : 0.0;
 }
 
-__global__ __launch_bounds__(64 * kTrackWaves) void track_assign_optimal_kernel(
-    int n_str, int K, int T, const long long *__restrict__ off, const long long *__restrict__ blocks,
-    const double *__restrict__ oks, const double *__restrict__ area, double match_thr, int max_age, double t,
-    long long *__restrict__ ids, double *__restrict__ match_oks, unsigned char *__restrict__ born,
-    int *__restrict__ slot_of, double *__restrict__ te, long long *__restrict__ total) {
-  const long long str = (long long)blockIdx.x * kTrackWaves + (threadIdx.x >> 6);
-  if (str >= n_str) return;
-  const int lane = threadIdx.x & 63;
-  const long long d0 = off[str], span = off[str + 1] - d0;
-  if (span < 0 || span > PP_TRACK_OPT_MAX || T < 1 || T > PP_TRACK_OPT_MAX) return;   // refused on the host
-  const int D = (int)span, m = D > T ? D : T, cols = (m + 63) >> 6;
-  const TrackState st = track_state(blocks[str], T, K);
-  const TrackOut out{area, t, ids, match_oks, born, slot_of, te};
-
-  unsigned long long valid, live, taken = 0, unmatched = 0;
-  track_slot_masks(st, lane, T, valid, live);
+// The matching of largest total weight between the stream's detections p0 .. p1-1 (the rows, in visiting
+// order) and the lane-owned slots of `live` (bit s: slot s * 64 + lane is a column; every other column weighs
+// nothing), m = max(rows, T), with track_weight at match_thr.  Matched pairs are stored by the slot's lane and marked
+// in `taken`; the rows left over are marked in `unmatched` (bit p / 64 of lane p % 64).  Returns the lane's share of
+// the sum of q over the matched pairs.  track_assign_optimal_kernel runs it on every row and every live slot, the
+// staged kernel once per stage.
+__device__ __forceinline__ long long track_optimal_rows(const TrackState &st, const TrackOut &out, int lane,
+                                                        long long d0, int p0, int p1, int T,
+                                                        const double *__restrict__ oks, unsigned long long live,
+                                                        double match_thr, unsigned long long &taken,
+                                                        unsigned long long &unmatched) {
+  const int D = p1 - p0, m = D > T ? D : T, cols = (m + 63) >> 6;
+  const double *rows = oks + (d0 + p0) * T;
 
   // lane-owned, column s * 64 + lane in element s: the potential v, the row the column holds (-1: none) and that
   // row's potential u (a row's u travels with the column that holds it; a row not yet added has u = 0)
@@ -286,11 +330,11 @@ __global__ __launch_bounds__(64 * kTrackWaves) void track_assign_optimal_kernel(
   // the OKS of the scanned row at the lane's columns.  A row's first step always scans that row itself, so its OKS are
   // loaded one row ahead, behind the previous row's path; only the later steps wait for a load their row index needs
   double x[kOptCols], ahead[kOptCols];
-  if (D > 0) opt_load_row(oks + d0 * T, lane, live, ahead);
+  if (D > 0) opt_load_row(rows, lane, live, ahead);
   for (int i = 0; i < D; ++i) {                           // the rows in visiting order, one augmenting path each
 #pragma unroll
     for (int s = 0; s < kOptCols; ++s) x[s] = ahead[s];
-    if (i + 1 < D) opt_load_row(oks + (d0 + i + 1) * T, lane, live, ahead);
+    if (i + 1 < D) opt_load_row(rows + (long long)(i + 1) * T, lane, live, ahead);
     long long minv[kOptCols];
     int way[kOptCols];
     unsigned used = 0;                                    // bit s: the lane's column s is on the tree
@@ -304,7 +348,7 @@ __global__ __launch_bounds__(64 * kTrackWaves) void track_assign_optimal_kernel(
     bool open = false;
     for (int step = 0; step <= m; ++step) {               // every step marks one more column: at most m + 1
       if (cur != kSapRoot && lane == (cur & 63)) used |= 1u << (cur >> 6);
-      if (step > 0) opt_load_row(oks + (d0 + i0) * T, lane, live, x);
+      if (step > 0) opt_load_row(rows + (long long)i0 * T, lane, live, x);
       long long delta = LLONG_MAX;
       int j1 = INT_MAX;
 #pragma unroll
@@ -370,12 +414,12 @@ __global__ __launch_bounds__(64 * kTrackWaves) void track_assign_optimal_kernel(
   for (int s = 0; s < kOptCols; ++s) {
     const int j = s * 64 + lane;
     if (j < T && ((live >> s) & 1ull) && held[s] >= 0) {
-      const double x = oks[(d0 + held[s]) * T + j];
+      const double x = rows[(long long)held[s] * T + j];
       const long long q = track_weight(x, match_thr);
       if (q > 0) {
         sum += q;
         taken |= 1ull << s;
-        track_take(st, out, d0 + held[s], j, x);
+        track_take(st, out, d0 + p0 + held[s], j, x);
       } else {
         held[s] = -1;
       }
@@ -383,15 +427,97 @@ __global__ __launch_bounds__(64 * kTrackWaves) void track_assign_optimal_kernel(
       held[s] = -1;
     }
   }
-  sum = wave_sum_i64(sum);
-  if (total && lane == 0) total[str] = sum;
   for (int p = 0; p < D; ++p) {
     bool mine = false;
 #pragma unroll
     for (int s = 0; s < kOptCols; ++s) mine |= held[s] == p;
-    if (!__any(mine) && lane == (p & 63)) unmatched |= 1ull << (p >> 6);
+    if (!__any(mine) && lane == ((p0 + p) & 63)) unmatched |= 1ull << ((p0 + p) >> 6);
   }
+  return sum;
+}
+
+__global__ __launch_bounds__(64 * kTrackWaves) void track_assign_optimal_kernel(
+    int n_str, int K, int T, const long long *__restrict__ off, const long long *__restrict__ blocks,
+    const double *__restrict__ oks, const double *__restrict__ area, double match_thr, int max_age, double t,
+    long long *__restrict__ ids, double *__restrict__ match_oks, unsigned char *__restrict__ born,
+    int *__restrict__ slot_of, double *__restrict__ te, long long *__restrict__ total) {
+  const long long str = (long long)blockIdx.x * kTrackWaves + (threadIdx.x >> 6);
+  if (str >= n_str) return;
+  const int lane = threadIdx.x & 63;
+  const long long d0 = off[str], span = off[str + 1] - d0;
+  if (span < 0 || span > PP_TRACK_OPT_MAX || T < 1 || T > PP_TRACK_OPT_MAX) return;   // refused on the host
+  const int D = (int)span;
+  const TrackState st = track_state(blocks[str], T, K);
+  const TrackOut out{area, t, ids, match_oks, born, slot_of, te};
+
+  unsigned long long valid, live, taken = 0, unmatched = 0;
+  track_slot_masks(st, lane, T, valid, live);
+  const long long sum = wave_sum_i64(track_optimal_rows(st, out, lane, d0, 0, D, T, oks, live, match_thr, taken,
+                                                         unmatched));
+  if (total && lane == 0) total[str] = sum;
   track_age_and_bear(st, out, lane, d0, D, max_age, valid, live, taken, unmatched);
+}
+
+// ---- the staged association (the rule: include/probpose_hip.h, tests/trackstage_reference.py) ---------
+// One wave per stream, the launch shape and lane-owns-slot layout of track_assign_kernel.  Stage 1: the detections
+// with score >= high_thr (a prefix of the visiting order) on the slots live at entry, at match_thr.  Stage 2: the
+// others on the live slots stage 1 left that had age <= low_max_age at entry, at low_match_thr.  Each stage is the
+// greedy walk or (kOptimal) the optimal matching.  Then the unmatched detections below birth_thr are dropped, by the
+// lane that owns their unmatched bit, and ageing and births follow for the rest.
+template <bool kOptimal>
+__global__ __launch_bounds__(64 * kTrackWaves) void track_assign_staged_kernel(
+    int n_str, int K, int T, const long long *__restrict__ off, const long long *__restrict__ blocks,
+    const double *__restrict__ oks, const double *__restrict__ area, const double *__restrict__ score,
+    double match_thr, double high_thr, double low_match_thr, int low_max_age, double birth_thr, int max_age, double t,
+    long long *__restrict__ ids, double *__restrict__ match_oks, unsigned char *__restrict__ born,
+    int *__restrict__ slot_of, double *__restrict__ te, unsigned char *__restrict__ dropped) {
+  const long long str = (long long)blockIdx.x * kTrackWaves + (threadIdx.x >> 6);
+  if (str >= n_str) return;
+  const int lane = threadIdx.x & 63;
+  const long long d0 = off[str], span = off[str + 1] - d0;
+  constexpr int kMaxD = kOptimal ? PP_TRACK_OPT_MAX : PP_TRACK_MAX_DETS;
+  constexpr int kMaxT = kOptimal ? PP_TRACK_OPT_MAX : PP_TRACK_MAX_TRACKS;
+  if (span < 0 || span > kMaxD || T < 1 || T > kMaxT) return;                  // refused on the host
+  const int D = (int)span;
+  const TrackState st = track_state(blocks[str], T, K);
+  const TrackOut out{area, t, ids, match_oks, born, slot_of, te};
+
+  unsigned long long valid, live, taken = 0, unmatched = 0, young = 0;
+  track_slot_masks(st, lane, T, valid, live);
+  for (unsigned long long m = live; m;) {                 // before stage 1 resets the ages of the slots it takes
+    const int s = __builtin_ctzll(m);
+    m &= m - 1;
+    if (st.age[s * 64 + lane] <= low_max_age) young |= 1ull << s;
+  }
+  long long high = 0;
+  for (int p = lane; p < D; p += 64) high += score[d0 + p] >= high_thr ? 1 : 0;
+  const int n_high = (int)wave_sum_i64(high);              // wave-uniform
+
+  for (int stage = 0; stage < 2; ++stage) {
+    const int p0 = stage ? n_high : 0, p1 = stage ? D : n_high;
+    if (p0 >= p1) continue;
+    const unsigned long long cols = stage ? live & ~taken & young : live;
+    const double thr = stage ? low_match_thr : match_thr;
+    if constexpr (kOptimal) (void)track_optimal_rows(st, out, lane, d0, p0, p1, T, oks, cols, thr, taken, unmatched);
+    else track_greedy_rows(st, out, lane, d0, p0, p1, T, oks, cols, thr, taken, unmatched);
+  }
+
+  unsigned long long bear = 0;
+  for (int p = lane; p < D; p += 64) {
+    const long long d = d0 + p;
+    const bool un = (unmatched >> (p >> 6)) & 1ull;
+    const bool drop = un && !(score[d] >= birth_thr);
+    if (un && !drop) bear |= 1ull << (p >> 6);
+    dropped[d] = drop ? 1 : 0;
+    if (drop) {
+      ids[d] = -1;
+      match_oks[d] = 0.0;
+      born[d] = 0;
+      slot_of[d] = -1;
+      te[d] = 0.0;
+    }
+  }
+  track_age_and_bear(st, out, lane, d0, D, max_age, valid, live, taken, bear);
 }
 
 __device__ __forceinline__ double track_alpha(double te, double fc) {
@@ -512,6 +638,29 @@ extern "C" int pp_track_oks(int n_str, int K, int max_tracks, long long Dtot, co
   return 0;
 }
 
+extern "C" int pp_track_oks_predicted(int n_str, int K, int max_tracks, long long Dtot, const long long *host_off,
+                                      const void *det_stream, const void *blocks, const void *kpts, const void *vis,
+                                      const void *area, const void *vars, double vis_thr, double t, double max_dt,
+                                      void *oks, void *stream) {
+  using namespace pp;
+  const char *who = "pp_track_oks_predicted";
+  if (int rc = track_check_common(who, n_str, K, max_tracks, Dtot)) return rc;
+  PP_REQUIRE(!vis || vis_thr == vis_thr, "%s: vis_thr is not a number", who);
+  PP_REQUIRE(isfinite(t), "%s: t=%g is not finite", who, t);
+  PP_REQUIRE(max_dt >= 0.0, "%s: max_dt=%g is negative or not a number", who, max_dt);
+  PP_REQUIRE(det_stream && blocks && kpts && area && vars && oks, "%s: null argument", who);
+  if (int rc = track_check_offsets(who, n_str, host_off, Dtot)) return rc;
+  if (n_str == 0 || Dtot == 0) return 0;
+  const long long lanes = Dtot * max_tracks, grid = (lanes + kTrackThreads - 1) / kTrackThreads;
+  PP_REQUIRE(grid < (1ll << 31), "%s: %lld pairs exceed one grid", who, lanes);
+  hipLaunchKernelGGL(track_oks_predicted_kernel, dim3((unsigned)grid), dim3(kTrackThreads), 0, (hipStream_t)stream, K,
+                     max_tracks, Dtot, (const long long *)det_stream, (const long long *)blocks, (const double *)kpts,
+                     (const double *)vis, (const double *)area, (const double *)vars, vis_thr, t, max_dt,
+                     (double *)oks);
+  PP_CHECK_LAUNCH("track_oks_predicted_kernel");
+  return 0;
+}
+
 extern "C" int pp_track_assign(int n_str, int K, int max_tracks, long long Dtot, const long long *host_off,
                                const void *off, const void *blocks, const void *oks, const void *area,
                                double match_thr, int max_age, double t, double t_prev, void *ids, void *match_oks,
@@ -553,6 +702,44 @@ extern "C" int pp_track_assign_optimal(int n_str, int K, int max_tracks, long lo
                      (const double *)area, match_thr, max_age, t, (long long *)ids, (double *)match_oks,
                      (unsigned char *)born, (int *)slot_of, (double *)te, (long long *)total);
   PP_CHECK_LAUNCH("track_assign_optimal_kernel");
+  return 0;
+}
+
+extern "C" int pp_track_assign_staged(int n_str, int K, int max_tracks, long long Dtot, const long long *host_off,
+                                      const void *off, const void *blocks, const void *oks, const void *area,
+                                      const void *score, double match_thr, double high_thr, double low_match_thr,
+                                      int low_max_age, double birth_thr, int optimal, int max_age, double t,
+                                      double t_prev, void *ids, void *match_oks, void *born, void *slot_of, void *te,
+                                      void *dropped, void *stream) {
+  using namespace pp;
+  const char *who = "pp_track_assign_staged";
+  if (int rc = track_check_assign(who, n_str, K, max_tracks, Dtot, host_off, match_thr, max_age, t, t_prev,
+                                  off && blocks && oks && area && score && ids && match_oks && born && slot_of && te &&
+                                      dropped))
+    return rc;
+  PP_REQUIRE(high_thr == high_thr, "%s: high_thr is not a number", who);
+  PP_REQUIRE(birth_thr == birth_thr, "%s: birth_thr is not a number", who);
+  PP_REQUIRE(low_match_thr >= 0.0 && low_match_thr < 1.0, "%s: low_match_thr=%g is outside [0, 1)", who,
+             low_match_thr);
+  PP_REQUIRE(low_max_age >= 0, "%s: low_max_age=%d", who, low_max_age);
+  PP_REQUIRE(optimal == 0 || optimal == 1, "%s: optimal=%d is neither 0 nor 1", who, optimal);
+  if (optimal) {
+    PP_REQUIRE(max_tracks <= PP_TRACK_OPT_MAX, "%s: max_tracks=%d is above PP_TRACK_OPT_MAX = %d", who, max_tracks,
+               PP_TRACK_OPT_MAX);
+    for (int i = 0; i < n_str; ++i)
+      PP_REQUIRE(host_off[i + 1] - host_off[i] <= PP_TRACK_OPT_MAX,
+                 "%s: stream %d has %lld detections, more than PP_TRACK_OPT_MAX = %d", who, i,
+                 host_off[i + 1] - host_off[i], PP_TRACK_OPT_MAX);
+  }
+  if (n_str == 0) return 0;
+  const unsigned grid = (unsigned)((n_str + kTrackWaves - 1) / kTrackWaves);
+  const auto kernel = optimal ? track_assign_staged_kernel<true> : track_assign_staged_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * kTrackWaves), 0, (hipStream_t)stream, n_str, K, max_tracks,
+                     (const long long *)off, (const long long *)blocks, (const double *)oks, (const double *)area,
+                     (const double *)score, match_thr, high_thr, low_match_thr, low_max_age, birth_thr, max_age, t,
+                     (long long *)ids, (double *)match_oks, (unsigned char *)born, (int *)slot_of, (double *)te,
+                     (unsigned char *)dropped);
+  PP_CHECK_LAUNCH("track_assign_staged_kernel");
   return 0;
 }
 

@@ -27,7 +27,10 @@ function, ``run_inference``: ``Codec(ProbMap(input_size, heatmap_size, sigmas))`
   links the poses across the frames (``tracker.PoseTracker``; ``--match-thr``, ``--max-age``, ``--fps``; ``--smooth
   [min_cutoff,beta,d_cutoff]`` adds the One-Euro filter; ``--assign optimal`` replaces the greedy association by the
   matching of largest total weight, for at most 256 people per frame).  ``--output`` gets ``tracks.json``: per frame and kept
-  detection its track id and (smoothed) keypoints; with ``--render`` also one picture per frame, drawn from those;
+  detection its track id and (smoothed) keypoints; with ``--render`` also one picture per frame, drawn from those.
+  ``--predict [MAX_DT]`` (with ``--smooth``) compares a pose with where its track expects it, and ``--high-thr``,
+  ``--low-match-thr``, ``--birth-thr`` associate in two stages by score and gate births (``PoseTracker``'s keywords of
+  the same names; off by default; a dropped pose has id -1);
 * ``--propagate [VIS_THR,PAD,IOU]`` (with ``--track``) follows the people from frame to frame (``follow.PoseFollower``):
   every track proposes its person's next box from its own last pose, so FILE needs boxes for a key frame only.  A frame
   FILE names uses its boxes and the proposals that do not duplicate them (IoU <= IOU), a frame it does not name uses
@@ -218,6 +221,16 @@ def main(argv=None):
     p.add_argument("--assign", type=str, default="greedy", choices=["greedy", "optimal"],
                    help="with --track: how poses take tracks: each in turn its best free one, or the best matching "
                         "overall (Hungarian)")
+    p.add_argument("--predict", type=float, nargs="?", const=float("inf"), default=None, metavar="MAX_DT",
+                   help="with --track --smooth: compare a pose with where its track's One-Euro speed expects it, "
+                        "extrapolating over at most MAX_DT seconds (no value: no limit)")
+    p.add_argument("--high-thr", type=float, default=None,
+                   help="with --track: poses scoring at least this take tracks first; the others only continue tracks "
+                        "seen in the previous frame and never start one")
+    p.add_argument("--low-match-thr", type=float, default=None,
+                   help="with --high-thr: OKS a pose below it needs to continue a track (default: --match-thr)")
+    p.add_argument("--birth-thr", type=float, default=None,
+                   help="with --track: score a pose needs to start a track (default: --high-thr)")
     p.add_argument("--fps", type=float, default=30.0, help="frame rate of --frames: the time base of --smooth")
     p.add_argument("--render", action="store_true",
                    help="with --output: also write heatmap_{i}.png and output_image.png, drawn on the GPU")
@@ -323,11 +336,14 @@ def _main_boxes(args, model, codec, boxes):
 
 def _track_options(p, args):
     """The tracking options of the command line, checked: None without --track, else dict(files, boxes, smooth,
-    propagate)."""
+    propagate, stage); ``stage`` holds PoseTracker's prediction and two-stage keywords."""
     if not args.track:
         for flag, given in (("--frames", args.frames is not None), ("--boxes-json", args.boxes_json is not None),
                             ("--smooth", args.smooth is not None), ("--propagate", args.propagate is not None),
-                            ("--assign", args.assign != "greedy")):
+                            ("--assign", args.assign != "greedy"), ("--predict", args.predict is not None),
+                            ("--high-thr", args.high_thr is not None),
+                            ("--low-match-thr", args.low_match_thr is not None),
+                            ("--birth-thr", args.birth_thr is not None)):
             if given:
                 p.error(f"{flag} needs --track")
         return None
@@ -355,6 +371,23 @@ def _track_options(p, args):
             smooth = OneEuro(*values)
         except (TypeError, ValueError) as e:
             p.error(f"--smooth: {e}")
+    stage = {}
+    if args.predict is not None:
+        if smooth is None:
+            p.error("--predict needs --smooth (the speed it moves a track by is the One-Euro filter's)")
+        if not args.predict >= 0:
+            p.error(f"--predict: {args.predict} is negative or not a number")
+        stage.update(predict=True, predict_max_dt=None if np.isinf(args.predict) else args.predict)
+    for flag, value in (("--high-thr", args.high_thr), ("--low-match-thr", args.low_match_thr),
+                        ("--birth-thr", args.birth_thr)):
+        if value is not None and not np.isfinite(value):
+            p.error(f"{flag}: {value} is not finite")
+    if args.low_match_thr is not None:
+        if args.high_thr is None:
+            p.error("--low-match-thr needs --high-thr")
+        if not 0.0 <= args.low_match_thr < 1.0:
+            p.error(f"--low-match-thr: {args.low_match_thr} is outside [0, 1)")
+    stage.update(high_thr=args.high_thr, low_match_thr=args.low_match_thr, birth_thr=args.birth_thr)
     propagate = None
     if args.propagate is not None:
         try:
@@ -386,7 +419,7 @@ def _track_options(p, args):
             boxes[f.name] = rows
     except (OSError, ValueError, AttributeError) as e:
         p.error(f"--boxes-json: {e}")
-    return dict(files=files, boxes=boxes, smooth=smooth, propagate=propagate)
+    return dict(files=files, boxes=boxes, smooth=smooth, propagate=propagate, stage=stage)
 
 
 def _main_frames(args, model, codec, track):
@@ -402,7 +435,7 @@ def _main_frames(args, model, codec, track):
     if track["propagate"] is not None:
         return _main_follow(args, model, codec, track, nms)
     tracker = PoseTracker(sigmas, match_thr=args.match_thr, max_age=args.max_age, smooth=track["smooth"], fps=args.fps,
-                          assign=args.assign)
+                          assign=args.assign, **track["stage"])
     args.output.mkdir(parents=True, exist_ok=True)
     record = []
     for path in track["files"]:
@@ -450,7 +483,7 @@ def _main_follow(args, model, codec, track, nms):
     K, dev = args.num_keypoints, "cuda"
     vis_thr, pad, iou = track["propagate"]
     tracker = PoseTracker(np.array([args.sigma] * K), match_thr=args.match_thr, max_age=args.max_age, vis_thr=vis_thr,
-                          smooth=track["smooth"], fps=args.fps, assign=args.assign)
+                          smooth=track["smooth"], fps=args.fps, assign=args.assign, **track["stage"])
     follower = PoseFollower(tracker, box_estimator(model, codec), nms=nms, pad=pad, iou_thr=iou)
     args.output.mkdir(parents=True, exist_ok=True)
     record = []

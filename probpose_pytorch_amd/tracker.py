@@ -31,6 +31,16 @@ shortest augmenting paths in int64, pp_track_assign_optimal in place of pp_track
 people close together then keep their ids where the greedy walk gives the first detection the other's track.  The mode
 takes at most ``OPT_MAX`` = 256 slots and 256 detections per stream and call; every other rule is unchanged.
 
+Two options, both off by default, each swapping one of the three launches (restated in
+tests/trackstage_reference.py).  ``predict=True`` (pp_track_oks_predicted for pp_track_oks) replaces the slot's stored
+raw keypoints in the second rule by where the track expects them: xhat + dxhat * min(t - t_last, predict_max_dt) for
+a keypoint whose filter is initialised, the raw keypoint otherwise, which is the pose ``propose_boxes`` moves the
+track's box by.  ``high_thr`` / ``birth_thr`` (pp_track_assign_staged for either assign launch) run the third rule in
+two stages: first the detections with score >= ``high_thr`` on the live slots at ``match_thr``, then the others on
+the live slots still untaken whose age at entry is <= ``low_max_age``, at ``low_match_thr``; a stage is the greedy
+walk or the optimal matching, by ``assign``.  An unmatched detection is born only with score >= ``birth_thr``; the
+others are dropped (id -1, ``TrackResult.dropped``) and do not count in ``overflow``.
+
 ``propose_boxes`` reads the state back out as the person box every track expects its person in next (one more launch,
 pp_track_boxes; restated in tests/trackbox_reference.py); follow.py builds the frame loop on it.
 
@@ -92,11 +102,13 @@ def state_layout(max_tracks: int, K: int) -> dict:
 class TrackResult:
     """What ``PoseTracker.update`` returns, in the order the detections were given, on the device: ``ids`` [M] int64
     (-1 = not tracked), ``keypoints`` [M, K, 2] float64 (smoothed; raw where not smoothed), ``oks`` [M] float64 (with the
-    matched track, 0 otherwise), ``born`` [M] bool; ``stream_ids``: host list in first-seen order."""
-    __slots__ = ("ids", "keypoints", "oks", "born", "stream_ids", "_staged")
+    matched track, 0 otherwise), ``born`` [M] bool, ``dropped`` [M] bool (unmatched and below ``birth_thr``: neither
+    tracked nor counted in ``overflow``; all False without ``high_thr`` / ``birth_thr``); ``stream_ids``: host list in
+    first-seen order."""
+    __slots__ = ("ids", "keypoints", "oks", "born", "dropped", "stream_ids", "_staged")
 
-    def __init__(self, ids, keypoints, oks, born, stream_ids, staged):
-        self.ids, self.keypoints, self.oks, self.born = ids, keypoints, oks, born
+    def __init__(self, ids, keypoints, oks, born, stream_ids, staged, dropped):
+        self.ids, self.keypoints, self.oks, self.born, self.dropped = ids, keypoints, oks, born, dropped
         self.stream_ids, self._staged = stream_ids, staged
 
     def __repr__(self):
@@ -153,10 +165,41 @@ class PoseTracker:
     a track; a track unseen for more than ``max_age`` frames of its stream is dropped; ``max_tracks`` slots per stream;
     ``vis_thr`` None lets every keypoint count; ``smooth`` is a ``OneEuro`` or None (raw keypoints out); ``fps`` gives
     the default time stamps; ``assign`` is "greedy" (each detection in turn takes its best free track) or "optimal"
-    (the matching of largest total weight; at most ``OPT_MAX`` slots and detections per stream and call)."""
+    (the matching of largest total weight; at most ``OPT_MAX`` slots and detections per stream and call).
+
+    Off by default (the module docstring has the rules): ``predict`` compares a detection with where the track's
+    One-Euro speed expects its pose at the frame's time, ``predict_max_dt`` (None: no limit) bounding the time it
+    extrapolates over; ``high_thr`` associates the detections scoring at least that much first and lets the others
+    only continue tracks unseen for at most ``low_max_age`` frames, at ``low_match_thr`` (default ``match_thr``);
+    ``birth_thr`` (default ``high_thr``) is the score an unmatched detection needs to start a track, the others are
+    dropped.  ``birth_thr`` alone gives one stage with gated births."""
 
     def __init__(self, sigmas, *, match_thr: float = 0.3, max_age: int = 30, max_tracks: int = 64, vis_thr=None,
-                 smooth: OneEuro | None = None, fps: float = 30.0, assign: str = "greedy"):
+                 smooth: OneEuro | None = None, fps: float = 30.0, assign: str = "greedy", predict: bool = False,
+                 predict_max_dt=None, high_thr=None, low_match_thr=None, low_max_age: int = 0, birth_thr=None):
+        if predict and smooth is None:
+            raise ValueError("predict: needs smooth (the speed it moves a track by is the One-Euro filter's)")
+        if predict_max_dt is not None and not predict:
+            raise ValueError("predict_max_dt: given without predict")
+        max_dt = np.inf if predict_max_dt is None else float(predict_max_dt)
+        if predict_max_dt is not None and not (np.isfinite(max_dt) and max_dt >= 0):
+            raise ValueError(f"predict_max_dt: {predict_max_dt} is not None or a finite value >= 0")
+        for name, v in (("high_thr", high_thr), ("birth_thr", birth_thr), ("low_match_thr", low_match_thr)):
+            if v is not None and not np.isfinite(v):
+                raise ValueError(f"{name}: {v} is not finite")
+        if high_thr is None and low_match_thr is not None:
+            raise ValueError("low_match_thr: given without high_thr, there is no second stage")
+        if high_thr is None and int(low_max_age) != 0:
+            raise ValueError("low_max_age: given without high_thr, there is no second stage")
+        if low_match_thr is not None and not 0.0 <= float(low_match_thr) < 1.0:
+            raise ValueError(f"low_match_thr: {low_match_thr} is outside [0, 1)")
+        if int(low_max_age) < 0:
+            raise ValueError(f"low_max_age: {low_max_age} is negative")
+        self.predict, self.predict_max_dt = bool(predict), max_dt
+        self.high_thr = None if high_thr is None else float(high_thr)
+        self.birth_thr = self.high_thr if birth_thr is None else float(birth_thr)
+        self.low_match_thr = None if low_match_thr is None else float(low_match_thr)
+        self.low_max_age = int(low_max_age)
         if assign not in ("greedy", "optimal"):
             raise ValueError(f'assign: expected "greedy" or "optimal", got {assign!r}')
         self.assign = assign
@@ -179,6 +222,8 @@ class PoseTracker:
         if not (np.isfinite(fps) and fps > 0):
             raise ValueError(f"fps: {fps} is not a positive number")
         self.match_thr, self.max_age, self.max_tracks = float(match_thr), int(max_age), int(max_tracks)
+        if self.low_match_thr is None:
+            self.low_match_thr = self.match_thr
         self.vis_thr = None if vis_thr is None else float(vis_thr)
         self.smooth, self.fps = smooth, float(fps)
         self.layout = state_layout(self.max_tracks, self.K)
@@ -361,9 +406,10 @@ class PoseTracker:
         return BoxProposals(*out, stream_list, staged)
 
     # ------------------------------------------------------------------------------------------- update
-    def _launch(self, n_str, off, off_dev, det_stream, blocks, kp_s, vis_s, ar_s, variances, t_now, t_prev):
+    def _launch(self, n_str, off, off_dev, det_stream, blocks, kp_s, vis_s, ar_s, sc_s, variances, t_now, t_prev):
         """The three launches on a batch in visiting order: (ids [M] int64, oks [M] float64, born [M] uint8, keypoints
-        [M, K, 2] float64), still in that order."""
+        [M, K, 2] float64, dropped [M] uint8 or None), still in that order.  ``sc_s`` is read by the staged launch
+        alone."""
         K, T, M, dev = self.K, self.max_tracks, int(off[-1]), kp_s.device
         new = partial(torch.empty, device=dev)
         oks_ws = new(M * T, dtype=torch.float64)
@@ -374,11 +420,22 @@ class PoseTracker:
         vis_hold = None if vis_s is None else _room(vis_s)
         hold = [_room(x) for x in (det_stream, kp_s, ar_s, oks_ws, ids_s, oks_s, born_s, slot_s, te_s, out_s)]
         det_stream_h, kp_h, ar_h, ws_h, ids_h, oks_h, born_h, slot_h, te_h, out_h = hold
-        _lib.launch("pp_track_oks", n_str, K, T, M, off, det_stream_h, _room(blocks), kp_h, vis_hold, ar_h, variances,
-                    vis_thr, ws_h)
+        oks_args = (n_str, K, T, M, off, det_stream_h, _room(blocks), kp_h, vis_hold, ar_h, variances, vis_thr)
+        if self.predict:
+            _lib.launch("pp_track_oks_predicted", *oks_args, t_now, self.predict_max_dt, ws_h)
+        else:
+            _lib.launch("pp_track_oks", *oks_args, ws_h)
         assign_args = (n_str, K, T, M, off, off_dev, _room(blocks), ws_h, ar_h, self.match_thr, self.max_age, t_now,
                        t_prev, ids_h, oks_h, born_h, slot_h, te_h)
-        if self.assign == "optimal":
+        dropped_s = None
+        if self.high_thr is not None or self.birth_thr is not None:
+            dropped_s = new(M, dtype=torch.uint8)
+            high = -np.inf if self.high_thr is None else self.high_thr      # birth_thr alone: everything is stage 1
+            # pp_track_assign's arguments with the scores and the stage options after `area`, `dropped` at the end
+            _lib.launch("pp_track_assign_staged", *assign_args[:9], _room(sc_s), self.match_thr, high,
+                        self.low_match_thr, self.low_max_age, self.birth_thr, int(self.assign == "optimal"),
+                        *assign_args[10:], _room(dropped_s))
+        elif self.assign == "optimal":
             _lib.launch("pp_track_assign_optimal", *assign_args, None)
         else:
             _lib.launch("pp_track_assign", *assign_args)
@@ -386,7 +443,7 @@ class PoseTracker:
         _lib.launch("pp_track_filter", K, T, M, det_stream_h, _room(blocks), kp_h, vis_hold, vis_thr, slot_h, born_h,
                     te_h, int(sm is not None), *((sm.min_cutoff, sm.beta, sm.d_cutoff) if sm else (1.0, 0.0, 1.0)),
                     out_h)
-        return ids_s, oks_s, born_s, out_s
+        return ids_s, oks_s, born_s, out_s, dropped_s
 
     def update(self, keypoints, areas, scores, kpt_scores=None, *, stream_ids=None, t=None, streams=None):
         """One frame of every named stream: keypoints [M, K, 2|3], areas [M], scores [M], kpt_scores [M, K] or None:
@@ -483,8 +540,11 @@ class PoseTracker:
         ar_s, det_stream = ar[perm].contiguous(), pos_dev[perm].contiguous()
         variances, off_dev, blocks = up((self.sigmas * 2) ** 2), up(off), up(addresses)
 
-        ids_s, oks_s, born_s, out_s = self._launch(n_str, off, off_dev, det_stream, blocks, kp_s, vis_s, ar_s, variances,
-                                                   t_now, self._t_prev)
+        staged_assign = self.high_thr is not None or self.birth_thr is not None
+        sc_s = sc[perm].contiguous() if staged_assign else None
+
+        ids_s, oks_s, born_s, out_s, dropped_s = self._launch(n_str, off, off_dev, det_stream, blocks, kp_s, vis_s,
+                                                              ar_s, sc_s, variances, t_now, self._t_prev)
         self._calls += 1
         self._t_prev = t_now
 
@@ -492,4 +552,7 @@ class PoseTracker:
         ids_out, oks_out = torch.empty_like(ids_s), torch.empty_like(oks_s)
         born_out, kp_out = new(M, dtype=torch.bool), torch.empty_like(out_s)
         ids_out[perm], oks_out[perm], born_out[perm], kp_out[perm] = ids_s, oks_s, born_s.to(torch.bool), out_s
-        return TrackResult(ids_out, kp_out, oks_out, born_out, stream_list, staged)
+        dropped_out = torch.zeros(M, dtype=torch.bool, device=dev)
+        if dropped_s is not None:
+            dropped_out[perm] = dropped_s.to(torch.bool)
+        return TrackResult(ids_out, kp_out, oks_out, born_out, stream_list, staged, dropped_out)

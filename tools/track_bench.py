@@ -17,6 +17,9 @@ tensors, as a decoder leaves them.  The frames are walked forwards and backwards
                alone (with their output allocations) on one OKS workspace and one state, those of the second frame of a
                tracker that has seen the first, so every detection has its track; and `update` of a tracker built with
                assign="optimal".  `optimal_over_greedy` holds the ratios of the medians
+  update_predict_*, update_cascade_*, update_predict_cascade_*   with `--stage`: `update` of trackers built with
+               predict=True, with high_thr 0.5 / birth_thr 0.6, and with both, for assign greedy and optimal (beside
+               `update` and `update_optimal`, which `--stage` times too)
   host_numpy   the same rules on the host: the D2H copy of keypoints, areas and scores, then per stream a vectorised
                OKS matrix, the greedy walk over the detections, vectorised ageing, births and One-Euro steps
 
@@ -39,6 +42,10 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 SIGMAS = np.array([.26, .25, .25, .35, .35, .79, .79, .72, .72, .62, .62, 1.07, 1.07, .87, .87, .89, .89]) / 10.0
 K, MAX_TRACKS, MATCH_THR, MAX_AGE, FPS = 17, 128, 0.3, 30, 30.0
+# --stage: the update with motion prediction, with the two-stage association (ByteTrack's usual thresholds; the scores
+# are uniform in (0.05, 0.99), so about half the detections are rows of stage 2), and with both
+STAGE_VARIANTS = {"predict": dict(predict=True), "cascade": dict(high_thr=0.5, birth_thr=0.6),
+                  "predict_cascade": dict(predict=True, high_thr=0.5, birth_thr=0.6)}
 EPS = float(np.spacing(1.0))
 TWO_PI = 2.0 * np.pi
 
@@ -172,7 +179,7 @@ def assign_launchers(tracker, frame):
     from probpose_pytorch_amd import _lib
     launch, made = tracker._launch, {}
 
-    def spy(n_str, off, off_dev, det_stream, blocks, kp_s, vis_s, ar_s, variances, t_now, t_prev):
+    def spy(n_str, off, off_dev, det_stream, blocks, kp_s, vis_s, ar_s, sc_s, variances, t_now, t_prev):
         T, M = tracker.max_tracks, int(off[-1])
         ws = torch.empty(M * T, dtype=torch.float64, device=kp_s.device)
         _lib.launch("pp_track_oks", n_str, K, T, M, off, det_stream, blocks, kp_s, None, ar_s, variances, 0.0, ws)
@@ -184,7 +191,7 @@ def assign_launchers(tracker, frame):
                         *tail)
         made["greedy"] = lambda: run("pp_track_assign")
         made["optimal"] = lambda: run("pp_track_assign_optimal", None)
-        return launch(n_str, off, off_dev, det_stream, blocks, kp_s, vis_s, ar_s, variances, t_now, t_prev)
+        return launch(n_str, off, off_dev, det_stream, blocks, kp_s, vis_s, ar_s, sc_s, variances, t_now, t_prev)
 
     tracker._launch = spy
     try:
@@ -220,6 +227,8 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--assign", choices=["greedy", "optimal"], default="greedy",
                     help="optimal: also time pp_track_assign_optimal beside pp_track_assign and the update in both modes")
+    ap.add_argument("--stage", action="store_true",
+                    help="also time the update with predict, with high_thr / birth_thr and with both, greedy and optimal")
     ap.add_argument("--out")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "track_bench needs the GPU: there is nothing to time without it"
@@ -236,8 +245,8 @@ def main():
             return frames[n if n < F else 2 * F - 2 - n]
         return nxt
 
-    new = lambda assign="greedy": PoseTracker(SIGMAS, match_thr=MATCH_THR, max_age=MAX_AGE, max_tracks=MAX_TRACKS,
-                                              smooth=OneEuro(), fps=FPS, assign=assign)
+    new = lambda assign="greedy", **kw: PoseTracker(SIGMAS, match_thr=MATCH_THR, max_age=MAX_AGE, max_tracks=MAX_TRACKS,
+                                                    smooth=OneEuro(), fps=FPS, assign=assign, **kw)
     variants, sizes = {}, {}
     for P in args.people:
         frames = make_video(args.streams, P, args.frames, args.seed + P)
@@ -266,7 +275,15 @@ def main():
         variants[f"{P}/propose"] = dev.propose_boxes
         box_args = box_launch_arguments(alone)
         variants[f"{P}/propose_launch"] = lambda alone=alone, a=box_args: alone._launch_boxes(*a)
-        if args.assign == "optimal":
+        for mode in ("greedy", "optimal") if args.stage else ():
+            for label, kw in STAGE_VARIANTS.items():
+                tr = new(mode, **kw)
+                for f in frames[:5]:
+                    tr.update(*f[1:], stream_ids=f[0])
+                step = walker(frames[5:])
+                variants[f"{P}/update_{label}_{mode}"] = lambda tr=tr, nxt=step: (
+                    lambda f: tr.update(*f[1:], stream_ids=f[0]))(nxt())
+        if args.assign == "optimal" or args.stage:
             opt, same = new("optimal"), True
             for f in frames[:5]:
                 same = same and bool(torch.equal(opt.update(*f[1:], stream_ids=f[0]).ids,
@@ -275,6 +292,7 @@ def main():
             step_opt = walker(frames[5:])
             variants[f"{P}/update_optimal"] = lambda opt=opt, nxt=step_opt: (
                 lambda f: opt.update(*f[1:], stream_ids=f[0]))(nxt())
+        if args.assign == "optimal":
             pair = new()
             pair.update(*frames[0][1:], stream_ids=frames[0][0])
             variants[f"{P}/assign_greedy"], variants[f"{P}/assign_optimal"] = assign_launchers(pair, frames[1])
