@@ -11,8 +11,10 @@ copied to the host) and evaluates them with three HIP launches of csrc/pp_cocoev
                           right-to-left precision envelope and the samples at the recall thresholds
 
 Between them run two kinds of torch device ops, none of which synchronises: stable sorts (per image by score to cut
-to ``max_dets``, and once over all kept detections) and gathers.  ``evaluate()`` synchronises exactly once, when it
-reads precision [T, R, A] and recall [T, A] back; the ten stats are means over those arrays.
+to ``max_dets``: _ragged.visiting_order, the order PoseNMS and PoseTracker visit by; and once over all kept
+detections) and gathers.  The shape and placement checks of ``add_detections`` and its read-back are _ragged.py's
+too.  ``evaluate()`` synchronises exactly once, when it reads precision [T, R, A] and recall [T, A] back; the ten
+stats are means over those arrays.
 
 Rules (restated in tests/cocoeval_reference.py, the gauge this module is tested against):
 * detections of an image are taken by descending score, equal scores in the order they were added, the first
@@ -46,11 +48,14 @@ import torch
 
 from . import _lib
 from ._buffers import host_array as _host, room, upload
+from ._ragged import FINITE, check_pose_batch, checked_f64, group_layout, host_ids, on_device, visiting_order
 
 STATS = ("AP", "AP50", "AP75", "APm", "APl", "AR", "AR50", "AR75", "ARm", "ARl")
 _AREA_RANGES = ((0.0, 1e10), (32.0 ** 2, 96.0 ** 2), (96.0 ** 2, 1e10))
 # the 17 COCO person keypoint constants, in the form they are published (tenths, divided by 10)
 COCO17_SIGMAS = np.array([.26, .25, .25, .35, .35, .79, .79, .72, .72, .62, .62, 1.07, 1.07, .87, .87, .89, .89]) / 10.0
+# what add_detections asks of a device tensor of presence probabilities (false for a NaN as well) and says if not
+_IN_UNIT = (lambda p: ((p >= 0) & (p <= 1)).all(), "non-finite values or values outside [0, 1]")
 
 
 def _mean_present(a: np.ndarray) -> float:
@@ -158,57 +163,36 @@ class CocoKeypointEval:
         is evaluated against zero ground truths.  ``presence`` [M, K] in [0, 1] are the presence probabilities of
         Ex-OKS (``Codec.decode_device``'s ``aux[0]``), on the same side as the rest; a device tensor of any float type
         is widened to float64 there.  Required with ``ex_oks=True``, checked and not used without."""
-        ids = image_ids.detach().cpu().numpy() if isinstance(image_ids, torch.Tensor) else np.asarray(image_ids)
+        ids = host_ids(image_ids)
         if ids.ndim != 1:
             raise ValueError(f"image_ids: expected [M], got {ids.shape}")
-        M = int(ids.shape[0])
-        keypoints, scores, areas = (a if isinstance(a, torch.Tensor) else np.asarray(a)
-                                    for a in (keypoints, scores, areas))
-        shape = tuple(keypoints.shape)
-        if len(shape) != 3 or shape[0] != M or shape[1] != self.K or shape[2] not in (2, 3):
-            raise ValueError(f"keypoints: expected [{M}, {self.K}, 2|3] (K = len(sigmas)), got {shape}")
-        for name, a in (("scores", scores), ("areas", areas)):
-            if tuple(a.shape) != (M,):
-                raise ValueError(f"{name}: expected [{M}], got {tuple(a.shape)}")
-        dev = [isinstance(a, torch.Tensor) and a.is_cuda for a in (keypoints, scores, areas)]
-        if any(dev) and not all(dev):
-            raise ValueError("keypoints / scores / areas: either all device tensors or all host arrays")
-        pr = None
+        named = [("keypoints", keypoints), ("scores", scores), ("areas", areas)]
         if presence is not None:
-            presence = presence if isinstance(presence, torch.Tensor) else np.asarray(presence)
-            if tuple(presence.shape) != (M, self.K):
-                raise ValueError(f"presence: expected [{M}, {self.K}], got {tuple(presence.shape)}")
-            if (isinstance(presence, torch.Tensor) and presence.is_cuda) != all(dev):
+            named.append(("presence", presence))
+        named, M = check_pose_batch(named, self.K, int(ids.shape[0]))
+        device = on_device(named[:3])
+        if presence is not None:
+            if (isinstance(named[3][1], torch.Tensor) and named[3][1].is_cuda) != device:
                 raise ValueError("presence: must be on the same side (device or host) as keypoints / scores / areas")
         elif self.ex_oks:
             raise ValueError("presence: Ex-OKS needs the presence probabilities of every detection")
-        if all(dev):
-            kp = keypoints.detach()[..., :2].to(torch.float64).contiguous()
-            sc, ar = scores.detach().to(torch.float64).contiguous(), areas.detach().to(torch.float64).contiguous()
-            finite = [torch.isfinite(sc).all(), torch.isfinite(ar).all(), torch.isfinite(kp).all()]
-            if presence is not None:
-                pr = presence.detach().to(torch.float64).contiguous()
-                finite.append(((pr >= 0) & (pr <= 1)).all())        # false for a NaN as well
-            # three or four booleans in one readback; the detections themselves stay where they are
-            finite = torch.stack(finite).cpu().numpy()
+        # a refusal names scores, areas, keypoints and presence in this order; a third keypoint column is not looked at
+        named = [named[1], named[2], ("keypoints", named[0][1][..., :2])] + named[3:]
+        if device:      # three or four booleans in one readback; the detections themselves stay where they are
+            sc, ar, kp, *pr = checked_f64(named, {"presence": _IN_UNIT})
         else:
-            kp = _host(keypoints, "keypoints", np.float64)[..., :2].copy()
-            sc, ar = _host(scores, "scores", np.float64).copy(), _host(areas, "areas", np.float64).copy()
-            finite = [np.all(np.isfinite(sc)), np.all(np.isfinite(ar)), np.all(np.isfinite(kp))]
-            if presence is not None:
-                pr = _host(presence, "presence", np.float64).copy()
-                finite.append(np.all((pr >= 0) & (pr <= 1)))
-        for name, ok in zip(("scores", "areas", "keypoints"), finite):
-            if not bool(ok):
-                raise ValueError(f"{name}: non-finite values")
-        if pr is not None and not bool(finite[3]):
-            raise ValueError("presence: non-finite values or values outside [0, 1]")
+            sc, ar, kp, *pr = (_host(a, n, np.float64).copy() for n, a in named)
+            for (n, _), a in zip(named, (sc, ar, kp)):
+                if not np.all(np.isfinite(a)):
+                    raise ValueError(f"{n}: {FINITE[1]}")
+            if pr and not np.all((pr[0] >= 0) & (pr[0] <= 1)):
+                raise ValueError(f"presence: {_IN_UNIT[1]}")
         known = len(self._index)
         pos = np.fromiter((self._position(i) for i in ids), dtype=np.int64, count=M)
         if len(self._index) != known:
             self._gt_cache = None
         self._dets.append((pos, kp, sc, ar))
-        self._presence.append(pr)
+        self._presence.append(pr[0] if pr else None)
 
     # ------------------------------------------------------------------------------------------- JSON helpers
     @classmethod
@@ -311,7 +295,7 @@ class CocoKeypointEval:
         n_img = len(self._index)
         gt_kp, gt_bb, gt_ar, gt_flags, g_cnt = self._ground_truth_arrays(n_img)
         pos = np.concatenate([d[0] for d in self._dets]) if self._dets else np.zeros(0, dtype=np.int64)
-        d_all = np.bincount(pos, minlength=n_img).astype(np.int64) if n_img else np.zeros(0, dtype=np.int64)
+        d_all = group_layout(pos, n_img)[0]
         d_cnt = np.minimum(d_all, self.max_dets)
         offs = np.zeros((3, n_img + 1), dtype=np.int64)
         offs[0, 1:], offs[1, 1:], offs[2, 1:] = np.cumsum(d_cnt), np.cumsum(g_cnt), np.cumsum(d_cnt * g_cnt)
@@ -323,11 +307,7 @@ class CocoKeypointEval:
             kp = torch.cat([up(d[1], dtype=torch.float64) for d in self._dets])
             sc = torch.cat([up(d[2], dtype=torch.float64) for d in self._dets])
             ar = torch.cat([up(d[3], dtype=torch.float64) for d in self._dets])
-            # descending score, then image: two stable sorts leave every image's detections in score order, equal
-            # scores in the order they were added
-            by_score = torch.sort(sc, descending=True, stable=True).indices
-            by_image = torch.sort(up(pos)[by_score], stable=True).indices
-            perm = by_score[by_image]
+            perm, _ = visiting_order(sc, pos, up)
             # positions of the sorted list whose rank within their image is below max_dets
             rank = np.arange(pos.size, dtype=np.int64) - np.repeat(np.cumsum(d_all) - d_all, d_all)
             sel = perm[up(np.nonzero(rank < self.max_dets)[0].astype(np.int64))]

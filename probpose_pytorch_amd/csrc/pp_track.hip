@@ -598,7 +598,7 @@ static int track_check_offsets(const char *who, int n_str, const long long *h, l
   return 0;
 }
 
-// what both assign entries check, in this order
+// what the assign entries check, in this order
 static int track_check_assign(const char *who, int n_str, int K, int T, long long Dtot, const long long *host_off,
                               double match_thr, int max_age, double t, double t_prev, bool pointers) {
   if (int rc = track_check_common(who, n_str, K, T, Dtot)) return rc;
@@ -607,6 +607,93 @@ static int track_check_assign(const char *who, int n_str, int K, int T, long lon
   PP_REQUIRE(t - t_prev > 0.0 && t < INFINITY, "%s: te <= 0 (t=%g after t_prev=%g)", who, t, t_prev);
   PP_REQUIRE(pointers, "%s: null argument", who);
   return track_check_offsets(who, n_str, host_off, Dtot);
+}
+
+// the workgroups of `lanes` one-lane items; 2^31 or more are refused, the entry `who` calling the items `what`
+static int track_grid(const char *who, long long lanes, const char *what, unsigned *grid) {
+  const long long g = (lanes + kTrackThreads - 1) / kTrackThreads;
+  PP_REQUIRE(g < (1ll << 31), "%s: %lld %s exceed one grid", who, lanes, what);
+  *grid = (unsigned)g;
+  return 0;
+}
+
+// pp_track_oks and (predicted: with t and max_dt) pp_track_oks_predicted
+static int track_launch_oks(const char *who, bool predicted, int n_str, int K, int T, long long Dtot,
+                            const long long *host_off, const void *det_stream, const void *blocks, const void *kpts,
+                            const void *vis, const void *area, const void *vars, double vis_thr, double t,
+                            double max_dt, void *oks, void *stream) {
+  if (int rc = track_check_common(who, n_str, K, T, Dtot)) return rc;
+  PP_REQUIRE(!vis || vis_thr == vis_thr, "%s: vis_thr is not a number", who);
+  if (predicted) {
+    PP_REQUIRE(isfinite(t), "%s: t=%g is not finite", who, t);
+    PP_REQUIRE(max_dt >= 0.0, "%s: max_dt=%g is negative or not a number", who, max_dt);
+  }
+  PP_REQUIRE(det_stream && blocks && kpts && area && vars && oks, "%s: null argument", who);
+  if (int rc = track_check_offsets(who, n_str, host_off, Dtot)) return rc;
+  if (n_str == 0 || Dtot == 0) return 0;
+  unsigned grid;
+  if (int rc = track_grid(who, Dtot * T, "pairs", &grid)) return rc;
+  const auto launch = [&](auto kernel, auto... when) {       // both kernels' arguments, `when` between vis_thr and oks
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kTrackThreads), 0, (hipStream_t)stream, K, T, Dtot,
+                       (const long long *)det_stream, (const long long *)blocks, (const double *)kpts,
+                       (const double *)vis, (const double *)area, (const double *)vars, vis_thr, when...,
+                       (double *)oks);
+  };
+  if (predicted) launch(track_oks_predicted_kernel, t, max_dt);
+  else launch(track_oks_kernel);
+  PP_CHECK_LAUNCH(predicted ? "track_oks_predicted_kernel" : "track_oks_kernel");
+  return 0;
+}
+
+// The three assign entries: pp_track_assign (optimal = 0), pp_track_assign_optimal (optimal = 1, with `total`) and
+// pp_track_assign_staged (staged: with `score` .. `birth_thr` and `dropped`; `optimal` is its argument, checked here).
+static int track_launch_assign(const char *who, bool staged, int optimal, int n_str, int K, int T, long long Dtot,
+                               const long long *host_off, const void *off, const void *blocks, const void *oks,
+                               const void *area, const void *score, double match_thr, double high_thr,
+                               double low_match_thr, int low_max_age, double birth_thr, int max_age, double t,
+                               double t_prev, void *ids, void *match_oks, void *born, void *slot_of, void *te,
+                               void *dropped, void *total, void *stream) {
+  if (int rc = track_check_assign(who, n_str, K, T, Dtot, host_off, match_thr, max_age, t, t_prev,
+                                  off && blocks && oks && area && ids && match_oks && born && slot_of && te &&
+                                      (!staged || (score && dropped))))
+    return rc;
+  if (staged) {
+    PP_REQUIRE(high_thr == high_thr, "%s: high_thr is not a number", who);
+    PP_REQUIRE(birth_thr == birth_thr, "%s: birth_thr is not a number", who);
+    PP_REQUIRE(low_match_thr >= 0.0 && low_match_thr < 1.0, "%s: low_match_thr=%g is outside [0, 1)", who,
+               low_match_thr);
+    PP_REQUIRE(low_max_age >= 0, "%s: low_max_age=%d", who, low_max_age);
+    PP_REQUIRE(optimal == 0 || optimal == 1, "%s: optimal=%d is neither 0 nor 1", who, optimal);
+  }
+  if (optimal) {
+    PP_REQUIRE(T <= PP_TRACK_OPT_MAX, "%s: max_tracks=%d is above PP_TRACK_OPT_MAX = %d", who, T, PP_TRACK_OPT_MAX);
+    for (int i = 0; i < n_str; ++i)
+      PP_REQUIRE(host_off[i + 1] - host_off[i] <= PP_TRACK_OPT_MAX,
+                 "%s: stream %d has %lld detections, more than PP_TRACK_OPT_MAX = %d", who, i,
+                 host_off[i + 1] - host_off[i], PP_TRACK_OPT_MAX);
+  }
+  if (n_str == 0) return 0;                                // a stream without detections still ages its tracks
+  const dim3 grid((unsigned)((n_str + kTrackWaves - 1) / kTrackWaves)), block(64 * kTrackWaves);
+  const auto *of = (const long long *)off, *bl = (const long long *)blocks;
+  const auto *ok = (const double *)oks, *ar = (const double *)area;
+  auto *id = (long long *)ids;
+  auto *mo = (double *)match_oks, *te_ = (double *)te;
+  auto *bo = (unsigned char *)born;
+  auto *sl = (int *)slot_of;
+  if (staged)
+    hipLaunchKernelGGL(optimal ? track_assign_staged_kernel<true> : track_assign_staged_kernel<false>, grid, block, 0,
+                       (hipStream_t)stream, n_str, K, T, of, bl, ok, ar, (const double *)score, match_thr, high_thr,
+                       low_match_thr, low_max_age, birth_thr, max_age, t, id, mo, bo, sl, te_,
+                       (unsigned char *)dropped);
+  else if (optimal)
+    hipLaunchKernelGGL(track_assign_optimal_kernel, grid, block, 0, (hipStream_t)stream, n_str, K, T, of, bl, ok, ar,
+                       match_thr, max_age, t, id, mo, bo, sl, te_, (long long *)total);
+  else
+    hipLaunchKernelGGL(track_assign_kernel, grid, block, 0, (hipStream_t)stream, n_str, K, T, of, bl, ok, ar,
+                       match_thr, max_age, t, id, mo, bo, sl, te_);
+  PP_CHECK_LAUNCH(staged ? "track_assign_staged_kernel" : optimal ? "track_assign_optimal_kernel"
+                                                                  : "track_assign_kernel");
+  return 0;
 }
 
 }  // namespace pp
@@ -623,60 +710,25 @@ extern "C" long long pp_track_state_bytes(int max_tracks, int K) {
 extern "C" int pp_track_oks(int n_str, int K, int max_tracks, long long Dtot, const long long *host_off,
                             const void *det_stream, const void *blocks, const void *kpts, const void *vis,
                             const void *area, const void *vars, double vis_thr, void *oks, void *stream) {
-  using namespace pp;
-  if (int rc = track_check_common("pp_track_oks", n_str, K, max_tracks, Dtot)) return rc;
-  PP_REQUIRE(!vis || vis_thr == vis_thr, "pp_track_oks: vis_thr is not a number");
-  PP_REQUIRE(det_stream && blocks && kpts && area && vars && oks, "pp_track_oks: null argument");
-  if (int rc = track_check_offsets("pp_track_oks", n_str, host_off, Dtot)) return rc;
-  if (n_str == 0 || Dtot == 0) return 0;
-  const long long lanes = Dtot * max_tracks, grid = (lanes + kTrackThreads - 1) / kTrackThreads;
-  PP_REQUIRE(grid < (1ll << 31), "pp_track_oks: %lld pairs exceed one grid", lanes);
-  hipLaunchKernelGGL(track_oks_kernel, dim3((unsigned)grid), dim3(kTrackThreads), 0, (hipStream_t)stream, K,
-                     max_tracks, Dtot, (const long long *)det_stream, (const long long *)blocks, (const double *)kpts,
-                     (const double *)vis, (const double *)area, (const double *)vars, vis_thr, (double *)oks);
-  PP_CHECK_LAUNCH("track_oks_kernel");
-  return 0;
+  return pp::track_launch_oks("pp_track_oks", false, n_str, K, max_tracks, Dtot, host_off, det_stream, blocks, kpts,
+                              vis, area, vars, vis_thr, 0.0, 0.0, oks, stream);
 }
 
 extern "C" int pp_track_oks_predicted(int n_str, int K, int max_tracks, long long Dtot, const long long *host_off,
                                       const void *det_stream, const void *blocks, const void *kpts, const void *vis,
                                       const void *area, const void *vars, double vis_thr, double t, double max_dt,
                                       void *oks, void *stream) {
-  using namespace pp;
-  const char *who = "pp_track_oks_predicted";
-  if (int rc = track_check_common(who, n_str, K, max_tracks, Dtot)) return rc;
-  PP_REQUIRE(!vis || vis_thr == vis_thr, "%s: vis_thr is not a number", who);
-  PP_REQUIRE(isfinite(t), "%s: t=%g is not finite", who, t);
-  PP_REQUIRE(max_dt >= 0.0, "%s: max_dt=%g is negative or not a number", who, max_dt);
-  PP_REQUIRE(det_stream && blocks && kpts && area && vars && oks, "%s: null argument", who);
-  if (int rc = track_check_offsets(who, n_str, host_off, Dtot)) return rc;
-  if (n_str == 0 || Dtot == 0) return 0;
-  const long long lanes = Dtot * max_tracks, grid = (lanes + kTrackThreads - 1) / kTrackThreads;
-  PP_REQUIRE(grid < (1ll << 31), "%s: %lld pairs exceed one grid", who, lanes);
-  hipLaunchKernelGGL(track_oks_predicted_kernel, dim3((unsigned)grid), dim3(kTrackThreads), 0, (hipStream_t)stream, K,
-                     max_tracks, Dtot, (const long long *)det_stream, (const long long *)blocks, (const double *)kpts,
-                     (const double *)vis, (const double *)area, (const double *)vars, vis_thr, t, max_dt,
-                     (double *)oks);
-  PP_CHECK_LAUNCH("track_oks_predicted_kernel");
-  return 0;
+  return pp::track_launch_oks("pp_track_oks_predicted", true, n_str, K, max_tracks, Dtot, host_off, det_stream, blocks,
+                              kpts, vis, area, vars, vis_thr, t, max_dt, oks, stream);
 }
 
 extern "C" int pp_track_assign(int n_str, int K, int max_tracks, long long Dtot, const long long *host_off,
                                const void *off, const void *blocks, const void *oks, const void *area,
                                double match_thr, int max_age, double t, double t_prev, void *ids, void *match_oks,
                                void *born, void *slot_of, void *te, void *stream) {
-  using namespace pp;
-  if (int rc = track_check_assign("pp_track_assign", n_str, K, max_tracks, Dtot, host_off, match_thr, max_age, t,
-                                  t_prev, off && blocks && oks && area && ids && match_oks && born && slot_of && te))
-    return rc;
-  if (n_str == 0) return 0;                                // a stream without detections still ages its tracks
-  const unsigned grid = (unsigned)((n_str + kTrackWaves - 1) / kTrackWaves);
-  hipLaunchKernelGGL(track_assign_kernel, dim3(grid), dim3(64 * kTrackWaves), 0, (hipStream_t)stream, n_str, K,
-                     max_tracks, (const long long *)off, (const long long *)blocks, (const double *)oks,
-                     (const double *)area, match_thr, max_age, t, (long long *)ids, (double *)match_oks,
-                     (unsigned char *)born, (int *)slot_of, (double *)te);
-  PP_CHECK_LAUNCH("track_assign_kernel");
-  return 0;
+  return pp::track_launch_assign("pp_track_assign", false, 0, n_str, K, max_tracks, Dtot, host_off, off, blocks, oks,
+                                 area, nullptr, match_thr, 0.0, 0.0, 0, 0.0, max_age, t, t_prev, ids, match_oks, born,
+                                 slot_of, te, nullptr, nullptr, stream);
 }
 
 extern "C" int pp_track_assign_optimal(int n_str, int K, int max_tracks, long long Dtot, const long long *host_off,
@@ -684,25 +736,9 @@ extern "C" int pp_track_assign_optimal(int n_str, int K, int max_tracks, long lo
                                        double match_thr, int max_age, double t, double t_prev, void *ids,
                                        void *match_oks, void *born, void *slot_of, void *te, void *total,
                                        void *stream) {
-  using namespace pp;
-  const char *who = "pp_track_assign_optimal";
-  if (int rc = track_check_assign(who, n_str, K, max_tracks, Dtot, host_off, match_thr, max_age, t, t_prev,
-                                  off && blocks && oks && area && ids && match_oks && born && slot_of && te))
-    return rc;
-  PP_REQUIRE(max_tracks <= PP_TRACK_OPT_MAX, "%s: max_tracks=%d is above PP_TRACK_OPT_MAX = %d", who, max_tracks,
-             PP_TRACK_OPT_MAX);
-  for (int i = 0; i < n_str; ++i)
-    PP_REQUIRE(host_off[i + 1] - host_off[i] <= PP_TRACK_OPT_MAX,
-               "%s: stream %d has %lld detections, more than PP_TRACK_OPT_MAX = %d", who, i,
-               host_off[i + 1] - host_off[i], PP_TRACK_OPT_MAX);
-  if (n_str == 0) return 0;
-  const unsigned grid = (unsigned)((n_str + kTrackWaves - 1) / kTrackWaves);
-  hipLaunchKernelGGL(track_assign_optimal_kernel, dim3(grid), dim3(64 * kTrackWaves), 0, (hipStream_t)stream, n_str,
-                     K, max_tracks, (const long long *)off, (const long long *)blocks, (const double *)oks,
-                     (const double *)area, match_thr, max_age, t, (long long *)ids, (double *)match_oks,
-                     (unsigned char *)born, (int *)slot_of, (double *)te, (long long *)total);
-  PP_CHECK_LAUNCH("track_assign_optimal_kernel");
-  return 0;
+  return pp::track_launch_assign("pp_track_assign_optimal", false, 1, n_str, K, max_tracks, Dtot, host_off, off,
+                                 blocks, oks, area, nullptr, match_thr, 0.0, 0.0, 0, 0.0, max_age, t, t_prev, ids,
+                                 match_oks, born, slot_of, te, nullptr, total, stream);
 }
 
 extern "C" int pp_track_assign_staged(int n_str, int K, int max_tracks, long long Dtot, const long long *host_off,
@@ -711,36 +747,9 @@ extern "C" int pp_track_assign_staged(int n_str, int K, int max_tracks, long lon
                                       int low_max_age, double birth_thr, int optimal, int max_age, double t,
                                       double t_prev, void *ids, void *match_oks, void *born, void *slot_of, void *te,
                                       void *dropped, void *stream) {
-  using namespace pp;
-  const char *who = "pp_track_assign_staged";
-  if (int rc = track_check_assign(who, n_str, K, max_tracks, Dtot, host_off, match_thr, max_age, t, t_prev,
-                                  off && blocks && oks && area && score && ids && match_oks && born && slot_of && te &&
-                                      dropped))
-    return rc;
-  PP_REQUIRE(high_thr == high_thr, "%s: high_thr is not a number", who);
-  PP_REQUIRE(birth_thr == birth_thr, "%s: birth_thr is not a number", who);
-  PP_REQUIRE(low_match_thr >= 0.0 && low_match_thr < 1.0, "%s: low_match_thr=%g is outside [0, 1)", who,
-             low_match_thr);
-  PP_REQUIRE(low_max_age >= 0, "%s: low_max_age=%d", who, low_max_age);
-  PP_REQUIRE(optimal == 0 || optimal == 1, "%s: optimal=%d is neither 0 nor 1", who, optimal);
-  if (optimal) {
-    PP_REQUIRE(max_tracks <= PP_TRACK_OPT_MAX, "%s: max_tracks=%d is above PP_TRACK_OPT_MAX = %d", who, max_tracks,
-               PP_TRACK_OPT_MAX);
-    for (int i = 0; i < n_str; ++i)
-      PP_REQUIRE(host_off[i + 1] - host_off[i] <= PP_TRACK_OPT_MAX,
-                 "%s: stream %d has %lld detections, more than PP_TRACK_OPT_MAX = %d", who, i,
-                 host_off[i + 1] - host_off[i], PP_TRACK_OPT_MAX);
-  }
-  if (n_str == 0) return 0;
-  const unsigned grid = (unsigned)((n_str + kTrackWaves - 1) / kTrackWaves);
-  const auto kernel = optimal ? track_assign_staged_kernel<true> : track_assign_staged_kernel<false>;
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * kTrackWaves), 0, (hipStream_t)stream, n_str, K, max_tracks,
-                     (const long long *)off, (const long long *)blocks, (const double *)oks, (const double *)area,
-                     (const double *)score, match_thr, high_thr, low_match_thr, low_max_age, birth_thr, max_age, t,
-                     (long long *)ids, (double *)match_oks, (unsigned char *)born, (int *)slot_of, (double *)te,
-                     (unsigned char *)dropped);
-  PP_CHECK_LAUNCH("track_assign_staged_kernel");
-  return 0;
+  return pp::track_launch_assign("pp_track_assign_staged", true, optimal, n_str, K, max_tracks, Dtot, host_off, off,
+                                 blocks, oks, area, score, match_thr, high_thr, low_match_thr, low_max_age, birth_thr,
+                                 max_age, t, t_prev, ids, match_oks, born, slot_of, te, dropped, nullptr, stream);
 }
 
 extern "C" int pp_track_filter(int K, int max_tracks, long long Dtot, const void *det_stream, const void *blocks,
@@ -757,9 +766,9 @@ extern "C" int pp_track_filter(int K, int max_tracks, long long Dtot, const void
                d_cutoff, beta);
   PP_REQUIRE(det_stream && blocks && kpts && slot_of && born && te && out, "pp_track_filter: null argument");
   if (Dtot == 0) return 0;
-  const long long lanes = Dtot * K, grid = (lanes + kTrackThreads - 1) / kTrackThreads;
-  PP_REQUIRE(grid < (1ll << 31), "pp_track_filter: %lld keypoints exceed one grid", lanes);
-  hipLaunchKernelGGL(track_filter_kernel, dim3((unsigned)grid), dim3(kTrackThreads), 0, (hipStream_t)stream, K,
+  unsigned grid;
+  if (int rc = track_grid("pp_track_filter", Dtot * K, "keypoints", &grid)) return rc;
+  hipLaunchKernelGGL(track_filter_kernel, dim3(grid), dim3(kTrackThreads), 0, (hipStream_t)stream, K,
                      max_tracks, Dtot, (const long long *)det_stream, (const long long *)blocks, (const double *)kpts,
                      (const double *)vis, vis_thr, (const int *)slot_of, (const unsigned char *)born,
                      (const double *)te, smooth, min_cutoff, beta, d_cutoff, (double *)out);
@@ -915,9 +924,9 @@ extern "C" int pp_track_boxes(int n_str, int K, int max_tracks, const void *bloc
   }
   if (n_str == 0) return 0;
   PP_REQUIRE(blocks && boxes && ids && scores && status, "pp_track_boxes: null argument (blocks or an output)");
-  const long long lanes = (long long)n_str * max_tracks, grid = (lanes + kTrackThreads - 1) / kTrackThreads;
-  PP_REQUIRE(grid < (1ll << 31), "pp_track_boxes: %lld slots exceed one grid", lanes);
-  hipLaunchKernelGGL(track_boxes_kernel, dim3((unsigned)grid), dim3(kTrackThreads), 0, (hipStream_t)stream, n_str, K,
+  unsigned grid;
+  if (int rc = track_grid("pp_track_boxes", (long long)n_str * max_tracks, "slots", &grid)) return rc;
+  hipLaunchKernelGGL(track_boxes_kernel, dim3(grid), dim3(kTrackThreads), 0, (hipStream_t)stream, n_str, K,
                      max_tracks, (const long long *)blocks, t, use_vis, vis_thr, smooth, extrapolate, max_dt, max_age,
                      min_keypoints, pad, min_side, aspect, (const double *)frame_wh, (const long long *)sup_off,
                      (const double *)sup_boxes, iou_thr, (double *)boxes, (long long *)ids, (double *)scores,

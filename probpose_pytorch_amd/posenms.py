@@ -10,7 +10,9 @@ csrc/pp_posenms.hip:
   pp_posenms           one wave per image; lane j % 64 owns detection j's live flag and current score
 
 Between them run torch device ops that do not synchronise: casts to float64, two stable sorts (descending score, then
-image: every image's detections end up in score order, equal scores in the order they were given) and gathers.
+image: every image's detections end up in score order, equal scores in the order they were given) and gathers.  That
+front end (the layout from the image ids, the shape, placement and finiteness checks, the visiting order and the way
+back) is _ragged.py's, which PoseTracker and CocoKeypointEval use too.
 
 Rules (restated in tests/posenms_reference.py, the gauge this module is tested against), float64 throughout:
 * rescoring: n = the keypoints with score > kpt_thr, score = box_score * (their sum in ascending k / n), 0 with n = 0;
@@ -36,47 +38,12 @@ import torch
 
 from . import _lib
 from ._buffers import host_array as _host, room as _room, upload
+from ._ragged import (check_pose_batch, device_f64, first_seen, group_layout, host_ids, unsorted, visibilities,
+                      visiting_order)
 
 MODES = {"hard": _lib.PP_POSENMS_HARD, "soft_gaussian": _lib.PP_POSENMS_SOFT_GAUSSIAN,
          "soft_linear": _lib.PP_POSENMS_SOFT_LINEAR}
 MAX_DETS_PER_IMAGE = _lib.PP_POSENMS_MAX_DETS
-
-
-def _device_f64(named) -> list:
-    """The named inputs as contiguous float64 device tensors.  Refuses host arrays, mixed placement, non-float
-    dtypes and non-finite values (one boolean per input is read back, as CocoKeypointEval.add_detections does)."""
-    names = " / ".join(n for n, _ in named)
-    dev = [isinstance(a, torch.Tensor) and a.is_cuda for _, a in named]
-    if any(dev) and not all(dev):
-        raise ValueError(f"{names}: either all device tensors or all host arrays")
-    if not all(dev):
-        _lib.require_device()
-        raise _lib.HipExtensionError(f"{names}: expected tensors on the GPU (cuda/HIP device); there is no CPU "
-                                     "fallback")
-    for n, a in named:
-        if not a.dtype.is_floating_point:
-            raise ValueError(f"{n}: expected a float dtype, got {a.dtype}")
-    out = [a.detach().to(torch.float64).contiguous() for _, a in named]
-    finite = torch.stack([torch.isfinite(t).all() for t in out]).cpu().numpy()
-    for (n, _), ok in zip(named, finite):
-        if not bool(ok):
-            raise ValueError(f"{n}: non-finite values")
-    return out
-
-
-def _first_seen(ids: np.ndarray):
-    """(the distinct ids in the order they first appear, every id's position in that list [M] int64)."""
-    if ids.dtype != object:
-        uniq, first, inverse = np.unique(ids, return_index=True, return_inverse=True)
-        by_first = np.argsort(first, kind="stable")
-        rank = np.empty(by_first.size, dtype=np.int64)
-        rank[by_first] = np.arange(by_first.size, dtype=np.int64)
-        return uniq[by_first].tolist(), rank[inverse.reshape(-1)]
-    index = {}
-    for i in ids.tolist():
-        if i not in index:
-            index[i] = len(index)
-    return list(index), np.fromiter((index[i] for i in ids.tolist()), dtype=np.int64, count=ids.shape[0])
 
 
 def _rescore(ks: torch.Tensor, bs: torch.Tensor, kpt_thr: float) -> torch.Tensor:
@@ -96,7 +63,7 @@ def rescore_instances(kpt_scores, box_scores, kpt_thr: float = 0.2) -> torch.Ten
         raise ValueError(f"box_scores: expected [{shape[0]}], got {bshape}")
     if not np.isfinite(kpt_thr):
         raise ValueError(f"kpt_thr: {kpt_thr} is not finite")
-    ks, bs = _device_f64((("kpt_scores", kpt_scores), ("box_scores", box_scores)))
+    ks, bs = device_f64((("kpt_scores", kpt_scores), ("box_scores", box_scores)))
     return _rescore(ks, bs, kpt_thr)
 
 
@@ -165,60 +132,29 @@ class PoseNMS:
         Apart from the finiteness booleans of the inputs nothing is read back and nothing waits for the device: the
         result's tensors are still being computed when this returns.  Boolean indexing by ``keep``
         (``keypoints[res.keep]``) is the caller's one readback, since the number of survivors decides a shape."""
-        ids = image_ids.detach().cpu().numpy() if isinstance(image_ids, torch.Tensor) else np.asarray(image_ids)
+        ids = host_ids(image_ids)
         if ids.ndim != 1:
             raise ValueError(f"image_ids: expected [M], got {ids.shape}")
-        M, K = int(ids.shape[0]), self.K
         named = [("keypoints", keypoints), ("box_scores", box_scores), ("areas", areas)]
         if kpt_scores is not None:
             named.append(("kpt_scores", kpt_scores))
-        named = [(n, a if isinstance(a, torch.Tensor) else np.asarray(a)) for n, a in named]
-        shape = tuple(named[0][1].shape)
-        if len(shape) != 3 or shape[0] != M or shape[1] != K or shape[2] not in (2, 3):
-            raise ValueError(f"keypoints: expected [{M}, {K}, 2|3] (K = len(sigmas)), got {shape}")
-        for n, a in named[1:3]:
-            if tuple(a.shape) != (M,):
-                raise ValueError(f"{n}: expected [{M}], got {tuple(a.shape)}")
-        if kpt_scores is not None and tuple(named[3][1].shape) != (M, K):
-            raise ValueError(f"kpt_scores: expected [{M}, {K}], got {tuple(named[3][1].shape)}")
-        if self.vis_thr is not None and kpt_scores is None and shape[2] != 3:
-            raise ValueError("vis_thr: needs visibilities, kpt_scores or a third keypoint column")
+        named, _ = check_pose_batch(named, self.K, int(ids.shape[0]), self.vis_thr)
+        image_list, pos = first_seen(ids)
+        _, off = group_layout(pos, image_list, "image_ids: image",
+                              [(MAX_DETS_PER_IMAGE, "that PoseNMS handles per image")])
 
-        # the ragged layout: host arithmetic on the image ids
-        image_list, pos = _first_seen(ids)
-        n_img = len(image_list)
-        d_cnt = np.bincount(pos, minlength=n_img).astype(np.int64) if n_img else np.zeros(0, dtype=np.int64)
-        if n_img and int(d_cnt.max()) > MAX_DETS_PER_IMAGE:
-            worst = int(d_cnt.argmax())
-            raise ValueError(f"image_ids: image {image_list[worst]!r} has {int(d_cnt[worst])} detections, more than "
-                             f"the {MAX_DETS_PER_IMAGE} that PoseNMS handles per image")
-        off = np.zeros(n_img + 1, dtype=np.int64)
-        off[1:] = np.cumsum(d_cnt)
-
-        tensors = _device_f64(named)
+        tensors = device_f64(named)
         kp3, bs, ar = tensors[:3]
         dev = kp3.device
-        if kpt_scores is not None:
-            sc = _rescore(tensors[3], bs, self.kpt_thr)
-            vis = tensors[3] if self.vis_thr is not None else None
-        else:
-            sc = bs
-            vis = kp3[..., 2] if self.vis_thr is not None else None
-
+        sc = bs if kpt_scores is None else _rescore(tensors[3], bs, self.kpt_thr)
+        vis = visibilities(tensors, self.vis_thr)
         staged = []
         up = partial(upload, device=dev, keep=staged)
-        # descending score, then image: two stable sorts leave every image's detections in score order, equal scores
-        # in the order they were given
-        by_score = torch.sort(sc, descending=True, stable=True).indices
-        by_image = torch.sort(up(pos)[by_score], stable=True).indices
-        perm = by_score[by_image]
+        perm, _ = visiting_order(sc, pos, up)
         kp_s = kp3[..., :2][perm].contiguous()
         vis_s = None if vis is None else vis[perm].contiguous()
         ar_s, sc_s = ar[perm].contiguous(), sc[perm].contiguous()
         variances, off_dev = up((self.sigmas * 2) ** 2), up(off)
-        out_s, keep_s, counts = self._launch(n_img, off, off_dev, kp_s, vis_s, ar_s, sc_s, variances)
-        keep = torch.empty(M, dtype=torch.bool, device=dev)
-        scores = torch.empty(M, dtype=torch.float64, device=dev)
-        keep[perm] = keep_s.to(torch.bool)
-        scores[perm] = out_s
+        out_s, keep_s, counts = self._launch(len(image_list), off, off_dev, kp_s, vis_s, ar_s, sc_s, variances)
+        keep, scores = unsorted(perm, keep_s.to(torch.bool)), unsorted(perm, out_s)
         return PoseNMSResult(keep, scores, counts, image_list, staged)

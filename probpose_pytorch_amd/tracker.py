@@ -6,8 +6,9 @@ leave on the device and keeps its state there, with the three launches of csrc/p
   pp_track_assign   one wave per stream; lane j % 64 owns slot j: association, ageing, births, ids
   pp_track_filter   one lane per (detection, keypoint): the One-Euro step, the output and the slot's new state
 
-Between them run torch device ops that do not synchronise: casts to float64, PoseNMS's two stable sorts (descending
-score, then stream) and gathers.
+Between them run torch device ops that do not synchronise: casts to float64, two stable sorts (descending score, then
+stream) and gathers.  The layout from the stream ids, the input checks with their one read-back, that visiting order
+and the way back are _ragged.py's, shared with PoseNMS and CocoKeypointEval.
 
 Rules (restated in tests/track_reference.py, the gauge this module is tested against), float64 throughout.  State per
 stream: ``max_tracks`` slots (id, age, t_last, area, raw keypoints and visibilities, filter state xhat, dxhat, init) and
@@ -55,7 +56,8 @@ import torch
 
 from . import _lib
 from ._buffers import host_array as _host, room as _room, upload
-from .posenms import _first_seen
+from ._ragged import (check_pose_batch, device_f64, first_seen, group_layout, host_ids, unsorted, visibilities,
+                      visiting_order)
 
 MAX_TRACKS = _lib.PP_TRACK_MAX_TRACKS
 MAX_DETS_PER_STREAM = _lib.PP_TRACK_MAX_DETS
@@ -143,19 +145,6 @@ class BoxProposals:
         ids, scores = raw[32 * n:40 * n].view(np.int64), raw[40 * n:48 * n].view(np.float64)
         rows = np.flatnonzero(raw[48 * n:] == _lib.PP_TRACK_BOX_PROPOSED)
         return boxes[rows].copy(), ids[rows].copy(), scores[rows].copy(), (rows // T).astype(np.int64)
-
-
-def _check_inputs(named) -> bool:
-    """Mixed placement and non-float dtypes raise ValueError; returns whether everything is on the device."""
-    names = " / ".join(n for n, _ in named)
-    dev = [isinstance(a, torch.Tensor) and a.is_cuda for _, a in named]
-    if any(dev) and not all(dev):
-        raise ValueError(f"{names}: either all device tensors or all host arrays")
-    for n, a in named:
-        floating = a.dtype.is_floating_point if isinstance(a, torch.Tensor) else np.issubdtype(a.dtype, np.floating)
-        if not floating:
-            raise ValueError(f"{n}: expected a float dtype, got {a.dtype}")
-    return all(dev)
 
 
 class PoseTracker:
@@ -286,6 +275,30 @@ class PoseTracker:
             return torch.zeros(0, dtype=torch.int64, device=self._device or "cpu")
         return torch.cat([self._field(c, "overflow").reshape(-1) for c in self._chunks])[:n]
 
+    def _time(self, t, previous: str) -> float:
+        """The time of an ``update`` or ``propose_boxes`` call: ``t`` or the next default, past the last update's."""
+        t_now = (self._calls + 1) / self.fps if t is None else float(t)
+        if not (np.isfinite(t_now) and t_now > self._t_prev):
+            raise ValueError(f"t: {t_now} is not greater than the previous {previous} {self._t_prev}")
+        return t_now
+
+    @staticmethod
+    def _named(streams):
+        """(the streams a call names as a list, stream -> its place in that list); a stream named twice raises."""
+        stream_list = list(streams)
+        where = {s: i for i, s in enumerate(stream_list)}
+        if len(where) != len(stream_list):
+            raise ValueError("streams: a stream is named twice")
+        return stream_list, where
+
+    @staticmethod
+    def _places(where: dict, names: list, who: str) -> np.ndarray:
+        """[len(names)] int64: every name's place in the call's streams; one the call does not name raises."""
+        missing = [s for s in names if s not in where]
+        if missing:
+            raise ValueError(f"{who}: stream {missing[0]!r} is not in streams")
+        return np.fromiter((where[s] for s in names), dtype=np.int64, count=len(names))
+
     # ------------------------------------------------------------------------------------------- boxes
     def _launch_boxes(self, n_str, blocks, t, frame_wh, sup_off, sup_off_dev, sup_boxes, opts, device):
         """The one launch of ``propose_boxes``: (boxes [S, T, 4], ids, scores, status) on ``device``."""
@@ -318,9 +331,7 @@ class PoseTracker:
         stream's frames or with fewer than ``min_keypoints`` counted keypoints propose nothing.  ``suppress`` = (boxes
         [n, 4] xywh, stream_ids [n] or None for the only stream): a proposal whose IoU with one of its stream's boxes
         exceeds ``iou_thr`` is marked SUPPRESSED.  The defaults are common top-down practice, not tuned on data."""
-        t_now = (self._calls + 1) / self.fps if t is None else float(t)
-        if not (np.isfinite(t_now) and t_now > self._t_prev):
-            raise ValueError(f"t: {t_now} is not greater than the previous update's {self._t_prev}")
+        t_now = self._time(t, "update's")
         for name, v in (("pad", pad), ("min_side", min_side)):
             if not (np.isfinite(v) and v > 0):
                 raise ValueError(f"{name}: {v} is not a positive number")
@@ -336,10 +347,7 @@ class PoseTracker:
             raise ValueError(f"max_dt: {max_dt} is negative or not a number")
         if not 0.0 <= float(iou_thr) <= 1.0:
             raise ValueError(f"iou_thr: {iou_thr} is outside [0, 1]")
-        stream_list = list(self._index) if streams is None else list(streams)
-        where = {s: i for i, s in enumerate(stream_list)}
-        if len(where) != len(stream_list):
-            raise ValueError("streams: a stream is named twice")
+        stream_list, where = self._named(self._index if streams is None else streams)
         for s in stream_list:
             if s not in self._index:
                 raise KeyError(f"stream: {s!r} has not been seen")
@@ -369,17 +377,12 @@ class PoseTracker:
                     raise ValueError(f"suppress: stream_ids are needed with {n_str} streams")
                 pos = np.zeros(n_sup, dtype=np.int64)
             else:
-                names = (sup_streams.detach().cpu().numpy() if isinstance(sup_streams, torch.Tensor)
-                         else np.asarray(sup_streams)).tolist()
+                names = host_ids(sup_streams).tolist()
                 if len(names) != n_sup:
                     raise ValueError(f"suppress: expected stream_ids [{n_sup}], got {len(names)}")
-                missing = [s for s in names if s not in where]
-                if missing:
-                    raise ValueError(f"suppress: stream {missing[0]!r} is not in streams")
-                pos = np.fromiter((where[s] for s in names), dtype=np.int64, count=n_sup)
+                pos = self._places(where, names, "suppress")
             sup_perm = np.argsort(pos, kind="stable")                   # by stream, the given order within it
-            sup_off = np.zeros(n_str + 1, dtype=np.int64)
-            sup_off[1:] = np.cumsum(np.bincount(pos, minlength=n_str)[:n_str])
+            sup_off = group_layout(pos, n_str)[1]
 
         _lib.require_device()
         dev = self._device if self._device is not None else torch.device("cuda")
@@ -418,29 +421,29 @@ class PoseTracker:
         out_s = new((M, K, 2), dtype=torch.float64)
         vis_thr = 0.0 if self.vis_thr is None else self.vis_thr
         vis_hold = None if vis_s is None else _room(vis_s)
-        hold = [_room(x) for x in (det_stream, kp_s, ar_s, oks_ws, ids_s, oks_s, born_s, slot_s, te_s, out_s)]
-        det_stream_h, kp_h, ar_h, ws_h, ids_h, oks_h, born_h, slot_h, te_h, out_h = hold
-        oks_args = (n_str, K, T, M, off, det_stream_h, _room(blocks), kp_h, vis_hold, ar_h, variances, vis_thr)
+        hold = [_room(x) for x in (det_stream, blocks, kp_s, ar_s, oks_ws, ids_s, oks_s, born_s, slot_s, te_s, out_s)]
+        det_stream_h, blocks_h, kp_h, ar_h, ws_h, ids_h, oks_h, born_h, slot_h, te_h, out_h = hold
+        oks_args = (n_str, K, T, M, off, det_stream_h, blocks_h, kp_h, vis_hold, ar_h, variances, vis_thr)
         if self.predict:
             _lib.launch("pp_track_oks_predicted", *oks_args, t_now, self.predict_max_dt, ws_h)
         else:
             _lib.launch("pp_track_oks", *oks_args, ws_h)
-        assign_args = (n_str, K, T, M, off, off_dev, _room(blocks), ws_h, ar_h, self.match_thr, self.max_age, t_now,
-                       t_prev, ids_h, oks_h, born_h, slot_h, te_h)
+        # the assign entries: batch, [scores,] match_thr, [stage options,] clock and outputs, [dropped / total]
+        batch = (n_str, K, T, M, off, off_dev, blocks_h, ws_h, ar_h)
+        clock_and_outputs = (self.max_age, t_now, t_prev, ids_h, oks_h, born_h, slot_h, te_h)
+        optimal = self.assign == "optimal"
         dropped_s = None
-        if self.high_thr is not None or self.birth_thr is not None:
+        if sc_s is not None:                                # update decides, once: it sorts the scores for this entry
             dropped_s = new(M, dtype=torch.uint8)
             high = -np.inf if self.high_thr is None else self.high_thr      # birth_thr alone: everything is stage 1
-            # pp_track_assign's arguments with the scores and the stage options after `area`, `dropped` at the end
-            _lib.launch("pp_track_assign_staged", *assign_args[:9], _room(sc_s), self.match_thr, high,
-                        self.low_match_thr, self.low_max_age, self.birth_thr, int(self.assign == "optimal"),
-                        *assign_args[10:], _room(dropped_s))
-        elif self.assign == "optimal":
-            _lib.launch("pp_track_assign_optimal", *assign_args, None)
+            _lib.launch("pp_track_assign_staged", *batch, _room(sc_s), self.match_thr, high, self.low_match_thr,
+                        self.low_max_age, self.birth_thr, int(optimal), *clock_and_outputs, _room(dropped_s))
+        elif optimal:
+            _lib.launch("pp_track_assign_optimal", *batch, self.match_thr, *clock_and_outputs, None)
         else:
-            _lib.launch("pp_track_assign", *assign_args)
+            _lib.launch("pp_track_assign", *batch, self.match_thr, *clock_and_outputs)
         sm = self.smooth
-        _lib.launch("pp_track_filter", K, T, M, det_stream_h, _room(blocks), kp_h, vis_hold, vis_thr, slot_h, born_h,
+        _lib.launch("pp_track_filter", K, T, M, det_stream_h, blocks_h, kp_h, vis_hold, vis_thr, slot_h, born_h,
                     te_h, int(sm is not None), *((sm.min_cutoff, sm.beta, sm.d_cutoff) if sm else (1.0, 0.0, 1.0)),
                     out_h)
         return ids_s, oks_s, born_s, out_s, dropped_s
@@ -455,104 +458,49 @@ class PoseTracker:
 
         With ``kpt_scores`` they are the visibilities ``vis_thr`` reads, otherwise a third keypoint column is.  Apart
         from one finiteness boolean per input nothing is read back and nothing waits for the device."""
-        K, T = self.K, self.max_tracks
         named = [("keypoints", keypoints), ("areas", areas), ("scores", scores)]
         if kpt_scores is not None:
             named.append(("kpt_scores", kpt_scores))
-        named = [(n, a if isinstance(a, torch.Tensor) else np.asarray(a)) for n, a in named]
-        shape = tuple(named[0][1].shape)
-        if len(shape) != 3 or shape[1] != K or shape[2] not in (2, 3):
-            raise ValueError(f"keypoints: expected [M, {K}, 2|3] (K = len(sigmas)), got {shape}")
-        M = shape[0]
-        for n, a in named[1:3]:
-            if tuple(a.shape) != (M,):
-                raise ValueError(f"{n}: expected [{M}], got {tuple(a.shape)}")
-        if kpt_scores is not None and tuple(named[3][1].shape) != (M, K):
-            raise ValueError(f"kpt_scores: expected [{M}, {K}], got {tuple(named[3][1].shape)}")
-        if self.vis_thr is not None and kpt_scores is None and shape[2] != 3:
-            raise ValueError("vis_thr: needs visibilities, kpt_scores or a third keypoint column")
-        if stream_ids is None:
-            ids = np.zeros(M, dtype=np.int64)
+        named, M = check_pose_batch(named, self.K, None, self.vis_thr)
+        ids = np.zeros(M, dtype=np.int64) if stream_ids is None else host_ids(stream_ids)
+        if ids.shape != (M,):
+            raise ValueError(f"stream_ids: expected [{M}], got {ids.shape}")
+        if streams is not None:
+            stream_list, where = self._named(streams)
+            pos = self._places(where, ids.tolist(), "stream_ids")
         else:
-            ids = (stream_ids.detach().cpu().numpy() if isinstance(stream_ids, torch.Tensor)
-                   else np.asarray(stream_ids))
-            if ids.shape != (M,):
-                raise ValueError(f"stream_ids: expected [{M}], got {ids.shape}")
-        if streams is None:
-            stream_list, pos = _first_seen(ids) if (M or stream_ids is not None) else ([0], np.zeros(0, np.int64))
-        else:
-            stream_list = list(streams)
-            where = {s: i for i, s in enumerate(stream_list)}
-            if len(where) != len(stream_list):
-                raise ValueError("streams: a stream is named twice")
-            missing = [s for s in ids.tolist() if s not in where]
-            if missing:
-                raise ValueError(f"stream_ids: stream {missing[0]!r} is not in streams")
-            pos = np.fromiter((where[s] for s in ids.tolist()), dtype=np.int64, count=M)
+            stream_list, pos = first_seen(ids) if (M or stream_ids is not None) else ([0], np.zeros(0, np.int64))
         n_str = len(stream_list)
-        d_cnt = np.bincount(pos, minlength=n_str).astype(np.int64) if n_str else np.zeros(0, dtype=np.int64)
-        if n_str and int(d_cnt.max()) > MAX_DETS_PER_STREAM:
-            worst = int(d_cnt.argmax())
-            raise ValueError(f"stream_ids: stream {stream_list[worst]!r} has {int(d_cnt[worst])} detections, more "
-                             f"than the {MAX_DETS_PER_STREAM} that PoseTracker takes per stream and call")
-        if self.assign == "optimal" and n_str and int(d_cnt.max()) > OPT_MAX:
-            worst = int(d_cnt.argmax())
-            raise ValueError(f"stream_ids: stream {stream_list[worst]!r} has {int(d_cnt[worst])} detections, more "
-                             f'than the {OPT_MAX} that assign="optimal" takes per stream and call')
-        t_now = (self._calls + 1) / self.fps if t is None else float(t)
-        if not (np.isfinite(t_now) and t_now > self._t_prev):
-            raise ValueError(f"t: {t_now} is not greater than the previous call's {self._t_prev}")
-        on_device = _check_inputs(named)
-        if not on_device:
-            _lib.require_device()
-            raise _lib.HipExtensionError("keypoints / areas / scores: expected tensors on the GPU (cuda/HIP device); "
-                                         "there is no CPU fallback")
-        tensors = [a.detach().to(torch.float64).contiguous() for _, a in named]
-        finite = torch.stack([torch.isfinite(x).all() for x in tensors]).cpu().numpy()      # the one read-back
-        for (n, _), ok in zip(named, finite):
-            if not bool(ok):
-                raise ValueError(f"{n}: non-finite values")
+        limits = [(MAX_DETS_PER_STREAM, "that PoseTracker takes per stream and call")]
+        if self.assign == "optimal":
+            limits.append((OPT_MAX, 'that assign="optimal" takes per stream and call'))
+        _, off = group_layout(pos, stream_list, "stream_ids: stream", limits)
+        t_now = self._time(t, "call's")
+        tensors = device_f64(named, "keypoints / areas / scores")      # the one read-back
         kp3, ar, sc = tensors[:3]
         dev = kp3.device
         if self._device is None:
             self._device = dev
         elif dev != self._device:
             raise ValueError(f"keypoints: on {dev}, the tracker's state is on {self._device}")
-        if self.vis_thr is None:
-            vis = None
-        else:
-            vis = tensors[3] if kpt_scores is not None else kp3[..., 2]
-
-        off = np.zeros(n_str + 1, dtype=np.int64)
-        off[1:] = np.cumsum(d_cnt)
-        numbers = [self._number(s, dev) for s in stream_list]
-        addresses = np.array([self._block(n).data_ptr() for n in numbers], dtype=np.int64)
+        vis = visibilities(tensors, self.vis_thr)
+        addresses = np.array([self._block(self._number(s, dev)).data_ptr() for s in stream_list], dtype=np.int64)
 
         staged = []
         up = partial(upload, device=dev, keep=staged)
-        # descending score, then stream: PoseNMS's two stable sorts
-        by_score = torch.sort(sc, descending=True, stable=True).indices
-        pos_dev = up(pos)
-        by_stream = torch.sort(pos_dev[by_score], stable=True).indices
-        perm = by_score[by_stream]
+        perm, pos_dev = visiting_order(sc, pos, up)
         kp_s = kp3[..., :2][perm].contiguous()
         vis_s = None if vis is None else vis[perm].contiguous()
         ar_s, det_stream = ar[perm].contiguous(), pos_dev[perm].contiguous()
         variances, off_dev, blocks = up((self.sigmas * 2) ** 2), up(off), up(addresses)
-
-        staged_assign = self.high_thr is not None or self.birth_thr is not None
-        sc_s = sc[perm].contiguous() if staged_assign else None
+        sc_s = sc[perm].contiguous() if self.high_thr is not None or self.birth_thr is not None else None
 
         ids_s, oks_s, born_s, out_s, dropped_s = self._launch(n_str, off, off_dev, det_stream, blocks, kp_s, vis_s,
                                                               ar_s, sc_s, variances, t_now, self._t_prev)
         self._calls += 1
         self._t_prev = t_now
 
-        new = partial(torch.empty, device=dev)
-        ids_out, oks_out = torch.empty_like(ids_s), torch.empty_like(oks_s)
-        born_out, kp_out = new(M, dtype=torch.bool), torch.empty_like(out_s)
-        ids_out[perm], oks_out[perm], born_out[perm], kp_out[perm] = ids_s, oks_s, born_s.to(torch.bool), out_s
-        dropped_out = torch.zeros(M, dtype=torch.bool, device=dev)
-        if dropped_s is not None:
-            dropped_out[perm] = dropped_s.to(torch.bool)
+        ids_out, oks_out, kp_out, born_out = (unsorted(perm, x) for x in (ids_s, oks_s, out_s, born_s.to(torch.bool)))
+        dropped_out = (torch.zeros(M, dtype=torch.bool, device=dev) if dropped_s is None
+                       else unsorted(perm, dropped_s.to(torch.bool)))
         return TrackResult(ids_out, kp_out, oks_out, born_out, stream_list, staged, dropped_out)
