@@ -1161,6 +1161,76 @@ int pp_viz_render(const void *image, int image_f32chw, void *out, int B, int H, 
 int pp_viz_colorize(const float *maps, void *out, long long M, int h, int w, const double *lut, int normalize,
                     void *stream);
 
+/* ------------------------------------------------------------------------
+ * ValidationMeter (probpose_pytorch_amd/valmeter.py): a whole validation pass accumulated on the device
+ * and read back once.  Replaces, per batch of the reference's validation loop (train.py:124-168),
+ *   get_binary_accuracy      probpose/loss.py:653-697  (its balanced subsample by its expectation, see below)
+ *   get_mae                  probpose/loss.py:699-712
+ *   the populations / labels probpose/loss.py:419, :473-500
+ *   the host averaging       train.py:146-167
+ *
+ * The state is `pp_valmeter_state_words(K, J)` int64 words, all zero when empty (a memset resets it).  It holds counts
+ * and fixed-point sums only, so it does not depend on the order or the split of the batches.  Q30(z) = rint(z 2^30) in
+ * float64 (ties to even), Q20 the same at 2^20; the fine bin of p in [0,1] is min(1023, floor(p * 1024)) in float32.
+ * Sections, in this order (h = 0 probability, 1 visibility; label 0 / 1):
+ *   hist     [2][K][2][1024]  samples per (head, keypoint, label, fine bin of p)
+ *   conf     [2][K][1024]     sum of Q30(p) per fine bin
+ *   above    [2][K][2][J]     samples with (double)p > thresholds[j], strictly
+ *   sum_p    [2][K][2]        sum of Q30(p)
+ *   sum_p2   [2][K][2]        sum of Q30(p p)
+ *   oks_hist [K][1024]        samples of the OKS head per fine bin of the prediction x
+ *   oks_sx   [K][1024]        sum of Q30(x) per fine bin
+ *   oks_st   [K][1024]        sum of Q30(t) per fine bin, t the achieved OKS
+ *   oks_sums [K][5]           sums of Q30 of |x - t|, (x - t)^2, x^2, t^2, x t (formed in float64)
+ *   err      [K][4]           n, sums of Q20 of x, t, |x - t| of the error head
+ *   pck      [2][K]           hits, valid (the sums of pck_counts)
+ *   all      [3]              samples, samples whose dt_prob is in [0,1], the sum of Q30(dt_prob) over those
+ *   rejected [5]              samples refused for: a mask value, the probability, visibility, OKS, error head
+ *   scalars  [15]             int64: batches, flagged batches, OR of the flag words, unflagged batches that had `res`,
+ *                             those that had pck_counts, batches that had map_max; then float64 bit patterns: the sums
+ *                             over the unflagged batches of res[1], res[3..8]; of the per-batch PCK average; the
+ *                             running maximum of map_max (a NaN wins).
+ *
+ * pp_valmeter_update adds one batch of B*K samples.  dt_prob, dt_vis, dt_oks, dt_err [B*K] f32 predictions; gt_oks,
+ * gt_err [B*K] f32 as pp_probpose_loss_terms writes them; in_image, annotated, visibility [B*K] int32; thresholds [J]
+ * f64 on the device, 1 <= J <= 64; optional (NULL to leave out): pck_counts [2][K] int32 of pp_pck_counts, map_max
+ * [B*K] f32 = the vals of pp_heatmap_argmax on the predicted maps, res [11] f32 = scalars[3] of pp_oks_heatmap_loss
+ * followed by results[8] of pp_probpose_loss_terms.  in_image / annotated other than 0 or 1 reject the sample for every
+ * head.  Populations: probability = annotated, label in_image; visibility, OKS and error = annotated and in the image,
+ * label visibility != 0.  Within its population a head skips (and counts in `rejected`) a sample whose prediction (or
+ * OKS target) is outside [0,1] or NaN, for the error head non-finite, negative or above 2^20.  A batch is flagged when
+ * res[9] != 0, res[2] != 0 or one of res[1], res[3..8] is not finite; the flag word is res[9]'s integer, | 256 for
+ * res[2] != 0, | 512 for a non-finite value.  A flagged batch's samples are counted like any other's; its losses, MAEs
+ * and PCK average are left out of the sums.  Nothing is ever raised per batch.  One launch: a grid of (K, chunks + 1)
+ * workgroups with LDS-private counters, 64-bit integer atomics on the state; the scalars are added by one thread.
+ *
+ * pp_valmeter_report writes report [K + 1][F] f64, F = 2 (10 + J + 3 E) + (5 + 3 E) + 3 + 1 + 18 with E = ece_bins (a
+ * divisor of 1024).  Row K pools the keypoints (the integer state summed over k).  Per row:
+ *   probability head, then visibility head, each: n_pos, n_neg, best_bal_acc, best_thr, auroc, brier, ece, mce,
+ *     mean_conf, base_rate, bal_acc[J], reliability [E][3] = (count, mean confidence, observed frequency).
+ *     bal_acc[j] = (TP_j / n_pos + TN_j / n_neg) / 2: the expectation of the reference's balanced subsample at that
+ *     threshold.  best_*: the first maximal j (np.argmax); both 0.0 when a class is empty (loss.py:670-673).
+ *     auroc = sum_b neg[b] (pos above b + pos[b] / 2) / (n_pos n_neg) over the fine bins.
+ *   OKS head: n, mae, rmse, bias (mean x - mean t), pearson, reliability [E][3] = (count, mean predicted, mean achieved)
+ *   error head: n, mae, bias
+ *   pck: hits / valid, -1 where valid == 0; in the pool row the mean over the keypoints that have any
+ *   whole set (pool row only, NaN elsewhere): the means over the unflagged batches of the kpt, probability,
+ *     visibility, oks and error losses, acc_kpt, acc_oks, acc_error; max_heatmap; mean_prob; batches; flagged_batches;
+ *     flags; rejected[5].
+ * Undefined values (an empty population, a zero variance) are NaN.  One launch, one workgroup per (row, head), suffix
+ * scan over the fine bins.  Integer intermediates are int64: n_pos n_neg must stay below 2^61.
+ *
+ * Both refuse on the host before any launch, with pp_last_error: null pointers, K <= 0, B <= 0, J outside 1..64,
+ * thresholds not given, an ece_bins that does not divide 1024.  pp_valmeter_state_words returns -1 for bad K or J.
+ * ---------------------------------------------------------------------- */
+long long pp_valmeter_state_words(int K, int J);
+int pp_valmeter_update(const float *dt_prob, const float *dt_vis, const float *dt_oks, const float *dt_err,
+                       const float *gt_oks, const float *gt_err, const int *in_image, const int *annotated,
+                       const int *visibility, const double *thresholds, int J, const int *pck_counts,
+                       const float *map_max, const float *res, int B, int K, long long *state, void *stream);
+int pp_valmeter_report(const long long *state, const double *thresholds, int K, int J, int ece_bins, double *report,
+                       void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -168,7 +168,11 @@ _SIGNATURES = {
     "pp_viz_render": (C.c_int, [_vp, _i, _vp, _i, _i, _i, _vp, _i, _i, _i] + [_vp] * 5 + [_i, _i, _vp, _i, _d, _i, _i,
                                                                                           _vp]),
     "pp_viz_colorize": (C.c_int, [_vp, _vp, C.c_longlong, _i, _i, _vp, _i, _vp]),
+    "pp_valmeter_state_words": (C.c_longlong, [_i, _i]),
+    "pp_valmeter_update": (C.c_int, [_vp] * 10 + [_i] + [_vp] * 3 + [_i, _i, _vp, _vp]),
+    "pp_valmeter_report": (C.c_int, [_vp, _vp, _i, _i, _i, _vp, _vp]),
 }
+PP_VALMETER_BINS, PP_VALMETER_MAX_THRESHOLDS = 1024, 64
 PP_VIZ_MAX_SIDE = 8192
 PP_AUGMENT_POST_TILE_W, PP_AUGMENT_POST_TILE_H, PP_AUGMENT_POST_WORDS = 64, 16, 24
 PP_EMA_LERP_F32, PP_EMA_COPY_WORDS = 0, 1

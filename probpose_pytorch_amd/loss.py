@@ -30,7 +30,7 @@ import torch
 import torch.nn.functional as F
 from torch import Tensor, nn
 
-from . import _lib
+from . import _buffers, _lib
 from .metrics import (compute_oks, get_heatmap_expected_value, get_heatmap_maximum,  # noqa: F401
                       keypoint_pck_accuracy, oks_batch, pck_counts, pose_pck_accuracy, pose_pck_accuracy_expected)
 from .util import to_numpy
@@ -417,8 +417,9 @@ class ProbPoseLoss(nn.Module):
         key = (str(dev), sig.dtype.str, sig.tobytes())
         v = self._variance.get(key)
         if v is None:
-            v = torch.from_numpy(np.ascontiguousarray((sig * 2) ** 2, dtype=np.float64)).to(dev)   # compute_oks :716
-            self._variance = {key: v}
+            keep = []       # the pinned source of the asynchronous upload lives as long as the cached copy
+            v = _buffers.upload(np.ascontiguousarray((sig * 2) ** 2, dtype=np.float64), dev, keep)   # compute_oks :716
+            self._variance, self._variance_host = {key: v}, keep
         if v.numel() != K:
             raise ValueError(f"{K} keypoints but {v.numel()} sigmas")
         return v
@@ -427,19 +428,29 @@ class ProbPoseLoss(nn.Module):
         """Every device-side quantity of one forward: the decodes (gt_kpts, dt_kpts), the B*K targets (gt_oks,
         gt_err, vis_weight, oks_weight), ``res`` = the 11 scalars of both kernels, the int masks on the device
         (``masks``: in_image, annotated, visibility) and on the host, and the heatmap weights (``heat_w``)."""
-        if self.freeze_oks:
-            raise NotImplementedError("freeze_oks is not supported (the reference never sets it)")
-        dt_heatmaps, dt_probs, dt_vis, dt_oks, dt_errs = pred
-        _refuse_grad(*pred)
-        _lib.require_device(dt_heatmaps)
-        dev = dt_heatmaps.device
-        B, C, H, W = dt_heatmaps.shape
-        hm = _f32(dt_heatmaps, dev)
-        gt_hm = _f32(gt["heatmaps"], dev).view(B, C, H, W)
+        dev, (B, C, _, _) = self._check_pred(pred)
         probs = _host_int(gt["in_image"], B, C)
         annotated = _host_int(gt["keypoints_visible"], B, C)
         vis = _host_int(gt["keypoints_visibility"], B, C)
         masks = torch.from_numpy(np.stack([probs, annotated, vis]).astype(np.int32)).to(dev)
+        T = self._device_terms(gt, pred, masks, keypoint_weights, learn_heatmaps_from_zeros)
+        T.update(probs=probs, annotated=annotated, vis=vis)
+        return T
+
+    def _check_pred(self, pred):
+        if self.freeze_oks:
+            raise NotImplementedError("freeze_oks is not supported (the reference never sets it)")
+        _refuse_grad(*pred)
+        _lib.require_device(pred[0])
+        return pred[0].device, pred[0].shape
+
+    def _device_terms(self, gt, pred, masks, keypoint_weights=None, learn_heatmaps_from_zeros: bool = False) -> dict:
+        """The launch sequence of ``terms`` for masks that are on the device already (``masks`` [3,B,K] int32:
+        in_image, annotated, visibility): nothing here reads a device value on the host."""
+        dev, (B, C, H, W) = self._check_pred(pred)
+        dt_heatmaps, dt_probs, dt_vis, dt_oks, dt_errs = pred
+        hm = _f32(dt_heatmaps, dev)
+        gt_hm = _f32(gt["heatmaps"], dev).view(B, C, H, W)
         if keypoint_weights is None:
             kw = torch.ones((B, C), device=dev, dtype=torch.float32)
         else:
@@ -468,8 +479,8 @@ class ProbPoseLoss(nn.Module):
             _lib.launch("pp_probpose_loss_terms", gt_kpts, dt_kpts, *masks[:3], *heads, var, float(oks_area), B, C,
                         int(bool(self.freeze_error)), gt_oks, gt_err, vis_weight, oks_weight, res[3:])
         return dict(hm=hm, gt_hm=gt_hm, kw=kw, heads=heads, gt_kpts=gt_kpts, dt_kpts=dt_kpts, gt_oks=gt_oks,
-                    gt_err=gt_err, vis_weight=vis_weight, oks_weight=oks_weight, res=res, probs=probs,
-                    annotated=annotated, vis=vis, masks=masks, heat_w=heat_weights)
+                    gt_err=gt_err, vis_weight=vis_weight, oks_weight=oks_weight, res=res, masks=masks,
+                    heat_w=heat_weights)
 
     def forward(self, gt, pred: Sequence[Tensor], keypoint_weights: Tensor | None = None,
                 learn_heatmaps_from_zeros: bool = False, compute_acc: bool = False):
