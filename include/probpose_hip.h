@@ -1231,6 +1231,49 @@ int pp_valmeter_update(const float *dt_prob, const float *dt_vis, const float *d
 int pp_valmeter_report(const long long *state, const double *thresholds, int K, int J, int ece_bins, double *report,
                        void *stream);
 
+/* ------------------------------------------------------------------------
+ * HeadCalibration (probpose_pytorch_amd/calibration.py): isotonic recalibration of the probability,
+ * visibility and OKS heads, fitted from a ValidationMeter state.  h = 0 probability, 1 visibility, 2 OKS; rows
+ * r = 0 .. K-1 are the keypoints and r = K the pool (the integer state summed over k, as in pp_valmeter_report).
+ *
+ * pp_calib_fit: for each (h, r) the weighted isotonic (non-decreasing) least-squares regression over the 1024 fine
+ * bins.  Binary heads: weight n_b = hist[h][k][0][b] + hist[h][k][1][b], numerator P_b = hist[h][k][1][b]; OKS head:
+ * n_b = oks_hist[k][b], P_b = oks_st[k][b].  Pool-adjacent-violators over the non-empty bins: two adjacent blocks
+ * pool while P_l N_r >= P_r N_l (128-bit products; equal neighbours pool too), so the blocks are the maximal runs of
+ * equal fitted value and the result does not depend on the pooling order.  An empty bin carries the block of the
+ * nearest non-empty bin to its left, the leading empty bins the first block.  Precondition: fewer than 2^31 samples
+ * per (h, r), the pool included.  Outputs, on the device:
+ *   blocks [3][K+1][1024][2] int64  (P, N) of the block that covers each bin; (0, 0) in a row with no sample
+ *   table  [3][K+1][1024]    f32    binary heads (float)((double)P / (double)N), OKS (float)(((double)P / (double)N)
+ *                                   * 2^-30), every conversion to nearest even; 0 in an empty row
+ *   row_of [3][K]            int32  k when row (h, k) has at least min_count samples, else K when the pool row has
+ *                                   at least one, else -1 (pass through)
+ * One launch, one workgroup per (h, r): singleton blocks joined by a merge tree in LDS.
+ *
+ * pp_calib_apply: aux_in, aux_out [3][B][K] f32 (the `aux` of the decode).  A p in [0,1] becomes
+ * table[h][row_of[h][k]][min(1023, floor(p * 1024))]; NaN, values outside [0,1] and entries whose row_of is -1 are
+ * copied bit for bit.  aux_in == aux_out is allowed, a partial overlap is refused.  One launch, nothing allocated.
+ *
+ * pp_calib_score: what the calibration makes of the samples of a meter state with the same K.  Keypoint k goes through
+ * table row row_of[h][k]; row K pools the keypoints, each through its own table; keypoints whose row_of is -1 are left
+ * out and counted.  The samples of fine bin b take the float32 table value y_b and are regrouped into E = ece_bins
+ * bins (a divisor of 1024) by e = min(E - 1, (int)(y_b * E)) in float32.  report [K+1][F] f64, F = 2 (6 + 3 E) + 3 + 3 E:
+ *   probability head, then visibility head, each: n, skipped, brier = sum_b (pos_b (1 - y_b)^2 + neg_b y_b^2) / n,
+ *     mean_conf = sum_b n_b y_b / n, ece, mce, reliability [E][3] = (count, mean calibrated value, observed frequency)
+ *   OKS head: n, skipped, ece, reliability [E][3] = (count, mean calibrated value, mean achieved OKS)
+ * Undefined values are NaN.  Sums of y are float64 sums in no fixed order (tests/test_calibration_gpu.py counts the
+ * roundings).
+ *
+ * All three refuse on the host before any launch, with pp_last_error: null pointers, K <= 0, B <= 0, J outside 1..64,
+ * min_count < 1, an ece_bins that does not divide 1024.
+ * ---------------------------------------------------------------------- */
+int pp_calib_fit(const long long *state, int K, int J, long long min_count, long long *blocks, float *table,
+                 int *row_of, void *stream);
+int pp_calib_apply(const float *aux_in, float *aux_out, int B, int K, const float *table, const int *row_of,
+                   void *stream);
+int pp_calib_score(const long long *state, int K, int J, const float *table, const int *row_of, int ece_bins,
+                   double *report, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,7 +14,7 @@ from .heatmap import get_heatmap_expected_value  # noqa: F401
 
 __all__ = ["to_numpy", "Codec", "ProbMap", "ArgMaxProbMap", "get_heatmap_expected_value", "FusedAdamW",
            "Augment", "ModelEma", "ema_update_", "CocoKeypointEval", "PoseNMS", "rescore_instances",
-           "PoseTracker", "OneEuro", "PoseFollower", "PoseTrackEval", "ValidationMeter"]
+           "PoseTracker", "OneEuro", "PoseFollower", "PoseTrackEval", "ValidationMeter", "HeadCalibration"]
 
 
 def __getattr__(name):  # lazy: the nn.Module side pulls in the engine
@@ -51,6 +51,9 @@ def __getattr__(name):  # lazy: the nn.Module side pulls in the engine
     if name == "ValidationMeter":
         from .valmeter import ValidationMeter
         return ValidationMeter
+    if name == "HeadCalibration":
+        from .calibration import HeadCalibration
+        return HeadCalibration
     if name == "Augment":
         from .dataset import Augment
         return Augment

@@ -171,6 +171,9 @@ _SIGNATURES = {
     "pp_valmeter_state_words": (C.c_longlong, [_i, _i]),
     "pp_valmeter_update": (C.c_int, [_vp] * 10 + [_i] + [_vp] * 3 + [_i, _i, _vp, _vp]),
     "pp_valmeter_report": (C.c_int, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    "pp_calib_fit": (C.c_int, [_vp, _i, _i, C.c_longlong, _vp, _vp, _vp, _vp]),
+    "pp_calib_apply": (C.c_int, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "pp_calib_score": (C.c_int, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp]),
 }
 PP_VALMETER_BINS, PP_VALMETER_MAX_THRESHOLDS = 1024, 64
 PP_VIZ_MAX_SIDE = 8192

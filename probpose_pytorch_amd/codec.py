@@ -192,10 +192,12 @@ class ArgMaxProbMap(ProbMap):
 
 
 class Codec:
-    """Reference codec.py:242-267."""
+    """Reference codec.py:242-267.  With ``calibration`` (a ``HeadCalibration``) the decoded probability, visibility
+    and OKS are recalibrated on the device, so ``decode`` and every consumer downstream see calibrated values."""
 
-    def __init__(self, probmap):
+    def __init__(self, probmap, calibration=None):
         self.probmap = probmap
+        self.calibration = calibration
 
     def decode_device(self, pred) -> dict:
         """Fused decode that leaves everything on the device (used by the
@@ -203,7 +205,10 @@ class Codec:
         aux (3,B,K) f32 = prob/vis/oks, err (B,K) f64 (already / diagonal)."""
         heatmaps, probabilities, visibilities, oks, errors = pred
         _lib.require_device(heatmaps)
-        return self.probmap.decode_device(heatmaps, aux=(probabilities, visibilities, oks, errors))
+        out = self.probmap.decode_device(heatmaps, aux=(probabilities, visibilities, oks, errors))
+        if self.calibration is not None:        # one more launch, in place; raises ValueError on another K
+            self.calibration.apply(out["aux"], out=out["aux"])
+        return out
 
     def decode(self, pred):
         """5-tuple (heatmaps, prob, vis, oks, err) -> ((kpts (B,K,2) f64, scores (B,K) f32),

@@ -1,0 +1,352 @@
+// HeadCalibration: isotonic recalibration of the probability, visibility and OKS heads from a ValidationMeter state.
+//
+// pp_calib_fit takes, per head h and row r (a keypoint, or r = K: the integer state summed over the keypoints), the
+// weighted isotonic least-squares regression over the meter's 1024 fine bins by pool-adjacent-violators, exactly:
+// blocks are (P, N) integer pairs and two neighbours pool while P_l N_r >= P_r N_l, compared as 128-bit products.  With
+// ">=" the final blocks are the maximal runs of equal fitted value, so the result does not depend on the pooling order
+// and tests/calibration_reference.py (a stack PAV in Python integers) must reproduce it bit for bit.  pp_calib_apply
+// maps decoded head values through the fitted table; pp_calib_score says what the table makes of the samples of any
+// meter state.  The definitions are in include/probpose_hip.h, the reasoning in DESIGN §4.5j.
+//
+// The sections of the meter's state this file reads (hist, oks_hist, oks_st) are restated from the header's layout.
+#include "pp_common.h"
+
+namespace pp {
+
+constexpr int CB_BINS = 1024;
+constexpr int CB_MAX_J = 64;
+constexpr int CB_HEADS = 3;
+constexpr int CB_BINARY_FIXED = 6, CB_OKS_FIXED = 3;
+constexpr double CB_Q30 = 1073741824.0;
+
+typedef unsigned long long u64;
+
+// word offsets of hist [2][K][2][1024], oks_hist [K][1024] and oks_st [K][1024] in the meter's state
+struct CbLayout {
+  long long hist, oks_hist, oks_st;
+};
+
+__host__ __device__ inline CbLayout cb_layout(int K, int J) {
+  const long long k = K;
+  CbLayout L;
+  L.hist = 0;
+  L.oks_hist = 2 * k * 2 * CB_BINS + 2 * k * CB_BINS + 2 * k * 2 * J + 2 * k * 2 + 2 * k * 2;
+  L.oks_st = L.oks_hist + 2 * k * CB_BINS;
+  return L;
+}
+
+// (weight n, numerator P) of fine bin b of keypoint k for head h
+__device__ __forceinline__ void cb_bin(const long long *__restrict__ state, const CbLayout &L, int K, int h, int k,
+                                       int b, long long &n, long long &p) {
+  if (h < 2) {
+    const long long at = L.hist + (((long long)h * K + k) * 2) * CB_BINS + b;
+    const long long neg = state[at], pos = state[at + CB_BINS];
+    n = neg + pos, p = pos;
+  } else {
+    n = state[L.oks_hist + (long long)k * CB_BINS + b];
+    p = state[L.oks_st + (long long)k * CB_BINS + b];
+  }
+}
+
+// value(l) >= value(r), exactly: P_l N_r >= P_r N_l as 128-bit products (P < 2^61, N < 2^31)
+__device__ __forceinline__ bool cb_ge(u64 pl, u64 nl, u64 pr, u64 nr) {
+  const u64 ah = __umul64hi(pl, nr), al = pl * nr, bh = __umul64hi(pr, nl), bl = pr * nl;
+  return ah > bh || (ah == bh && al >= bl);
+}
+
+// Do the neighbours l, r pool?  An empty right block always joins its left neighbour (an empty bin carries the block to
+// its left); an empty left block -- only the first block of a list can be one -- waits: the leading empty bins take the
+// first block at the very end.
+__device__ __forceinline__ bool cb_pool(long long pl, long long nl, long long pr, long long nr) {
+  if (nr == 0) return true;
+  if (nl == 0) return false;
+  return cb_ge((u64)pl, (u64)nl, (u64)pr, (u64)nr);
+}
+
+__device__ __forceinline__ float cb_value(int h, long long P, long long N) {
+  if (N <= 0) return 0.0f;
+  const double q = (double)P / (double)N;
+  return h < 2 ? (float)q : (float)(q * (1.0 / CB_Q30));
+}
+
+__device__ __forceinline__ long long cb_block_sum(long long v, long long *red, int tid) {
+  __syncthreads();
+  red[tid] = v;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (tid < o) red[tid] += red[tid + o];
+    __syncthreads();
+  }
+  return red[0];
+}
+
+// grid (K + 1, 3): workgroup (r, h) fits row r of head h.  256 threads.
+//
+// The blocks of a list live in place: a block that covers the bins [s, e) keeps P[s], N[s], nxt[s] = e and
+// beg[e - 1] = s; head[s] says that s still starts a block.  Every bin starts as its own block; level j of a merge tree
+// joins the lists of the segments [2m 2^j, (2m+1) 2^j) and [(2m+1) 2^j, (2m+2) 2^j), one thread per pair: both lists are
+// strictly increasing, so only the junction can violate, and the junction block grows to the left and to the right
+// until both of its neighbours are strictly on their side.  A merge touches its own segment only.
+__global__ __launch_bounds__(256) void calib_fit_kernel(const long long *__restrict__ state, int K, int J,
+                                                        long long min_count, long long *__restrict__ blocks,
+                                                        float *__restrict__ table, int *__restrict__ row_of) {
+  __shared__ long long P[CB_BINS], N[CB_BINS];
+  __shared__ short nxt[CB_BINS], beg[CB_BINS];
+  __shared__ unsigned char head[CB_BINS];
+  __shared__ long long red[256];
+  __shared__ int scan[256];
+  const CbLayout L = cb_layout(K, J);
+  const int tid = threadIdx.x, row = blockIdx.x, h = blockIdx.y;
+  const int k0 = row < K ? row : 0, k1 = row < K ? row + 1 : K;
+
+  long long mine = 0;
+  for (int b = tid; b < CB_BINS; b += 256) {
+    long long n = 0, p = 0;
+    for (int k = k0; k < k1; ++k) {
+      long long nk, pk;
+      cb_bin(state, L, K, h, k, b, nk, pk);
+      n += nk, p += pk;
+    }
+    P[b] = p, N[b] = n;
+    nxt[b] = (short)(b + 1), beg[b] = (short)b, head[b] = 1;
+    mine += n;
+  }
+  const long long total = cb_block_sum(mine, red, tid);     // ends with a barrier: the lists are in place
+
+  for (int half = 1; half < CB_BINS; half <<= 1) {
+    const int merges = CB_BINS / (2 * half);
+    for (int m = tid; m < merges; m += 256) {
+      const int lo = m * 2 * half, mid = lo + half, hi = mid + half;
+      int cs = beg[mid - 1], ce = nxt[mid];
+      long long cp = P[cs], cn = N[cs];
+      if (cb_pool(cp, cn, P[mid], N[mid])) {
+        cp += P[mid], cn += N[mid], head[mid] = 0;
+        bool grew;
+        do {
+          grew = false;
+          if (cs > lo) {
+            const int s = beg[cs - 1];
+            if (cb_pool(P[s], N[s], cp, cn)) cp += P[s], cn += N[s], head[cs] = 0, cs = s, grew = true;
+          }
+          if (ce < hi && cb_pool(cp, cn, P[ce], N[ce])) cp += P[ce], cn += N[ce], head[ce] = 0, ce = nxt[ce], grew = true;
+        } while (grew);
+        P[cs] = cp, N[cs] = cn, nxt[cs] = (short)ce, beg[ce - 1] = (short)cs;
+      }
+    }
+    __syncthreads();
+  }
+  // the leading empty bins carry the first block
+  if (tid == 0 && N[0] == 0 && nxt[0] < CB_BINS) {
+    const int e = nxt[0];
+    P[0] = P[e], N[0] = N[e], head[e] = 0;
+  }
+  __syncthreads();
+
+  // the block that covers a bin starts at the last head at or before it: thread t owns the bins 4t .. 4t+3
+  int last = -1;
+  for (int i = 0; i < 4; ++i)
+    if (head[4 * tid + i]) last = 4 * tid + i;
+  scan[tid] = last;
+  __syncthreads();
+  for (int off = 1; off < 256; off <<= 1) {
+    const int v = tid >= off ? scan[tid - off] : -1;
+    __syncthreads();
+    scan[tid] = max(scan[tid], v);
+    __syncthreads();
+  }
+  int cur = tid > 0 ? scan[tid - 1] : 0;      // bin 0 always starts a block
+  const long long out = ((long long)h * (K + 1) + row) * CB_BINS;
+  for (int i = 0; i < 4; ++i) {
+    const int b = 4 * tid + i;
+    if (head[b]) cur = b;
+    const long long p = P[cur], n = N[cur];
+    blocks[(out + b) * 2] = p;
+    blocks[(out + b) * 2 + 1] = n;
+    table[out + b] = cb_value(h, p, n);
+  }
+
+  // row_of, by the pool's workgroup (it knows whether the pool holds a sample): wave w counts the rows w, w + 4, ...
+  if (row != K) return;
+  const int lane = tid & 63;
+  for (int k = tid >> 6; k < K; k += 4) {
+    long long n = 0;
+    for (int b = lane; b < CB_BINS; b += 64) {
+      long long nk, pk;
+      cb_bin(state, L, K, h, k, b, nk, pk);
+      n += nk;
+    }
+    for (int o = 32; o > 0; o >>= 1) n += __shfl_down(n, o, 64);
+    if (lane == 0) row_of[(long long)h * K + k] = n >= min_count ? k : (total >= 1 ? K : -1);
+  }
+}
+
+__device__ __forceinline__ int cb_fine_bin(float p) { return min(CB_BINS - 1, (int)floorf(p * 1024.0f)); }
+
+// grid (ceil(B K / 256), 3): one value each.  Reads its element before it writes it, so in place is safe.
+__global__ __launch_bounds__(256) void calib_apply_kernel(const float *__restrict__ in, float *__restrict__ out, int BK,
+                                                          int K, const float *__restrict__ table,
+                                                          const int *__restrict__ row_of) {
+  const int i = blockIdx.x * 256 + threadIdx.x, h = blockIdx.y;
+  if (i >= BK) return;
+  const long long at = (long long)h * BK + i;
+  float p = in[at];
+  const int r = row_of[h * K + i % K];
+  if (p >= 0.0f && p <= 1.0f && r >= 0 && r <= K)       // NaN: false
+    p = table[((long long)h * (K + 1) + r) * CB_BINS + cb_fine_bin(p)];
+  out[at] = p;
+}
+
+__device__ __forceinline__ double cb_nan() { return __builtin_nan(""); }
+
+__device__ __forceinline__ double cb_block_sum_f(double v, double *red, int tid) {
+  __syncthreads();
+  red[tid] = v;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (tid < o) red[tid] += red[tid + o];
+    __syncthreads();
+  }
+  return red[0];
+}
+
+// grid (K + 1, 3): workgroup (r, h) scores row r of head h; row K pools the keypoints, each through its own table.
+// Thread t takes the fine bins t, t + 256, ... of every keypoint of the row; the samples of a bin are regrouped by the
+// float32 value y the apply emits for it into E bins kept in LDS (integer counts, float64 sum of n y).
+__global__ __launch_bounds__(256) void calib_score_kernel(const long long *__restrict__ state, int K, int J,
+                                                          const float *__restrict__ table,
+                                                          const int *__restrict__ row_of, int E, int F,
+                                                          double *__restrict__ report) {
+  __shared__ u64 cnt[CB_BINS], num[CB_BINS];      // per E bin: samples; positives, or the Q30 sum of the achieved OKS
+  __shared__ double conf[CB_BINS];                // per E bin: the sum of n_b y_b
+  __shared__ double redf[256];
+  __shared__ long long red[256];
+  const CbLayout L = cb_layout(K, J);
+  const int tid = threadIdx.x, row = blockIdx.x, h = blockIdx.y;
+  const int k0 = row < K ? row : 0, k1 = row < K ? row + 1 : K;
+  for (int e = tid; e < E; e += 256) cnt[e] = 0, num[e] = 0, conf[e] = 0.0;
+  __syncthreads();
+
+  long long my_n = 0, my_skipped = 0;
+  double my_brier = 0.0, my_conf = 0.0;
+  for (int k = k0; k < k1; ++k) {
+    const int r = row_of[h * K + k];
+    const bool use = r >= 0 && r <= K;
+    const float *t = table + ((long long)h * (K + 1) + (use ? r : 0)) * CB_BINS;
+    for (int b = tid; b < CB_BINS; b += 256) {
+      long long n, p;
+      cb_bin(state, L, K, h, k, b, n, p);
+      if (n == 0) continue;
+      if (!use) {
+        my_skipped += n;
+        continue;
+      }
+      const float y = t[b];
+      const int e = min(E - 1, max(0, (int)(y * (float)E)));
+      const double yd = (double)y, c = (double)n * yd;
+      my_n += n, my_conf += c;
+      atomicAdd(&cnt[e], (u64)n);
+      atomicAdd(&num[e], (u64)p);
+      atomicAdd(&conf[e], c);
+      if (h < 2) {
+        const double w = 1.0 - yd;
+        my_brier += (double)p * (w * w) + (double)(n - p) * (yd * yd);
+      }
+    }
+  }
+  const long long n = cb_block_sum(my_n, red, tid);
+  const long long skipped = cb_block_sum(my_skipped, red, tid);
+  const double brier = cb_block_sum_f(my_brier, redf, tid), sconf = cb_block_sum_f(my_conf, redf, tid);
+
+  const int fixed = h < 2 ? CB_BINARY_FIXED : CB_OKS_FIXED;
+  double *o = report + (long long)row * F + (h < 2 ? h * (CB_BINARY_FIXED + 3 * E) : 2 * (CB_BINARY_FIXED + 3 * E));
+  double my_abs = 0.0, my_mce = -1.0;
+  for (int e = tid; e < E; e += 256) {
+    const double c = (double)cnt[e];
+    const double target = h < 2 ? (double)num[e] : (double)num[e] / CB_Q30;
+    const double d = fabs(conf[e] - target);
+    double *t = o + fixed + 3 * e;
+    t[0] = c;
+    if (cnt[e] > 0) {
+      my_abs += d;
+      my_mce = fmax(my_mce, d / c);
+      t[1] = conf[e] / c;
+      t[2] = target / c;
+    } else {
+      t[1] = t[2] = cb_nan();
+    }
+  }
+  const double abs_sum = cb_block_sum_f(my_abs, redf, tid);
+  __syncthreads();
+  redf[tid] = my_mce;
+  __syncthreads();
+  if (tid != 0) return;
+  double mce = -1.0;
+  for (int i = 0; i < 256; ++i) mce = fmax(mce, redf[i]);
+  o[0] = (double)n;
+  o[1] = (double)skipped;
+  const bool any = n > 0;
+  if (h < 2) {
+    o[2] = any ? brier / (double)n : cb_nan();
+    o[3] = any ? sconf / (double)n : cb_nan();
+    o[4] = any ? abs_sum / (double)n : cb_nan();
+    o[5] = any ? mce : cb_nan();
+  } else {
+    o[2] = any ? abs_sum / (double)n : cb_nan();
+  }
+}
+
+static int cb_check_shape(const char *who, int K, int J) {
+  PP_REQUIRE(K > 0 && K <= 65535, "%s: bad K=%d (1 .. 65535 keypoints)", who, K);
+  PP_REQUIRE(J >= 1 && J <= CB_MAX_J, "%s: bad J=%d (1 .. %d thresholds)", who, J, CB_MAX_J);
+  return 0;
+}
+
+}  // namespace pp
+
+extern "C" int pp_calib_fit(const long long *state, int K, int J, long long min_count, long long *blocks, float *table,
+                            int *row_of, void *stream) {
+  using namespace pp;
+  if (int rc = cb_check_shape("pp_calib_fit", K, J)) return rc;
+  PP_REQUIRE(min_count >= 1, "pp_calib_fit: bad min_count=%lld (at least 1)", min_count);
+  PP_REQUIRE(state, "pp_calib_fit: null state");
+  PP_REQUIRE(blocks && table && row_of, "pp_calib_fit: null output");
+  hipLaunchKernelGGL(calib_fit_kernel, dim3(K + 1, CB_HEADS), dim3(256), 0, (hipStream_t)stream, state, K, J, min_count,
+                     blocks, table, row_of);
+  PP_CHECK_LAUNCH("calib_fit_kernel");
+  return 0;
+}
+
+extern "C" int pp_calib_apply(const float *aux_in, float *aux_out, int B, int K, const float *table, const int *row_of,
+                              void *stream) {
+  using namespace pp;
+  PP_REQUIRE(K > 0 && K <= 65535, "pp_calib_apply: bad K=%d (1 .. 65535 keypoints)", K);
+  PP_REQUIRE(B > 0 && (long long)B * K * CB_HEADS < (1ll << 31), "pp_calib_apply: bad B=%d (B > 0, 3*B*K < 2^31)", B);
+  PP_REQUIRE(aux_in && aux_out, "pp_calib_apply: null aux");
+  PP_REQUIRE(table && row_of, "pp_calib_apply: null calibration");
+  const long long count = (long long)CB_HEADS * B * K;
+  const float *in_end = aux_in + count;
+  const float *out_end = aux_out + count;
+  PP_REQUIRE(aux_in == aux_out || in_end <= aux_out || out_end <= aux_in,
+             "pp_calib_apply: aux_in and aux_out overlap in part (in place means the same address)");
+  const int BK = B * K;
+  hipLaunchKernelGGL(calib_apply_kernel, dim3(cdiv(BK, 256), CB_HEADS), dim3(256), 0, (hipStream_t)stream, aux_in,
+                     aux_out, BK, K, table, row_of);
+  PP_CHECK_LAUNCH("calib_apply_kernel");
+  return 0;
+}
+
+extern "C" int pp_calib_score(const long long *state, int K, int J, const float *table, const int *row_of, int ece_bins,
+                              double *report, void *stream) {
+  using namespace pp;
+  if (int rc = cb_check_shape("pp_calib_score", K, J)) return rc;
+  PP_REQUIRE(ece_bins >= 1 && ece_bins <= CB_BINS && CB_BINS % ece_bins == 0,
+             "pp_calib_score: ece_bins=%d does not divide %d", ece_bins, CB_BINS);
+  PP_REQUIRE(state, "pp_calib_score: null state");
+  PP_REQUIRE(table && row_of, "pp_calib_score: null calibration");
+  PP_REQUIRE(report, "pp_calib_score: null report");
+  const int F = 2 * (CB_BINARY_FIXED + 3 * ece_bins) + CB_OKS_FIXED + 3 * ece_bins;
+  hipLaunchKernelGGL(calib_score_kernel, dim3(K + 1, CB_HEADS), dim3(256), 0, (hipStream_t)stream, state, K, J, table,
+                     row_of, ece_bins, F, report);
+  PP_CHECK_LAUNCH("calib_score_kernel");
+  return 0;
+}

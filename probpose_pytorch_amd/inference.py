@@ -184,6 +184,21 @@ def save_png(array: np.ndarray, path: Path) -> None:
     PIL.Image.fromarray(array).save(path)
 
 
+def build_codec(parser, args, input_size, heatmap_size, device="cuda") -> Codec:
+    """The codec of the command line: ``ProbMap`` with one sigma, and the ``--calibration`` file loaded into it."""
+    calibration = None
+    if args.calibration is not None:
+        from .calibration import HeadCalibration
+        try:
+            calibration = HeadCalibration.load(args.calibration, device)
+        except Exception as e:      # noqa: BLE001  (whatever the file holds instead of a calibration)
+            parser.error(f"--calibration: {args.calibration}: {e}")
+        if calibration.K != args.num_keypoints:
+            parser.error(f"--calibration: {args.calibration} holds {calibration.K} keypoints; --num_keypoints is "
+                         f"{args.num_keypoints}")
+    return Codec(ProbMap(input_size, heatmap_size, np.array([args.sigma] * args.num_keypoints)), calibration)
+
+
 def main(argv=None):
     p = argparse.ArgumentParser(description="Inference script for ProbPose (MI355X-native path)")
     p.add_argument("--model", type=Path, default=None, help="state_dict checkpoint (omit: seeded synthetic weights)")
@@ -236,8 +251,12 @@ def main(argv=None):
                    help="with --output: also write heatmap_{i}.png and output_image.png, drawn on the GPU")
     p.add_argument("--render-threshold", type=float, default=0.9,
                    help="--render draws the keypoints whose probability is at least this")
+    p.add_argument("--calibration", type=Path, default=None,
+                   help="a HeadCalibration.save file: recalibrate probability, visibility and OKS in the decode")
     args = p.parse_args(argv)
     flip_pairs = resolve_flip_pairs(p, args)
+    if args.calibration is not None and not args.calibration.is_file():
+        p.error(f"--calibration: {args.calibration} is not a file")
     boxes = None
     if args.boxes is not None:
         try:
@@ -266,7 +285,7 @@ def main(argv=None):
     if args.bf16:
         model.set_compute_dtype(torch.bfloat16)
     model.set_flip_test(flip_pairs)
-    codec = Codec(ProbMap(input_size, heatmap_size, np.array([args.sigma] * args.num_keypoints)))
+    codec = build_codec(p, args, input_size, heatmap_size)
     if track is not None:
         return _main_frames(args, model, codec, track)
     if boxes is not None:
