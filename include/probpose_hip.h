@@ -1172,7 +1172,7 @@ int pp_viz_colorize(const float *maps, void *out, long long M, int h, int w, con
  * The state is `pp_valmeter_state_words(K, J)` int64 words, all zero when empty (a memset resets it).  It holds counts
  * and fixed-point sums only, so it does not depend on the order or the split of the batches.  Q30(z) = rint(z 2^30) in
  * float64 (ties to even), Q20 the same at 2^20; the fine bin of p in [0,1] is min(1023, floor(p * 1024)) in float32.
- * Sections, in this order (h = 0 probability, 1 visibility; label 0 / 1):
+ * Sections, in this order (h = 0 probability, 1 visibility; label 0 / 1; in code: csrc/pp_valmeter_state.h):
  *   hist     [2][K][2][1024]  samples per (head, keypoint, label, fine bin of p)
  *   conf     [2][K][1024]     sum of Q30(p) per fine bin
  *   above    [2][K][2][J]     samples with (double)p > thresholds[j], strictly
@@ -1235,6 +1235,8 @@ int pp_valmeter_report(const long long *state, const double *thresholds, int K, 
  * HeadCalibration (probpose_pytorch_amd/calibration.py): isotonic recalibration of the probability,
  * visibility and OKS heads, fitted from a ValidationMeter state.  h = 0 probability, 1 visibility, 2 OKS; rows
  * r = 0 .. K-1 are the keypoints and r = K the pool (the integer state summed over k, as in pp_valmeter_report).
+ * `state` is the meter's own state of pp_valmeter_state_words(K, J) words; hist, oks_hist and oks_st below are its
+ * sections as the ValidationMeter paragraph above lays them out, and the fine bin is the one stated there.
  *
  * pp_calib_fit: for each (h, r) the weighted isotonic (non-decreasing) least-squares regression over the 1024 fine
  * bins.  Binary heads: weight n_b = hist[h][k][0][b] + hist[h][k][1][b], numerator P_b = hist[h][k][1][b]; OKS head:

@@ -25,10 +25,10 @@ import torch
 from torch import Tensor
 
 from . import _lib
+from .valmeter import BINS, check_ece_bins, head_fields
 
 __all__ = ["HeadCalibration", "score_fields", "parse_score"]
 
-BINS = _lib.PP_VALMETER_BINS
 HEADS = ("probability", "visibility", "oks")
 _BINARY = ("n", "skipped", "brier", "mean_conf", "ece", "mce")
 _OKS = ("n", "skipped", "ece")
@@ -41,15 +41,9 @@ def score_fields(E: int) -> int:
 def parse_score(rep: np.ndarray, ece_bins: int) -> dict:
     """The [K+1][F] float64 report of ``pp_calib_score`` as a dict per head; every field is an array of K+1 (the last
     entry pools the keypoints), ``reliability`` [K+1][E][3]."""
-    E = ece_bins
     out, o = {}, 0
     for head in HEADS:
-        names = _OKS if head == "oks" else _BINARY
-        d = {name: rep[:, o + i].copy() for i, name in enumerate(names)}
-        o += len(names)
-        d["reliability"] = rep[:, o:o + 3 * E].reshape(-1, E, 3).copy()
-        o += 3 * E
-        out[head] = d
+        out[head], o = head_fields(rep, o, _OKS if head == "oks" else _BINARY, ece_bins)
     return out
 
 
@@ -81,10 +75,8 @@ class HeadCalibration:
         _lib.require_device()
         if min_count < 1:
             raise ValueError(f"min_count is at least 1, got {min_count}")
-        state = meter._state
-        if state is None:
-            raise RuntimeError("the meter has seen no batch yet")
-        K, J, dev = meter._K, len(meter.thresholds), state.device
+        state, K, J = meter.device_state()
+        dev = state.device
         blocks = torch.empty((3, K + 1, BINS, 2), dtype=torch.int64, device=dev)
         table = torch.empty((3, K + 1, BINS), dtype=torch.float32, device=dev)
         row_of = torch.empty((3, K), dtype=torch.int32, device=dev)
@@ -123,19 +115,15 @@ class HeadCalibration:
         for the two binary heads also brier, mean_conf and mce.  The numbers before calibration are
         ``meter.compute()``'s.  This is the one synchronisation."""
         _lib.require_device()
-        if ece_bins < 1 or BINS % ece_bins:
-            raise ValueError(f"ece_bins must divide {BINS}, got {ece_bins}")
-        state = meter._state
-        if state is None:
-            raise RuntimeError("the meter has seen no batch yet")
-        if meter._K != self.K:
-            raise ValueError(f"the calibration holds {self.K} keypoints; the meter {meter._K}")
+        check_ece_bins(ece_bins)
+        state, K, J = meter.device_state()
+        if K != self.K:
+            raise ValueError(f"the calibration holds {self.K} keypoints; the meter {K}")
         if state.device != self.table.device:
             raise ValueError(f"the calibration is on {self.table.device}; the meter on {state.device}")
         rep = torch.empty((self.K + 1, score_fields(ece_bins)), dtype=torch.float64, device=state.device)
         with torch.cuda.device(state.device):
-            _lib.launch("pp_calib_score", state, self.K, len(meter.thresholds), self.table, self.row_of, int(ece_bins),
-                        rep)
+            _lib.launch("pp_calib_score", state, K, J, self.table, self.row_of, int(ece_bins), rep)
         return parse_score(rep.cpu().numpy(), ece_bins)
 
     # ------------------------------------------------------------------------------------------- persistence

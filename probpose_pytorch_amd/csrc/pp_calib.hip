@@ -7,46 +7,12 @@
 // and tests/calibration_reference.py (a stack PAV in Python integers) must reproduce it bit for bit.  pp_calib_apply
 // maps decoded head values through the fitted table; pp_calib_score says what the table makes of the samples of any
 // meter state.  The definitions are in include/probpose_hip.h, the reasoning in DESIGN §4.5j.
-//
-// The sections of the meter's state this file reads (hist, oks_hist, oks_st) are restated from the header's layout.
-#include "pp_common.h"
+#include "pp_valmeter_state.h"
 
 namespace pp {
 
-constexpr int CB_BINS = 1024;
-constexpr int CB_MAX_J = 64;
 constexpr int CB_HEADS = 3;
 constexpr int CB_BINARY_FIXED = 6, CB_OKS_FIXED = 3;
-constexpr double CB_Q30 = 1073741824.0;
-
-typedef unsigned long long u64;
-
-// word offsets of hist [2][K][2][1024], oks_hist [K][1024] and oks_st [K][1024] in the meter's state
-struct CbLayout {
-  long long hist, oks_hist, oks_st;
-};
-
-__host__ __device__ inline CbLayout cb_layout(int K, int J) {
-  const long long k = K;
-  CbLayout L;
-  L.hist = 0;
-  L.oks_hist = 2 * k * 2 * CB_BINS + 2 * k * CB_BINS + 2 * k * 2 * J + 2 * k * 2 + 2 * k * 2;
-  L.oks_st = L.oks_hist + 2 * k * CB_BINS;
-  return L;
-}
-
-// (weight n, numerator P) of fine bin b of keypoint k for head h
-__device__ __forceinline__ void cb_bin(const long long *__restrict__ state, const CbLayout &L, int K, int h, int k,
-                                       int b, long long &n, long long &p) {
-  if (h < 2) {
-    const long long at = L.hist + (((long long)h * K + k) * 2) * CB_BINS + b;
-    const long long neg = state[at], pos = state[at + CB_BINS];
-    n = neg + pos, p = pos;
-  } else {
-    n = state[L.oks_hist + (long long)k * CB_BINS + b];
-    p = state[L.oks_st + (long long)k * CB_BINS + b];
-  }
-}
 
 // value(l) >= value(r), exactly: P_l N_r >= P_r N_l as 128-bit products (P < 2^61, N < 2^31)
 __device__ __forceinline__ bool cb_ge(u64 pl, u64 nl, u64 pr, u64 nr) {
@@ -66,18 +32,7 @@ __device__ __forceinline__ bool cb_pool(long long pl, long long nl, long long pr
 __device__ __forceinline__ float cb_value(int h, long long P, long long N) {
   if (N <= 0) return 0.0f;
   const double q = (double)P / (double)N;
-  return h < 2 ? (float)q : (float)(q * (1.0 / CB_Q30));
-}
-
-__device__ __forceinline__ long long cb_block_sum(long long v, long long *red, int tid) {
-  __syncthreads();
-  red[tid] = v;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) red[tid] += red[tid + o];
-    __syncthreads();
-  }
-  return red[0];
+  return h < 2 ? (float)q : (float)(q * (1.0 / VM_Q30));
 }
 
 // grid (K + 1, 3): workgroup (r, h) fits row r of head h.  256 threads.
@@ -90,31 +45,31 @@ __device__ __forceinline__ long long cb_block_sum(long long v, long long *red, i
 __global__ __launch_bounds__(256) void calib_fit_kernel(const long long *__restrict__ state, int K, int J,
                                                         long long min_count, long long *__restrict__ blocks,
                                                         float *__restrict__ table, int *__restrict__ row_of) {
-  __shared__ long long P[CB_BINS], N[CB_BINS];
-  __shared__ short nxt[CB_BINS], beg[CB_BINS];
-  __shared__ unsigned char head[CB_BINS];
+  __shared__ long long P[VM_BINS], N[VM_BINS];
+  __shared__ short nxt[VM_BINS], beg[VM_BINS];
+  __shared__ unsigned char head[VM_BINS];
   __shared__ long long red[256];
   __shared__ int scan[256];
-  const CbLayout L = cb_layout(K, J);
+  const VmLayout L = vm_layout(K, J);
   const int tid = threadIdx.x, row = blockIdx.x, h = blockIdx.y;
-  const int k0 = row < K ? row : 0, k1 = row < K ? row + 1 : K;
+  const auto [k0, k1] = vm_row_range(row, K);
 
   long long mine = 0;
-  for (int b = tid; b < CB_BINS; b += 256) {
+  for (int b = tid; b < VM_BINS; b += 256) {
     long long n = 0, p = 0;
     for (int k = k0; k < k1; ++k) {
       long long nk, pk;
-      cb_bin(state, L, K, h, k, b, nk, pk);
+      vm_bin(state, L, K, h, k, b, nk, pk);
       n += nk, p += pk;
     }
     P[b] = p, N[b] = n;
     nxt[b] = (short)(b + 1), beg[b] = (short)b, head[b] = 1;
     mine += n;
   }
-  const long long total = cb_block_sum(mine, red, tid);     // ends with a barrier: the lists are in place
+  const long long total = vm_block_sum(mine, red, tid);     // ends with a barrier: the lists are in place
 
-  for (int half = 1; half < CB_BINS; half <<= 1) {
-    const int merges = CB_BINS / (2 * half);
+  for (int half = 1; half < VM_BINS; half <<= 1) {
+    const int merges = VM_BINS / (2 * half);
     for (int m = tid; m < merges; m += 256) {
       const int lo = m * 2 * half, mid = lo + half, hi = mid + half;
       int cs = beg[mid - 1], ce = nxt[mid];
@@ -136,7 +91,7 @@ __global__ __launch_bounds__(256) void calib_fit_kernel(const long long *__restr
     __syncthreads();
   }
   // the leading empty bins carry the first block
-  if (tid == 0 && N[0] == 0 && nxt[0] < CB_BINS) {
+  if (tid == 0 && N[0] == 0 && nxt[0] < VM_BINS) {
     const int e = nxt[0];
     P[0] = P[e], N[0] = N[e], head[e] = 0;
   }
@@ -155,7 +110,7 @@ __global__ __launch_bounds__(256) void calib_fit_kernel(const long long *__restr
     __syncthreads();
   }
   int cur = tid > 0 ? scan[tid - 1] : 0;      // bin 0 always starts a block
-  const long long out = ((long long)h * (K + 1) + row) * CB_BINS;
+  const long long out = ((long long)h * (K + 1) + row) * VM_BINS;
   for (int i = 0; i < 4; ++i) {
     const int b = 4 * tid + i;
     if (head[b]) cur = b;
@@ -170,17 +125,15 @@ __global__ __launch_bounds__(256) void calib_fit_kernel(const long long *__restr
   const int lane = tid & 63;
   for (int k = tid >> 6; k < K; k += 4) {
     long long n = 0;
-    for (int b = lane; b < CB_BINS; b += 64) {
+    for (int b = lane; b < VM_BINS; b += 64) {
       long long nk, pk;
-      cb_bin(state, L, K, h, k, b, nk, pk);
+      vm_bin(state, L, K, h, k, b, nk, pk);
       n += nk;
     }
     for (int o = 32; o > 0; o >>= 1) n += __shfl_down(n, o, 64);
     if (lane == 0) row_of[(long long)h * K + k] = n >= min_count ? k : (total >= 1 ? K : -1);
   }
 }
-
-__device__ __forceinline__ int cb_fine_bin(float p) { return min(CB_BINS - 1, (int)floorf(p * 1024.0f)); }
 
 // grid (ceil(B K / 256), 3): one value each.  Reads its element before it writes it, so in place is safe.
 __global__ __launch_bounds__(256) void calib_apply_kernel(const float *__restrict__ in, float *__restrict__ out, int BK,
@@ -191,22 +144,9 @@ __global__ __launch_bounds__(256) void calib_apply_kernel(const float *__restric
   const long long at = (long long)h * BK + i;
   float p = in[at];
   const int r = row_of[h * K + i % K];
-  if (p >= 0.0f && p <= 1.0f && r >= 0 && r <= K)       // NaN: false
-    p = table[((long long)h * (K + 1) + r) * CB_BINS + cb_fine_bin(p)];
+  if (vm_unit_ok(p) && r >= 0 && r <= K)
+    p = table[((long long)h * (K + 1) + r) * VM_BINS + vm_fine_bin(p)];
   out[at] = p;
-}
-
-__device__ __forceinline__ double cb_nan() { return __builtin_nan(""); }
-
-__device__ __forceinline__ double cb_block_sum_f(double v, double *red, int tid) {
-  __syncthreads();
-  red[tid] = v;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) red[tid] += red[tid + o];
-    __syncthreads();
-  }
-  return red[0];
 }
 
 // grid (K + 1, 3): workgroup (r, h) scores row r of head h; row K pools the keypoints, each through its own table.
@@ -216,13 +156,13 @@ __global__ __launch_bounds__(256) void calib_score_kernel(const long long *__res
                                                           const float *__restrict__ table,
                                                           const int *__restrict__ row_of, int E, int F,
                                                           double *__restrict__ report) {
-  __shared__ u64 cnt[CB_BINS], num[CB_BINS];      // per E bin: samples; positives, or the Q30 sum of the achieved OKS
-  __shared__ double conf[CB_BINS];                // per E bin: the sum of n_b y_b
+  __shared__ u64 cnt[VM_BINS], num[VM_BINS];      // per E bin: samples; positives, or the Q30 sum of the achieved OKS
+  __shared__ double conf[VM_BINS];                // per E bin: the sum of n_b y_b
   __shared__ double redf[256];
   __shared__ long long red[256];
-  const CbLayout L = cb_layout(K, J);
+  const VmLayout L = vm_layout(K, J);
   const int tid = threadIdx.x, row = blockIdx.x, h = blockIdx.y;
-  const int k0 = row < K ? row : 0, k1 = row < K ? row + 1 : K;
+  const auto [k0, k1] = vm_row_range(row, K);
   for (int e = tid; e < E; e += 256) cnt[e] = 0, num[e] = 0, conf[e] = 0.0;
   __syncthreads();
 
@@ -231,10 +171,10 @@ __global__ __launch_bounds__(256) void calib_score_kernel(const long long *__res
   for (int k = k0; k < k1; ++k) {
     const int r = row_of[h * K + k];
     const bool use = r >= 0 && r <= K;
-    const float *t = table + ((long long)h * (K + 1) + (use ? r : 0)) * CB_BINS;
-    for (int b = tid; b < CB_BINS; b += 256) {
+    const float *t = table + ((long long)h * (K + 1) + (use ? r : 0)) * VM_BINS;
+    for (int b = tid; b < VM_BINS; b += 256) {
       long long n, p;
-      cb_bin(state, L, K, h, k, b, n, p);
+      vm_bin(state, L, K, h, k, b, n, p);
       if (n == 0) continue;
       if (!use) {
         my_skipped += n;
@@ -253,16 +193,16 @@ __global__ __launch_bounds__(256) void calib_score_kernel(const long long *__res
       }
     }
   }
-  const long long n = cb_block_sum(my_n, red, tid);
-  const long long skipped = cb_block_sum(my_skipped, red, tid);
-  const double brier = cb_block_sum_f(my_brier, redf, tid), sconf = cb_block_sum_f(my_conf, redf, tid);
+  const long long n = vm_block_sum(my_n, red, tid);
+  const long long skipped = vm_block_sum(my_skipped, red, tid);
+  const double brier = vm_block_sum(my_brier, redf, tid), sconf = vm_block_sum(my_conf, redf, tid);
 
   const int fixed = h < 2 ? CB_BINARY_FIXED : CB_OKS_FIXED;
   double *o = report + (long long)row * F + (h < 2 ? h * (CB_BINARY_FIXED + 3 * E) : 2 * (CB_BINARY_FIXED + 3 * E));
   double my_abs = 0.0, my_mce = -1.0;
   for (int e = tid; e < E; e += 256) {
     const double c = (double)cnt[e];
-    const double target = h < 2 ? (double)num[e] : (double)num[e] / CB_Q30;
+    const double target = h < 2 ? (double)num[e] : (double)num[e] / VM_Q30;
     const double d = fabs(conf[e] - target);
     double *t = o + fixed + 3 * e;
     t[0] = c;
@@ -272,10 +212,10 @@ __global__ __launch_bounds__(256) void calib_score_kernel(const long long *__res
       t[1] = conf[e] / c;
       t[2] = target / c;
     } else {
-      t[1] = t[2] = cb_nan();
+      t[1] = t[2] = vm_nan();
     }
   }
-  const double abs_sum = cb_block_sum_f(my_abs, redf, tid);
+  const double abs_sum = vm_block_sum(my_abs, redf, tid);
   __syncthreads();
   redf[tid] = my_mce;
   __syncthreads();
@@ -286,19 +226,13 @@ __global__ __launch_bounds__(256) void calib_score_kernel(const long long *__res
   o[1] = (double)skipped;
   const bool any = n > 0;
   if (h < 2) {
-    o[2] = any ? brier / (double)n : cb_nan();
-    o[3] = any ? sconf / (double)n : cb_nan();
-    o[4] = any ? abs_sum / (double)n : cb_nan();
-    o[5] = any ? mce : cb_nan();
+    o[2] = any ? brier / (double)n : vm_nan();
+    o[3] = any ? sconf / (double)n : vm_nan();
+    o[4] = any ? abs_sum / (double)n : vm_nan();
+    o[5] = any ? mce : vm_nan();
   } else {
-    o[2] = any ? abs_sum / (double)n : cb_nan();
+    o[2] = any ? abs_sum / (double)n : vm_nan();
   }
-}
-
-static int cb_check_shape(const char *who, int K, int J) {
-  PP_REQUIRE(K > 0 && K <= 65535, "%s: bad K=%d (1 .. 65535 keypoints)", who, K);
-  PP_REQUIRE(J >= 1 && J <= CB_MAX_J, "%s: bad J=%d (1 .. %d thresholds)", who, J, CB_MAX_J);
-  return 0;
 }
 
 }  // namespace pp
@@ -306,7 +240,7 @@ static int cb_check_shape(const char *who, int K, int J) {
 extern "C" int pp_calib_fit(const long long *state, int K, int J, long long min_count, long long *blocks, float *table,
                             int *row_of, void *stream) {
   using namespace pp;
-  if (int rc = cb_check_shape("pp_calib_fit", K, J)) return rc;
+  if (int rc = vm_check_shape("pp_calib_fit", K, J)) return rc;
   PP_REQUIRE(min_count >= 1, "pp_calib_fit: bad min_count=%lld (at least 1)", min_count);
   PP_REQUIRE(state, "pp_calib_fit: null state");
   PP_REQUIRE(blocks && table && row_of, "pp_calib_fit: null output");
@@ -338,9 +272,9 @@ extern "C" int pp_calib_apply(const float *aux_in, float *aux_out, int B, int K,
 extern "C" int pp_calib_score(const long long *state, int K, int J, const float *table, const int *row_of, int ece_bins,
                               double *report, void *stream) {
   using namespace pp;
-  if (int rc = cb_check_shape("pp_calib_score", K, J)) return rc;
-  PP_REQUIRE(ece_bins >= 1 && ece_bins <= CB_BINS && CB_BINS % ece_bins == 0,
-             "pp_calib_score: ece_bins=%d does not divide %d", ece_bins, CB_BINS);
+  if (int rc = vm_check_shape("pp_calib_score", K, J)) return rc;
+  PP_REQUIRE(ece_bins >= 1 && ece_bins <= VM_BINS && VM_BINS % ece_bins == 0,
+             "pp_calib_score: ece_bins=%d does not divide %d", ece_bins, VM_BINS);
   PP_REQUIRE(state, "pp_calib_score: null state");
   PP_REQUIRE(table && row_of, "pp_calib_score: null calibration");
   PP_REQUIRE(report, "pp_calib_score: null report");

@@ -4,52 +4,21 @@
 // ProbPoseLoss.forward(compute_acc=True): get_binary_accuracy (loss.py:653-697), get_mae (loss.py:699-712), the
 // averaging of the losses and accuracies (train.py:146-167).  pp_valmeter_update adds one batch to an INTEGER state
 // (counts and fixed-point sums, 64-bit atomics), so the state does not depend on batch order, batch split or atomic
-// order; pp_valmeter_report turns the state into float64 statistics per keypoint and pooled.  The state layout and
-// the report fields are documented in include/probpose_hip.h; tests/valmeter_reference.py restates both.
+// order; pp_valmeter_report turns the state into float64 statistics per keypoint and pooled.  The state layout
+// (pp_valmeter_state.h) and the report fields are documented in include/probpose_hip.h; tests/valmeter_reference.py
+// restates both.
 //
 // Compiled -ffp-contract=off: Q30 / Q20 round one float64 product, exactly as numpy does.
 #include <algorithm>
 
-#include "pp_common.h"
+#include "pp_valmeter_state.h"
 
 namespace pp {
 
-constexpr int VM_BINS = 1024;
-constexpr int VM_MAX_J = 64;
-constexpr int VM_SCALARS = 15;
 constexpr int VM_GLOBALS = 18;
 constexpr int VM_BINARY_FIXED = 10, VM_OKS_FIXED = 5, VM_ERR_FIELDS = 3;
-constexpr double VM_Q30 = 1073741824.0, VM_Q20 = 1048576.0;
 // flag bits the meter adds to those of pp_probpose_loss_terms
 constexpr long long VM_FLAG_TARGET_RANGE = 256, VM_FLAG_NONFINITE = 512;
-
-// word offsets of the sections of the state (include/probpose_hip.h)
-struct VmLayout {
-  long long hist, conf, above, sum_p, sum_p2, oks_hist, oks_sx, oks_st, oks_sums, err, pck, all, rejected, scalars,
-      words;
-};
-
-__host__ __device__ inline VmLayout vm_layout(int K, int J) {
-  VmLayout L;
-  const long long k = K;
-  long long o = 0;
-  L.hist = o, o += 2 * k * 2 * VM_BINS;
-  L.conf = o, o += 2 * k * VM_BINS;
-  L.above = o, o += 2 * k * 2 * J;
-  L.sum_p = o, o += 2 * k * 2;
-  L.sum_p2 = o, o += 2 * k * 2;
-  L.oks_hist = o, o += k * VM_BINS;
-  L.oks_sx = o, o += k * VM_BINS;
-  L.oks_st = o, o += k * VM_BINS;
-  L.oks_sums = o, o += k * 5;
-  L.err = o, o += k * 4;
-  L.pck = o, o += 2 * k;
-  L.all = o, o += 3;
-  L.rejected = o, o += 5;
-  L.scalars = o, o += VM_SCALARS;
-  L.words = o;
-  return L;
-}
 
 struct VmBatch {
   const float *dt_prob, *dt_vis, *dt_oks, *dt_err, *gt_oks, *gt_err;
@@ -59,15 +28,11 @@ struct VmBatch {
   const float *map_max, *res;
 };
 
-typedef unsigned long long u64;
-
 __device__ __forceinline__ u64 q_fixed(double z, double scale) { return (u64)(long long)__builtin_rint(z * scale); }
-__device__ __forceinline__ int fine_bin(float p) { return min(VM_BINS - 1, (int)floorf(p * 1024.0f)); }
-__device__ __forceinline__ bool unit_ok(float p) { return p >= 0.0f && p <= 1.0f; }         // NaN: false
 __device__ __forceinline__ bool err_ok(float x) { return x >= 0.0f && x <= 1048576.0f; }    // NaN, inf: false
 
-// the workgroup's private counters: above[2][2][J], sum_p[2][2], sum_p2[2][2], oks sums[5], err[4], all[3], rejected[5]
-constexpr int VM_LOCAL_FIXED = 25;
+// the workgroup's private counters: above[2][2][J], sum_p[2][2], sum_p2[2][2], oks sums, err, all, rejected
+constexpr int VM_LOCAL_FIXED = 4 + 4 + VM_OKS_SUMS + VM_ERR_SUMS + VM_ALL + VM_REJECTED;
 
 // grid (K, chunks + 1): workgroup (k, c < chunks) takes the samples b = c * 256 + t, + chunks * 256, ... of keypoint k;
 // the workgroups (k, chunks) add keypoint k's PCK counts, and (0, chunks) reduces map_max and adds the batch scalars.
@@ -167,7 +132,7 @@ __global__ __launch_bounds__(256) void valmeter_update_kernel(VmBatch in, int B,
     const long long idx = b * K + k;
     const float prob = in.dt_prob[idx];
     atomicAdd(&l_all[0], 1ull);
-    if (unit_ok(prob)) {
+    if (vm_unit_ok(prob)) {
       atomicAdd(&l_all[1], 1ull);
       atomicAdd(&l_all[2], q_fixed((double)prob, VM_Q30));
     }
@@ -182,12 +147,12 @@ __global__ __launch_bounds__(256) void valmeter_update_kernel(VmBatch in, int B,
       if (h == 1 && !im) break;
       const float p = h == 0 ? prob : in.dt_vis[idx];
       const int label = h == 0 ? im : (in.visibility[idx] != 0);
-      if (!unit_ok(p)) {
+      if (!vm_unit_ok(p)) {
         atomicAdd(&l_rej[1 + h], 1ull);
         continue;
       }
       const double pd = (double)p;
-      const int bin = fine_bin(p);
+      const int bin = vm_fine_bin(p);
       const long long hk = (long long)h * K + k;
       atomicAdd(&state[L.hist + (hk * 2 + label) * VM_BINS + bin], 1ull);
       atomicAdd(&state[L.conf + hk * VM_BINS + bin], q_fixed(pd, VM_Q30));
@@ -199,11 +164,11 @@ __global__ __launch_bounds__(256) void valmeter_update_kernel(VmBatch in, int B,
     if (!im) continue;
     {
       const float x = in.dt_oks[idx], t = in.gt_oks[idx];
-      if (!unit_ok(x) || !unit_ok(t)) {
+      if (!vm_unit_ok(x) || !vm_unit_ok(t)) {
         atomicAdd(&l_rej[3], 1ull);
       } else {
         const double xd = (double)x, td = (double)t, d = xd - td;
-        const int bin = fine_bin(x);
+        const int bin = vm_fine_bin(x);
         atomicAdd(&state[L.oks_hist + (long long)k * VM_BINS + bin], 1ull);
         atomicAdd(&state[L.oks_sx + (long long)k * VM_BINS + bin], q_fixed(xd, VM_Q30));
         atomicAdd(&state[L.oks_st + (long long)k * VM_BINS + bin], q_fixed(td, VM_Q30));
@@ -239,8 +204,8 @@ __global__ __launch_bounds__(256) void valmeter_update_kernel(VmBatch in, int B,
       const int f = i - 4 * J;
       if (f < 4) at = L.sum_p + ((long long)(f >> 1) * K + k) * 2 + (f & 1);
       else if (f < 8) at = L.sum_p2 + ((long long)((f - 4) >> 1) * K + k) * 2 + (f & 1);
-      else if (f < 13) at = L.oks_sums + (long long)k * 5 + (f - 8);
-      else if (f < 17) at = L.err + (long long)k * 4 + (f - 13);
+      else if (f < 13) at = L.oks_sums + (long long)k * VM_OKS_SUMS + (f - 8);
+      else if (f < 17) at = L.err + (long long)k * VM_ERR_SUMS + (f - 13);
       else if (f < 20) at = L.all + (f - 17);
       else at = L.rejected + (f - 20);
     }
@@ -256,8 +221,6 @@ __device__ __forceinline__ long long vm_sum_k(const long long *state, long long 
   return s;
 }
 
-__device__ __forceinline__ double vm_nan() { return __builtin_nan(""); }
-
 // grid (K + 1, 4): row = keypoint (K = the pool, summed from the integer state); part 0 / 1 = the probability /
 // visibility head, 2 = the OKS head, 3 = the error head, PCK and the whole-set fields.  256 threads.
 __global__ __launch_bounds__(256) void valmeter_report_kernel(const long long *__restrict__ state,
@@ -270,7 +233,7 @@ __global__ __launch_bounds__(256) void valmeter_report_kernel(const long long *_
   __shared__ double mx[256];
   const VmLayout L = vm_layout(K, J);
   const int tid = threadIdx.x, row = blockIdx.x, part = blockIdx.y;
-  const int k0 = row < K ? row : 0, k1 = row < K ? row + 1 : K;
+  const auto [k0, k1] = vm_row_range(row, K);
   const int bin_fields = VM_BINARY_FIXED + J + 3 * E, oks_fields = VM_OKS_FIXED + 3 * E;
   double *o = out + (long long)row * F;
   const int width = VM_BINS / E;
@@ -466,12 +429,6 @@ __global__ __launch_bounds__(256) void valmeter_report_kernel(const long long *_
   o[11] = (double)S[1];
   o[12] = (double)S[2];
   for (int i = 0; i < 5; ++i) o[13 + i] = (double)state[L.rejected + i];
-}
-
-static int vm_check_shape(const char *who, int K, int J) {
-  PP_REQUIRE(K > 0 && K <= 65535, "%s: bad K=%d (1 .. 65535 keypoints)", who, K);
-  PP_REQUIRE(J >= 1 && J <= VM_MAX_J, "%s: bad J=%d (1 .. %d thresholds)", who, J, VM_MAX_J);
-  return 0;
 }
 
 }  // namespace pp

@@ -60,23 +60,30 @@ def report_fields(J: int, E: int) -> int:
     return 2 * (len(_BINARY) + J + 3 * E) + len(_OKS) + 3 * E + len(_ERR) + 1 + _GLOBALS
 
 
+def check_ece_bins(ece_bins: int) -> None:
+    if ece_bins < 1 or BINS % ece_bins:
+        raise ValueError(f"ece_bins must divide {BINS}, got {ece_bins}")
+
+
+def head_fields(rep: np.ndarray, o: int, names, E: int, J: int = 0):
+    """One head of a [K+1][F] report from column ``o``: the named scalars, ``bal_acc`` [J] where J > 0, then the
+    ``reliability`` table [E][3].  Returns the dict and the column after the head."""
+    d = {name: rep[:, o + i].copy() for i, name in enumerate(names)}
+    o += len(names)
+    if J:
+        d["bal_acc"] = rep[:, o:o + J].copy()
+        o += J
+    d["reliability"] = rep[:, o:o + 3 * E].reshape(-1, E, 3).copy()
+    return d, o + 3 * E
+
+
 def parse_report(rep: np.ndarray, thresholds: np.ndarray, ece_bins: int) -> dict:
     """The [K+1][F] float64 report as a nested dict; per-row fields are arrays of K+1 (the last entry is the pool)."""
     J, E = len(thresholds), ece_bins
     out, o = {"thresholds": np.array(thresholds)}, 0
     for head in ("probability", "visibility"):
-        d = {name: rep[:, o + i].copy() for i, name in enumerate(_BINARY)}
-        o += len(_BINARY)
-        d["bal_acc"] = rep[:, o:o + J].copy()
-        o += J
-        d["reliability"] = rep[:, o:o + 3 * E].reshape(-1, E, 3).copy()
-        o += 3 * E
-        out[head] = d
-    d = {name: rep[:, o + i].copy() for i, name in enumerate(_OKS)}
-    o += len(_OKS)
-    d["reliability"] = rep[:, o:o + 3 * E].reshape(-1, E, 3).copy()
-    o += 3 * E
-    out["oks"] = d
+        out[head], o = head_fields(rep, o, _BINARY, E, J)
+    out["oks"], o = head_fields(rep, o, _OKS, E)
     out["error"] = {name: rep[:, o + i].copy() for i, name in enumerate(_ERR)}
     o += len(_ERR)
     out["pck"] = rep[:, o].copy()
@@ -101,8 +108,7 @@ class ValidationMeter:
         thr = np.arange(0.1, 1.0, 0.05) if thresholds is None else np.asarray(thresholds, dtype=np.float64).reshape(-1)
         if not 1 <= len(thr) <= _lib.PP_VALMETER_MAX_THRESHOLDS:
             raise ValueError(f"1 to {_lib.PP_VALMETER_MAX_THRESHOLDS} thresholds, got {len(thr)}")
-        if ece_bins < 1 or BINS % ece_bins:
-            raise ValueError(f"ece_bins must divide {BINS}, got {ece_bins}")
+        check_ece_bins(ece_bins)
         self.loss_fn, self.thresholds, self.ece_bins = loss_fn, np.ascontiguousarray(thr), int(ece_bins)
         self._state = self._thr = self._K = self._device = None
         self._pinned = []           # pinned sources of the uploads that stay for the meter's life
@@ -121,13 +127,17 @@ class ValidationMeter:
         self._thr = _buffers.upload(self.thresholds, dev, self._pinned)
         self._K, self._device = K, dev
 
+    def device_state(self):
+        """``(state, K, J)``: the int64 words on the device as ``pp_valmeter_report`` and ``pp_calib_fit`` take them."""
+        if self._state is None:
+            raise RuntimeError("the meter has seen no batch yet")
+        return self._state, self._K, len(self.thresholds)
+
     @property
     def state(self) -> dict:
         """int64 device views into the state by the header's section names (``scalars``: the raw words)."""
-        if self._state is None:
-            raise RuntimeError("the meter has seen no batch yet")
-        lay = state_layout(self._K, len(self.thresholds))
-        return {name: self._state[o:o + int(np.prod(shape))].view(shape) for name, (o, shape) in lay.items()
+        words, K, J = self.device_state()
+        return {name: words[o:o + int(np.prod(shape))].view(shape) for name, (o, shape) in state_layout(K, J).items()
                 if name != "words"}
 
     def reset(self) -> None:
@@ -212,12 +222,11 @@ class ValidationMeter:
     # ------------------------------------------------------------------------------------------- report
     def compute(self) -> dict:
         """The one synchronisation: ``pp_valmeter_report`` and a copy of its float64 table."""
-        if self._state is None:
-            raise RuntimeError("the meter has seen no batch yet")
-        J, E = len(self.thresholds), self.ece_bins
-        rep = torch.empty((self._K + 1, report_fields(J, E)), dtype=torch.float64, device=self._device)
-        with torch.cuda.device(self._device):
-            _lib.launch("pp_valmeter_report", self._state, self._thr, self._K, J, E, rep)
+        state, K, J = self.device_state()
+        E = self.ece_bins
+        rep = torch.empty((K + 1, report_fields(J, E)), dtype=torch.float64, device=state.device)
+        with torch.cuda.device(state.device):
+            _lib.launch("pp_valmeter_report", state, self._thr, K, J, E, rep)
         host = rep.cpu().numpy()
         self._in_flight = []
         return parse_report(host, self.thresholds, E)

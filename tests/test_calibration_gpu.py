@@ -48,9 +48,9 @@ def words(state) -> torch.Tensor:
 
 
 def meter_with(state, K, J):
-    """A ValidationMeter whose device state is ``state``."""
+    """A ValidationMeter whose device state is ``state`` (the calibration reads J, never the thresholds)."""
     from probpose_pytorch_amd import ValidationMeter
-    meter = ValidationMeter(None, thresholds=THR[:J])
+    meter = ValidationMeter(None, thresholds=THR[:J] if J <= len(THR) else np.linspace(0.01, 0.99, J))
     meter._ensure(K, torch.device("cuda", torch.cuda.current_device()))
     w = words(state)
     assert w.shape == meter._state.shape
@@ -197,6 +197,33 @@ def test_min_count_just_above_and_below():
     for mc, want in ((count, 2), (count + 1, K), (count - 1, 2)):
         _, (_, _, row_of) = check_fit(state, K, J, mc)
         assert row_of[1, 2] == want
+
+
+def test_fit_and_score_read_their_sections_whatever_lies_between():
+    """The same hist / oks_hist / oks_st at K = 2 (the smallest K at which every section's keypoint stride counts) under
+    J = 1, 7 and 64 (the cap), which moves ``above`` and all behind it; every word of the sections the calibration does
+    not read is -1.  An offset that is off lands in a sentinel or in another keypoint's bins."""
+    K = 2
+    content = random_state(31, K, 1)
+    got = []
+    for J in (1, 7, 64):
+        state = vr.empty_state(K, J)
+        for name in ("hist", "oks_hist", "oks_st"):
+            state[name][:] = content[name]
+        for name in ("conf", "above", "sum_p", "sum_p2", "oks_sx"):
+            state[name][:] = -1
+        cal, (_, table, row_of) = check_fit(state, K, J, 70)     # rows of their own and rows sent to the pool
+        assert set(row_of.reshape(-1).tolist()) == {0, 1, K}
+        score, want = cal.score(meter_with(state, K, J)), cr.score(state, K, J, table, row_of, 16)
+        counts = [score[head][name] if name != "reliability" else score[head][name][:, :, 0]
+                  for head in cr.HEADS for name in ("n", "skipped", "reliability")]
+        for c, head in zip(counts[::3], cr.HEADS):
+            assert np.array_equal(c, want[head]["n"]) and c[-1] > 0, head
+        got.append((cal, counts))
+    for cal, counts in got[1:]:
+        for name in ("blocks", "table", "row_of"):
+            assert torch.equal(getattr(cal, name), getattr(got[0][0], name)), name
+        assert all(np.array_equal(a, b) for a, b in zip(counts, got[0][1]))
 
 
 # ----------------------------------------------------------------------------------------------- apply

@@ -71,16 +71,16 @@ def kernel_times(B, K, blocker, batches=32):
     from probpose_pytorch_amd.calibration import score_fields
     out = {}
     meters = {"rising": fed_meter(B, K, batches, False, 1), "against": fed_meter(B, K, batches, True, 2)}
-    J = len(meters["rising"].thresholds)
     cal = HeadCalibration.fit(meters["rising"])
     for name, meter in meters.items():
+        state, _, J = meter.device_state()
         out[f"fit ({name})"] = device_us(
-            lambda: _lib.launch("pp_calib_fit", meter._state, K, J, 1000, cal.blocks, cal.table, cal.row_of), blocker)
+            lambda: _lib.launch("pp_calib_fit", state, K, J, 1000, cal.blocks, cal.table, cal.row_of), blocker)
     cal = HeadCalibration.fit(meters["rising"])
     blocks = cal.blocks.cpu()
     out["blocks_per_row"] = round(float((blocks[:, :, 1:] != blocks[:, :, :-1]).any(-1).sum(-1).float().mean()) + 1, 1)
     rep = torch.empty((K + 1, score_fields(16)), dtype=torch.float64, device="cuda")
-    state = meters["rising"]._state
+    state, _, J = meters["rising"].device_state()
     out["score"] = device_us(
         lambda: _lib.launch("pp_calib_score", state, K, J, cal.table, cal.row_of, 16, rep), blocker)
     g = torch.Generator(device="cuda").manual_seed(3)

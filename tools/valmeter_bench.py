@@ -118,16 +118,16 @@ def kernel_times(B, K, blocker, launches=200, repeats=7):
     f = [torch.rand(B, K, device="cuda", generator=g) for _ in range(6)]
     m = [(torch.rand(B, K, device="cuda", generator=g) < 0.7).int() for _ in range(3)]
     meter.update_heads(*f[:4], *m, f[4], f[5])
-    J = len(meter.thresholds)
+    state, _, J = meter.device_state()
     pck = torch.ones((2, K), dtype=torch.int32, device="cuda")
     res = torch.zeros((11,), dtype=torch.float32, device="cuda")
     rep = torch.empty((K + 1, report_fields(J, meter.ece_bins)), dtype=torch.float64, device="cuda")
 
     def update():
-        _lib.launch("pp_valmeter_update", *f[:4], f[4], f[5], *m, meter._thr, J, pck, f[0], res, B, K, meter._state)
+        _lib.launch("pp_valmeter_update", *f[:4], f[4], f[5], *m, meter._thr, J, pck, f[0], res, B, K, state)
 
     def report():
-        _lib.launch("pp_valmeter_report", meter._state, meter._thr, K, J, meter.ece_bins, rep)
+        _lib.launch("pp_valmeter_report", state, meter._thr, K, J, meter.ece_bins, rep)
 
     out = {}
     for name, fn in (("update", update), ("report", report)):
@@ -147,7 +147,7 @@ def kernel_times(B, K, blocker, launches=200, repeats=7):
             b.synchronize()
             us.append(a.elapsed_time(b) * 1e3 / launches)
         out[name] = dict(us_median=round(statistics.median(us), 2), us_min=round(min(us), 2), us_max=round(max(us), 2))
-    out["state_bytes"] = int(meter._state.numel()) * 8
+    out["state_bytes"] = int(state.numel()) * 8
     out["report_bytes"] = int(rep.numel()) * 8
     return out
 
